@@ -12,12 +12,19 @@ already resident in HBM.  Pairs are independent, so ranks shard the pair
 stream with no data-path collective (weak scaling); the only collectives are
 the timing barrier and the max-over-ranks of the elapsed time.
 
-Rank 0 prints ONE JSON line (contract in the task statement) including
+Rank 0 prints ONE JSON result line.  A plain run
+sets up, warms up, times `--steps` forwards and prints the headline figures
+(`value`, `ms_per_step`, ...).  `--full` adds everything else:
   roofline      HBM roofline of the dominant kernel (fused KPConv gather):
                 algorithmic bytes / HIP-event duration measured inside the
                 timed region on the launch stream
+  extra legs    exact-f32 / other attention modes / two streams / training
+                step, short runs of their own after the headline timing
   cpu_baseline  the CPU oracle (port of the reference path) timed on this
                 host's cores on a bounded sample (four pairs), N == 1 only.
+
+`--dump-outputs DIR` writes what the last timed forward returned (rank 0) as
+DIR/<name>.npy, so that two builds can be compared output for output.
 """
 import argparse
 import ctypes
@@ -74,7 +81,54 @@ def parse():
                     help="ascending-voxel-key point order instead of the reference's hash-map order")
     ap.add_argument("--skip-upsamples", action="store_true",
                     help="skip the up-sampling neighbour search the encoder never reads")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline timing: the per-kernel roofline figures (HIP events inside the timed "
+                         "steps), the extra legs and the CPU baseline (--no-extra-legs / --no-train-leg / "
+                         "--no-cpu-baseline trim them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BUDGET = 64 << 20   # bytes, all files of --dump-outputs together
+DUMP_FEAT_ROWS = 16384   # per side: a larger feature matrix is written as a fixed, seeded sample of its rows
+
+
+def dump_outputs(out, path):
+    """The forward's result (regtr.RegTR._forward: lists over the batch) flattened into arrays: per-pair lists are
+    concatenated along their point axis, with the per-pair lengths beside them.  Float results keep float32
+    (float64 if computed so), integer ones are written as float64 (exact)."""
+    os.makedirs(path, exist_ok=True)
+
+    def host(t):
+        a = t.detach().cpu().numpy()
+        return a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+
+    def cat(key, width=None):
+        parts = [host(t) for t in out[key]]
+        parts = [p.reshape(-1) if width is None else p.reshape(-1, width) for p in parts]
+        return np.concatenate(parts, 0), np.array([p.shape[0] for p in parts], np.float64)
+
+    arrays = {"pose": host(out["pose"])}
+    for side in ("src", "tgt"):
+        arrays[f"{side}_kp"], arrays[f"{side}_lens"] = cat(f"{side}_kp", 3)
+        arrays[f"{side}_overlap"], _ = cat(f"{side}_overlap")
+        arrays[f"{side}_corr"], arrays[f"{side}_corr_lens"] = cat(f"{side}_corr", 3)
+        feat, _ = cat(f"{side}_feat", out[f"{side}_feat"][0].shape[-1])
+        if feat.shape[0] > DUMP_FEAT_ROWS:
+            rows = np.sort(np.random.default_rng(0).choice(feat.shape[0], DUMP_FEAT_ROWS, replace=False))
+            arrays[f"{side}_feat_rows"] = rows.astype(np.float64)
+            feat = feat[rows]
+        arrays[f"{side}_feat"] = feat
+    arrays["overlap_prob"], _ = cat("overlap_prob_list")
+    arrays["ind"], _ = cat("ind_list")
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BUDGET, f"--dump-outputs: {total} bytes exceed the {DUMP_BUDGET}-byte budget"
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 def kpconv_alg_bytes(meta, model):
@@ -230,9 +284,14 @@ def main():
     ops.set_gemm_mode(args.gemm_mode)
     ops.set_attn_mode(args.attn_mode)
 
+    last = [None]   # the newest step's result, kept only for --dump-outputs
+
     def step():
         with torch.no_grad():
-            return runner(batch)   # leaves the pyramid(s) in batch['kpconv_meta']
+            out = runner(batch)   # leaves the pyramid(s) in batch['kpconv_meta']
+        if args.dump_outputs:
+            last[0] = out
+        return out
 
     for _ in range(max(args.warmup, 1)):
         out = step()
@@ -240,16 +299,19 @@ def main():
     L = _lib.lib()
 
     # ---- timed region: barrier + sync, K steps, sync + barrier, MAX over ranks ----
-    L.spr_prof_enable(1)
+    if args.full:
+        L.spr_prof_enable(1)
     elapsed, own = sharding.timed_steps(step, args.steps, dist=dist, sync=torch.cuda.synchronize, device=dev,
                                         return_own=True)
     per_rank_ms = sharding.gather_ms(1e3 * own / args.steps, dist=dist, device=dev)   # every rank's own time
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last[0], args.dump_outputs)
 
     # ---- roofline of the dominant kernel (rank 0) -----------------------------
     roofline = None
     roofline_attn = None
     attn_flops_per_call = None
-    if rank == 0:
+    if rank == 0 and args.full:
         cap = 256 * max(args.steps, 1)
         codes = (ctypes.c_int * cap)()
         nqs = (ctypes.c_int * cap)()
@@ -339,12 +401,13 @@ def main():
                                 launches=a['count'], avg_ms=round(a['ms'] / a['count'], 5),
                                 gbs=round(fwd_bytes[c] / fwd_launches[c] / (a['ms'] / a['count'] * 1e-3) / 1e9, 1))
                                 for c, a in agg.items() if c in fwd_bytes})
-    L.spr_prof_enable(0)
+    if args.full:
+        L.spr_prof_enable(0)
 
     # ---- extra legs (N == 1): the same workload in exact-f32 arithmetic and with single-pass
     # fp16 attention operands; short, after the headline timing, never part of `value`
     extra = {}
-    if world == 1 and not args.no_extra_legs:
+    if args.full and world == 1 and not args.no_extra_legs:
         def leg(gm, am, steps):
             ops.set_gemm_mode(gm)
             ops.set_attn_mode(am)
@@ -455,6 +518,7 @@ def main():
                                                       f"f32 storage/accumulate, gemm_mode={args.gemm_mode}, "
                                                       f"attn_mode={args.attn_mode}"),
         "data": "synthetic",
+        "full": args.full,   # false: the --full-only entries below are null (not measured)
         "config": {"workload": f"{cloud_desc}, full KPConv backbone + superpoint attn "
                                f"+ {'Sinkhorn-' if cfg.use_sinkhorn else ''}SVD pose ({args.config} config, "
                                f"{baseline_cfg})",
@@ -480,7 +544,7 @@ def main():
                   "backend": (dist.get_backend() if dist is not None else None),
                   "ms_per_step_per_rank": per_rank_ms},
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(cfg, sd_cpu, args.points)
     else:
         result["cpu_baseline"] = None

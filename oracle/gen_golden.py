@@ -551,6 +551,20 @@ def gen_formats():
     print(report)
 
 
+def gen_shim():
+    """tests/test_gpu_shim.py: two box clouds and what the reference's own C++ (oracle/_ref) makes of them --
+    subsample_batch at 0.05 and batch_query of the subsampled points into the clouds at 0.09."""
+    rng = np.random.default_rng(5)
+    a = (synthetic.box_faces(3000, rng, 1.0) + rng.normal(0, 0.004, (3000, 3))).astype(np.float32)
+    b = (synthetic.box_faces(2400, rng, 0.8) + rng.normal(0, 0.004, (2400, 3))).astype(np.float32)
+    pts, lens = np.concatenate([a, b]), np.array([3000, 2400], np.int32)
+    sub, sub_lens = native.ref_grid_subsample(pts, lens, 0.05, 0)
+    nb = native.ref_radius_neighbors(sub, pts, sub_lens, lens, 0.09)
+    path = os.path.join(OUT, 'shim.npz')
+    np.savez_compressed(path, pts=pts, lens=lens, sub=sub, sub_lens=sub_lens, nb=_idx16(nb))
+    print(os.path.basename(path), os.path.getsize(path) // 1024, 'KB')
+
+
 def main():
     assert ref_harness.available(), "needs /root/reference (dev container only)"
     os.makedirs(OUT, exist_ok=True)
@@ -578,6 +592,8 @@ def main():
             gen_refine('kitti', 2)
         if 'formats' in what:
             gen_formats()
+        if 'shim' in what:
+            gen_shim()
         for case in ('c2', 'c3', 'c3w', 'c4'):
             if f'sized_{case}' in what or 'sized' in what:
                 gen_sized(case)
