@@ -348,8 +348,8 @@ int spr_attn_varlen_fwd(const float* q, int q_stride, const float* k,
                         float* out, int o_stride, void* ws, size_t ws_bytes,
                         void* stream);
 /* The same, additionally handing out lse [t, nhead] = log2 sum_j 2^(log2(e) scale q_i.k_j) per query and head
- * for spr_attn_varlen_bwd_lse (training: what torch's SDPA backward keeps as `logsumexp`).  *lse_written = 0 when
- * the configured core does not produce it (exact-f32 mode, the eager-softmax experiment): lse is then untouched. */
+ * for spr_attn_varlen_bwd_lse (training: what torch's SDPA backward keeps as `logsumexp`).  *lse_written = 0 in
+ * exact-f32 mode (attention mode 0, whose core does not produce it): lse is then untouched. */
 int spr_attn_varlen_fwd_lse(const float* q, int q_stride, const float* k, int k_stride, const float* v,
                             int v_stride, const int* cu, const int* kv_seg, int t, int nseg, int max_len_host,
                             int nhead, int head_dim, float scale, float* out, int o_stride, float* lse,

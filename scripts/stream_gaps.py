@@ -7,7 +7,7 @@ win = float(sys.argv[2]) if len(sys.argv) > 2 else 250.0
 import os
 f = max(glob.glob(d + "/*/*kernel_trace.csv"), key=os.path.getmtime)          # gpurun merges without deleting: newest
 rows = list(csv.DictReader(open(f)))
-loop = [r for r in rows if "k_xenc_chain" in r["Kernel_Name"] or "k_attn_h3" in r["Kernel_Name"]]
+loop = [r for r in rows if "k_xenc_chain" in r["Kernel_Name"] or "k_attn_s" in r["Kernel_Name"]]
 tmax = max(int(r["End_Timestamp"]) for r in loop)            # end of the last timed forward's transformer
 t0 = tmax - int(win * 1e6)
 byq = collections.defaultdict(list)

@@ -15,7 +15,6 @@ and nothing below is touched.
 """
 import ctypes
 import math
-import os
 
 import numpy as np
 import torch
@@ -355,9 +354,6 @@ class GatherRowsFn(torch.autograd.Function):
         return dx, None
 
 
-_LSE_HANDOVER = os.environ.get("SPR_NO_LSE_HANDOVER", "0") != "1"   # experiment switch (A/B timing)
-
-
 class AttentionFn(torch.autograd.Function):
     """Varlen multi-head attention core (spr_attn_varlen_fwd).  Backward = spr_attn_varlen_bwd: the
     probabilities are recomputed tile by tile inside two kernels (dQ; dK and dV) -- nothing of size
@@ -366,10 +362,7 @@ class AttentionFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, cu, kv_seg, max_len, nhead, lens_host, kv_seg_host):
         with torch.no_grad():
-            if _LSE_HANDOVER:
-                out, lse = _ops.attention_raw(q, k, v, cu, kv_seg, max_len, nhead, want_lse=True)
-            else:
-                out, lse = _ops.attention_raw(q, k, v, cu, kv_seg, max_len, nhead), None
+            out, lse = _ops.attention_raw(q, k, v, cu, kv_seg, max_len, nhead, want_lse=True)
         kvs = [int(x) for x in kv_seg_host]
         if sorted(kvs) != list(range(len(kvs))):
             raise NotImplementedError("attention backward needs kv_seg to be a permutation of the segments")

@@ -196,7 +196,7 @@ __global__ __launch_bounds__(256) void k_attn(
 }
 
 // ---------------------------------------------------------------------------
-// Split-fp16 variant ("h3"): fp32-level accuracy, ~5x less matrix-core time.
+// Split-fp16 variant: fp32-level accuracy, ~5x less matrix-core time.
 // Every operand x is carried as hi = fp16(x m) and lo = fp16(x m - hi) with a
 // per-tensor multiplier m (below); a.b ~= ah.bh + ah.bl + al.bh in ONE fp32
 // accumulator (the matrix cores honour fp16 subnormals, scripts/abl/denorm.hip).
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(256) void k_attn(
 // 2^ev (max |v| 2^ev in [2^14, 2^15)) and the output by 2^-ev.  The bounds are
 // measured (unfused entry: launch_absmax on q, k, v) or derived (fused entry:
 // max|x| * max row L1 norm of the projection block + max|bias|).
-// Mode 2 ("h1") runs the same kernel with the hi planes only: single-pass fp16
+// Mode 2 runs the same kernel with the hi planes only: single-pass fp16
 // operands (11 significand bits), fp32 softmax and accumulators, 1/3 of the MFMAs.
 //
 // Two kernels:
@@ -218,25 +218,22 @@ __global__ __launch_bounds__(256) void k_attn(
 //     wants 4 consecutive keys of one feature.  Token columns of segment s
 //     start at vstart(s) = (cu[s] + 8 s) & ~7 (16-byte aligned rows for the
 //     wide loads); gap and tail columns are written as zeros.
-//   k_attn_h3    streams 64-key tiles of those planes through LDS (pure 16-byte
-//     copies, no conversion in the loop) and runs, per wave of 32 queries:
+//   k_attn_s     streams 64-key tiles of those planes through LDS (LDS-DMA,
+//     no conversion in the loop) and runs, per wave of 32 queries:
 //       S^T = K Q^T : 2 key sub-tiles x 2 k-steps x 3 v_mfma_f32_32x32x16_f16
-//       online softmax, lane = query, base 2, lazy rescale; P is scaled by
-//         2^10 so small probabilities stay in fp16's normal range (cancels in
-//         the final 1/l), hi by packed RTZ conversion, lo by v_fma_mix*_f16
+//       online softmax, lane = query, base 2, lazy reference (the row maximum
+//         sits at 2^4 after a recentring), hi by packed conversion, lo by
+//         v_fma_mix*_f16
 //       O^T = V^T P^T: the probabilities in the S^T accumulator are converted
 //         in place -- registers 8s..8s+7 of a lane are exactly the B fragment
 //         of k-step s with key order kappa(s,h,j) = 16s + 8(j>>2) + 4h + (j&3);
-//         the V^T A-fragment is read with the same order (two 8-byte reads).
+//         the V^T A-fragment is read with the same order.
 typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 constexpr int KT2 = 64;  // keys per tile (two 32-key MFMA sub-tiles)
-constexpr int KH = 40;   // K tile row stride in halves (80 B: conflict-free ds_read_b128)
-constexpr int VH = 72;   // V^T tile row stride in halves (144 B: 2-pass ds_read_b64)
 constexpr int PT = 64;   // token columns per pack workgroup
 constexpr int PS = 72;   // pack transposition row stride (halves)
 
@@ -341,9 +338,6 @@ __global__ __launch_bounds__(256) void k_attn_pack(
   }
 }
 
-constexpr int QW2 = 64;    // queries per wave (two 32-query MFMA column blocks) of the default form
-constexpr int QB2 = 256;   // queries per workgroup of the default form
-
 // max over the two half-waves (lanes l and l^32) without touching LDS
 __device__ __forceinline__ float half_swap_max(float x) {
   const unsigned int u = __float_as_uint(x);
@@ -351,491 +345,9 @@ __device__ __forceinline__ float half_swap_max(float x) {
   return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
 }
 
-// H3 = true: split-fp16 (hi + lo planes, 3 MFMAs per product); false: hi planes only.
-// NQ = 32-query blocks per wave: 2 (default: 64 queries per wave, 256 per workgroup, ~250 VGPRs, two waves per
-// SIMD) or 1 (32 queries per wave, 128 per workgroup, <= 128 VGPRs: four waves per SIMD -- the same instruction
-// stream at twice the occupancy; K / V^T fragments are then read from LDS twice as often per query).
-template <bool H3, bool LAZY = false, int NQ = 2, int WPS = (NQ == 1 ? 3 : 2), bool PIPE = false>
-__global__ __launch_bounds__(256, WPS) void k_attn_h3(
-    const _Float16* __restrict__ qh_g, const _Float16* __restrict__ ql_g,
-    const _Float16* __restrict__ kh_g, const _Float16* __restrict__ kl_g,
-    const _Float16* __restrict__ vth_g, const _Float16* __restrict__ vtl_g, int t_total, int tp,
-    const int* __restrict__ cu, const int* __restrict__ kv_seg, int nseg, int nhead,
-    const float* __restrict__ scales, float* __restrict__ out, int o_stride, float* __restrict__ lse_out) {
-  __shared__ __align__(16) _Float16 Kh[2][KT2 * KH], Kl[2][KT2 * KH];
-  __shared__ __align__(16) _Float16 Vth[2][HD * VH], Vtl[2][HD * VH];
-  // 1-D grid: all query tiles of one (segment, head) -- which stream the same
-  // K/V -- are placed on one XCD (ids b and b+8 share an L2)
-  int seg, head, qt;
-  {
-    const int nqt = gridDim.x / (nhead * nseg);
-    const int ngrp = nhead * nseg;
-    const int b = blockIdx.x;
-    if ((ngrp & 7) == 0) {
-      const int xcd = b & 7, idx = b >> 3;
-      const int g = xcd + 8 * (idx / nqt);
-      qt = idx % nqt;
-      head = g % nhead;
-      seg = g / nhead;
-    } else {
-      qt = b % nqt;
-      head = (b / nqt) % nhead;
-      seg = b / (nqt * nhead);
-    }
-  }
-  const int qbeg = cu[seg], qlen = cu[seg + 1] - qbeg;
-  constexpr int QWN = 32 * NQ, QBN = 4 * QWN;   // queries per wave / workgroup
-  const int q0 = qt * QBN;
-  if (q0 >= qlen) return;
-  const int ks = kv_seg[seg];
-  const int kbeg = cu[ks], klen = cu[ks + 1] - kbeg;
-  const int vbeg = vstart(cu, ks);
-
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int l31 = lane & 31, lh = lane >> 5;
-  const int hoff = head * HD;
-
-  // Q^T B-fragments of the wave's two 32-query blocks: lane (query l31, half
-  // lh), k-step s: d = 16 s + 8 lh + j
-  h16x8 qh[NQ][2], ql[NQ][2];
-#pragma unroll
-  for (int h = 0; h < NQ; ++h) {
-    const int qi = min(q0 + wave * QWN + 32 * h + l31, qlen - 1);
-    const size_t row = ((size_t)head * t_total + qbeg + qi) * HD + 8 * lh;
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      qh[h][s] = *reinterpret_cast<const h16x8*>(qh_g + row + 16 * s);
-      if constexpr (H3) ql[h][s] = *reinterpret_cast<const h16x8*>(ql_g + row + 16 * s);
-    }
-  }
-
-  f32x16 o[NQ];
-  float m_run[NQ];
-  f32x2 psum2[NQ];   // per-lane partial row sums; the two half-waves are joined at the end
-  float psum_a[NQ], psum_b[NQ];   // the same for the lazy form (even / odd registers)
-  // LAZY: the softmax reference m_ref of the lane's two queries rides into the score MFMAs as
-  // their C operand (all 16 registers = 4 - m_ref: scores come out as s - m_ref + 4, ready for
-  // exp2), and is moved -- with the accumulator rescale -- only on the first tile and when a score
-  // would push a scaled probability out of fp16's range; see tile().
-  f32x16 negm[NQ];
-#pragma unroll
-  for (int h = 0; h < NQ; ++h) {
-    m_run[h] = -INFINITY;
-    psum2[h] = (f32x2){0.f, 0.f};
-    psum_a[h] = psum_b[h] = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      o[h][r] = 0.f;
-      negm[h][r] = 0.f;
-    }
-  }
-
-  // staging roles: K -- key row tid>>2, 16-byte chunk tid&3; V^T -- feature row
-  // tid>>3, 16-byte chunk tid&7 (hi and lo planes each)
-  const int skr = tid >> 2, skc = (tid & 3) * 8;
-  const int svr = tid >> 3, svc = (tid & 7) * 8;
-  u32x4 rkh, rkl, rvh, rvl;
-  auto fetch = [&](int kt) {
-    const size_t krow = ((size_t)head * t_total + kbeg + min(kt + skr, klen - 1)) * HD + skc;
-    const size_t vrow = attn_v_off(hoff + svr, (size_t)(vbeg + kt + svc), nhead * HD);
-    const _Float16 *a = kh_g + krow, *b = kl_g + krow, *c = vth_g + vrow, *d = vtl_g + vrow;
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(rkh) : "v"(a));
-    if constexpr (H3) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(rkl) : "v"(b));
-    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(rvh) : "v"(c));
-    if constexpr (H3) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(rvl) : "v"(d));
-  };
-  auto stash = [&](int buf) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    *reinterpret_cast<u32x4*>(Kh[buf] + skr * KH + skc) = rkh;
-    if constexpr (H3) *reinterpret_cast<u32x4*>(Kl[buf] + skr * KH + skc) = rkl;
-    *reinterpret_cast<u32x4*>(Vth[buf] + svr * VH + svc) = rvh;
-    if constexpr (H3) *reinterpret_cast<u32x4*>(Vtl[buf] + svr * VH + svc) = rvl;
-  };
-
-  // One 64-key tile.  Branch-free inside (the online-softmax rescale is applied
-  // every tile) so that the compiler can run one query block's softmax VALU in
-  // the shadow of the other block's MFMAs.
-  auto tile = [&](int kt, int buf, auto tail_tag) {
-    constexpr bool TAIL = decltype(tail_tag)::value;
-    // K A-fragments (shared by both query blocks; NQ = 1: read per key sub-tile, right before its MFMAs -- the
-    // register budget of four waves per SIMD has no room for all eight at once)
-    h16x8 kfh[2][2], kfl[2][2];
-    auto load_kf = [&](int kk) __attribute__((always_inline)) {
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        kfh[kk][s] = *reinterpret_cast<const h16x8*>(Kh[buf] + (32 * kk + l31) * KH + 16 * s + 8 * lh);
-        if constexpr (H3)
-          kfl[kk][s] = *reinterpret_cast<const h16x8*>(Kl[buf] + (32 * kk + l31) * KH + 16 * s + 8 * lh);
-      }
-    };
-    if constexpr (NQ == 2) {
-      load_kf(0);
-      load_kf(1);
-    }
-    // ---- S^T = K Q^T (rows = keys, cols = queries) ----
-    f32x16 sacc[NQ][2];
-#pragma unroll
-    for (int h = 0; h < NQ; ++h)
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        if constexpr (NQ == 1) {
-          if (kk == 1) __builtin_amdgcn_sched_barrier(0);
-          load_kf(kk);
-        }
-        if constexpr (LAZY) {
-          sacc[h][kk] = negm[h];
-        } else {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) sacc[h][kk][r] = 0.f;
-        }
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          if constexpr (H3) {
-            sacc[h][kk] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kfh[kk][s], ql[h][s], sacc[h][kk], 0, 0, 0);
-            sacc[h][kk] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kfl[kk][s], qh[h][s], sacc[h][kk], 0, 0, 0);
-          }
-          sacc[h][kk] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kfh[kk][s], qh[h][s], sacc[h][kk], 0, 0, 0);
-        }
-      }
-    // V^T A-fragments (shared by both query blocks; NQ = 1: read per key sub-tile in front of its MFMAs)
-    h16x8 vfh[2][2], vfl[2][2];
-    auto load_vf = [&](int kk) __attribute__((always_inline)) {
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        // (round 5: the planes hold every 16-key group in fragment order, attn_vperm: one 16-byte read)
-        vfh[kk][s] = *reinterpret_cast<const h16x8*>(Vth[buf] + l31 * VH + 32 * kk + 16 * s + 8 * lh);
-        if constexpr (H3) vfl[kk][s] = *reinterpret_cast<const h16x8*>(Vtl[buf] + l31 * VH + 32 * kk + 16 * s + 8 * lh);
-      }
-    };
-    if constexpr (NQ == 2) {
-      load_vf(0);
-      load_vf(1);
-    }
-#pragma unroll
-    for (int h = 0; h < NQ; ++h) {
-      // ---- online softmax (lane = query; reg r of sub-tile kk <-> key
-      //      32 kk + (r&3) + 8 (r>>2) + 4 lh) ----
-      if (TAIL) {
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int j = kt + 32 * kk + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            if (j >= klen) sacc[h][kk][r] = -INFINITY;
-          }
-      }
-      float mx = fmaxf(sacc[h][0][0], sacc[h][1][0]);
-#pragma unroll
-      for (int r = 1; r < 16; ++r) mx = fmaxf(mx, fmaxf(sacc[h][0][r], sacc[h][1][r]));
-      mx = half_swap_max(mx);
-      if constexpr (LAZY) {
-        // sacc = s - m_ref + kLazyOff.  Recentre (first tile: always; later: some query of the wave
-        // has a score more than 2^(15.5 - kLazyOff) above its reference -- the scaled probability
-        // would leave fp16's range): delta moves every lane's reference to its current maximum, like
-        // the eager form does on every tile.  kLazyOff = 4 (the eager form uses 10): probabilities
-        // below 2^-18 of the row maximum go subnormal in the hi plane, an absolute error of
-        // 2^-29 of the maximum -- and a reference has 11.5 octaves of headroom before it must move.
-        constexpr float kLazyOff = 4.0f;
-        const bool first = kt == 0;
-        if (first || __builtin_amdgcn_ballot_w64(mx > 15.5f) != 0) {
-          const float delta = first ? mx - kLazyOff : fmaxf(mx - kLazyOff, 0.f);
-          const float corr = first ? 1.0f : __builtin_amdgcn_exp2f(-delta);   // o, psum are 0 on the first tile
-          psum_a[h] *= corr;
-          psum_b[h] *= corr;
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            o[h][r] *= corr;
-            negm[h][r] -= delta;
-            sacc[h][0][r] -= delta;
-            sacc[h][1][r] -= delta;
-          }
-        }
-        unsigned int ph_u[2][8], pl_u[2][8];
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-          for (int r = 0; r < 16; r += 2) {
-            f32x2 pv;
-            pv[0] = __builtin_amdgcn_exp2f(sacc[h][kk][r]);
-            pv[1] = __builtin_amdgcn_exp2f(sacc[h][kk][r + 1]);
-            psum_a[h] += pv[0];   // two plain adds (the file is built with -fno-slp-vectorize): v_pk_add_f32 issues
-            psum_b[h] += pv[1];   // slower than the pair beside MFMAs (MI355X_MICROARCH price list)
-            const unsigned int hi_u =
-                __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_pkrtz(pv[0], pv[1]));
-            ph_u[kk][r >> 1] = hi_u;
-            if constexpr (H3) {
-              unsigned int lo_u;
-              asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]\n\t"
-                  "v_fma_mixhi_f16 %0, %1, -1.0, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-                  : "=&v"(lo_u)
-                  : "v"(hi_u), "v"(pv[0]), "v"(pv[1]));
-              pl_u[kk][r >> 1] = lo_u;
-            }
-          }
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-          if constexpr (NQ == 1) {
-            if (kk == 1) __builtin_amdgcn_sched_barrier(0);
-            load_vf(kk);
-          }
-#pragma unroll
-          for (int s = 0; s < 2; ++s) {
-            const u32x4 pa = {ph_u[kk][4 * s], ph_u[kk][4 * s + 1], ph_u[kk][4 * s + 2], ph_u[kk][4 * s + 3]};
-            const h16x8 pbh = __builtin_bit_cast(h16x8, pa);
-            if constexpr (H3) {
-              const u32x4 pb = {pl_u[kk][4 * s], pl_u[kk][4 * s + 1], pl_u[kk][4 * s + 2], pl_u[kk][4 * s + 3]};
-              const h16x8 pbl = __builtin_bit_cast(h16x8, pb);
-              o[h] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vfh[kk][s], pbl, o[h], 0, 0, 0);
-              o[h] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vfl[kk][s], pbh, o[h], 0, 0, 0);
-            }
-            o[h] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vfh[kk][s], pbh, o[h], 0, 0, 0);
-          }
-        }
-        continue;
-      }
-      const float m_new = fmaxf(m_run[h], mx);
-      const float corr = __builtin_amdgcn_exp2f(m_run[h] - m_new);   // first tile: exp2(-inf) = 0
-      m_run[h] = m_new;
-      const f32x2 c2 = {corr, corr};
-      psum2[h] *= c2;
-#pragma unroll
-      for (int r = 0; r < 16; r += 2) {
-        f32x2 t = {o[h][r], o[h][r + 1]};
-        t *= c2;
-        o[h][r] = t[0];
-        o[h][r + 1] = t[1];
-      }
-      // p' = 2^10 * exp2(s - m): the 2^10 keeps small probabilities inside fp16's
-      // normal range; the row sum accumulates the same scaled values, so it
-      // cancels in the final 1/l.
-      const float mshift = m_new - 10.0f;
-      const f32x2 ms2 = {mshift, mshift};
-      unsigned int ph_u[2][8], pl_u[2][8];
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-        for (int r = 0; r < 16; r += 2) {
-          const f32x2 sv = {sacc[h][kk][r], sacc[h][kk][r + 1]};
-          const f32x2 dv = sv - ms2;                       // v_pk_add_f32
-          f32x2 pv;
-          pv[0] = __builtin_amdgcn_exp2f(dv[0]);
-          pv[1] = __builtin_amdgcn_exp2f(dv[1]);
-          psum2[h] += pv;                                  // v_pk_add_f32
-          const unsigned int hi_u =
-              __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_pkrtz(pv[0], pv[1]));
-          ph_u[kk][r >> 1] = hi_u;
-          if constexpr (H3) {
-            unsigned int lo_u;
-            asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]\n\t"
-                "v_fma_mixhi_f16 %0, %1, -1.0, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-                : "=&v"(lo_u)
-                : "v"(hi_u), "v"(pv[0]), "v"(pv[1]));
-            pl_u[kk][r >> 1] = lo_u;
-          }
-        }
-      // ---- O^T += V^T P^T ----
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          const u32x4 pa = {ph_u[kk][4 * s], ph_u[kk][4 * s + 1], ph_u[kk][4 * s + 2], ph_u[kk][4 * s + 3]};
-          const h16x8 pbh = __builtin_bit_cast(h16x8, pa);
-          if constexpr (H3) {
-            const u32x4 pb = {pl_u[kk][4 * s], pl_u[kk][4 * s + 1], pl_u[kk][4 * s + 2], pl_u[kk][4 * s + 3]};
-            const h16x8 pbl = __builtin_bit_cast(h16x8, pb);
-            o[h] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vfh[kk][s], pbl, o[h], 0, 0, 0);
-            o[h] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vfl[kk][s], pbh, o[h], 0, 0, 0);
-          }
-          o[h] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vfh[kk][s], pbh, o[h], 0, 0, 0);
-        }
-    }
-  };
-
-  // PIPE (NQ = 1, lazy softmax): the same tile as two 32-key halves whose phases are staggered inside the wave --
-  // the score MFMAs of half 1 are independent of the exponentials of half 0, and the PV MFMAs of half 0 of the
-  // exponentials of half 1, so 12 of the tile's 24 MFMAs have vector work of the same wave to run beside.  The lazy
-  // reference is checked per half; a recentring at half 1 finds the probabilities of half 0 already converted: its
-  // shift is rounded up to an integer so that they can be rescaled exactly (a power of two) in their fp16 planes.
-  auto tile_pipe = [&](int kt, int buf, auto tail_tag) {
-    constexpr bool TAIL = decltype(tail_tag)::value;
-    constexpr float kLazyOff = 4.0f;
-    h16x8 kfh[2], kfl[2], vfh[2], vfl[2];
-    auto load_kf = [&](int kk) __attribute__((always_inline)) {
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        kfh[s] = *reinterpret_cast<const h16x8*>(Kh[buf] + (32 * kk + l31) * KH + 16 * s + 8 * lh);
-        if constexpr (H3) kfl[s] = *reinterpret_cast<const h16x8*>(Kl[buf] + (32 * kk + l31) * KH + 16 * s + 8 * lh);
-      }
-    };
-    auto load_vf = [&](int kk) __attribute__((always_inline)) {
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        vfh[s] = *reinterpret_cast<const h16x8*>(Vth[buf] + l31 * VH + 32 * kk + 16 * s + 8 * lh);
-        if constexpr (H3) vfl[s] = *reinterpret_cast<const h16x8*>(Vtl[buf] + l31 * VH + 32 * kk + 16 * s + 8 * lh);
-      }
-    };
-    auto scores = [&](f32x16& acc) __attribute__((always_inline)) {
-      acc = negm[0];
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        if constexpr (H3) {
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kfh[s], ql[0][s], acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kfl[s], qh[0][s], acc, 0, 0, 0);
-        }
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kfh[s], qh[0][s], acc, 0, 0, 0);
-      }
-    };
-    auto rowmax = [&](f32x16& acc, int kk) __attribute__((always_inline)) {
-      if (TAIL) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int j = kt + 32 * kk + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          if (j >= klen) acc[r] = -INFINITY;
-        }
-      }
-      float mx = fmaxf(acc[0], acc[1]);
-#pragma unroll
-      for (int r = 2; r < 16; ++r) mx = fmaxf(mx, acc[r]);
-      return half_swap_max(mx);
-    };
-    auto convert = [&](const f32x16& acc, unsigned int (&ph)[8], unsigned int (&pl)[8]) __attribute__((always_inline)) {
-#pragma unroll
-      for (int r = 0; r < 16; r += 2) {
-        const float p0 = __builtin_amdgcn_exp2f(acc[r]), p1 = __builtin_amdgcn_exp2f(acc[r + 1]);
-        psum_a[0] += p0;
-        psum_b[0] += p1;
-        const unsigned int hi_u = __builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_pkrtz(p0, p1));
-        ph[r >> 1] = hi_u;
-        if constexpr (H3) {
-          unsigned int lo_u;
-          asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]\n\t"
-              "v_fma_mixhi_f16 %0, %1, -1.0, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]"
-              : "=&v"(lo_u)
-              : "v"(hi_u), "v"(p0), "v"(p1));
-          pl[r >> 1] = lo_u;
-        }
-      }
-    };
-    auto pv = [&](const unsigned int (&ph)[8], const unsigned int (&pl)[8]) __attribute__((always_inline)) {
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const u32x4 pa = {ph[4 * s], ph[4 * s + 1], ph[4 * s + 2], ph[4 * s + 3]};
-        const h16x8 pbh = __builtin_bit_cast(h16x8, pa);
-        if constexpr (H3) {
-          const u32x4 pb = {pl[4 * s], pl[4 * s + 1], pl[4 * s + 2], pl[4 * s + 3]};
-          const h16x8 pbl = __builtin_bit_cast(h16x8, pb);
-          o[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vfh[s], pbl, o[0], 0, 0, 0);
-          o[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vfl[s], pbh, o[0], 0, 0, 0);
-        }
-        o[0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vfh[s], pbh, o[0], 0, 0, 0);
-      }
-    };
-    // ---- half 0: scores, reference check ----
-    f32x16 s0, s1;
-    load_kf(0);
-    scores(s0);
-    const float mx0 = rowmax(s0, 0);
-    const bool first = kt == 0;
-    if (first || __builtin_amdgcn_ballot_w64(mx0 > 15.5f) != 0) {
-      const float delta = first ? mx0 - kLazyOff : fmaxf(mx0 - kLazyOff, 0.f);
-      const float corr = first ? 1.0f : __builtin_amdgcn_exp2f(-delta);   // o, psum are 0 on the first tile
-      psum_a[0] *= corr;
-      psum_b[0] *= corr;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        o[0][r] *= corr;
-        negm[0][r] -= delta;
-        s0[r] -= delta;
-      }
-    }
-    // ---- scores of half 1 beside the exponentials of half 0 ----
-    unsigned int ph0[8], pl0[8], ph1[8], pl1[8];
-    load_kf(1);
-    scores(s1);
-    convert(s0, ph0, pl0);
-    const float mx1 = rowmax(s1, 1);
-    if (__builtin_amdgcn_ballot_w64(mx1 > 15.5f) != 0) {
-      const float delta = ceilf(fmaxf(mx1 - kLazyOff, 0.f));          // integer: corr is an exact power of two
-      const float corr = __builtin_amdgcn_exp2f(-delta);
-      psum_a[0] *= corr;
-      psum_b[0] *= corr;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        o[0][r] *= corr;
-        negm[0][r] -= delta;
-        s1[r] -= delta;
-      }
-      typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
-      const _Float16 ch = (_Float16)corr;                              // below 2^-24: the old probabilities vanish
-      const h16x2 c2 = {ch, ch};
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        ph0[i] = __builtin_bit_cast(unsigned int, __builtin_bit_cast(h16x2, ph0[i]) * c2);
-        if constexpr (H3) pl0[i] = __builtin_bit_cast(unsigned int, __builtin_bit_cast(h16x2, pl0[i]) * c2);
-      }
-    }
-    // ---- PV of half 0 beside the exponentials of half 1, then PV of half 1 ----
-    load_vf(0);
-    pv(ph0, pl0);
-    convert(s1, ph1, pl1);
-    load_vf(1);
-    pv(ph1, pl1);
-  };
-
-  if (klen > 0) {
-    fetch(0);
-    stash(0);
-  }
-  __syncthreads();
-
-  int buf = 0, kt = 0;
-  for (; kt + KT2 <= klen; kt += KT2, buf ^= 1) {
-    const bool more = kt + KT2 < klen;
-    if (more) fetch(kt + KT2);
-    __builtin_amdgcn_sched_barrier(0);
-    if constexpr (PIPE) tile_pipe(kt, buf, std::false_type{});
-    else tile(kt, buf, std::false_type{});
-    __builtin_amdgcn_sched_barrier(0);
-    if (more) stash(buf ^ 1);
-    __syncthreads();
-  }
-  if (kt < klen) {
-    if constexpr (PIPE) tile_pipe(kt, buf, std::true_type{});
-    else tile(kt, buf, std::true_type{});
-  }
-
-#pragma unroll
-  for (int h = 0; h < NQ; ++h) {
-    float l_run = LAZY ? psum_a[h] + psum_b[h] : psum2[h][0] + psum2[h][1];
-    l_run += __shfl_xor(l_run, 32, 64);
-    const int qi = q0 + wave * QWN + 32 * h + l31;
-    if constexpr (LAZY) {
-      // log2 sum_j 2^(s_ij) of the query's scores (s in the kernel's base-2 units = log2(e) q.k / sqrt(d)): the
-      // probabilities above are 2^(s - m_ref + off) with negm = off - m_ref.  Handed to the backward (training).
-      if (lse_out != nullptr && qi < qlen && lh == 0)
-        lse_out[(size_t)(qbeg + qi) * nhead + head] = __builtin_amdgcn_logf(l_run) - negm[h][0];
-    }
-    if (qi < qlen) {
-      const float inv = (l_run > 0.f ? 1.0f / l_run : 0.f) * scales[3];   // 2^-ev undoes the V multiplier
-      float* op = out + (size_t)(qbeg + qi) * o_stride + hoff;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        float4 w4;
-        w4.x = o[h][4 * g + 0] * inv;
-        w4.y = o[h][4 * g + 1] * inv;
-        w4.z = o[h][4 * g + 2] * inv;
-        w4.w = o[h][4 * g + 3] * inv;
-        *reinterpret_cast<float4*>(op + 8 * g + 4 * lh) = w4;
-      }
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------------------------------
-// Round 5 core ("s" = sum-checked).  Same contract, operand planes, LDS images and staging as
-// k_attn_h3<H3, /*LAZY*/ true, /*NQ*/ 1>, with two changes that take vector instructions off the per-score path
-// (the kernel is bound by vector-instruction issue: profiles/r04_attn_counters.txt):
+// The split-fp16 core ("s" = sum-checked): 32 queries per wave, 128 per workgroup.  Two choices take vector
+// instructions off the per-score path (the kernel is bound by vector-instruction issue: profiles/r04_attn_counters.txt):
 //  * no row-maximum pass in the steady state.  The lazy reference is set from the true maximum on the first tile;
 //    afterwards a tile is exponentiated optimistically and the row sums the softmax needs anyway are the check: a
 //    lane's 32 probabilities of the tile are all below their sum, so "sum < 2^15" proves that nothing left fp16's
@@ -844,27 +356,21 @@ __global__ __launch_bounds__(256, WPS) void k_attn_h3(
 //    accumulated yet.  24 v_max + swap + compare per tile become one add and one compare.
 //  * PLO = false ("single probability plane", attention mode 3): P is carried as ONE fp16 plane (round toward
 //    zero) instead of hi + lo, O^T = (V_hi + V_lo)^T P_hi: 8 instead of 12 MFMAs for the second product and no
-//    v_fma_mix pair per probability.  The row sum is formed from the ROUNDED plane (v_dot2c_f32_f16 with a ones
-//    vector), so numerator and denominator use the same weights: the output is an exact convex combination of the
-//    value rows with weights perturbed by < 2^-10 relative each; the systematic part of the rounding cancels in
-//    1 / l, what is left is sum_j w_j delta_j (v_j - o), delta uniform over one fp16 ulp.
+//    v_fma_mix pair per probability.  The row sum is formed from the ROUNDED plane (one v_fma_mix_f32 per half), so
+//    numerator and denominator use the same weights: the output is an exact convex combination of the value rows
+//    with weights perturbed by < 2^-10 relative each; the systematic part of the rounding cancels in 1 / l, what is
+//    left is sum_j w_j delta_j (v_j - o), delta uniform over one fp16 ulp.
 //    Q K^T keeps the three-product split in every H3 mode: score errors are amplified by the exponential.
-// PRIO > 0: s_setprio PRIO around the score MFMAs (A/B switch SPR_ATTN_PRIO).
-// ABL (diagnostic builds only, -DSPR_ATTN_ABLATE; results are garbage): 1 = no fragment reads from LDS (the Q registers
-// stand in), 2 = no K / V staging (no global loads, no LDS writes), 4 = no per-tile barrier.
+// s_setprio 2 around the score MFMAs (-1.5 % in every mode).
 // ADAPT (attention mode 4, needs H3 && PLO): the lo plane of the probabilities only where it matters.  A tile is
-// "significant" for a wave when some lane holds a probability of at least 2^-7 of that lane's running row sum (the
-// maximum of the tile's hi plane: 15 v_pk_max_f16); only such tiles pay for the lo plane (32 quarter-rate
-// v_fma_mix*_f16), the f32 sums and the third MFMA of every k-step.  The other tiles run as mode 3 (row sum from the
-// rounded plane).  Every key with weight w_j >= 2^-7 is then carried with full accuracy; what the rest can contribute is
-// bounded by 2^-10 sqrt(sum w_j^2) <= 2^-10 sqrt(2^-7) = 8.6e-5 of the value spread in the worst case (128 keys
-// of exactly that weight) and is ~5e-6 for flat rows of 2 000 keys -- the peaked rows mode 3 is inaccurate on
-// (few keys with large weights) are exact here.
-// PF (round 5): fragment prefetch.  The sensitivity builds (profiles/r05_attn_ablate.txt) price the LDS fragment
-// reads at a quarter of the kernel: every group of MFMAs waits for four ds_read_b128 issued right in front of it.
-// PF = 1 issues a tile's V^T fragments (both 32-key halves) at the top of the tile -- they land under the score
-// MFMAs and the exponentials -- and the K fragments of both halves before the first score MFMA.
-template <bool H3, bool PLO, int WPS, int PRIO, int ABL = 0, bool ADAPT = false, int PF = 0>
+// "significant" for a wave when some lane holds a probability of at least sig_thr = 2^-5 (kAttnSigThr) of that lane's
+// running row sum (the maximum of the tile's hi plane: 15 v_pk_max_f16); only such tiles pay for the lo plane (32
+// quarter-rate v_fma_mix*_f16), the f32 sums and the third MFMA of every k-step.  The other tiles run as mode 3 (row
+// sum from the rounded plane).  Every key with weight w_j >= 2^-5 is then carried with full accuracy; what the rest
+// can contribute is bounded by 2^-10 sqrt(sum w_j^2) <= 2^-10 sqrt(2^-5) = 1.7e-4 of the value spread in the worst
+// case (32 keys of exactly that weight) and is ~5e-6 for flat rows of 2 000 keys -- the peaked rows mode 3 is
+// inaccurate on (few keys with large weights) are exact here.
+template <bool H3, bool PLO, int WPS, bool ADAPT = false>
 __global__ __launch_bounds__(256, WPS) void k_attn_s(
     const _Float16* __restrict__ qh_g, const _Float16* __restrict__ ql_g,
     const _Float16* __restrict__ kh_g, const _Float16* __restrict__ kl_g,
@@ -944,22 +450,14 @@ __global__ __launch_bounds__(256, WPS) void k_attn_s(
                  : "memory", "m0");
   };
   auto fetch = [&](int kt, int nbuf) {     // nbuf: the buffer tile kt will be read from
-    if constexpr (ABL & 2) return;
     const unsigned koff = (unsigned)((((size_t)head * t_total + kbeg + min(kt + skr, klen - 1)) * HD + skc) * 2);
     const unsigned voff = (unsigned)(attn_v_off(hoff + svr, (size_t)(vbeg + kt + svc), nhead * HD) * 2);
     dma16(kh_g, koff, kdst_h + (unsigned)nbuf * 4096u);
     if constexpr (H3) dma16(kl_g, koff, kdst_l + (unsigned)nbuf * 4096u);
     dma16(vth_g, voff, vdst_h + (unsigned)nbuf * 4096u);
     if constexpr (H3) dma16(vtl_g, voff, vdst_l + (unsigned)nbuf * 4096u);
-    if constexpr (ABL & 16) {   // sensitivity: the same four pieces once more
-      dma16(kh_g, koff, kdst_h + (unsigned)nbuf * 4096u);
-      dma16(kl_g, koff, kdst_l + (unsigned)nbuf * 4096u);
-      dma16(vth_g, voff, vdst_h + (unsigned)nbuf * 4096u);
-      dma16(vtl_g, voff, vdst_l + (unsigned)nbuf * 4096u);
-    }
   };
   auto stash = [&](int) {
-    if constexpr (ABL & 2) return;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's pieces of the next tile have landed
   };
 
@@ -973,48 +471,22 @@ __global__ __launch_bounds__(256, WPS) void k_attn_s(
     unsigned int ph_u[2][8], pl_u[2][8];
     float ts = 0.f;
     bool redo = false;
-    h16x8 pvh[2][2], pvl[2][2];     // PF: V^T fragments of the whole tile
-    if constexpr (PF > 0) {
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          const int vpos = l31 * KT2 + 8 * ((4 * kk + 2 * s + lh) ^ ((l31 >> 1) & 7));
-          pvh[kk][s] = *reinterpret_cast<const h16x8*>(Vth[buf] + vpos);
-          if constexpr (H3) pvl[kk][s] = *reinterpret_cast<const h16x8*>(Vtl[buf] + vpos);
-        }
-    }
     bool sigk[2] = {PLO, PLO};      // does the 32-key sub-tile carry a lo plane (ADAPT: decided per sub-tile)
     for (;;) {
       // ---- S^T = K Q^T + (off - m_ref)   (rows = keys, cols = queries) ----
-      if constexpr (PRIO > 0) __builtin_amdgcn_s_setprio(PRIO);
+      __builtin_amdgcn_s_setprio(2);
       h16x8 kfh[2][2], kfl[2][2];
       auto load_kf = [&](int kk) __attribute__((always_inline)) {
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-          if constexpr (ABL & 1) {
-            kfh[kk][s] = qh[s];
-            if constexpr (H3) kfl[kk][s] = ql[s];
-            continue;
-          }
           const int kpos = (32 * kk + l31) * HD + 8 * ((2 * s + lh) ^ ((l31 >> 2) & 3));
           kfh[kk][s] = *reinterpret_cast<const h16x8*>(Kh[buf] + kpos);
           if constexpr (H3) kfl[kk][s] = *reinterpret_cast<const h16x8*>(Kl[buf] + kpos);
-          if constexpr (ABL & 8) {    // sensitivity: the same reads once more (volatile: not merged), data unchanged
-            const h16x8 d0 = *reinterpret_cast<const volatile h16x8*>(Kh[buf ^ 1] + kpos);
-            const h16x8 d1 = *reinterpret_cast<const volatile h16x8*>(Kl[buf ^ 1] + kpos);
-            asm volatile("" ::"v"(d0), "v"(d1));
-          }
         }
       };
-      if constexpr (PF > 0) {
-        load_kf(0);
-        load_kf(1);
-        __builtin_amdgcn_sched_barrier(0);
-      }
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) {
-        if constexpr (PF == 0) load_kf(kk);
+        load_kf(kk);
         sc[kk] = negm;
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
@@ -1026,7 +498,7 @@ __global__ __launch_bounds__(256, WPS) void k_attn_s(
         }
         if (kk == 0) __builtin_amdgcn_sched_barrier(0);
       }
-      if constexpr (PRIO > 0) __builtin_amdgcn_s_setprio(0);
+      __builtin_amdgcn_s_setprio(0);
       if (TAIL) {
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk)
@@ -1109,11 +581,6 @@ __global__ __launch_bounds__(256, WPS) void k_attn_s(
         for (int r = 0; r < 16; r += 2) {
           const float p0 = __builtin_amdgcn_exp2f(sc[kk][r]);
           const float p1 = __builtin_amdgcn_exp2f(sc[kk][r + 1]);
-          if constexpr (ABL & 64) {   // sensitivity: two more exponentials per pair, results discarded
-            float e0, e1;
-            asm volatile("v_exp_f32 %0, %2\n\tv_exp_f32 %1, %3" : "=v"(e0), "=v"(e1) : "v"(sc[kk][r]), "v"(sc[kk][r + 1]));
-            asm volatile("" ::"v"(e0), "v"(e1));
-          }
           const auto hi_h = __builtin_amdgcn_cvt_pkrtz(p0, p1);
           const unsigned int hi_u = __builtin_bit_cast(unsigned int, hi_h);
           ph_u[kk][r >> 1] = hi_u;
@@ -1145,24 +612,9 @@ __global__ __launch_bounds__(256, WPS) void k_attn_s(
       h16x8 vfh[2], vfl[2];
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
-        if constexpr (ABL & 1) {
-          vfh[s] = qh[s];
-          if constexpr (H3) vfl[s] = ql[s];
-          continue;
-        }
-        if constexpr (PF > 0) {
-          vfh[s] = pvh[kk][s];
-          if constexpr (H3) vfl[s] = pvl[kk][s];
-          continue;
-        }
         const int vpos = l31 * KT2 + 8 * ((4 * kk + 2 * s + lh) ^ ((l31 >> 1) & 7));
         vfh[s] = *reinterpret_cast<const h16x8*>(Vth[buf] + vpos);
         if constexpr (H3) vfl[s] = *reinterpret_cast<const h16x8*>(Vtl[buf] + vpos);
-        if constexpr (ABL & 8) {
-          const h16x8 d0 = *reinterpret_cast<const volatile h16x8*>(Vth[buf ^ 1] + vpos);
-          const h16x8 d1 = *reinterpret_cast<const volatile h16x8*>(Vtl[buf ^ 1] + vpos);
-          asm volatile("" ::"v"(d0), "v"(d1));
-        }
       }
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
@@ -1203,15 +655,14 @@ __global__ __launch_bounds__(256, WPS) void k_attn_s(
     tile(kt, buf, std::false_type{});
     __builtin_amdgcn_sched_barrier(0);
     if (more) stash(buf ^ 1);
-    if constexpr (!(ABL & 4)) __syncthreads();
-    if constexpr (ABL & 32) __syncthreads();
+    __syncthreads();
   }
   if (kt < klen) tile(kt, buf, std::true_type{});
 
   float l_run = psum;
   l_run += __shfl_xor(l_run, 32, 64);
   const int qi = q0 + wave * 32 + l31;
-  // log2 sum_j 2^(s_ij): handed to the backward (training), as k_attn_h3's lazy form does
+  // log2 sum_j 2^(s_ij): handed to the backward (training)
   if (lse_out != nullptr && qi < qlen && lh == 0)
     lse_out[(size_t)(qbeg + qi) * nhead + head] = __builtin_amdgcn_logf(l_run) - negm[0];
   if (o_tiles != nullptr) {
@@ -1360,154 +811,29 @@ int carve(void* ws, size_t ws_bytes, int t, int nseg, int d, size_t tp, AttnPlan
   return 0;
 }
 
-int env_attn_nq() {
-  static const int nq = [] { const char* e = getenv("SPR_ATTN_NQ"); return (e != nullptr && e[0] == '2') ? 2 : 1; }();
-  return nq;
-}
-bool env_attn_lazy() {   // lazy softmax reference (k_attn_h3<*, true>) unless SPR_ATTN_LAZY=0 (A/B against the eager form)
-  static const bool lazy = [] { const char* e = getenv("SPR_ATTN_LAZY"); return e == nullptr || e[0] != '0'; }();
-  return lazy;
-}
-// does the core launched for `mode` write the per-query log-sum-exp (lse_out)?  Every lazy-softmax form does.
-bool attn_core_writes_lse(int mode) { return mode != 0 && (env_attn_nq() == 1 || env_attn_lazy()); }
+// does the core launched for `mode` write the per-query log-sum-exp (lse_out)?  k_attn_s does, k_attn does not.
+bool attn_core_writes_lse(int mode) { return mode != 0; }
 
+// attention mode 4: a tile needs the lo plane of its probabilities when one of them reaches this share of the lane's
+// running row sum (k_attn_s, ADAPT)
+constexpr float kAttnSigThr = 0x1p-5f;
+
+// modes 1 .. 4: the sum-checked core k_attn_s, one instantiation per mode.  Three waves per SIMD (168-register
+// budget); mode 4 four.
 int launch_core(const AttnPlanes& pl, int t, size_t tp, const int* cu, const int* kv_seg, int nseg,
                 int max_len_host, int nhead, float* out, int o_stride, int mode, hipStream_t stream,
                 float* lse_out = nullptr, const int* o_tiles = nullptr) {
   ProfScope prof(stream, -1, t);
-  // Default since round 4: 32 queries per wave with a 168-register budget, three waves per SIMD (147 VGPRs in split
-  // mode): 927 vs 956 us per call at the bench shape, 452 vs 458 us in mode 2.  SPR_ATTN_NQ=2 selects the 64-query /
-  // two-wave form.  (Four waves per SIMD -- 118 VGPRs in mode 2, 128 with 42 spilled registers in split mode --
-  // measured 452 and 1 171 us: occupancy is not what this kernel waits for)
-  const int nq = env_attn_nq();
-  // Round 5 default: the sum-checked core k_attn_s (no row-maximum pass; mode 3 = one probability plane).
-  // SPR_ATTN_CORE=h3 selects the round-4 kernel for A/B (modes 1 and 2 only); s_setprio 2 around the score MFMAs
-  // (-1.5 % in every mode) unless SPR_ATTN_PRIO=0.
-  static const bool core_h3 = [] { const char* e = getenv("SPR_ATTN_CORE"); return e != nullptr && e[0] == 'h'; }();
-  static const int prio = [] { const char* e = getenv("SPR_ATTN_PRIO"); return e != nullptr ? atoi(e) : 2; }();
-  if (mode >= 3 || (nq == 1 && !core_h3)) {
-    // mode 4: significance threshold 2^-SPR_ATTN_SIG of the lane's running sum (default 2^-5)
-    static const float sig = [] { const char* e = getenv("SPR_ATTN_SIG"); return ldexpf(1.0f, -(e != nullptr ? atoi(e) : 5)); }();
-    dim3 grid1(cdiv(max_len_host, QB2 / 2) * nhead * nseg);
-#define SPR_ATTN_S(H3_, PLO_, PR_)                                                                                   \
-    hipLaunchKernelGGL((k_attn_s<H3_, PLO_, 3, PR_>), grid1, dim3(256), 0, stream, pl.qh, pl.ql, pl.kh, pl.kl, pl.vth, \
-                       pl.vtl, t, (int)tp, cu, kv_seg, nseg, nhead, pl.scales, out, o_stride, lse_out, o_tiles, sig)
-#ifdef SPR_ATTN_ABLATE
-    static const int abl = [] { const char* e = getenv("SPR_ATTN_ABL"); return e != nullptr ? atoi(e) : 0; }();
-#define SPR_ATTN_SA(A_)                                                                                               \
-    hipLaunchKernelGGL((k_attn_s<true, true, 3, 2, A_>), grid1, dim3(256), 0, stream, pl.qh, pl.ql, pl.kh, pl.kl, pl.vth, \
-                       pl.vtl, t, (int)tp, cu, kv_seg, nseg, nhead, pl.scales, out, o_stride, lse_out, o_tiles, sig)
-    if (abl != 0 && mode == 1) {
-      switch (abl) {
-        case 1: SPR_ATTN_SA(1); break;
-        case 4: SPR_ATTN_SA(4); break;
-        case 8: SPR_ATTN_SA(8); break;
-        case 16: SPR_ATTN_SA(16); break;
-        case 32: SPR_ATTN_SA(32); break;
-        case 64: SPR_ATTN_SA(64); break;
-        default: SPR_ATTN_SA(7); break;
-      }
-      SPR_LAUNCH_CHECK();
-      return 0;
-    }
-#undef SPR_ATTN_SA
-#endif
-    static const int pf = [] { const char* e = getenv("SPR_ATTN_PF"); return e != nullptr ? atoi(e) : 0; }();
-    if (pf > 0 && (mode == 1 || mode == 3)) {
-      if (mode == 1)
-        hipLaunchKernelGGL((k_attn_s<true, true, 3, 2, 0, false, 1>), grid1, dim3(256), 0, stream, pl.qh, pl.ql, pl.kh, pl.kl,
-                           pl.vth, pl.vtl, t, (int)tp, cu, kv_seg, nseg, nhead, pl.scales, out, o_stride, lse_out, o_tiles, sig);
-      else
-        hipLaunchKernelGGL((k_attn_s<true, false, 3, 2, 0, false, 1>), grid1, dim3(256), 0, stream, pl.qh, pl.ql, pl.kh, pl.kl,
-                           pl.vth, pl.vtl, t, (int)tp, cu, kv_seg, nseg, nhead, pl.scales, out, o_stride, lse_out, o_tiles, sig);
-      SPR_LAUNCH_CHECK();
-      return 0;
-    }
-    if (mode == 4) {
-      static const int awps = [] { const char* e = getenv("SPR_ATTN_ADAPT_WPS"); return e != nullptr ? atoi(e) : 4; }();
-      if (awps == 3)
-        hipLaunchKernelGGL((k_attn_s<true, true, 3, 2, 0, true>), grid1, dim3(256), 0, stream, pl.qh, pl.ql, pl.kh, pl.kl, pl.vth,
-                           pl.vtl, t, (int)tp, cu, kv_seg, nseg, nhead, pl.scales, out, o_stride, lse_out, o_tiles, sig);
-      else
-      hipLaunchKernelGGL((k_attn_s<true, true, 4, 2, 0, true>), grid1, dim3(256), 0, stream, pl.qh, pl.ql, pl.kh, pl.kl, pl.vth,
-                         pl.vtl, t, (int)tp, cu, kv_seg, nseg, nhead, pl.scales, out, o_stride, lse_out, o_tiles, sig);
-    } else if (prio > 0) {
-      if (mode == 2) SPR_ATTN_S(false, false, 2);
-      else if (mode == 3) SPR_ATTN_S(true, false, 2);
-      else SPR_ATTN_S(true, true, 2);
-    } else {
-      if (mode == 2) SPR_ATTN_S(false, false, 0);
-      else if (mode == 3) SPR_ATTN_S(true, false, 0);
-      else SPR_ATTN_S(true, true, 0);
-    }
+  dim3 grid(cdiv(max_len_host, QB) * nhead * nseg);
+#define SPR_ATTN_S(H3_, PLO_, WPS_, ADAPT_)                                                                          \
+  hipLaunchKernelGGL((k_attn_s<H3_, PLO_, WPS_, ADAPT_>), grid, dim3(256), 0, stream, pl.qh, pl.ql, pl.kh, pl.kl,   \
+                     pl.vth, pl.vtl, t, (int)tp, cu, kv_seg, nseg, nhead, pl.scales, out, o_stride, lse_out, o_tiles, \
+                     kAttnSigThr)
+  if (mode == 4) SPR_ATTN_S(true, true, 4, true);
+  else if (mode == 3) SPR_ATTN_S(true, false, 3, false);
+  else if (mode == 2) SPR_ATTN_S(false, false, 3, false);
+  else SPR_ATTN_S(true, true, 3, false);
 #undef SPR_ATTN_S
-    SPR_LAUNCH_CHECK();
-    return 0;
-  }
-  SPR_REQUIRE(o_tiles == nullptr, "attention core: tiled output needs the k_attn_s core (attn_core_tiled_ok)");
-  if (nq == 1) {
-    dim3 grid1(cdiv(max_len_host, QB2 / 2) * nhead * nseg);
-    // experiment switch (profiles/r04_attn_counters.txt): the same kernel compiled for FOUR waves per SIMD
-    static const bool wps4 = [] { const char* e = getenv("SPR_ATTN_WPS"); return e != nullptr && e[0] == '4'; }();
-    if (wps4) {
-      if (mode == 2)
-        hipLaunchKernelGGL((k_attn_h3<false, true, 1, 4>), grid1, dim3(256), 0, stream, pl.qh, pl.ql, pl.kh, pl.kl, pl.vth,
-                           pl.vtl, t, (int)tp, cu, kv_seg, nseg, nhead, pl.scales, out, o_stride, lse_out);
-      else
-        hipLaunchKernelGGL((k_attn_h3<true, true, 1, 4>), grid1, dim3(256), 0, stream, pl.qh, pl.ql, pl.kh, pl.kl, pl.vth,
-                           pl.vtl, t, (int)tp, cu, kv_seg, nseg, nhead, pl.scales, out, o_stride, lse_out);
-      SPR_LAUNCH_CHECK();
-      return 0;
-    }
-    static const int pipe = [] { const char* e = getenv("SPR_ATTN_PIPE"); return e != nullptr ? atoi(e) : 0; }();
-    if (pipe == 1) {        // experiment: the two key halves of a tile staggered inside the wave (tile_pipe)
-      if (mode == 2)
-        hipLaunchKernelGGL((k_attn_h3<false, true, 1, 3, true>), grid1, dim3(256), 0, stream, pl.qh, pl.ql, pl.kh, pl.kl,
-                           pl.vth, pl.vtl, t, (int)tp, cu, kv_seg, nseg, nhead, pl.scales, out, o_stride, lse_out);
-      else
-        hipLaunchKernelGGL((k_attn_h3<true, true, 1, 3, true>), grid1, dim3(256), 0, stream, pl.qh, pl.ql, pl.kh, pl.kl,
-                           pl.vth, pl.vtl, t, (int)tp, cu, kv_seg, nseg, nhead, pl.scales, out, o_stride, lse_out);
-      SPR_LAUNCH_CHECK();
-      return 0;
-    }
-    if (pipe == 2) {        // the same at two waves per SIMD (256 registers)
-      if (mode == 2)
-        hipLaunchKernelGGL((k_attn_h3<false, true, 1, 2, true>), grid1, dim3(256), 0, stream, pl.qh, pl.ql, pl.kh, pl.kl,
-                           pl.vth, pl.vtl, t, (int)tp, cu, kv_seg, nseg, nhead, pl.scales, out, o_stride, lse_out);
-      else
-        hipLaunchKernelGGL((k_attn_h3<true, true, 1, 2, true>), grid1, dim3(256), 0, stream, pl.qh, pl.ql, pl.kh, pl.kl,
-                           pl.vth, pl.vtl, t, (int)tp, cu, kv_seg, nseg, nhead, pl.scales, out, o_stride, lse_out);
-      SPR_LAUNCH_CHECK();
-      return 0;
-    }
-    if (mode == 2)
-      hipLaunchKernelGGL((k_attn_h3<false, true, 1, 3>), grid1, dim3(256), 0, stream, pl.qh, pl.ql, pl.kh, pl.kl, pl.vth,
-                         pl.vtl, t, (int)tp, cu, kv_seg, nseg, nhead, pl.scales, out, o_stride, lse_out);
-    else
-      hipLaunchKernelGGL((k_attn_h3<true, true, 1, 3>), grid1, dim3(256), 0, stream, pl.qh, pl.ql, pl.kh, pl.kl, pl.vth,
-                         pl.vtl, t, (int)tp, cu, kv_seg, nseg, nhead, pl.scales, out, o_stride, lse_out);
-    SPR_LAUNCH_CHECK();
-    return 0;
-  }
-  dim3 grid(cdiv(max_len_host, QB2) * nhead * nseg);
-  // lazy softmax reference (k_attn_h3<*, true>) unless SPR_ATTN_LAZY=0 (A/B timing against the eager form)
-  const bool lazy = env_attn_lazy();
-  if (lazy) {
-    if (mode == 2)
-      hipLaunchKernelGGL((k_attn_h3<false, true>), grid, dim3(256), 0, stream, pl.qh, pl.ql, pl.kh, pl.kl, pl.vth,
-                         pl.vtl, t, (int)tp, cu, kv_seg, nseg, nhead, pl.scales, out, o_stride, lse_out);
-    else
-      hipLaunchKernelGGL((k_attn_h3<true, true>), grid, dim3(256), 0, stream, pl.qh, pl.ql, pl.kh, pl.kl, pl.vth,
-                         pl.vtl, t, (int)tp, cu, kv_seg, nseg, nhead, pl.scales, out, o_stride, lse_out);
-    SPR_LAUNCH_CHECK();
-    return 0;
-  }
-  if (mode == 2)
-    hipLaunchKernelGGL(k_attn_h3<false>, grid, dim3(256), 0, stream, pl.qh, pl.ql, pl.kh, pl.kl, pl.vth, pl.vtl,
-                       t, (int)tp, cu, kv_seg, nseg, nhead, pl.scales, out, o_stride, lse_out);
-  else
-    hipLaunchKernelGGL(k_attn_h3<true>, grid, dim3(256), 0, stream, pl.qh, pl.ql, pl.kh, pl.kl, pl.vth, pl.vtl,
-                       t, (int)tp, cu, kv_seg, nseg, nhead, pl.scales, out, o_stride, lse_out);
   SPR_LAUNCH_CHECK();
   return 0;
 }
@@ -1562,8 +888,8 @@ extern "C" int spr_attn_varlen_fwd(const float* q, int q_stride, const float* k,
 }
 
 // The same, additionally handing out lse [t, nhead] = log2 sum_j 2^(log2(e) q_i.k_j scale) per query and head for
-// spr_attn_varlen_bwd_lse (the backward then skips its own pass over the keys).  *lse_written = 0 when the
-// configured core does not produce it (exact-f32 mode, the eager-softmax experiment): lse is then untouched.
+// spr_attn_varlen_bwd_lse (the backward then skips its own pass over the keys).  *lse_written = 0 in
+// exact-f32 mode (attention mode 0, whose core does not produce it): lse is then untouched.
 extern "C" int spr_attn_varlen_fwd_lse(const float* q, int q_stride, const float* k, int k_stride, const float* v,
                                        int v_stride, const int* cu, const int* kv_seg, int t, int nseg,
                                        int max_len_host, int nhead, int head_dim, float scale, float* out, int o_stride,
@@ -1657,7 +983,7 @@ extern "C" int spr_attn_inproj_varlen_fwd_r(const float* x_qk, const float* x_v,
     return spr_attn_varlen_fwd(qkv, 3 * d, qkv + d, 3 * d, qkv + 2 * d, 3 * d, cu, kv_seg, t, nseg,
                                max_len_host, nhead, head_dim, scale, out, o_stride, ws, planes_bytes, stream_);
   }
-  SPR_REQUIRE((long)cdiv(max_len_host, QB2 / 2) * nhead * nseg < (1l << 31), "attention: grid too large");
+  SPR_REQUIRE((long)cdiv(max_len_host, QB) * nhead * nseg < (1l << 31), "attention: grid too large");
   pl.cu = cu;
   pl.nseg = nseg;
   pl.t_total = t;
@@ -1723,16 +1049,11 @@ int spr::attn_zero_gaps(const AttnPlanes& pl, int d, hipStream_t stream) {
   SPR_LAUNCH_CHECK();
   return 0;
 }
-// does launch_core() pick k_attn_s (the only core that can write the chains' tiled output) for `mode`?
-bool spr::attn_core_tiled_ok(int mode) {
-  static const bool core_h3 = [] { const char* e = getenv("SPR_ATTN_CORE"); return e != nullptr && e[0] == 'h'; }();
-  return mode >= 3 || ((mode == 1 || mode == 2) && env_attn_nq() == 1 && !core_h3);
-}
 int spr::attn_core_on_planes(const AttnPlanes& pl, const int* kv_seg, int max_len_host, int nhead, float* out,
                              int o_stride, int mode, hipStream_t stream, const int* o_tiles) {
   SPR_REQUIRE(mode >= 1 && mode <= 4, "attention core on planes: mode must be 1 .. 4 (got %d)", mode);
-  SPR_REQUIRE((long)cdiv(max_len_host, QB2 / 2) * nhead * pl.nseg < (1l << 31), "attention: grid too large");
-  SPR_REQUIRE(o_tiles == nullptr || (nhead == 8 && attn_core_tiled_ok(mode)), "attention core: tiled output unavailable");
+  SPR_REQUIRE((long)cdiv(max_len_host, QB) * nhead * pl.nseg < (1l << 31), "attention: grid too large");
+  SPR_REQUIRE(o_tiles == nullptr || nhead == 8, "attention core: tiled output needs 8 heads (got %d)", nhead);
   return launch_core(pl, pl.t_total, (size_t)pl.tp, pl.cu, kv_seg, pl.nseg, max_len_host, nhead, out, o_stride, mode,
                      stream, nullptr, o_tiles);
 }

@@ -1034,9 +1034,8 @@ static int attn_varlen_bwd_impl(const float* q, int q_stride, const float* k, in
     hipLaunchKernelGGL(k_attn_bwd_scales, dim3(1), dim3(256), 0, stream, parts, scales);
     constexpr size_t dkv_lds = (size_t)NB * DKV_BUF_HALVES * 2 + 4 * BT * sizeof(float);
     static_assert(dkv_lds >= sizeof(float) * 2 * 2 * 16 * 64, "the final reduction reuses the tile buffers");
-    static const bool no_planes = getenv("SPR_ATTN_BWD_PLANES") != nullptr && getenv("SPR_ATTN_BWD_PLANES")[0] == '0';
     BwdPlanes pl{};
-    if (!no_planes && ws_bytes >= spr_attn_bwd_workspace_bytes2(t, nseg, nhead)) {
+    if (ws_bytes >= spr_attn_bwd_workspace_bytes2(t, nseg, nhead)) {
       // operand planes written once (k_attn_bwd_pack), staged by 16-byte copies
       const int tc = attn_bwd_tc(t, nseg);
       _Float16** r[4] = {pl.rq, pl.rk, pl.rv, pl.ro};

@@ -35,16 +35,15 @@ struct AttnPlanes {
 // Shared by attention.hip and xenc.hip (the fused cross-encoder chains write the planes themselves):
 // padded column count of the transposed V planes, carving of the planes out of a workspace of
 // spr_attn_workspace_bytes(t, nseg, nhead, 32) bytes, zeroing of the gap / tail columns, and the
-// attention core over planes that are already in place.  `mode`: 1 split-fp16, 2 single pass.
+// attention core over planes that are already in place.  `mode`: 1 .. 4 (spr_set_attn_mode).
 size_t attn_tp(int t, int nseg);
 int attn_carve_planes(void* ws, size_t ws_bytes, int t, int nseg, int d, AttnPlanes& pl);
 int attn_zero_gaps(const AttnPlanes& pl, int d, hipStream_t stream);
 // o_tiles != nullptr: `out` is a TILED token tensor of the fused chains (xenc.hip; o_tiles[s] = chain tiles in front
-// of segment s); only where attn_core_tiled_ok(mode).
+// of segment s; 8 heads).
 int attn_core_on_planes(const AttnPlanes& pl, const int* kv_seg, int max_len_host, int nhead, float* out,
                         int o_stride, int mode, hipStream_t stream, const int* o_tiles = nullptr);
-bool attn_core_tiled_ok(int mode);
-int attn_mode();   // 1 split-fp16, 0 exact f32, 2 single-pass fp16
+int attn_mode();   // spr_set_attn_mode: 0 exact f32, 1 split-fp16, 2 single-pass fp16, 3 one probability plane, 4 adaptive
 
 // Split-fp16 GEMM  planes <- x [m, k] . w [n, k]^T + bias  for the n output
 // features [f0, f0 + n) of the packed in-projection (0..255 = Q, 256..511 = K,

@@ -491,8 +491,7 @@ extern "C" int spr_bgemm(const float* A, const float* B, float* C, const void* d
   SPR_REQUIRE(nbatch <= 65535, "bgemm: too many batches (%d)", nbatch);
   // tile shape by the largest batch entry: big square outputs -> 128 x 128, tall d_head-wide ones
   // -> 128 x 32, everything small stays on the 64 x 64 kernel (all three accumulate identically)
-  static const int force = getenv("SPR_BGEMM_TILE") ? atoi(getenv("SPR_BGEMM_TILE")) : 0;   // A/B switch: 64 = old kernel
-  if (force != 64 && max_m >= 128 && max_n >= 96) {
+  if (max_m >= 128 && max_n >= 96) {
     const long tiles = (long)cdiv(max_m, 128) * cdiv(max_n, 128);
     SPR_REQUIRE(tiles < (1l << 31), "bgemm: grid too large");
     if (tiles * nbatch < 160) {
@@ -508,7 +507,7 @@ extern "C" int spr_bgemm(const float* A, const float* B, float* C, const void* d
     SPR_LAUNCH_CHECK();
     return 0;
   }
-  if (force != 64 && max_m >= 128 && max_n <= 32) {
+  if (max_m >= 128 && max_n <= 32) {
     const long tiles = (long)cdiv(max_m, 128) * cdiv(max_n, 32);
     SPR_REQUIRE(tiles < (1l << 31), "bgemm: grid too large");
     hipLaunchKernelGGL((k_bgemm_f32_t<128, 32>), dim3((unsigned)tiles, nbatch), dim3(256), 0, stream, A, B, C,

@@ -855,8 +855,7 @@ int launch_gemm(const float* x, int m, int k, const float* w, int n, const float
     SPR_REQUIRE(a_parts != nullptr && w_parts != nullptr, "linear: split-fp16 mode needs the absmax partials");
     // LDS bytes of a BM x BN tile's slab (hi + lo planes of both operands)
     auto lds = [](int bm, int bn) { return (size_t)(bm + bn) * spr::HS * 2 * sizeof(_Float16); };
-    static const bool use_p = [] { const char* e = getenv("SPR_GEMM_PERSIST"); return e == nullptr || e[0] != '0'; }();
-    if (use_p && !RES && ACT <= SPR_ACT_SIGMOID && n >= 256 && k == 256 && m >= 1024 && m < 32768) {
+    if (!RES && ACT <= SPR_ACT_SIGMOID && n >= 256 && k == 256 && m >= 1024 && m < 32768) {
       // persistent 128x256 tiles (k_gemm_nt_h3p): for a few thousand rows the finer tiles fill the
       // chip better (27 vs 43 us at 5 000 x 256 x 300); at 60 k rows both forms sit on the CU's
       // vector-memory throughput and the 256x256 tiles move fewer operand bytes

@@ -1426,9 +1426,8 @@ extern "C" int spr_match_sinkhorn(const float* feat, int d, const float* xyz, co
     }
     const dim3 grow(cdiv((long)c.max_n * 64, 256), np), gcol(cdiv(c.max_m, 64), np);
     // the dual softmax's row / column pass and the first Sinkhorn iteration's in two sweeps instead of four
-    // (k_row_lse_v2 / k_col_lse_v2: same bits); SPR_MATCH_NO_FUSE=1 = the separate launches
-    static const bool no_fuse = [] { const char* e = getenv("SPR_MATCH_NO_FUSE"); return e != nullptr && e[0] == '1'; }();
-    const bool fuse = !no_fuse && n_iters >= 1 && c.max_m <= 2048 && c.min_m >= 4;
+    // (k_row_lse_v2 / k_col_lse_v2: same bits); the separate launches for the shapes the fused sweeps do not take
+    const bool fuse = n_iters >= 1 && c.max_m <= 2048 && c.min_m >= 4;
     if (fuse) {
       if (c.max_m <= 1024)
         hipLaunchKernelGGL(k_row_lse_v2<4>, grow, dim3(256), 0, stream, c.mat, pg, row_lse, u, (const float*)v, (const float*)aff);

@@ -927,8 +927,8 @@ int table_build(const float* s_xyz, const int* s_cu, int ns, int nb, float radiu
   return 0;
 }
 
-// algo: 0 = thread per query (k_scan_table + rank sort), 1 = wave per query (k_knn_wave), -1 = the library's default
-// (0, or 1 under SPR_NBR_ALGO=wave).  Rows are identical either way.
+// algo: 1 = wave per query (k_knn_wave), anything else = thread per query (k_scan_table + rank sort).  Rows are
+// identical either way.
 int table_query(const float* q_xyz, const int* q_cu, int nq, int self, int ns, int nb, float radius, int limit,
                 int slot, const void* blob, int* out_idx, int* max_count, void* ws, size_t ws_bytes,
                 hipStream_t stream, int algo = -1) {
@@ -937,8 +937,7 @@ int table_query(const float* q_xyz, const int* q_cu, int nq, int self, int ns, i
   // limits up to kRegRows: the scratch rows are capped there and sorted in registers (k_sort_rows_reg); a query with
   // more candidates in range than the cap takes the scan's second (histogram-cut) pass, as before beyond 2 * limit
   constexpr int kRegRows = 64;
-  static const bool reg_sort = [] { const char* e = getenv("SPR_NBR_LDS_SORT"); return e == nullptr || e[0] != '1'; }();
-  const bool use_reg = reg_sort && limit <= kRegRows;
+  const bool use_reg = limit <= kRegRows;
   const int rcap = use_reg ? min(nbr_row_cap(limit), kRegRows) : nbr_row_cap(limit);
   unsigned long long* tmp_key = w.take<unsigned long long>((size_t)nq * rcap);
   int* kept = w.take<int>((size_t)nq);
@@ -946,13 +945,7 @@ int table_query(const float* q_xyz, const int* q_cu, int nq, int self, int ns, i
   SPR_REQUIRE(qid != nullptr, "radius query: workspace carve failed");
   const float r2 = radius * radius;  // neighbors.cpp:226 (float32)
   const float inv_cell = 1.0f / (radius * (1.0f + 1.0f / 256.0f));
-  // SPR_NBR_ALGO=wave: the one-pass wave-per-query selection (k_knn_wave) instead of scan + rank sort
-  static const int env_algo = [] {
-    const char* e = getenv("SPR_NBR_ALGO");
-    return e == nullptr ? -1 : (e[0] == 'w' ? 1 : 0);     // "wave" / "scan": force one of them (A/B)
-  }();
-  const bool knn_wave = env_algo >= 0 ? env_algo == 1 : algo == 1;
-  if (knn_wave) {
+  if (algo == 1) {   // the one-pass wave-per-query selection instead of scan + rank sort
     SPR_HIP_CHECK(hipMemsetAsync(qid, 0, sizeof(int), stream));
     const int nblk = min(cdiv(nq, 4 * kKnnChunk), 8 * device_cu_count());
     if (limit <= 64)

@@ -63,7 +63,7 @@ struct Workspace {
 };
 
 // ---- optional per-launch HIP-event timing (bench.py roofline legs) ----------
-// code: fused KPConv = cin * 100000 + cout; attention core (k_attn_h3 / k_attn) = -1.
+// code: fused KPConv = cin * 100000 + cout; attention core (k_attn_s) = -1.
 // Records are appended under a mutex (launches may come from several host
 // threads, one per stream); see spr_prof_enable / spr_prof_read in include/spr.h.
 bool prof_enabled();

@@ -292,14 +292,14 @@ __device__ unsigned long long g_xenc_stamps[64 * 64];
 #endif
 
 // TAIL: 0 = x_out only, 1 = LayerNorm -> ln_out (final norm), 2 = LayerNorm + pos -> in-projection -> planes
-// Layouts: HEAD chains read x_g TILED and o_g tiled (o_tiled) or row-major; the prologue (!HEAD) reads x_g and pos_g
+// Layouts: HEAD chains read x_g and o_g TILED; the prologue (!HEAD) reads x_g and pos_g
 // row-major and writes their tiled copies to xo_g and pos_t; xo_g is tiled unless TAIL == 0 (then it is the stack's
 // row-major output); pos_t is read by every HEAD chain with an in-projection tail; ln_g is row-major.
 template <bool HEAD, bool FFN, int TAIL>
 __global__ __launch_bounds__(256, 1) void k_xenc_chain(ChainConsts c, const float* o_g, const float* x_g, float* xo_g,
                                                        const float* pos_g, float* pos_t, float* ln_g, AttnPlanes pl, int T,
                                                        int ntiles, int* tile_ctr, const int* __restrict__ tfirst_g,
-                                                       int o_tiled, int stamp_on) {
+                                                       int stamp_on) {
   constexpr bool XO_TILED = TAIL != 0;
   extern __shared__ __align__(16) unsigned char ring[];
   float* tab = reinterpret_cast<float*>(ring + XSLOTS * XCHUNK);
@@ -502,8 +502,7 @@ __global__ __launch_bounds__(256, 1) void k_xenc_chain(ChainConsts c, const floa
 
     if constexpr (HEAD) {
       // ---- x' = o Wo^T + bo + x ------------------------------------------------------------------
-      if (o_tiled) load_t(o_g, wb4, lane, v);
-      else load_c(o_g, tokc, h, v);
+      load_t(o_g, wb4, lane, v);
 #pragma unroll
       for (int b = 0; b < 8; ++b) split_block(v[b], c.o_scale, ph[2 * b], pw[2 * b], ph[2 * b + 1], pw[2 * b + 1]);
 #pragma unroll
@@ -888,7 +887,7 @@ __global__ void k_xenc_tiles(const int* __restrict__ cu, int nseg, int* __restri
 
 template <bool HEAD, bool FFN, int TAIL>
 int launch_chain(const ChainConsts& c, const float* o, const float* x, float* xo, const float* pos, float* pos_t,
-                 float* ln, const AttnPlanes& pl, int T, int* tile_ctr, const int* tfirst, int o_tiled,
+                 float* ln, const AttnPlanes& pl, int T, int* tile_ctr, const int* tfirst,
                  hipStream_t stream) {
   auto kern = k_xenc_chain<HEAD, FFN, TAIL>;
   const size_t lds = xenc_lds_bytes(32 * c.nf, pl.nseg);
@@ -909,7 +908,7 @@ int launch_chain(const ChainConsts& c, const float* o, const float* x, float* xo
   }
 #endif
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, c, o, x, xo, pos, pos_t, ln, pl, T, ntiles, tile_ctr, tfirst,
-                     o_tiled, stamp_on);
+                     stamp_on);
   SPR_LAUNCH_CHECK();
   return 0;
 }
@@ -1185,7 +1184,7 @@ extern "C" int spr_xenc_forward(const void* plan_host, const float* x, const flo
   SPR_REQUIRE(ws != nullptr && ws_bytes >= spr_xenc_workspace_bytes(t, nseg), "xenc_forward: workspace too small");
   const int mode = attn_mode();
   SPR_REQUIRE(gemm_mode() == 1 && (mode >= 1 && mode <= 4),
-              "xenc_forward: needs the split-fp16 arithmetic (gemm mode 1, attention mode 1 or 2)");
+              "xenc_forward: needs the split-fp16 arithmetic (gemm mode 1, attention mode 1 .. 4)");
   const size_t planes_bytes = spr_attn_workspace_bytes(t, nseg, 8, 32);
   AttnPlanes pl{};
   if (int rc = attn_carve_planes(ws, planes_bytes, t, nseg, XD, pl)) return rc;
@@ -1195,7 +1194,7 @@ extern "C" int spr_xenc_forward(const void* plan_host, const float* x, const flo
   pl.tp = (int)attn_tp(t, nseg);
   const size_t act = xenc_tiled_bytes(t, nseg);
   SPR_REQUIRE(act < (1ull << 32), "xenc_forward: too many tokens");
-  float* obuf = (float*)((char*)ws + planes_bytes);            // attention output (tiled when the core can write tiles)
+  float* obuf = (float*)((char*)ws + planes_bytes);            // attention output, tiled
   float* xa = (float*)((char*)ws + planes_bytes + act);        // residual stream, tiled, ping
   float* xb = (float*)((char*)ws + planes_bytes + 2 * act);    //                          pong
   float* pos_t = (float*)((char*)ws + planes_bytes + 3 * act); // positional embedding, tiled
@@ -1205,28 +1204,26 @@ extern "C" int spr_xenc_forward(const void* plan_host, const float* x, const flo
   hipLaunchKernelGGL(k_xenc_tiles, dim3(1), dim3(64), 0, stream, cu, nseg, tfirst);
   if (int rc = attn_zero_gaps(pl, XD, stream)) return rc;
   const int L = plan->n_layers;
-  const int o_tiled = attn_core_tiled_ok(mode) ? 1 : 0;
-  const int* o_tiles = o_tiled ? tfirst : nullptr;
   // prologue: planes of layer 0's self attention + the tiled copies of x (into xb) and pos
-  if (int rc = launch_chain<false, false, 2>(plan->prologue, nullptr, x, xb, pos, pos_t, nullptr, pl, t, ctr++, tfirst, 0, stream)) return rc;
+  if (int rc = launch_chain<false, false, 2>(plan->prologue, nullptr, x, xb, pos, pos_t, nullptr, pl, t, ctr++, tfirst, stream)) return rc;
   const float* cur = xb;
   float* nxt = xa;
   for (int l = 0; l < L; ++l) {
     pl.scales = plan->scales_self[l];
-    if (int rc = attn_core_on_planes(pl, kv_self, max_len_host, 8, obuf, XD, mode, stream, o_tiles)) return rc;
-    if (int rc = launch_chain<true, false, 2>(plan->a[l], obuf, cur, nxt, nullptr, pos_t, nullptr, pl, t, ctr++, tfirst, o_tiled, stream)) return rc;
+    if (int rc = attn_core_on_planes(pl, kv_self, max_len_host, 8, obuf, XD, mode, stream, tfirst)) return rc;
+    if (int rc = launch_chain<true, false, 2>(plan->a[l], obuf, cur, nxt, nullptr, pos_t, nullptr, pl, t, ctr++, tfirst, stream)) return rc;
     cur = nxt;
     nxt = (nxt == xa) ? xb : xa;
     pl.scales = plan->scales_cross[l];
-    if (int rc = attn_core_on_planes(pl, kv_cross, max_len_host, 8, obuf, XD, mode, stream, o_tiles)) return rc;
+    if (int rc = attn_core_on_planes(pl, kv_cross, max_len_host, 8, obuf, XD, mode, stream, tfirst)) return rc;
     if (l + 1 < L) {
-      if (int rc = launch_chain<true, true, 2>(plan->b[l], obuf, cur, nxt, nullptr, pos_t, nullptr, pl, t, ctr++, tfirst, o_tiled, stream)) return rc;
+      if (int rc = launch_chain<true, true, 2>(plan->b[l], obuf, cur, nxt, nullptr, pos_t, nullptr, pl, t, ctr++, tfirst, stream)) return rc;
       cur = nxt;
       nxt = (nxt == xa) ? xb : xa;
     } else if (plan->has_final) {
-      if (int rc = launch_chain<true, true, 1>(plan->b[l], obuf, cur, nxt, nullptr, pos_t, out, pl, t, ctr++, tfirst, o_tiled, stream)) return rc;
+      if (int rc = launch_chain<true, true, 1>(plan->b[l], obuf, cur, nxt, nullptr, pos_t, out, pl, t, ctr++, tfirst, stream)) return rc;
     } else {
-      if (int rc = launch_chain<true, true, 0>(plan->b[l], obuf, cur, out, nullptr, pos_t, nullptr, pl, t, ctr++, tfirst, o_tiled, stream)) return rc;
+      if (int rc = launch_chain<true, true, 0>(plan->b[l], obuf, cur, out, nullptr, pos_t, nullptr, pl, t, ctr++, tfirst, stream)) return rc;
     }
   }
   return 0;

@@ -18,7 +18,6 @@ preprocessor consume, instead of two hand-rolled loops with running state.
 from dataclasses import dataclass
 from typing import List
 
-import os
 import torch
 import torch.nn as nn
 
@@ -183,9 +182,6 @@ class _IndexList(list):
         return (self._conv(i) for i in range(len(self)))
 
 
-_POOL_ORDER = os.environ.get("SPR_NO_POOL_ORDER", "") == ""   # A/B switch: max-pool in storage order
-
-
 class Preprocessor(nn.Module):
     """Builds the KPConv pyramid metadata for a list of clouds.
 
@@ -287,7 +283,7 @@ class Preprocessor(nn.Module):
                 pool = search((l, 'pool'), sub_points, sub_cu, points, cu, lv.radius, lv.limit)
                 # spatial walk order of the level's pooled queries (kpconv_blocks.max_pool): one key + sort pass here,
                 # off the main stream, saves the max-pool most of its re-reads of the finer level's features
-                meta['pool_order'].append(ops.cell_order(sub_points, sub_cu, dl) if _POOL_ORDER else None)
+                meta['pool_order'].append(ops.cell_order(sub_points, sub_cu, dl))
                 if self.compute_upsamples:
                     up = search((l, 'up'), points, cu, sub_points, sub_cu, 2 * lv.radius, lv.limit)
             if not lv.down:

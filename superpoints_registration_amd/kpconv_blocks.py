@@ -15,12 +15,8 @@ import torch.nn as nn
 from torch.nn.init import kaiming_uniform_
 from torch.nn.parameter import Parameter
 
-import os
-
 from . import _concurrency, ops
 from .kernel_points import load_kernels
-
-_NORM_FOLD = os.environ.get("SPR_NO_NORM_FOLD", "0") != "1"   # experiment switch (A/B timing)
 
 
 def _cu_of(batch, layer_ind):
@@ -311,8 +307,8 @@ class ResnetBottleneckBlock(nn.Module):
         x = self.KPConv(q_pts, s_pts, neighb_inds, x)
         # Inference with the fused tail: the norm + LeakyReLU behind the KPConv runs while the tail stages its
         # tiles (ops.block_tail(xa_stats=...)): only the statistics passes remain of it, the normalised tensor is
-        # never written or read back (SPR_NO_NORM_FOLD=1: the separate operator, for A/B).
-        fold = fused and self.use_bn and _NORM_FOLD
+        # never written or read back.
+        fold = fused and self.use_bn
         conv_stats = None
         if fold:
             conv_stats = ops.instnorm_stats(x, cu_post, eps=self.batch_norm_conv.eps, max_len=ml_post)

@@ -6,7 +6,6 @@ tensors -- a CPU tensor raises, there is no fallback.
 """
 import ctypes
 import math
-import os
 import threading
 from typing import Optional, Sequence, Tuple
 
@@ -60,12 +59,7 @@ def _set_range(t: torch.Tensor, parts: torch.Tensor, n: int, guard=None) -> None
         t._spr_range = (parts, int(n), t._version, t.data_ptr(), _range_epoch[0], guard)
 
 
-_HANDOVER = os.environ.get("SPR_NO_RANGE_HANDOVER", "0") != "1"   # experiment switch (A/B timing)
-
-
 def _get_range(t):
-    if not _HANDOVER:
-        return None, 0
     r = getattr(t, '_spr_range', None)
     if r is None or r[2] != t._version or r[3] != t.data_ptr() or r[4] != _range_epoch[0]:
         return None, 0
@@ -117,8 +111,6 @@ def _static_range(w: torch.Tensor):
     """Range partials of a tensor that rarely changes (weights): measured once per (storage,
     version) with spr_absmax and kept on the tensor like a published range -- an optimizer step
     bumps the version counter and the next call measures again."""
-    if not _HANDOVER:
-        return None, 0
     r, n = _get_range(w)
     if r is not None:
         return r, n
@@ -140,8 +132,6 @@ def prime_weight_ranges(params) -> int:
     (spr_absmax_multi) and attaches them like _static_range would: after an optimizer step every weight's version
     counter has moved, and ~150 separate measuring launches (16 us each) opened every training forward.  Returns the
     number of tensors measured."""
-    if not _HANDOVER:
-        return 0
     todo = [p for p in params if isinstance(p, torch.Tensor) and p.is_cuda and p.dtype == torch.float32
             and p.dim() >= 2 and p.is_contiguous() and p.numel() > 0 and _get_range(p)[0] is None]
     if not todo:
@@ -183,7 +173,7 @@ def ensure_range(t: torch.Tensor) -> torch.Tensor:
     """Measures max |t| once (spr_absmax) and publishes it on the tensor like a producer kernel would, unless a
     valid range is already attached: a gradient that feeds two products (dX and dW of a projection) is then
     scanned once instead of once per product."""
-    if not _HANDOVER or t.dim() != 2 or not t.is_contiguous() or _get_range(t)[0] is not None:
+    if t.dim() != 2 or not t.is_contiguous() or _get_range(t)[0] is not None:
         return t
     L = _lib.lib()
     n = L.spr_range_parts()
@@ -371,16 +361,11 @@ def kpconv(q_pts, s_pts, nbr, x, weights, kernel_points, kp_extent: float, rows_
     return kpconv_raw(q_pts, s_pts, nbr, x, weights, kernel_points, kp_extent, rows_sorted, impl)
 
 
-_KP_IMPL_AB = os.environ.get("SPR_KPCONV_IMPL")   # experiment switch (A/B timing): "2" = round-2 streamed kernel
-
-
 def kpconv_raw(q_pts, s_pts, nbr, x, weights, kernel_points, kp_extent: float, rows_sorted: bool = False,
                impl: int = 0, order: Optional[torch.Tensor] = None) -> torch.Tensor:
     """order: optional int32 permutation of the queries (the tile walk of the ring kernel, e.g. a
     spatial order so that the workgroups of an XCD share neighbour rows in its L2); the output is
     bitwise independent of it."""
-    if _KP_IMPL_AB is not None and impl == 0:
-        impl = int(_KP_IMPL_AB)
     q_pts = _dev(q_pts, "q_pts", torch.float32)
     s_pts = _dev(s_pts, "s_pts", torch.float32)
     x = _dev(x, "x", torch.float32)
@@ -496,7 +481,7 @@ def instnorm_raw(x, cu, eps: float = 1e-5, norm: bool = True, add=None, slope: f
     max_len = n if max_len is None else max(1, min(int(max_len), n))
     ws = _workspace(L.spr_instnorm_workspace_bytes(max_len, nb, c), x.device)
     cnt = _STREAM_SLOTS
-    rng = _zero_slots(cnt, x.device) if _HANDOVER else None
+    rng = _zero_slots(cnt, x.device)
     _lib.check(L.spr_instnorm_r(_ptr(x), _ptr(cu), n, nb, max_len, c, float(eps), int(bool(norm)), _ptr(add),
                                 float(slope), _ptr(out), _ptr(rng), cnt, _ptr(ws), ws.numel(), _stream(x)),
                "spr_instnorm_r")
@@ -505,13 +490,10 @@ def instnorm_raw(x, cu, eps: float = 1e-5, norm: bool = True, add=None, slope: f
     return out
 
 
-_BLOCK_TAIL = os.environ.get("SPR_NO_BLOCK_TAIL", "0") != "1"   # experiment switch (A/B timing)
-
-
 def block_tail_tile_rows(ka: int, kb: int, n_out: int) -> int:
     """Rows per statistics tile of the fused block tail for this shape; 0 = no kernel (use the separate
-    operators).  Also 0 outside the split-fp16 product mode and under SPR_NO_BLOCK_TAIL=1."""
-    if not _BLOCK_TAIL or _modes["gemm"] != 1:
+    operators).  Also 0 outside the split-fp16 product mode."""
+    if _modes["gemm"] != 1:
         return 0
     return int(_lib.lib().spr_block_tail_tile_rows(int(ka), int(kb), int(n_out)))
 
@@ -606,7 +588,7 @@ def block_tail(xa, wa, cu, xb=None, wb=None, add=None, eps: float = 1e-5, slope:
         xbr, xbr_n = _get_range(xb)
         wbr, wbr_n = _static_range(wb)
     cnt = _STREAM_SLOTS
-    rng = _zero_slots(cnt, xa.device) if _HANDOVER else None
+    rng = _zero_slots(cnt, xa.device)
     if xa_stats is not None:
         mean, rstd = xa_stats
         assert mean.shape == (nb, ka) and rstd.shape == (nb, ka) and mean.is_contiguous() and rstd.is_contiguous()
@@ -659,7 +641,7 @@ def maxpool_raw(x, idx, order=None) -> torch.Tensor:
     out = torch.empty((nq, c), dtype=torch.float32, device=x.device)
     L = _lib.lib()
     cnt = _STREAM_SLOTS
-    rng = _zero_slots(cnt, x.device) if _HANDOVER else None
+    rng = _zero_slots(cnt, x.device)
     if order is not None:
         if order.dtype != torch.int32 or order.numel() != nq or not order.is_contiguous():
             raise ValueError("maxpool: order must be a contiguous int32 permutation of the query rows")
@@ -709,7 +691,11 @@ def linear_raw(x, weight, bias=None, residual=None, act: int = ACT_NONE) -> torc
     return out
 
 
-_modes = {"gemm": 1, "attn": 1}   # host mirror of the library's arithmetic switches
+# the attention arithmetic a fresh process runs (csrc/attention.hip, g_attn_mode): split-fp16 scores, split-fp16
+# probabilities where a 32-key block holds a weight of at least 2^-5 of the running row sum, one rounded plane elsewhere
+DEFAULT_ATTN_MODE = 4
+
+_modes = {"gemm": 1, "attn": DEFAULT_ATTN_MODE}   # host mirror of the library's arithmetic switches
 
 
 def set_gemm_mode(mode: int) -> None:
@@ -851,8 +837,6 @@ def attention_bwd(q, k, v, out, dout, cu, kv_seg_host, max_len: int, nhead: int,
 def inproj_prepare(w_in: torch.Tensor):
     """Weight-side inputs of the fused in-projection (max |w| partials + row L1 norms), measured
     once per weight version and cached on the tensor like _static_range."""
-    if not _HANDOVER:
-        return None
     r = getattr(w_in, '_spr_inproj', None)
     if r is not None and r[1] == w_in._version and r[2] == w_in.data_ptr() and r[3] == _range_epoch[0]:
         r[4].acquire()
@@ -898,7 +882,6 @@ def attention_inproj(x_qk, x_v, w_in, b_in, cu, kv_seg, max_len: int, nhead: int
 
 
 # ---- fused cross-encoder stack (csrc/xenc.hip) ---------------------------------------------------
-_XENC_ON = os.environ.get("SPR_NO_XENC", "0") != "1"   # experiment switch (A/B against the per-operator route)
 _xenc_lock = threading.Lock()
 XENC_PTRS_PER_LAYER = 18                                # SPR_XENC_PTRS_PER_LAYER of include/spr.h
 
@@ -925,7 +908,7 @@ def _no_plan():
 
 
 def xenc_available() -> bool:
-    return _XENC_ON and _modes["gemm"] == 1 and _modes["attn"] in (1, 2, 3, 4)
+    return _modes["gemm"] == 1 and _modes["attn"] in (1, 2, 3, 4)
 
 
 def xenc_prepare(layer_params, layer_eps, final, nhead: int, d_ff: int, pos_bound: float, cached=None) -> XencPlan:
@@ -977,16 +960,11 @@ def xenc_forward(plan: XencPlan, x, pos, cu, seg_self, seg_cross, max_len: int) 
     return out
 
 
-# the attention arithmetic a fresh process runs (csrc/attention.hip, g_attn_mode): split-fp16 scores, split-fp16
-# probabilities where a 32-key block holds a weight of at least 2^-5 of the running row sum, one rounded plane elsewhere
-DEFAULT_ATTN_MODE = 4
-
-
 def set_attn_mode(mode: int) -> None:
-    """1 = split-fp16 MFMA (default), 0 = exact f32 MFMA, 2 = single-pass fp16 MFMA, 3 = split-fp16 scores with ONE
-    probability plane (weights rounded to 11 bits, row sum from the rounded plane), 4 = as 1 with the lo plane of the
-    probabilities only on tiles that hold a weight of at least 2^-7 of the running row sum (csrc/attention.hip,
-    k_attn_s; accuracy table in DESIGN.md section 4)."""
+    """4 = split-fp16 MFMA with the lo plane of the probabilities only on tiles that hold a weight of at least 2^-5 of
+    the running row sum (default, DEFAULT_ATTN_MODE), 1 = split-fp16 MFMA everywhere, 0 = exact f32 MFMA, 2 =
+    single-pass fp16 MFMA, 3 = split-fp16 scores with ONE probability plane (weights rounded to 11 bits, row sum from
+    the rounded plane) (csrc/attention.hip, k_attn_s; accuracy table in DESIGN.md section 4)."""
     _lib.check(_lib.lib().spr_set_attn_mode(int(mode)), "spr_set_attn_mode")
     _modes["attn"] = int(mode)
 
