@@ -372,6 +372,30 @@ int spr_attn_inproj_varlen_fwd(const float* x_qk, const float* x_v, int t,
                                float scale, float* out, int o_stride, void* ws,
                                size_t ws_bytes, void* stream);
 
+/* ---- a9, analysis: the attention maps of the varlen core ------------------------------------
+ * Replaces the weights nn.MultiheadAttention returns with need_weights=True at the four calls per
+ * layer of TransformerCrossEncoderLayer (transformers.py:198-227 pre-norm, :133-165 post-norm), which
+ * the reference keeps in satt_weights / xatt_weights (:179-180, :242-243) for get_attentions (:61-82):
+ *   P_h[i, j] = softmax_j(scale q_i,h . k_j,h) for the queries of segment s over the keys of segment
+ *   kv_seg[s]; per_head = 0 writes the mean over the heads (the reference's default), 1 every head.
+ * Own split-fp16 Q / K planes and fp32 row statistics: the result does not depend on spr_set_attn_mode,
+ * and two calls on the same inputs are bitwise equal.  Rows sum to 1.
+ *   q, k: [t, *] f32 views, row strides q_stride / k_stride (multiples of 4 floats, 16-byte aligned rows),
+ *   head h in columns [h*32, (h+1)*32); cu [nseg+1], kv_seg [nseg] as for spr_attn_varlen_fwd;
+ *   max_len_host >= every segment length.
+ *   place [nseg][5] int64 (device): {element offset into out, row stride, head stride, rows, cols} of
+ *   segment s.  Its rows x cols entries (per head) are ALL written: the Lq x Lk block of probabilities in
+ *   the top-left corner, exact zeros elsewhere (padded query rows and key columns), nothing outside.
+ *   rows / cols <= max_rows_host / max_cols_host (they size the grid).  This fills the reference's
+ *   padded (B, Ls, Ls), (B, Ls, Lt) and (B, H, L, S) tensors in place in one call.
+ *   ws: spr_attn_probs_workspace_bytes(t, nhead, head_dim) bytes (0 for bad sizes).  head_dim must be 32.
+ */
+size_t spr_attn_probs_workspace_bytes(int t, int nhead, int head_dim);
+int spr_attn_probs(const float* q, int q_stride, const float* k, int k_stride, const int* cu,
+                   const int* kv_seg, int t, int nseg, int max_len_host, int nhead, int head_dim,
+                   float scale, int per_head, float* out, const long long* place, int max_rows_host,
+                   int max_cols_host, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- a9, fused: the whole cross-encoder stack of an inference forward -----------------------
  * Replaces TransformerCrossEncoder.forward (models/transformer/transformers.py:45-80) over
  * TransformerCrossEncoderLayer.forward_pre (:184-245) for the configuration every shipped experiment

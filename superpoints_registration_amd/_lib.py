@@ -84,6 +84,9 @@ SIGNATURES = {
                                      _vp, _sz, _vp]),
     "spr_attn_varlen_bwd_lse": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i,
                                      _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "spr_attn_probs_workspace_bytes": (_sz, [_i, _i, _i]),
+    "spr_attn_probs": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _i, _i, _vp, _sz,
+                            _vp]),
     "spr_attn_bwd_workspace_bytes": (_sz, [_i, _i]),
     "spr_attn_bwd_workspace_bytes2": (_sz, [_i, _i, _i]),
     "spr_attn_varlen_bwd": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f,

@@ -794,6 +794,67 @@ def attention_raw(q, k, v, cu, kv_seg, max_len: int, nhead: int, out=None, want_
     return out
 
 
+def attention_probs(q, k, cu, kv_seg, max_len: int, nhead: int, average: bool = True, out=None, place=None,
+                    max_rows: Optional[int] = None, max_cols: Optional[int] = None) -> torch.Tensor:
+    """The softmax attention maps of the varlen core (spr_attn_probs): softmax_j(q_i,h . k_j,h / sqrt(32)) for the
+    queries of segment s over the keys of segment kv_seg[s], averaged over the heads (average=True, what
+    nn.MultiheadAttention returns by default) or per head.  q, k: [T, nhead*32] views as for attention().
+    Always detached (the maps are not differentiable); independent of set_attn_mode.
+
+    Without `out`: a zero-padded [nseg, max_len, max_len] (or [nseg, nhead, max_len, max_len]) tensor.
+    With `out`: any float32 device tensor, and `place` = int64 [nseg, 5] rows {element offset into out, row
+    stride, head stride, rows, cols} (host or device; max_rows / max_cols = the largest rows / cols, required for a
+    device `place`).  Every segment's rows x cols entries are written -- the probabilities in the top-left Lq x Lk
+    corner, exact zeros elsewhere -- and nothing else of `out`."""
+    for t, nm in ((q, "q"), (k, "k")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"attention_probs: {nm} must be a tensor on the MI355X device; the HIP path has no "
+                               "CPU fallback")
+        if t.dtype != torch.float32 or t.stride(1) != 1:
+            raise RuntimeError(f"attention_probs: {nm} must be float32 with unit inner stride")
+    q, k = q.detach(), k.detach()
+    T, d = q.shape
+    hd = d // nhead
+    cu = _dev(cu, "cu", torch.int32)
+    kv_seg = _dev(kv_seg, "kv_seg", torch.int32)
+    nseg = cu.numel() - 1
+    L = int(max_len)
+    if out is None:
+        if place is not None:
+            raise RuntimeError("attention_probs: `place` needs `out`")
+        shape = (nseg, L, L) if average else (nseg, nhead, L, L)
+        out = torch.empty(shape, dtype=torch.float32, device=q.device)
+        per = L * L * (1 if average else nhead)
+        pl = np.zeros((nseg, 5), dtype=np.int64)
+        pl[:, 0] = np.arange(nseg, dtype=np.int64) * per
+        pl[:, 1], pl[:, 2], pl[:, 3], pl[:, 4] = L, L * L, L, L
+        place, max_rows, max_cols = pl, L, L
+    else:
+        if not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous():
+            raise RuntimeError("attention_probs: out must be a contiguous float32 device tensor")
+        if place is None:
+            raise RuntimeError("attention_probs: `out` needs `place`")
+    if isinstance(place, np.ndarray) or (isinstance(place, torch.Tensor) and not place.is_cuda):
+        pl = np.asarray(place.cpu().numpy() if isinstance(place, torch.Tensor) else place, dtype=np.int64)
+        if pl.shape != (nseg, 5):
+            raise RuntimeError(f"attention_probs: place must be [nseg={nseg}, 5] (got {pl.shape})")
+        nh = 1 if average else nhead
+        last = pl[:, 0] + (nh - 1) * pl[:, 2] + (pl[:, 3] - 1) * pl[:, 1] + pl[:, 4]
+        if (pl[:, 0] < 0).any() or (pl[:, 3] < 1).any() or (pl[:, 4] < 1).any() or (pl[:, 4] > pl[:, 1]).any() \
+                or int(last.max()) > out.numel():
+            raise RuntimeError("attention_probs: place describes entries outside `out`")
+        max_rows, max_cols = int(pl[:, 3].max()), int(pl[:, 4].max())
+        place = torch.from_numpy(pl).to(q.device)
+    elif max_rows is None or max_cols is None:
+        raise RuntimeError("attention_probs: a device `place` needs max_rows and max_cols")
+    Lb = _lib.lib()
+    ws = _workspace(Lb.spr_attn_probs_workspace_bytes(T, nhead, hd), q.device)
+    _lib.check(Lb.spr_attn_probs(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(cu), _ptr(kv_seg), T, nseg, L,
+                                 nhead, hd, 1.0 / math.sqrt(hd), 0 if average else 1, _ptr(out), _ptr(place),
+                                 int(max_rows), int(max_cols), _ptr(ws), ws.numel(), _stream(q)), "spr_attn_probs")
+    return out
+
+
 _seg_perm_cache = {}
 
 

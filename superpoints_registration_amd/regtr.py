@@ -9,6 +9,10 @@ Differences by design (documented in DESIGN.md):
     no per-pair Python loop in the matching head;
   * `attn` (the dense N x M dual-softmax matrices) is not materialised; the
     entry is a list of None unless `return_attn=True`;
+  * the cross-encoder's attention maps (transformers.py:61-82) are recorded only with
+    `RegTR(cfg, record_attn=True)`: the encoder then runs operator by operator (not the fused
+    chains) and `model.transformer_encoder.get_attentions()` returns the reference's stacked
+    (num_layers, B, L, S) maps, padded to the longest src / tgt cloud with zeros;
   * the config-off refinements of softmax_correlation (ratio test, median threshold, overlap
     weighting, top-k pruning, LGR, RANSAC -- qk_regtr_full.py:370-421, :465-556) are available
     on the inference path (`_refined_pose`); the two dead "affinity" switches
@@ -59,7 +63,7 @@ def _meta_tensors(meta):
 
 class RegTR(nn.Module):
     def __init__(self, cfg, *args, compute_upsamples=True, order=ops.ORDER_REFERENCE,
-                 return_attn=False, **kwargs):
+                 return_attn=False, record_attn=False, **kwargs):
         super().__init__()
         self.cfg = cfg
         self.return_attn = return_attn
@@ -89,6 +93,8 @@ class RegTR(nn.Module):
         encoder_norm = nn.LayerNorm(cfg.d_embed) if cfg.pre_norm else None
         self.transformer_encoder = TransformerCrossEncoder(encoder_layer, cfg.num_encoder_layers,
                                                            encoder_norm, return_intermediate=False)
+        # opt-in: keep the cross-encoder's attention maps (transformer_encoder.get_attentions())
+        self.transformer_encoder.record_attn = record_attn
         self.beta = nn.Parameter(torch.tensor(1.0))
         self.alpha = nn.Parameter(torch.tensor(1.0))
         self.overlap_predictor = nn.Linear(cfg.d_embed, 1)

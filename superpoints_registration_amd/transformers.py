@@ -14,11 +14,17 @@ Two entry points:
   * forward(src, tgt, ..., src_key_padding_mask, ...)  the reference signature
     (padded (L,B,D) in, (1,L,B,D) out) for drop-in use;
   * forward_packed(x, cu, ...)  the native packed path RegTR uses.
+
+Attention maps (transformers.py:61-82, :179-180, :242-243) are recorded only when
+TransformerCrossEncoder.record_attn is True (off by default): each layer then keeps
+satt_weights / xatt_weights with the reference's padded shapes, written by the
+spr_attn_probs kernel, and get_attentions() stacks them.
 """
 import copy
 import math
 from typing import Optional
 
+import numpy as np
 import torch
 from torch import nn, Tensor
 
@@ -59,6 +65,52 @@ def _pack(padded: Tensor, key_padding_mask: Optional[Tensor]):
         lens = (~key_padding_mask).sum(dim=1).tolist()
     seqs = [padded[:lens[b], b, :] for b in range(B)]
     return torch.cat(seqs, dim=0).contiguous(), lens
+
+
+class AttnLayout:
+    """Where one recorded forward puts the attention maps of clouds stacked [src_0..src_{B-1}, tgt_0..tgt_{B-1}]
+    (self kv map = identity, cross kv map = the partner cloud, as make_segments builds them): the reference's
+    padded (B, Ls, Ls) / (B, Lt, Lt) self maps and (B, Ls, Lt) / (B, Lt, Ls) cross maps, each pair carved out of
+    one buffer, described per segment for ops.attention_probs."""
+
+    def __init__(self, lens, pad, device):
+        if len(lens) % 2:
+            raise RuntimeError("attention recording needs the segments [src_0..src_{B-1}, tgt_0..tgt_{B-1}]")
+        B = len(lens) // 2
+        Ls, Lt = pad if pad is not None else (max(lens[:B]), max(lens[B:]))
+        self.B, self.Ls, self.Lt = B, int(Ls), int(Lt)
+        b = np.arange(B, dtype=np.int64)
+
+        def place(ra, ca, rb, cb):
+            # segment b: ra x ca entries at b ra ca; segment B + b: rb x cb entries behind all of those
+            pl = np.zeros((2 * B, 5), dtype=np.int64)
+            pl[:B, 0], pl[B:, 0] = b * ra * ca, B * ra * ca + b * rb * cb
+            pl[:B, 1], pl[:B, 3], pl[:B, 4] = ca, ra, ca
+            pl[B:, 1], pl[B:, 3], pl[B:, 4] = cb, rb, cb
+            return torch.from_numpy(pl).to(device)
+
+        Ls, Lt = self.Ls, self.Lt
+        self.place_self, self.place_cross = place(Ls, Ls, Lt, Lt), place(Ls, Lt, Lt, Ls)
+        self.n_self, self.n_cross = B * (Ls * Ls + Lt * Lt), 2 * B * Ls * Lt
+        self.max_rc = max(Ls, Lt)     # largest rows / cols of any segment (sizes the kernel's grid)
+        self.device = device
+
+    @staticmethod
+    def of(cu, seg_host, pad=None):
+        lens = list(seg_host[0]) if seg_host is not None else (cu[1:] - cu[:-1]).tolist()
+        return AttnLayout([int(n) for n in lens], pad, cu.device)
+
+    def buffers(self):
+        return (torch.empty(self.n_self, dtype=torch.float32, device=self.device),
+                torch.empty(self.n_cross, dtype=torch.float32, device=self.device))
+
+    def split_self(self, buf):
+        B, Ls, Lt = self.B, self.Ls, self.Lt
+        return buf[:B * Ls * Ls].view(B, Ls, Ls), buf[B * Ls * Ls:].view(B, Lt, Lt)
+
+    def split_cross(self, buf):
+        B, Ls, Lt = self.B, self.Ls, self.Lt
+        return buf[:B * Ls * Lt].view(B, Ls, Lt), buf[B * Ls * Lt:].view(B, Lt, Ls)
 
 
 def _unpack(packed: Tensor, lens, L: int):
@@ -102,14 +154,18 @@ class TransformerCrossEncoderLayer(nn.Module):
         self.normalize_before = normalize_before
         self.sa_val_has_pos_emb = sa_val_has_pos_emb
         self.ca_val_has_pos_emb = ca_val_has_pos_emb
-        self.satt_weights, self.xatt_weights = None, None  # never materialised here
+        # (src, tgt) attention maps of the last forward with record_attn (TransformerCrossEncoder.record_attn)
+        self.satt_weights, self.xatt_weights = None, None
+        self.record_attn = False
 
     # -- one MHA over packed tokens: in_proj GEMM, attention core, out_proj GEMM (+ residual)
-    def _mha(self, mha: nn.MultiheadAttention, qk_in, v_in, cu, kv_seg, max_len, residual, seg_host=None):
+    # rec: (maps buffer, placement, max rows / cols) -- recording forces the operator branch (q and k materialised)
+    # and adds the map kernel behind the attention core
+    def _mha(self, mha: nn.MultiheadAttention, qk_in, v_in, cu, kv_seg, max_len, residual, seg_host=None, rec=None):
         d = self.d_model
         W, b = mha.in_proj_weight, mha.in_proj_bias
         training = torch.is_grad_enabled() and (qk_in.requires_grad or W.requires_grad)
-        if d == 256 and not training:
+        if d == 256 and not training and rec is None:
             # in-projection GEMM writes the attention operand planes directly (inference path)
             o = ops.attention_inproj(qk_in, v_in, W.detach(), b.detach(), cu, kv_seg, max_len, self.nhead,
                                      w_prep=ops.inproj_prepare(W))   # cached on the parameter object
@@ -123,6 +179,10 @@ class TransformerCrossEncoderLayer(nn.Module):
                 v = ops.linear(v_in, W[2 * d:], b[2 * d:])
             lens_host, kv_host = seg_host if seg_host is not None else (None, None)
             o = ops.attention(q, k, v, cu, kv_seg, max_len, self.nhead, lens_host=lens_host, kv_seg_host=kv_host)
+            if rec is not None:
+                buf, place, mx = rec
+                ops.attention_probs(q, k, cu, kv_seg, max_len, self.nhead, out=buf, place=place, max_rows=mx,
+                                    max_cols=mx)
         return ops.linear(o, mha.out_proj.weight, mha.out_proj.bias, residual=residual)
 
     def _ln(self, norm: nn.LayerNorm, x, pos, need_plain):
@@ -130,21 +190,29 @@ class TransformerCrossEncoderLayer(nn.Module):
                                         pos=pos, want_norm=need_plain or pos is None)
         return plain, (with_pos if pos is not None else plain)
 
-    def forward_packed(self, x, cu, seg_self, seg_cross, max_len, pos=None, seg_host=None):
+    def forward_packed(self, x, cu, seg_self, seg_cross, max_len, pos=None, seg_host=None, attn_layout=None):
         """x: [T, d] packed tokens of all 2B clouds; returns the updated tokens.
         Pre-norm (transformers.py:184-245) or post-norm (:124-182).  seg_host: optional
-        (lens, self map, cross map) host lists -- spares the attention backward a device read."""
+        (lens, self map, cross map) host lists -- spares the attention backward a device read.
+        With record_attn the layer keeps its attention maps in satt_weights / xatt_weights (attn_layout:
+        an AttnLayout shared by the stack; made here from the segment lengths if None)."""
         sh_self = (seg_host[0], seg_host[1]) if seg_host is not None else None
         sh_cross = (seg_host[0], seg_host[2]) if seg_host is not None else None
+        rec_s = rec_x = None
+        if self.record_attn:
+            lay = attn_layout if attn_layout is not None else AttnLayout.of(cu, seg_host)
+            buf_s, buf_x = lay.buffers()
+            rec_s, rec_x = (buf_s, lay.place_self, lay.max_rc), (buf_x, lay.place_cross, lay.max_rc)
+            self.satt_weights, self.xatt_weights = lay.split_self(buf_s), lay.split_cross(buf_x)
         if self.normalize_before:
             # self attention (same weights for src and tgt clouds)
             x2, x2p = self._ln(self.norm1, x, pos, need_plain=not self.sa_val_has_pos_emb)
             x = self._mha(self.self_attn, x2p, x2p if self.sa_val_has_pos_emb else x2, cu, seg_self,
-                          max_len, residual=x, seg_host=sh_self)
+                          max_len, residual=x, seg_host=sh_self, rec=rec_s)
             # cross attention (keys/values from the partner cloud)
             x2, x2p = self._ln(self.norm2, x, pos, need_plain=not self.ca_val_has_pos_emb)
             x = self._mha(self.multihead_attn, x2p, x2p if self.ca_val_has_pos_emb else x2, cu,
-                          seg_cross, max_len, residual=x, seg_host=sh_cross)
+                          seg_cross, max_len, residual=x, seg_host=sh_cross, rec=rec_x)
             # feed forward
             x2, _ = self._ln(self.norm3, x, None, need_plain=True)
             h = ops.linear(x2, self.linear1.weight, self.linear1.bias, act=ops.ACT_RELU)
@@ -153,11 +221,11 @@ class TransformerCrossEncoderLayer(nn.Module):
         # post-norm
         xp = x + pos if pos is not None else x
         y = self._mha(self.self_attn, xp, xp if self.sa_val_has_pos_emb else x, cu, seg_self, max_len,
-                      residual=x, seg_host=sh_self)
+                      residual=x, seg_host=sh_self, rec=rec_s)
         x, _ = self._ln(self.norm1, y, None, True)
         xp = x + pos if pos is not None else x
         y = self._mha(self.multihead_attn, xp, xp if self.ca_val_has_pos_emb else x, cu, seg_cross,
-                      max_len, residual=x, seg_host=sh_cross)
+                      max_len, residual=x, seg_host=sh_cross, rec=rec_x)
         x, _ = self._ln(self.norm2, y, None, True)
         h = ops.linear(x, self.linear1.weight, self.linear1.bias, act=ops.ACT_RELU)
         y = ops.linear(h, self.linear2.weight, self.linear2.bias, residual=x)
@@ -192,6 +260,31 @@ class TransformerCrossEncoder(nn.Module):
         self.num_layers = num_layers
         self.norm = norm
         self.return_intermediate = return_intermediate
+        self.record_attn = False
+
+    @property
+    def record_attn(self) -> bool:
+        """Opt-in: keep every layer's attention maps (get_attentions).  Forces the per-operator route."""
+        return self._record_attn
+
+    @record_attn.setter
+    def record_attn(self, on: bool) -> None:
+        self._record_attn = bool(on)
+        for layer in self.layers:
+            layer.record_attn = self._record_attn
+
+    def get_attentions(self):
+        """transformers.py:61-82: ((src_satt, tgt_satt), (src_xatt, tgt_xatt)) of the last forward, each stacked to
+        (num_layers, B, L, S) -- self (B, Ls, Ls) / (B, Lt, Lt), cross (B, Ls, Lt) / (B, Lt, Ls), averaged over the
+        heads.  Padded query rows and key columns are 0."""
+        if any(l.satt_weights is None or l.xatt_weights is None for l in self.layers):
+            raise RuntimeError("get_attentions: no attention maps recorded -- set record_attn = True (RegTR(cfg, "
+                               "record_attn=True)) and run a forward first")
+        ss = torch.stack([l.satt_weights[0] for l in self.layers])
+        ts = torch.stack([l.satt_weights[1] for l in self.layers])
+        sx = torch.stack([l.xatt_weights[0] for l in self.layers])
+        tx = torch.stack([l.xatt_weights[1] for l in self.layers])
+        return (ss, ts), (sx, tx)
 
     # -- fused stack (csrc/xenc.hip): two attention cores + two row-chain kernels per layer ---------
     def _xenc_eligible(self, x, pos, pos_bound, nseg: int = 0) -> bool:
@@ -225,14 +318,21 @@ class TransformerCrossEncoder(nn.Module):
         self._spr_xenc = plan
         return plan
 
-    def forward_packed(self, x, cu, seg_self, seg_cross, max_len, pos=None, seg_host=None, pos_bound=None):
+    def forward_packed(self, x, cu, seg_self, seg_cross, max_len, pos=None, seg_host=None, pos_bound=None,
+                       attn_pad=None):
         """pos_bound: an upper bound of max |pos| the caller guarantees (1.0 for the sine embedding).  With it
         (and the shipped layer configuration, inference) the stack runs as the fused chains of csrc/xenc.hip;
-        without it operator by operator."""
-        if self._xenc_eligible(x, pos, pos_bound, int(cu.numel()) - 1):
+        without it operator by operator.  record_attn: operator by operator, every layer keeping its maps
+        (attn_pad = (Ls, Lt) padded lengths; default the longest src / tgt cloud)."""
+        if not self.record_attn:
+            for layer in self.layers:
+                layer.satt_weights = layer.xatt_weights = None
+        if not self.record_attn and self._xenc_eligible(x, pos, pos_bound, int(cu.numel()) - 1):
             return ops.xenc_forward(self._xenc_plan(float(pos_bound)), x, pos, cu, seg_self, seg_cross, max_len)
+        lay = AttnLayout.of(cu, seg_host, attn_pad) if self.record_attn else None
         for layer in self.layers:
-            x = layer.forward_packed(x, cu, seg_self, seg_cross, max_len, pos=pos, seg_host=seg_host)
+            x = layer.forward_packed(x, cu, seg_self, seg_cross, max_len, pos=pos, seg_host=seg_host,
+                                     attn_layout=lay)
         if self.norm is not None:
             x, _ = ops.layernorm(x, self.norm.weight, self.norm.bias, self.norm.eps)
         return x
@@ -253,6 +353,6 @@ class TransformerCrossEncoder(nn.Module):
             tpp, _ = _pack(tgt_pos, tgt_key_padding_mask)
             pos = torch.cat([spp, tpp], dim=0)
         cu, seg_self, seg_cross, max_len = make_segments(slens, tlens, x.device)
-        y = self.forward_packed(x, cu, seg_self, seg_cross, max_len, pos=pos)
+        y = self.forward_packed(x, cu, seg_self, seg_cross, max_len, pos=pos, attn_pad=(Ls, Lt))
         ns = sum(slens)
         return _unpack(y[:ns], slens, Ls).unsqueeze(0), _unpack(y[ns:], tlens, Lt).unsqueeze(0)
