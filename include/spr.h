@@ -603,8 +603,11 @@ int spr_sum_scaled(const float* values, int n, float scale, float* out,
  * spr_layernorm_bwd / spr_instnorm_bwd / spr_maxpool_bwd / spr_scatter_rows_add: gradients of
  *   spr_layernorm (both outputs), spr_instnorm (incl. fused add + LeakyReLU), spr_maxpool_gather,
  *   spr_gather_rows.
- * spr_kpconv_weighted_features: recomputes wf[n,p,c] = sum_k infl[n,p,k] x[idx[n,k],c]
- *   (kpconv_blocks.py:394) and the neighbour count (:409-411); spr_kpconv_bwd_dx scatters
+ * spr_kpconv_weighted_features_f: recomputes wf[n,p,c] = sum_k infl[n,p,k] x[idx[n,k],c]
+ *   (kpconv_blocks.py:394) and the neighbour count (:409-411) from the per-support flags the
+ *   forward computes (same kernel, same summation order; ws: spr_kpconv_weighted_features_workspace_bytes(ns)).
+ *   spr_kpconv_weighted_features (no workspace) sums each row in an order of its own: on a row whose feature sum
+ *   is ~0 its count can differ from the forward's -- kept for existing callers only.  spr_kpconv_bwd_dx scatters
  *   d wf back to d x.  Together with two spr_bgemm calls = KPConv backward.
  * spr_softmax_rows / spr_softmax_bwd_rows: row softmax of per-batch matrices (located by
  *   c_off, m rows, n columns of the same descriptor records) and its backward -- the
@@ -651,6 +654,11 @@ int spr_kpconv_weighted_features(const float* q_xyz, int nq, const float* s_xyz,
                                  const int* nbr, int nbr_stride, int kmax, const float* x, int cin,
                                  const float* kernel_points, int n_kp, float kp_extent,
                                  float* wf, float* cnt, void* stream);
+int spr_kpconv_weighted_features_f(const float* q_xyz, int nq, const float* s_xyz, int ns,
+                                   const int* nbr, int nbr_stride, int kmax, const float* x, int cin,
+                                   const float* kernel_points, int n_kp, float kp_extent,
+                                   float* wf, float* cnt, void* ws, size_t ws_bytes, void* stream);
+size_t spr_kpconv_weighted_features_workspace_bytes(int ns);
 int spr_kpconv_bwd_dx(const float* q_xyz, int nq, const float* s_xyz, int ns, const int* nbr,
                       int nbr_stride, int kmax, int cin, const float* kernel_points, int n_kp,
                       float kp_extent, const float* dwf, float* dx, void* ws, size_t ws_bytes,

@@ -133,7 +133,9 @@ SIGNATURES = {
     "spr_scatter_workspace_bytes": (_sz, [_l, _i]),
     "spr_maxpool_bwd": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "spr_scatter_rows_add": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "spr_kpconv_weighted_features_workspace_bytes": (_sz, [_i]),
     "spr_kpconv_weighted_features": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _f, _vp, _vp, _vp]),
+    "spr_kpconv_weighted_features_f": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _f, _vp, _vp, _vp, _sz, _vp]),
     "spr_kpconv_bwd_dx": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _f, _vp, _vp, _vp, _sz, _vp]),
     "spr_kpconv_bwd_dx_r": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _f, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
     "spr_softmax_rows": (_i, [_vp, _vp, _i, _i, _vp]),

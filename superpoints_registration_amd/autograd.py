@@ -209,10 +209,12 @@ class KPConvFn(torch.autograd.Function):
         xd = x.detach().contiguous()
         wf = torch.empty((nq, n_kp * cin), dtype=torch.float32, device=x.device)
         cnt = torch.empty((nq,), dtype=torch.float32, device=x.device)
-        _lib.check(L.spr_kpconv_weighted_features(_ops._ptr(q_pts), nq, _ops._ptr(s_pts), ns, _ops._ptr(nbr32), int(stride),
+        ws = _ops._workspace(L.spr_kpconv_weighted_features_workspace_bytes(ns), x.device)
+        _lib.check(L.spr_kpconv_weighted_features_f(_ops._ptr(q_pts), nq, _ops._ptr(s_pts), ns, _ops._ptr(nbr32), int(stride),
                                                   kmax, _ops._ptr(xd), cin, _ops._ptr(kp.detach().contiguous()), n_kp,
-                                                  ctx.kp_extent, _ops._ptr(wf), _ops._ptr(cnt), _ops._stream(x)),
-                   "spr_kpconv_weighted_features")
+                                                  ctx.kp_extent, _ops._ptr(wf), _ops._ptr(cnt), _ops._ptr(ws), ws.numel(),
+                                                  _ops._stream(x)),
+                   "spr_kpconv_weighted_features_f")
         g = (dout / cnt.unsqueeze(1)).contiguous()
         # |wf| <= kmax max|x| (every influence weight is <= 1): a bound within 2^3..2^5 of the true maximum, well
         # inside what the split arithmetic absorbs -- the 1 GB tensor is not scanned for its range

@@ -113,11 +113,17 @@ __global__ __launch_bounds__(256) void k_layernorm_bwd(const float* __restrict__
       g[i] = ok ? (dy_a ? dy_a[o] : 0.f) + (dy_b ? dy_b[o] : 0.f) : 0.f;
       s += v[i];
     }
+    // the mean as mean + corr: with |mean| >> spread one rounded float mean is off by up to 2^-24 |mean| (1e3 +- 1e-2:
+    // ~6e-3 of the spread, the whole error of dx); v - mean is exact there, and corr carries what a float mean cannot
     const float mean = wave_sum(s) / (float)c;
+    float sd = 0.f;
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) sd += i < nv ? v[i] - mean : 0.f;
+    const float corr = wave_sum(sd) / (float)c;
     float ss = 0.f;
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) {
-      const float d = i < nv ? v[i] - mean : 0.f;
+      const float d = i < nv ? (v[i] - mean) - corr : 0.f;
       ss += d * d;
     }
     const float rstd = 1.0f / sqrtf(wave_sum(ss) / (float)c + eps);
@@ -126,7 +132,7 @@ __global__ __launch_bounds__(256) void k_layernorm_bwd(const float* __restrict__
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) {
       const bool ok = i < nv;
-      xh[i] = ok ? (v[i] - mean) * rstd : 0.f;
+      xh[i] = ok ? ((v[i] - mean) - corr) * rstd : 0.f;
       dxh[i] = ok ? g[i] * gamma[i * 64 + lane] : 0.f;
       s1 += dxh[i];
       s2 += dxh[i] * xh[i];
@@ -180,8 +186,10 @@ __global__ __launch_bounds__(256) void k_layernorm_bwd256(const float* __restric
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float mean = wave_sum((v[j].x + v[j].y) + (v[j].z + v[j].w)) * (1.0f / 256.0f);
-      const float4 d = make_float4(v[j].x - mean, v[j].y - mean, v[j].z - mean, v[j].w - mean);
+      const float mean = wave_sum((v[j].x + v[j].y) + (v[j].z + v[j].w)) * (1.0f / 256.0f);   // + corr: as above
+      const float corr = wave_sum(((v[j].x - mean) + (v[j].y - mean)) + ((v[j].z - mean) + (v[j].w - mean))) * (1.0f / 256.0f);
+      const float4 d = make_float4((v[j].x - mean) - corr, (v[j].y - mean) - corr, (v[j].z - mean) - corr,
+                                   (v[j].w - mean) - corr);
       const float rstd = 1.0f / sqrtf(wave_sum((d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w)) * (1.0f / 256.0f) + eps);
       const float4 xh = make_float4(d.x * rstd, d.y * rstd, d.z * rstd, d.w * rstd);
       const float4 dh = make_float4(g[j].x * gm.x, g[j].y * gm.y, g[j].z * gm.z, g[j].w * gm.w);
@@ -218,8 +226,21 @@ __global__ __launch_bounds__(256) void k_layernorm_bwd256(const float* __restric
 // contribution sits near 2^40 -- and added with integer atomics: integer addition is associative, the
 // result does not depend on the order.  Resolution 2^-40 of the largest contribution (finer than the
 // 2^-24 of a float running sum); 2^22 maximal contributions fit before overflow.  k_fx_to_float converts.
+//
+// The exponent is NOT pow2_exp_for's (clamped to +-60 for the split-fp16 planes): a clamp left gradients below
+// ~2^-46 with fewer than 40 bits (every contribution rounded to 0 below ~2^-85) and overflowed the 64-bit sums
+// above ~2^74.  fx_exp_for is exact for every finite positive bound amax * factor (denormals and results
+// beyond float range included): fx lies in [-93, 188], so fx / 2 and fx - fx / 2 are valid pow2f exponents.
+// Where pow2_exp_for is not clamped (bounds in [2^-46, 2^75)) the two agree, and so do the sums, bit for bit.
+__device__ __forceinline__ int fx_exp_for(float amax, float factor) {
+  if (!(amax > 0.f) || !(amax < 3.0e38f)) return 0;
+  int e1, e2;
+  const float m = frexpf(amax, &e1);            // amax = m 2^e1, m in [0.5, 1): exact, denormals included
+  frexpf(m * factor, &e2);                      // factor > 0: amax * factor in [2^(e1+e2-1), 2^(e1+e2))
+  return 40 - (e1 + e2);                        // max |v| 2^fx in [2^39, 2^40)
+}
 __device__ __forceinline__ int fx_exp(const float* __restrict__ parts, float* sh, float factor) {
-  return pow2_exp_for(block_absmax(parts, sh) * factor) + 25;    // max |v| 2^fx in [2^39, 2^40)
+  return fx_exp_for(block_absmax(parts, sh), factor);
 }
 __device__ __forceinline__ void fx_add(unsigned long long* acc, float v, int fx) {
   // v * 2^fx exactly (two exact power-of-two factors keep the intermediate in float range)
@@ -230,7 +251,7 @@ __global__ void k_fx_to_float(const unsigned long long* __restrict__ acc, long n
                               float factor, float* __restrict__ out) {
   __shared__ float sh[17];
   const float amax = block_absmax(parts, sh);
-  const int fx = pow2_exp_for(amax * factor) + 25;
+  const int fx = fx_exp_for(amax, factor);
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   if (!(amax < 3.0e38f)) {   // the incoming gradient holds an inf or a NaN (k_absmax maps NaN to inf): a float
@@ -334,7 +355,8 @@ __global__ __launch_bounds__(256) void k_scatter_rows_add(const float* __restric
 // ---- KPConv backward helpers (kpconv_blocks.py:309-412) --------------------------------------
 // One wave per query.
 //   WF mode : wf[n, p * cin + c] = sum_k infl[p][k] x[idx[n,k], c]     (recomputed forward, un-normalised)
-//             cnt[n] = max(1, #{k : sum_c x[idx[n,k], :] > 0})
+//             cnt[n] = max(1, #{k : flag[idx[n,k]]}), flag = (sum_c x[i, :] > 0) as k_rowflag summed it
+//             (flag == NULL: the legacy entry's own sequential sum)
 //   DX mode : dx[idx[n,k], c] += sum_p infl[p][k] dwf[n, p * cin + c]
 constexpr int kKPmax = 16;
 // The influence weights of up to 64 neighbours are computed side by side (lane =
@@ -350,7 +372,8 @@ __global__ __launch_bounds__(256) void k_kpconv_aux2(const float* __restrict__ q
                                                      const float* __restrict__ x, int cin,
                                                      const float* __restrict__ kpts, int n_kp, float inv_extent,
                                                      const float* __restrict__ dwf, float* __restrict__ wf,
-                                                     float* __restrict__ cnt_out, const float* __restrict__ parts,
+                                                     float* __restrict__ cnt_out, const unsigned char* __restrict__ flag,
+                                                     const float* __restrict__ parts,
                                                      unsigned long long* __restrict__ dx_acc) {
   __shared__ __align__(16) float infl_s[4][64][kKPmax];
   __shared__ int id_s[4][64];
@@ -395,9 +418,12 @@ __global__ __launch_bounds__(256) void k_kpconv_aux2(const float* __restrict__ q
       }
     }
     if (!DX) {   // neighbour count of the reference: rows whose feature sum is > 0
-      float s = 0.f;
-      if (ok) {
+      bool pos = false;
+      if (flag != nullptr) {              // as the forward's kernel flagged them (spr_kpconv_weighted_features_f)
+        pos = ok && flag[id] != 0;
+      } else if (ok) {                    // legacy entry: its own sequential sum (may differ at a sum of ~0)
         const float* xr = x + (size_t)id * cin;
+        float s = 0.f;
         if ((cin & 3) == 0) {
           for (int c = 0; c < cin; c += 4) {
             const float4 v = *reinterpret_cast<const float4*>(xr + c);
@@ -406,8 +432,9 @@ __global__ __launch_bounds__(256) void k_kpconv_aux2(const float* __restrict__ q
         } else {
           for (int c = 0; c < cin; ++c) s += xr[c];
         }
+        pos = s > 0.f;
       }
-      cnt += __builtin_popcountll(__builtin_amdgcn_ballot_w64(ok && s > 0.f));
+      cnt += __builtin_popcountll(__builtin_amdgcn_ballot_w64(pos));
     }
     if (cin == 1) {
       if (!DX) {
@@ -643,23 +670,58 @@ extern "C" int spr_scatter_rows_add(const float* dy, const int* idx, int n, int 
   return 0;
 }
 
+namespace spr {
+void launch_rowflag(const float* x, const float* s_xyz, int ns, int cin, unsigned char* flag, float4* sxf,
+                    int* tile_ctr, hipStream_t stream);   // kpconv.hip
+}
+
+// the forward's per-support flags (launch_rowflag): flag[ns], its support records [ns + 1], one counter
+extern "C" size_t spr_kpconv_weighted_features_workspace_bytes(int ns) {
+  const size_t n = ns > 0 ? (size_t)ns : 1;
+  return align_up(n, 256) + align_up((n + 1) * 16, 256) + 256;
+}
+
+static int kpconv_weighted_features_impl(const float* q_xyz, int nq, const float* s_xyz, int ns, const int* nbr,
+                                         int nbr_stride, int kmax, const float* x, int cin, const float* kernel_points,
+                                         int n_kp, float kp_extent, float* wf, float* cnt, const unsigned char* flag,
+                                         hipStream_t stream) {
+  if (cin == 32)
+    hipLaunchKernelGGL((k_kpconv_aux2<false, true>), dim3(cdiv(nq, 4)), dim3(256), 0, stream, q_xyz, nq, s_xyz, ns, nbr,
+                       nbr_stride, kmax, x, cin, kernel_points, n_kp, 1.0f / kp_extent, (const float*)nullptr, wf, cnt,
+                       flag, (const float*)nullptr, (unsigned long long*)nullptr);
+  else
+    hipLaunchKernelGGL((k_kpconv_aux2<false, false>), dim3(cdiv(nq, 4)), dim3(256), 0, stream, q_xyz, nq, s_xyz, ns, nbr,
+                       nbr_stride, kmax, x, cin, kernel_points, n_kp, 1.0f / kp_extent, (const float*)nullptr, wf, cnt,
+                       flag, (const float*)nullptr, (unsigned long long*)nullptr);
+  SPR_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" int spr_kpconv_weighted_features(const float* q_xyz, int nq, const float* s_xyz, int ns, const int* nbr,
                                             int nbr_stride, int kmax, const float* x, int cin,
                                             const float* kernel_points, int n_kp, float kp_extent, float* wf,
                                             float* cnt, void* stream_) {
+  SPR_REQUIRE(nq > 0 && ns > 0 && cin >= 1 && n_kp >= 1 && n_kp <= kKPmax && kp_extent > 0.f && kmax >= 1 &&
+                  kmax <= nbr_stride, "kpconv_weighted_features: bad arguments");
+  return kpconv_weighted_features_impl(q_xyz, nq, s_xyz, ns, nbr, nbr_stride, kmax, x, cin, kernel_points, n_kp,
+                                       kp_extent, wf, cnt, nullptr, (hipStream_t)stream_);
+}
+
+extern "C" int spr_kpconv_weighted_features_f(const float* q_xyz, int nq, const float* s_xyz, int ns, const int* nbr,
+                                              int nbr_stride, int kmax, const float* x, int cin,
+                                              const float* kernel_points, int n_kp, float kp_extent, float* wf,
+                                              float* cnt, void* ws, size_t ws_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   SPR_REQUIRE(nq > 0 && ns > 0 && cin >= 1 && n_kp >= 1 && n_kp <= kKPmax && kp_extent > 0.f && kmax >= 1 &&
                   kmax <= nbr_stride, "kpconv_weighted_features: bad arguments");
-  if (cin == 32)
-    hipLaunchKernelGGL((k_kpconv_aux2<false, true>), dim3(cdiv(nq, 4)), dim3(256), 0, stream, q_xyz, nq, s_xyz, ns, nbr,
-                       nbr_stride, kmax, x, cin, kernel_points, n_kp, 1.0f / kp_extent, (const float*)nullptr, wf, cnt,
-                       (const float*)nullptr, (unsigned long long*)nullptr);
-  else
-    hipLaunchKernelGGL((k_kpconv_aux2<false, false>), dim3(cdiv(nq, 4)), dim3(256), 0, stream, q_xyz, nq, s_xyz, ns, nbr,
-                       nbr_stride, kmax, x, cin, kernel_points, n_kp, 1.0f / kp_extent, (const float*)nullptr, wf, cnt,
-                       (const float*)nullptr, (unsigned long long*)nullptr);
-  SPR_LAUNCH_CHECK();
-  return 0;
+  SPR_REQUIRE(ws && ws_bytes >= spr_kpconv_weighted_features_workspace_bytes(ns),
+              "kpconv_weighted_features: workspace too small");
+  unsigned char* flag = (unsigned char*)ws;
+  float4* sxf = (float4*)((char*)ws + align_up((size_t)ns, 256));
+  int* tile_ctr = (int*)((char*)sxf + align_up(((size_t)ns + 1) * 16, 256));
+  launch_rowflag(x, s_xyz, ns, cin, flag, sxf, tile_ctr, stream);
+  return kpconv_weighted_features_impl(q_xyz, nq, s_xyz, ns, nbr, nbr_stride, kmax, x, cin, kernel_points, n_kp,
+                                       kp_extent, wf, cnt, flag, stream);
 }
 
 namespace {
@@ -712,11 +774,11 @@ static int kpconv_bwd_dx_impl(const float* q_xyz, int nq, const float* s_xyz, in
   if (cin == 32)
     hipLaunchKernelGGL((k_kpconv_aux2<true, true>), dim3(cdiv(nq, 4)), dim3(256), 0, stream, q_xyz, nq, s_xyz, ns, nbr,
                        nbr_stride, kmax, (const float*)nullptr, cin, kernel_points, n_kp, 1.0f / kp_extent, dwf,
-                       (float*)nullptr, (float*)nullptr, f.parts, f.acc);
+                       (float*)nullptr, (float*)nullptr, (const unsigned char*)nullptr, f.parts, f.acc);
   else
     hipLaunchKernelGGL((k_kpconv_aux2<true, false>), dim3(cdiv(nq, 4)), dim3(256), 0, stream, q_xyz, nq, s_xyz, ns, nbr,
                        nbr_stride, kmax, (const float*)nullptr, cin, kernel_points, n_kp, 1.0f / kp_extent, dwf,
-                       (float*)nullptr, (float*)nullptr, f.parts, f.acc);
+                       (float*)nullptr, (float*)nullptr, (const unsigned char*)nullptr, f.parts, f.acc);
   hipLaunchKernelGGL(k_fx_to_float, dim3(cdiv((long)ns * cin, 256)), dim3(256), 0, stream, f.acc, (long)ns * cin,
                      f.parts, (float)n_kp, dx);
   SPR_LAUNCH_CHECK();

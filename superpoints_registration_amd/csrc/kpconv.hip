@@ -1298,6 +1298,17 @@ int launch_ring(const float* q_xyz, int nq, int ns, const int* nbr, int nbr_stri
 }
 
 }  // namespace
+
+// k_rowflag over ns support points: flag[ns], sxf[ns + 1], tile_ctr[1].  The KPConv backward
+// (spr_kpconv_weighted_features) counts neighbours from these same flags: the flag is the sign of a float
+// sum, and a second summation order could count a row whose sum sits at 0 differently from the forward.
+void launch_rowflag(const float* x, const float* s_xyz, int ns, int cin, unsigned char* flag, float4* sxf,
+                    int* tile_ctr, hipStream_t stream) {
+  const int c4 = cin >> 2;
+  const bool wide = (cin & 3) == 0 && c4 <= 64 && (c4 & (c4 - 1)) == 0;
+  const long waves = wide ? cdiv(ns, (64 / c4) * 4) : (long)ns;     // matches k_rowflag's two layouts
+  hipLaunchKernelGGL(k_rowflag, dim3(cdiv(waves * 64, 256)), dim3(256), 0, stream, x, s_xyz, ns, cin, flag, sxf, tile_ctr);
+}
 }  // namespace spr
 
 using namespace spr;
@@ -1420,12 +1431,7 @@ extern "C" int spr_kpconv_fwd_p(const float* q_xyz, int nq, const float* s_xyz, 
     return 0;
   }
 
-  {
-    const int c4 = cin >> 2;
-    const bool wide = (cin & 3) == 0 && c4 <= 64 && (c4 & (c4 - 1)) == 0;
-    const long waves = wide ? cdiv(ns, (64 / c4) * 4) : (long)ns;     // matches k_rowflag's two layouts
-    hipLaunchKernelGGL(k_rowflag, dim3(cdiv(waves * 64, 256)), dim3(256), 0, stream, x, s_xyz, ns, cin, flag, sxf, tile_ctr);
-  }
+  launch_rowflag(x, s_xyz, ns, cin, flag, sxf, tile_ctr, stream);
   SPR_LAUNCH_CHECK();
 
   if ((impl == 0 || impl == 2) && n_kp == kKP && cin % 32 == 0 && cout % 32 == 0 && cout <= 256) {
