@@ -704,6 +704,28 @@ int spr_sinkhorn_bwd(const float* feat, int d, const float* xyz, const int* cu,
                      int n_iters, const float* dw, const float* dthat, float* dfeat,
                      float* dalpha, float* dbeta, void* ws, size_t ws_bytes, void* stream);
 
+/* Circle feature loss (CircleLossFull, dist_type 'euclidean': models/losses/feature_loss.py:160-243;
+ * feature_loss_type: circle, qk_regtr_full.py:91-96), all pairs of a step in one set of launches.
+ * src_feat [sum N, d] / tgt_feat [sum M, d] (16-byte aligned, d % 4 == 0), src_xyz [sum N, 3] (transformed
+ * by pose_gt [nbatch, 3, 4] inside), tgt_xyz [sum M, 3]; pair b owns rows cu_src[b] .. cu_src[b + 1] and
+ * cu_tgt[b] .. cu_tgt[b + 1] (DEVICE int32 [nbatch + 1]); max_n / max_m bound every pair's sizes.
+ * spr_circle_loss: out[b] = the pair's loss (NaN if no row or no column has both a positive and a
+ *   negative, as the reference's empty mean).  Masked and zero-weight entries have logit 0.
+ * spr_circle_loss_bwd: given gout[nbatch] = d L / d out, writes G[b][i][j] (row stride max_m, pair stride
+ *   max_n * max_m) = (d L / d fd_ij) / fd_ij and initialises d_src = rowsum(G) src_feat, d_tgt =
+ *   colsum(G) tgt_feat; the gradients are complete after d_src -= G tgt_feat and d_tgt -= G^T src_feat
+ *   (two spr_bgemm calls, alpha -1, beta 1).
+ * Deterministic (fixed-order float64 merges, no atomics).  ws: spr_circle_loss_workspace_bytes. */
+size_t spr_circle_loss_workspace_bytes(int nbatch, int max_n, int max_m);
+int spr_circle_loss(const float* src_feat, const float* tgt_feat, int d, const float* src_xyz,
+                    const float* pose_gt, const float* tgt_xyz, const int* cu_src, const int* cu_tgt,
+                    int nbatch, int max_n, int max_m, float r_p, float r_n, float* out, void* ws,
+                    size_t ws_bytes, void* stream);
+int spr_circle_loss_bwd(const float* src_feat, const float* tgt_feat, int d, const float* src_xyz,
+                        const float* pose_gt, const float* tgt_xyz, const int* cu_src, const int* cu_tgt,
+                        int nbatch, int max_n, int max_m, float r_p, float r_n, const float* gout, float* G,
+                        float* d_src, float* d_tgt, void* ws, size_t ws_bytes, void* stream);
+
 /* Per-launch timing of the fused KPConv kernel and of the attention core kernel
  * with HIP events recorded on the launch stream (used by bench.py for the
  * roofline figures; off by default).

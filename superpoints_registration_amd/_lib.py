@@ -148,6 +148,10 @@ SIGNATURES = {
     "spr_weighted_procrustes_bwd": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "spr_sinkhorn_bwd_workspace_bytes": (_sz, [_vp, _i, _i]),
     "spr_sinkhorn_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "spr_circle_loss_workspace_bytes": (_sz, [_i, _i, _i]),
+    "spr_circle_loss": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _sz, _vp]),
+    "spr_circle_loss_bwd": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp,
+                                 _sz, _vp]),
     "spr_selftest": (_i, [_vp]),
     "spr_prof_enable": (_i, [_i]),
     "spr_prof_read": (_i, [_i, _vp, _vp, _vp]),

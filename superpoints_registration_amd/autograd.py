@@ -579,3 +579,44 @@ class InfoNCEFn(torch.autograd.Function):
         dW = torch.empty((d, d), dtype=torch.float32, device=dev)
         _lib.check(L.spr_wsym_bwd(_ops._ptr(dws), d, _ops._ptr(dW), _ops._stream(a)), "spr_wsym_bwd")
         return da, dp, None, None, None, dW, None, None
+
+
+class CircleLossFn(torch.autograd.Function):
+    """Per-pair CircleLossFull losses of a step (spr_circle_loss); backward: spr_circle_loss_bwd writes
+    G = (d L / d fd) / fd per pair and d_src = rowsum(G) a, d_tgt = colsum(G) b; then d_src -= G b and
+    d_tgt -= G^T a as two batched spr_bgemm calls (one record per pair)."""
+
+    @staticmethod
+    def forward(ctx, a, b, xa, pose_gt, xb, src_lens, tgt_lens, r_p, r_n):
+        with torch.no_grad():
+            out = _ops.circle_loss_raw(a, b, xa, pose_gt, xb, src_lens, tgt_lens, r_p, r_n)
+        ctx.meta = (src_lens, tgt_lens, float(r_p), float(r_n))
+        ctx.save_for_backward(a, b, xa, pose_gt, xb)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        src_lens, tgt_lens, r_p, r_n = ctx.meta
+        a, b, xa, pose, xb, src_lens, tgt_lens = _ops._circle_args(*(t.detach() for t in ctx.saved_tensors),
+                                                                   src_lens, tgt_lens)
+        dev = a.device
+        B, d = len(src_lens), a.shape[1]
+        max_n, max_m = max(src_lens), max(tgt_lens)
+        L = _lib.lib()
+        ws = _ops._workspace(L.spr_circle_loss_workspace_bytes(B, max_n, max_m), dev)
+        G = torch.empty((B, max_n, max_m), dtype=torch.float32, device=dev)
+        da, db = torch.empty_like(a), torch.empty_like(b)
+        g = gout.detach().float().contiguous()
+        cu_a, cu_b = _ops.lengths_to_cu(src_lens, dev), _ops.lengths_to_cu(tgt_lens, dev)
+        _lib.check(L.spr_circle_loss_bwd(_ops._ptr(a), _ops._ptr(b), d, _ops._ptr(xa), _ops._ptr(pose), _ops._ptr(xb),
+                                         _ops._ptr(cu_a), _ops._ptr(cu_b), B, max_n, max_m, r_p, r_n,
+                                         _ops._ptr(g), _ops._ptr(G), _ops._ptr(da), _ops._ptr(db), _ops._ptr(ws),
+                                         ws.numel(), _ops._stream(a)), "spr_circle_loss_bwd")
+        oa = np.concatenate([[0], np.cumsum(src_lens)])
+        ob = np.concatenate([[0], np.cumsum(tgt_lens)])
+        pg = max_n * max_m
+        bgemm(G, b, da, [(k * pg, int(ob[k]) * d, int(oa[k]) * d, src_lens[k], d, tgt_lens[k]) for k in range(B)],
+              (max_m, 1), (d, 1), (d, 1), alpha=-1.0, beta=1.0)                       # d_src -= G b
+        bgemm(G, a, db, [(k * pg, int(oa[k]) * d, int(ob[k]) * d, tgt_lens[k], d, src_lens[k]) for k in range(B)],
+              (1, max_m), (d, 1), (d, 1), alpha=-1.0, beta=1.0)                       # d_tgt -= G^T a
+        return da, db, None, None, None, None, None, None, None

@@ -1255,6 +1255,67 @@ def infonce_pair_raw(anchor_feat, positive_feat, anchor_xyz, pose_gt, positive_x
     return out[0]
 
 
+def circle_loss(src_feat, tgt_feat, src_kp, pose_gt, tgt_kp, r_p: float, r_n: float):
+    """CircleLossFull(dist_type='euclidean') (feature_loss.py:160-243) of every pair of a step in one
+    batched call.  Lists over the pairs: src_feat [N_b, D], tgt_feat [M_b, D], src_kp [N_b, 3] (transformed
+    by pose_gt [B, 3, 4] inside), tgt_kp [M_b, 3].  Returns the per-pair losses [B]; the reference's loss
+    is their mean (:236-243).  Differentiable in the features (autograd.CircleLossFn)."""
+    B = len(src_feat)
+    if not (len(tgt_feat) == len(src_kp) == len(tgt_kp) == B >= 1):
+        raise ValueError("circle_loss: src_feat, tgt_feat, src_kp and tgt_kp need one entry per pair")
+    for name, ts in (("src_feat", src_feat), ("tgt_feat", tgt_feat), ("src_kp", src_kp), ("tgt_kp", tgt_kp)):
+        for t in ts:
+            _dev(t, name)
+    src_lens = [int(t.shape[0]) for t in src_feat]
+    tgt_lens = [int(t.shape[0]) for t in tgt_feat]
+    cat = lambda ts: ts[0] if len(ts) == 1 else torch.cat(list(ts))   # noqa: E731
+    return circle_loss_packed(cat(src_feat), cat(tgt_feat), cat(src_kp), pose_gt, cat(tgt_kp), src_lens, tgt_lens,
+                              r_p, r_n)
+
+
+def circle_loss_packed(src_feat, tgt_feat, src_kp, pose_gt, tgt_kp, src_lens, tgt_lens, r_p: float, r_n: float):
+    """circle_loss on packed rows: pair b owns src_lens[b] consecutive rows of src_feat / src_kp and
+    tgt_lens[b] of tgt_feat / tgt_kp (host lengths, each >= 1)."""
+    if _wants_grad(src_feat, tgt_feat):
+        from .autograd import CircleLossFn
+        return CircleLossFn.apply(_dev(src_feat, "src_feat", torch.float32), _dev(tgt_feat, "tgt_feat", torch.float32),
+                                  src_kp, pose_gt, tgt_kp, tuple(src_lens), tuple(tgt_lens), float(r_p), float(r_n))
+    return circle_loss_raw(src_feat, tgt_feat, src_kp, pose_gt, tgt_kp, src_lens, tgt_lens, r_p, r_n)
+
+
+def _circle_args(src_feat, tgt_feat, src_kp, pose_gt, tgt_kp, src_lens, tgt_lens):
+    a = _dev(src_feat, "src_feat", torch.float32)
+    b = _dev(tgt_feat, "tgt_feat", torch.float32)
+    xa = _dev(src_kp, "src_kp", torch.float32)
+    xb = _dev(tgt_kp, "tgt_kp", torch.float32)
+    pose = _dev(pose_gt, "pose_gt", torch.float32)
+    src_lens, tgt_lens = [int(n) for n in src_lens], [int(m) for m in tgt_lens]
+    B = len(src_lens)
+    d = a.shape[1] if a.dim() == 2 else -1
+    if not (B >= 1 and len(tgt_lens) == B and min(src_lens) >= 1 and min(tgt_lens) >= 1):
+        raise ValueError(f"circle_loss: every pair needs >= 1 row on both sides (got {src_lens}, {tgt_lens})")
+    if a.shape != (sum(src_lens), d) or b.shape != (sum(tgt_lens), d) or d < 4 or d % 4:
+        raise ValueError(f"circle_loss: features {tuple(a.shape)} / {tuple(b.shape)} do not match the lengths, "
+                         "or D is not a multiple of 4")
+    if xa.shape != (sum(src_lens), 3) or xb.shape != (sum(tgt_lens), 3) or pose.numel() != 12 * B:
+        raise ValueError("circle_loss: keypoints or pose_gt do not match the lengths")
+    return a, b, xa, pose, xb, src_lens, tgt_lens
+
+
+def circle_loss_raw(src_feat, tgt_feat, src_kp, pose_gt, tgt_kp, src_lens, tgt_lens, r_p: float, r_n: float):
+    a, b, xa, pose, xb, src_lens, tgt_lens = _circle_args(src_feat, tgt_feat, src_kp, pose_gt, tgt_kp, src_lens,
+                                                          tgt_lens)
+    B, max_n, max_m = len(src_lens), max(src_lens), max(tgt_lens)
+    L = _lib.lib()
+    out = torch.empty((B,), dtype=torch.float32, device=a.device)
+    ws = _workspace(L.spr_circle_loss_workspace_bytes(B, max_n, max_m), a.device)
+    cu_a, cu_b = lengths_to_cu(src_lens, a.device), lengths_to_cu(tgt_lens, a.device)   # both alive until the launch
+    _lib.check(L.spr_circle_loss(_ptr(a), _ptr(b), a.shape[1], _ptr(xa), _ptr(pose), _ptr(xb), _ptr(cu_a), _ptr(cu_b), B,
+                                 max_n, max_m, float(r_p), float(r_n), _ptr(out), _ptr(ws), ws.numel(), _stream(a)),
+               "spr_circle_loss")
+    return out
+
+
 def transform_l1_pair(pose_gt, pose_pred, xyz):
     if _wants_grad(pose_pred):
         from .autograd import TransformL1Fn

@@ -255,14 +255,15 @@ class RegTR(nn.Module):
     # ------------------------------------------------------------------ #
     def compute_loss(self, pred, batch):
         """Forward of RegTR.compute_loss (qk_regtr_full.py:313-368): overlap BCE on the
-        coarsest level of compute_overlaps, InfoNCE feature loss against the ground-truth
-        transformed keypoints, L1 transform loss; total = T + 0.1 feature + overlap.
+        coarsest level of compute_overlaps, InfoNCE or circle feature loss (cfg.feature_loss_type)
+        against the ground-truth transformed keypoints, L1 transform loss; total = T + 0.1 feature + overlap.
         batch needs 'pose' [B,3,4], 'src_overlap' / 'tgt_overlap' (per-point masks) and the
         'kpconv_meta' a forward left there.  Differentiable when `pred` came from a forward with
         gradients enabled: losses['total'].backward() then runs the HIP backward (autograd.py)."""
         cfg = self.cfg
-        if cfg.get('feature_loss_type', 'infonce') != 'infonce':
-            raise NotImplementedError("only the InfoNCE feature loss is selected by the shipped configs")
+        circle = cfg.get('feature_loss_type', 'infonce') == 'circle'
+        if not circle and cfg.get('feature_loss_type', 'infonce') != 'infonce':
+            raise NotImplementedError("feature_loss_type must be 'infonce' or 'circle' (qk_regtr_full.py:91-96)")
         if cfg.get('inlier_loss_on', False):
             raise NotImplementedError("inlier_loss_on is off in every shipped config")
         meta = batch['kpconv_meta']
@@ -283,13 +284,17 @@ class RegTR(nn.Module):
         pred_ov = torch.cat([o[0, :, 0] for o in list(pred['src_overlap']) + list(pred['tgt_overlap'])])
         losses = {'overlap': ops.bce_logits_mean(pred_ov.contiguous(), ov)}
 
-        W = self.feature_criterion.W
+        W = None if circle else self.feature_criterion.W
         feat, t_l1 = [], []
         # the reference overwrites `feature_loss` for every entry of feature_loss_on
         # (qk_regtr_full.py:340-345): only the LAST index contributes
         last = list(cfg.get('feature_loss_on', [0]))[-1:]
-        for b in range(B):
+        if circle:   # CircleLossFull (qk_regtr_full.py:94-96): every pair in one batched call
             for i in last:
+                feat = list(ops.circle_loss([s[i] for s in pred['src_feat']], [t[i] for t in pred['tgt_feat']],
+                                            pred['src_kp'], pose_gt, pred['tgt_kp'], cfg.r_p, cfg.r_n))
+        for b in range(B):
+            for i in ([] if circle else last):
                 feat.append(ops.infonce_pair(pred['src_feat'][b][i].contiguous(), pred['tgt_feat'][b][i].contiguous(),
                                              pred['src_kp'][b].contiguous(), pose_gt[b], pred['tgt_kp'][b].contiguous(),
                                              W, cfg.r_p, cfg.r_n))
