@@ -903,6 +903,14 @@ __global__ __launch_bounds__(256) void k_procrustes_bwd(const float* __restrict_
     gt[k] = bc[9 + k];
     ga[k] = bc[12 + k];
   }
+  // Below the clamp the normalised weights sum to s = sum w / 1e-6 < 1, and H = sum w~ a b^T - (2 - s) abar bbar^T
+  // keeps a dependence on the centroids that vanishes at s = 1: om = 1 - s, GHcb = GH bbar, GHca = GH^T abar.
+  const double om = clamped ? 1.0 - acc[0] / den : 0.0;
+  double GHcb[3], GHca[3];
+  for (int r = 0; r < 3; ++r) {
+    GHcb[r] = om * (GH[3 * r] * cb[0] + GH[3 * r + 1] * cb[1] + GH[3 * r + 2] * cb[2]);
+    GHca[r] = om * (GH[r] * ca[0] + GH[3 + r] * ca[1] + GH[6 + r] * ca[2]);
+  }
   // first pass: dL/dw~_i and its weighted sum
   double s2[1] = {0.0};
   for (int i = beg + threadIdx.x; i < end; i += 256) {
@@ -918,13 +926,16 @@ __global__ __launch_bounds__(256) void k_procrustes_bwd(const float* __restrict_
     for (int r = 0; r < 3; ++r)
       for (int c = 0; c < 3; ++c) q += ac[r] * GH[3 * r + c] * bcv[c];
     for (int d = 0; d < 3; ++d) q += ga[d] * ai[d] + gt[d] * bi[d];
+    if (clamped) q -= ai[0] * GHcb[0] + ai[1] * GHcb[1] + ai[2] * GHcb[2] + GHca[0] * bi[0] + GHca[1] * bi[1] + GHca[2] * bi[2];
     s2[0] += wt * q;
     if (db)
       for (int c = 0; c < 3; ++c)
-        db[3 * (size_t)i + c] = (float)(wt * (GH[c] * ac[0] + GH[3 + c] * ac[1] + GH[6 + c] * ac[2] + gt[c]));
+        db[3 * (size_t)i + c] =
+            (float)(wt * (GH[c] * ac[0] + GH[3 + c] * ac[1] + GH[6 + c] * ac[2] + gt[c] - (clamped ? GHca[c] : 0.0)));
     if (da)
       for (int r = 0; r < 3; ++r)
-        da[3 * (size_t)i + r] = (float)(wt * (GH[3 * r] * bcv[0] + GH[3 * r + 1] * bcv[1] + GH[3 * r + 2] * bcv[2] + ga[r]));
+        da[3 * (size_t)i + r] = (float)(wt * (GH[3 * r] * bcv[0] + GH[3 * r + 1] * bcv[1] + GH[3 * r + 2] * bcv[2] +
+                                              ga[r] - (clamped ? GHcb[r] : 0.0)));
     if (dw) dw[i] = (float)q;   // completed below
   }
   block_reduce_d(s2, 1, sh);
