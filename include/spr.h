@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define SPR_VERSION 5
+#define SPR_VERSION 6
 
 /* activation codes for spr_linear / spr_instnorm */
 #define SPR_ACT_NONE 0
@@ -95,7 +95,11 @@ int spr_radius_neighbors(const float* q_xyz, const int* q_cu, int nq,
  *   table: spr_radius_table_bytes(ns, nb) bytes, 256-byte aligned, owned by the caller;
  *   self != 0: the queries are the table's supports (same array and cu) -> cell-order walk;
  *   slot in [0, spr_radius_table_slots()): one per query call against a build (its max row count);
- *   *max_count as in spr_radius_neighbors (-2: geometry too large for the table -> algo 1).
+ *   *max_count as in spr_radius_neighbors (-2: geometry too large for the table -> algo 1);
+ *   algo of spr_radius_table_query = the K-nearest selection -- 0: one thread per query (cell scan into a scratch
+ *   row + rank sort in registers; cheaper for sparse rows), 1: one wave per query (one pass over the coalesced
+ *   record runs, the row kept sorted in the wave's registers, no scratch, no sort kernel; faster when more
+ *   supports lie in range than `limit`: LiDAR-shaped clouds), -1: the library's choice.  Identical rows.
  */
 size_t spr_radius_table_bytes(int ns, int nb);
 size_t spr_radius_table_build_workspace_bytes(int ns, int nb);
@@ -105,14 +109,7 @@ int spr_radius_table_build(const float* s_xyz, const int* s_cu, int ns, int nb, 
                            void* table, size_t table_bytes, void* ws, size_t ws_bytes, void* stream);
 int spr_radius_table_query(const float* q_xyz, const int* q_cu, int nq, int self, int ns, int nb,
                            float radius, int limit, int slot, const void* table, int* out_idx,
-                           int* max_count, void* ws, size_t ws_bytes, void* stream);
-/* Round 5: the same with the K-nearest selection chosen by the caller -- algo 0: one thread per query (cell scan into
- * a scratch row + rank sort in registers; cheaper for sparse rows), algo 1: one wave per query (one pass over the
- * coalesced record runs, the row kept sorted in the wave's registers, no scratch, no sort kernel; faster when more
- * supports lie in range than `limit`: LiDAR-shaped clouds).  Identical rows. */
-int spr_radius_table_query_a(const float* q_xyz, const int* q_cu, int nq, int self, int ns, int nb,
-                             float radius, int limit, int slot, const void* table, int* out_idx,
-                             int* max_count, int algo, void* ws, size_t ws_bytes, void* stream);
+                           int* max_count, int algo, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- a4: KPConv forward ---------------------------------------------------
  * Replaces KPConv.forward(q_pts, s_pts, neighb_inds, x)
@@ -125,14 +122,32 @@ int spr_radius_table_query_a(const float* q_xyz, const int* q_cu, int nq, int se
  * for spr_radius_neighbors output) and enables early exit.
  * impl: 0 = default (ring kernel for 32/64-channel inputs, streamed MFMA tile kernel otherwise),
  *       1 = simple reference kernel, 2 = the streamed MFMA tile kernel for every MFMA shape (A/B).
+ * x_range / w_range: operand ranges of x and the weights as in spr_linear (NULL = measured here).
+ * plan / wplanes: the static inputs of the ring KPConv (csrc/kpconv.hip, k_kpconv_ring), hoisted out of the
+ * per-call path (NULL = built per call).  Both are pure functions of their arguments; callers cache them per
+ * neighbour matrix / per weight version (ops.py does).  The reference recomputes everything per call
+ * (kpconv_blocks.py:269-414); these have no counterpart there.
+ *   spr_kpconv_plan: tile descriptors of a neighbour matrix -- tiles of 16 queries (in `order` if
+ *     given: a permutation of [0, nq), e.g. a spatial order; NULL = natural order), the 16 queries of
+ *     a tile dealt to the eight waves by live neighbour-block count.  The plan depends on
+ *     (nbr contents, nq, ns, nbr_stride, kmax, rows_sorted, order) only.
+ *   spr_kpconv_prep_weights: the [15, cin, cout] weights as range-scaled split-fp16 planes in
+ *     MFMA-fragment order; w_range = spr_absmax partials of the same weights (required, and the same
+ *     w_range goes to spr_kpconv_fwd with the planes).
  */
 size_t spr_kpconv_workspace_bytes(int nq, int ns, int cin, int cout);
-int spr_kpconv_fwd(const float* q_xyz, int nq, const float* s_xyz, int ns,
-                   const int* nbr, int nbr_stride, int kmax, int rows_sorted,
-                   const float* x, int cin, const float* weights, int cout,
-                   const float* kernel_points, int n_kp, float kp_extent,
-                   float* out, int impl, void* ws, size_t ws_bytes,
-                   void* stream);
+size_t spr_kpconv_plan_bytes(int nq);
+int spr_kpconv_plan(const int* nbr, int nq, int ns, int nbr_stride, int kmax, int rows_sorted,
+                    const int* order, void* plan, size_t plan_bytes, void* stream);
+size_t spr_kpconv_wplanes_bytes(int cin, int cout);
+int spr_kpconv_prep_weights(const float* weights, int n_kp, int cin, int cout, const float* w_range,
+                            int w_range_n, void* wplanes, size_t wplanes_bytes, void* stream);
+int spr_kpconv_fwd(const float* q_xyz, int nq, const float* s_xyz, int ns, const int* nbr,
+                   int nbr_stride, int kmax, int rows_sorted, const float* x, int cin,
+                   const float* weights, int cout, const float* kernel_points, int n_kp,
+                   float kp_extent, float* out, int impl, const float* x_range, int x_range_n,
+                   const float* w_range, int w_range_n, const void* plan, const void* wplanes,
+                   void* ws, size_t ws_bytes, void* stream);
 
 /* ---- a5: per-cloud InstanceNorm (+ residual add) (+ LeakyReLU) ------------
  * Replaces BatchNormBlock.forward (kpconv_blocks.py:497-525: per-cloud
@@ -144,11 +159,16 @@ int spr_kpconv_fwd(const float* q_xyz, int nq, const float* s_xyz, int ns,
  * upper bound of the longest cloud (sizes the statistics grid: fixed 512-row
  * slices relative to each cloud, so results are batch-invariant bit for bit).
  * norm = 0 skips the normalisation (out = lrelu(x + add)).
+ * out_range (or NULL): out_range_n zeroed slots, a power of two chosen by the caller, that receive partial
+ * maxima of |out| (operand-range hand-over, see spr_linear).
+ * spr_instnorm_stats: mean / rstd [nb][c] of the statistics passes alone (same workspace).
  */
 size_t spr_instnorm_workspace_bytes(int max_len_host, int nb, int c);
-int spr_instnorm(const float* x, const int* cu, int n, int nb, int max_len_host,
-                 int c, float eps, int norm, const float* add, float slope,
-                 float* out, void* ws, size_t ws_bytes, void* stream);
+int spr_instnorm(const float* x, const int* cu, int n, int nb, int max_len_host, int c,
+                 float eps, int norm, const float* add, float slope, float* out,
+                 float* out_range, int out_range_n, void* ws, size_t ws_bytes, void* stream);
+int spr_instnorm_stats(const float* x, const int* cu, int n, int nb, int max_len_host, int c, float eps,
+                       float* mean, float* rstd, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- a5: tail of a ResNet bottleneck block, fused -----------------------------
  * Replaces the last three statements of ResnetBottleneckBlock.forward
@@ -159,10 +179,15 @@ int spr_instnorm(const float* x, const int* cu, int n, int nb, int max_len_host,
  * xa [n,ka], wa [n_out,ka]; xb [n,kb], wb [n_out,kb] (kb = 0: xb = wb = NULL and
  * add [n,n_out] or NULL is added instead); cu [nb+1].  The projections are computed
  * twice (statistics pass, output pass) and never written: only `out` goes to memory.
- * Split-fp16 product mode only (spr_set_gemm_mode(1)); ranges as in spr_linear_r
- * (NULL: measured here); out_range as in spr_instnorm_r.
+ * Split-fp16 product mode only (spr_set_gemm_mode(1)); ranges as in spr_linear
+ * (NULL: measured here); out_range as in spr_instnorm.
+ * xa_mean / xa_rstd [nb][ka] (both or neither; NULL = xa is already normalised, xa_slope is then ignored):
+ * xa is the RAW input of a per-cloud InstanceNorm + LeakyReLU(xa_slope) (the KPConv output of a bottleneck
+ * block, kpconv_blocks.py:717-719 of the reference) whose statistics the caller holds (spr_instnorm_stats);
+ * the normalisation runs while a tile is staged -- the normalised tensor is never written.  xa_range is then
+ * required and bounds the NORMALISED values: sqrt(longest cloud) is always valid.
  * spr_block_tail_tile_rows: rows per statistics tile of a supported (ka, kb, n_out), 0 if
- * the shape has no kernel (the caller then uses spr_linear_r + spr_instnorm_r);
+ * the shape has no kernel (the caller then uses spr_linear + spr_instnorm);
  * spr_block_tail_tiles: the tile table of a batch (int32 [spr_block_tail_tiles_len], 16-byte
  * aligned): the exclusive prefix of ceil(len / tile_rows) per cloud and one {first row, valid
  * rows, cloud} record per tile -- tiles start at each cloud's first row, so a cloud's result
@@ -172,33 +197,29 @@ int spr_block_tail_tile_rows(int ka, int kb, int n_out);
 size_t spr_block_tail_tiles_len(int n, int nb, int tile_rows);
 int spr_block_tail_tiles(const int* cu, int n, int nb, int tile_rows, int* tiles, void* stream);
 size_t spr_block_tail_workspace_bytes(int n, int nb, int kb, int n_out, int tile_rows);
-int spr_block_tail(const float* xa, int ka, const float* wa, const float* xb, int kb,
-                   const float* wb, const float* add, const int* cu, const int* tiles, int n,
-                   int nb, int n_out, float eps, float slope, float* out,
-                   const float* xa_range, int xa_range_n, const float* wa_range, int wa_range_n,
-                   const float* xb_range, int xb_range_n, const float* wb_range, int wb_range_n,
-                   float* out_range, int out_range_n, void* ws, size_t ws_bytes, void* stream);
-/* Round 5: the same with xa = the RAW input of a per-cloud InstanceNorm + LeakyReLU(xa_slope) (the KPConv output of a
- * bottleneck block, kpconv_blocks.py:717-719 of the reference) whose statistics the caller holds (spr_instnorm_stats:
- * xa_mean, xa_rstd [nb][ka]); the normalisation runs while a tile is staged -- the normalised tensor is never written.
- * xa_range (required) bounds the NORMALISED values: sqrt(longest cloud) is always valid. */
-int spr_block_tail_n(const float* xa, int ka, const float* wa, const float* xb, int kb, const float* wb,
-                     const float* add, const int* cu, const int* tiles, int n, int nb, int n_out, float eps,
-                     float slope, float* out, const float* xa_range, int xa_range_n, const float* wa_range,
-                     int wa_range_n, const float* xb_range, int xb_range_n, const float* wb_range,
-                     int wb_range_n, float* out_range, int out_range_n, const float* xa_mean,
-                     const float* xa_rstd, float xa_slope, void* ws, size_t ws_bytes, void* stream);
-/* mean / rstd [nb][c] of spr_instnorm's statistics passes alone (workspace: spr_instnorm_workspace_bytes). */
-int spr_instnorm_stats(const float* x, const int* cu, int n, int nb, int max_len_host, int c, float eps,
-                       float* mean, float* rstd, void* ws, size_t ws_bytes, void* stream);
+int spr_block_tail(const float* xa, int ka, const float* wa, const float* xb, int kb, const float* wb,
+                   const float* add, const int* cu, const int* tiles, int n, int nb, int n_out, float eps,
+                   float slope, float* out, const float* xa_range, int xa_range_n, const float* wa_range,
+                   int wa_range_n, const float* xb_range, int xb_range_n, const float* wb_range,
+                   int wb_range_n, float* out_range, int out_range_n, const float* xa_mean,
+                   const float* xa_rstd, float xa_slope, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- a5: strided max pooling ----------------------------------------------
  * Replaces max_pool(x, inds) (kpconv_blocks.py:127-143): max over the pooling
  * neighbours, shadow index ns reads a zero row.  idx [nq, idx_stride], first
  * k columns used.
+ * order (or NULL = natural order): int32 [nq], a permutation in which the queries are WALKED (spr_cell_order of
+ * the query points).  Results are identical; queries in flight together then share support rows, which L2
+ * serves instead of HBM (the reference has no counterpart of the order).
+ * out_range / out_range_n (or NULL): as in spr_instnorm.
+ * spr_cell_order: order [n] = the points of every cloud (cu [nb + 1]) sorted by the Morton code of their cell of
+ * size `cell` (clouds in batch order): a spatial walk order for gather operators, not part of any result.
  */
-int spr_maxpool_gather(const float* x, int ns, int c, const int* idx, int nq,
-                       int idx_stride, int k, float* out, void* stream);
+int spr_maxpool_gather(const float* x, int ns, int c, const int* idx, int nq, int idx_stride, int k,
+                       const int* order, float* out, float* out_range, int out_range_n, void* stream);
+size_t spr_cell_order_workspace_bytes(int n);
+int spr_cell_order(const float* xyz, const int* cu, int n, int nb, float cell, int* order, void* ws, size_t ws_bytes,
+                   void* stream);
 
 /* ---- dense projection -------------------------------------------------------
  * out[m,n] = act(x[m,k] @ w[n,k]^T + bias[n] + residual[m,n])
@@ -211,9 +232,10 @@ int spr_maxpool_gather(const float* x, int ns, int c, const int* idx, int nq,
  * max-|x| partials; may be NULL in mode 0).
  */
 size_t spr_linear_workspace_bytes(void);
-int spr_linear(const float* x, int m, int k, const float* w, int n,
-               const float* bias, const float* residual, int act, float* out,
-               void* ws, size_t ws_bytes, void* stream);
+int spr_linear(const float* x, int m, int k, const float* w, int n, const float* bias,
+               const float* residual, int act, float* out, const float* x_range,
+               int x_range_n, const float* w_range, int w_range_n, float* out_range,
+               int out_range_cap, int* out_range_n_host, void* ws, size_t ws_bytes, void* stream);
 /* Operand-range hand-over.  The split-fp16 arithmetic scales every operand tensor by a power of
  * two derived from max |x|; by default spr_linear measures it with a pass over x.  A producer
  * that has just written x can publish the range instead, as an array of per-workgroup partial
@@ -222,82 +244,18 @@ int spr_linear(const float* x, int m, int k, const float* w, int n,
  *   w_range / w_range_n     range of the weights (NULL: measure).  Weights do not change between
  *     inference calls: measure them once with spr_absmax (spr_range_parts() floats) and pass
  *     the result on every call; with both ranges handed in the call has no pre-pass at all;
- *   out_range (capacity out_range_cap floats): if the GEMM runs with <= out_range_cap
- *     workgroups it writes one partial per workgroup and sets *out_range_n_host (a HOST int)
- *     to their number, else 0 (nothing published).
- * spr_layernorm_r publishes the ranges of its two outputs into spr_layernorm_range_count(m)
- * slots each, which the CALLER MUST ZERO beforehand (the kernel combines its workgroups'
- * maxima with atomic max); spr_attn_inproj_varlen_fwd_r accepts the input ranges and publishes a bound of
- * its output (1 float: the attention output is a convex combination of value rows).
- * spr_instnorm_r and spr_maxpool_gather_r publish |out| the same way as spr_layernorm_r
- * (out_range_n zeroed slots, a power of two chosen by the caller); spr_kpconv_fwd_r accepts x_range / w_range. */
+ *   out_range (capacity out_range_cap floats; NULL: nothing published): if the GEMM runs with
+ *     <= out_range_cap workgroups it writes one partial per workgroup and sets *out_range_n_host
+ *     (a HOST int) to their number, else 0 (nothing published).
+ * The other operators take and publish ranges under the same argument names: where an operator
+ * combines its workgroups' maxima with atomic max (spr_layernorm, spr_instnorm, spr_maxpool_gather,
+ * spr_block_tail), the CALLER MUST ZERO the out_range slots beforehand. */
 int spr_range_parts(void);
 int spr_absmax(const float* x, long rows, int cols, long stride, float* parts, void* stream);
 /* max |x| of many contiguous tensors in ONE launch (all weights of a model at the start of a training step).
  * jobs_dev: njobs device records {const float* x; long long n_elements;}; parts_out [njobs][parts_per_job]:
  * row j is a range (parts_per_job partials) of tensor j, usable wherever spr_absmax partials are. */
 int spr_absmax_multi(const void* jobs_dev, int njobs, int parts_per_job, float* parts_out, void* stream);
-int spr_linear_r(const float* x, int m, int k, const float* w, int n, const float* bias,
-                 const float* residual, int act, float* out, const float* x_range,
-                 int x_range_n, const float* w_range, int w_range_n, float* out_range,
-                 int out_range_cap, int* out_range_n_host, void* ws, size_t ws_bytes, void* stream);
-int spr_kpconv_fwd_r(const float* q_xyz, int nq, const float* s_xyz, int ns, const int* nbr,
-                     int nbr_stride, int kmax, int rows_sorted, const float* x, int cin,
-                     const float* weights, int cout, const float* kernel_points, int n_kp,
-                     float kp_extent, float* out, int impl, const float* x_range, int x_range_n,
-                     const float* w_range, int w_range_n, void* ws, size_t ws_bytes, void* stream);
-/* Static inputs of the ring KPConv (csrc/kpconv.hip, k_kpconv_ring), hoisted out of the per-call
- * path.  Both are pure functions of their arguments; callers cache them per neighbour matrix / per
- * weight version (ops.py does).  The reference recomputes everything per call
- * (kpconv_blocks.py:269-414); these have no counterpart there.
- *   spr_kpconv_plan: tile descriptors of a neighbour matrix -- tiles of 16 queries (in `order` if
- *     given: a permutation of [0, nq), e.g. a spatial order; NULL = natural order), the 16 queries of
- *     a tile dealt to the eight waves by live neighbour-block count.  The plan depends on
- *     (nbr contents, nq, ns, nbr_stride, kmax, rows_sorted, order) only.
- *   spr_kpconv_prep_weights: the [15, cin, cout] weights as range-scaled split-fp16 planes in
- *     MFMA-fragment order; w_range = spr_absmax partials of the same weights (required).
- *   spr_kpconv_fwd_p: spr_kpconv_fwd_r with plan / wplanes handed in (NULL = built per call). */
-size_t spr_kpconv_plan_bytes(int nq);
-int spr_kpconv_plan(const int* nbr, int nq, int ns, int nbr_stride, int kmax, int rows_sorted,
-                    const int* order, void* plan, size_t plan_bytes, void* stream);
-size_t spr_kpconv_wplanes_bytes(int cin, int cout);
-int spr_kpconv_prep_weights(const float* weights, int n_kp, int cin, int cout, const float* w_range,
-                            int w_range_n, void* wplanes, size_t wplanes_bytes, void* stream);
-int spr_kpconv_fwd_p(const float* q_xyz, int nq, const float* s_xyz, int ns, const int* nbr,
-                     int nbr_stride, int kmax, int rows_sorted, const float* x, int cin,
-                     const float* weights, int cout, const float* kernel_points, int n_kp,
-                     float kp_extent, float* out, int impl, const float* x_range, int x_range_n,
-                     const float* w_range, int w_range_n, const void* plan, const void* wplanes,
-                     void* ws, size_t ws_bytes, void* stream);
-int spr_instnorm_r(const float* x, const int* cu, int n, int nb, int max_len_host, int c,
-                   float eps, int norm, const float* add, float slope, float* out,
-                   float* out_range, int out_range_n, void* ws, size_t ws_bytes, void* stream);
-int spr_maxpool_gather_r(const float* x, int ns, int c, const int* idx, int nq, int idx_stride,
-                         int k, float* out, float* out_range, int out_range_n, void* stream);
-/* The same rows with the queries WALKED in `order` (int32 [nq], a permutation: spr_cell_order of the query points;
- * NULL = spr_maxpool_gather_r).  Results are identical; queries in flight together then share support rows, which L2
- * serves instead of HBM (reference: kpconv_blocks.py:127-140 max_pool, no counterpart of the order there). */
-int spr_maxpool_gather_o(const float* x, int ns, int c, const int* idx, int nq, int idx_stride, int k,
-                         const int* order, float* out, float* out_range, int out_range_n, void* stream);
-/* order [n] = the points of every cloud (cu [nb + 1]) sorted by the Morton code of their cell of size `cell`
- * (clouds in batch order): a spatial walk order for gather operators, not part of any result. */
-size_t spr_cell_order_workspace_bytes(int n);
-int spr_cell_order(const float* xyz, const int* cu, int n, int nb, float cell, int* order, void* ws, size_t ws_bytes,
-                   void* stream);
-int spr_layernorm_range_count(int m);
-int spr_layernorm_r(const float* x, int m, int c, const float* gamma, const float* beta,
-                    float eps, const float* pos, float* out_norm, float* out_pos,
-                    float* range_norm, float* range_pos, void* stream);
-/* w_prep (or NULL): the weight-side inputs of the fused in-projection -- spr_range_parts() partial
- * maxima of |w_in| followed by its 3 d row L1 norms -- from spr_attn_inproj_prepare, measured once
- * per weight version. */
-int spr_attn_inproj_prepare(const float* w_in, int d, float* out, void* stream);
-int spr_attn_inproj_varlen_fwd_r(const float* x_qk, const float* x_v, int t, const float* w_in,
-                                 const float* b_in, const int* cu, const int* kv_seg, int nseg,
-                                 int max_len_host, int nhead, int head_dim, float scale,
-                                 float* out, int o_stride, const float* xqk_range,
-                                 int xqk_range_n, const float* xv_range, int xv_range_n,
-                                 float* out_range, const float* w_prep, void* ws, size_t ws_bytes, void* stream);
 
 /* Arithmetic of spr_linear (and of the correlation GEMMs inside the matching
  * head):
@@ -314,10 +272,14 @@ int spr_set_gemm_mode(int mode);
  * Replaces norm1/2/3 + with_pos_embed (transformers.py:121,:196-197,:212-214,
  * :234) and the final encoder norm (:46-48).
  *   out_norm = LN(x) (may be NULL); out_pos = LN(x) + pos (NULL if pos NULL)
+ *   range_norm / range_pos (each may be NULL): the ranges of the two outputs, published into
+ *   spr_layernorm_range_count(m) slots each, which the CALLER MUST ZERO beforehand (the kernel combines its
+ *   workgroups' maxima with atomic max; operand-range hand-over, see spr_linear).
  */
-int spr_layernorm(const float* x, int m, int c, const float* gamma,
-                  const float* beta, float eps, const float* pos,
-                  float* out_norm, float* out_pos, void* stream);
+int spr_layernorm_range_count(int m);
+int spr_layernorm(const float* x, int m, int c, const float* gamma, const float* beta,
+                  float eps, const float* pos, float* out_norm, float* out_pos,
+                  float* range_norm, float* range_pos, void* stream);
 
 /* ---- a7: sine positional embedding -----------------------------------------
  * Replaces PositionEmbeddingCoordsSine.forward (transformer/
@@ -339,21 +301,16 @@ int spr_posemb_sine(const float* xyz, int n, int d_model, float scale,
  *   segment length (sizes the grid).  ws: spr_attn_workspace_bytes(t, nseg,
  *   nhead, head_dim) bytes of device scratch (the split-fp16 operand planes;
  *   may be NULL in mode 0).
+ *   lse (NULL = not wanted) [t, nhead]: receives log2 sum_j 2^(log2(e) scale q_i.k_j) per query and head for
+ *   spr_attn_varlen_bwd (training: what torch's SDPA backward keeps as `logsumexp`).  lse_written (a HOST int,
+ *   required only with lse): *lse_written = 0 in exact-f32 mode (attention mode 0, whose core does not
+ *   produce it): lse is then untouched.
  */
 size_t spr_attn_workspace_bytes(int t, int nseg, int nhead, int head_dim);
-int spr_attn_varlen_fwd(const float* q, int q_stride, const float* k,
-                        int k_stride, const float* v, int v_stride,
-                        const int* cu, const int* kv_seg, int t, int nseg,
-                        int max_len_host, int nhead, int head_dim, float scale,
-                        float* out, int o_stride, void* ws, size_t ws_bytes,
-                        void* stream);
-/* The same, additionally handing out lse [t, nhead] = log2 sum_j 2^(log2(e) scale q_i.k_j) per query and head
- * for spr_attn_varlen_bwd_lse (training: what torch's SDPA backward keeps as `logsumexp`).  *lse_written = 0 in
- * exact-f32 mode (attention mode 0, whose core does not produce it): lse is then untouched. */
-int spr_attn_varlen_fwd_lse(const float* q, int q_stride, const float* k, int k_stride, const float* v,
-                            int v_stride, const int* cu, const int* kv_seg, int t, int nseg, int max_len_host,
-                            int nhead, int head_dim, float scale, float* out, int o_stride, float* lse,
-                            int* lse_written, void* ws, size_t ws_bytes, void* stream);
+int spr_attn_varlen_fwd(const float* q, int q_stride, const float* k, int k_stride, const float* v,
+                        int v_stride, const int* cu, const int* kv_seg, int t, int nseg, int max_len_host,
+                        int nhead, int head_dim, float scale, float* out, int o_stride, float* lse,
+                        int* lse_written, void* ws, size_t ws_bytes, void* stream);
 
 /* In-projection + attention core in one call: replaces
  * F.multi_head_attention_forward's packed in-projection (q, k from x_qk,
@@ -363,14 +320,21 @@ int spr_attn_varlen_fwd_lse(const float* q, int q_stride, const float* k, int k_
  * operand planes straight from its accumulators (no fp32 [t, 3d] round trip);
  * in exact mode it equals spr_linear + spr_attn_varlen_fwd.  d_model = 256.
  *   x_qk, x_v [t, d] contiguous (may be the same pointer); out [t, d].
+ *   xqk_range / xv_range (NULL: measured here): the input ranges, as in spr_linear; out_range (or NULL): receives
+ *   a bound of the output (1 float: the attention output is a convex combination of value rows), on the fused
+ *   split-fp16 path only.
+ *   w_prep (or NULL): the weight-side inputs of the fused in-projection -- spr_range_parts() partial
+ *   maxima of |w_in| followed by its 3 d row L1 norms -- from spr_attn_inproj_prepare, measured once
+ *   per weight version.
  */
 size_t spr_attn_inproj_workspace_bytes(int t, int nseg, int nhead, int head_dim);
-int spr_attn_inproj_varlen_fwd(const float* x_qk, const float* x_v, int t,
-                               const float* w_in, const float* b_in,
-                               const int* cu, const int* kv_seg, int nseg,
-                               int max_len_host, int nhead, int head_dim,
-                               float scale, float* out, int o_stride, void* ws,
-                               size_t ws_bytes, void* stream);
+int spr_attn_inproj_prepare(const float* w_in, int d, float* out, void* stream);
+int spr_attn_inproj_varlen_fwd(const float* x_qk, const float* x_v, int t, const float* w_in,
+                               const float* b_in, const int* cu, const int* kv_seg, int nseg,
+                               int max_len_host, int nhead, int head_dim, float scale,
+                               float* out, int o_stride, const float* xqk_range,
+                               int xqk_range_n, const float* xv_range, int xv_range_n,
+                               float* out_range, const float* w_prep, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- a9, analysis: the attention maps of the varlen core ------------------------------------
  * Replaces the weights nn.MultiheadAttention returns with need_weights=True at the four calls per
@@ -432,22 +396,18 @@ int spr_xenc_forward(const void* plan_host, const float* x, const float* pos, co
  * tile by tile and never written.  out = the forward's output, dout = its gradient; kv_seg must be a
  * permutation of the segments, q_seg its inverse.  Exact f32 MFMA, fixed summation order (bitwise
  * reproducible).  dq, dk, dv [t, nhead * 32] contiguous, fully written.  head_dim = 32.
+ * lse: what spr_attn_varlen_fwd handed out for the same q, k (the backward then skips its own pass over the
+ * keys); NULL = computed here.
+ * ws: spr_attn_bwd_workspace_bytes has room for the pre-split operand planes of the split-fp16 form (faster);
+ * with at least spr_attn_bwd_min_workspace_bytes the kernels convert the fp32 tiles they stage themselves.
  */
-size_t spr_attn_bwd_workspace_bytes(int t, int nhead);
-/* the same with room for the pre-split operand planes of the split-fp16 form (faster; optional) */
-size_t spr_attn_bwd_workspace_bytes2(int t, int nseg, int nhead);
+size_t spr_attn_bwd_workspace_bytes(int t, int nseg, int nhead);
+size_t spr_attn_bwd_min_workspace_bytes(int t, int nhead);
 int spr_attn_varlen_bwd(const float* q, int q_stride, const float* k, int k_stride, const float* v,
-                        int v_stride, const float* out, int o_stride, const float* dout,
-                        int do_stride, const int* cu, const int* kv_seg, const int* q_seg, int t,
-                        int nseg, int max_len_host, int nhead, int head_dim, float scale,
-                        float* dq, float* dk, float* dv, void* ws, size_t ws_bytes, void* stream);
-/* lse: what spr_attn_varlen_fwd_lse handed out for the same q, k (the backward then skips its own pass over the
- * keys); NULL = spr_attn_varlen_bwd */
-int spr_attn_varlen_bwd_lse(const float* q, int q_stride, const float* k, int k_stride, const float* v,
-                            int v_stride, const float* out, int o_stride, const float* dout, int do_stride,
-                            const float* lse, const int* cu, const int* kv_seg, const int* q_seg, int t, int nseg,
-                            int max_len_host, int nhead, int head_dim, float scale, float* dq, float* dk,
-                            float* dv, void* ws, size_t ws_bytes, void* stream);
+                        int v_stride, const float* out, int o_stride, const float* dout, int do_stride,
+                        const float* lse, const int* cu, const int* kv_seg, const int* q_seg, int t, int nseg,
+                        int max_len_host, int nhead, int head_dim, float scale, float* dq, float* dk,
+                        float* dv, void* ws, size_t ws_bytes, void* stream);
 
 /* Arithmetic of the attention core:
  *   1 = split-fp16 MFMA (Q, K, V and the probabilities carried as fp16
@@ -463,7 +423,7 @@ int spr_attn_varlen_bwd_lse(const float* q, int q_stride, const float* k, int k_
  *     of the value rows with weights perturbed by < 2^-10 each (5e-6 of the
  *     output scale on flat rows of ~2 000 keys, up to ~3e-4 on rows carried by a
  *     few keys); 20 instead of 24 MFMAs per 64-key tile;
- *   4 (default since round 5) = as 1, the lo plane of the probabilities only on
+ *   4 (default) = as 1, the lo plane of the probabilities only on
  *     the 32-key blocks that hold a weight of at least 2^-5 of the running row
  *     sum: every key that carries a row is exact as in mode 1, the many small
  *     weights travel in one fp16 plane rounded to nearest (their rounded values
@@ -486,19 +446,14 @@ int spr_set_attn_mode(int mode);
  *   that owns the match (tgt token when N>M, else src token); ind is LOCAL to
  *   the partner cloud.  corr_ws: caller scratch for the correlation matrices,
  *   size from spr_match_workspace_bytes (host needs the seg lengths).
+ *   match_val2 (may be NULL): the runner-up value of every match -- what RegTR.ratio_test needs
+ *   (Lowe ratio, qk_regtr_full.py:370-384; cfg.use_ratio_test).
  */
 size_t spr_match_workspace_bytes(const int* cu_host, int npairs);
 int spr_match_dualsoftmax(const float* feat, int d, const int* cu,
                           const int* cu_host, int npairs, float* match_val,
-                          int* match_ind, void* ws, size_t ws_bytes,
+                          float* match_val2, int* match_ind, void* ws, size_t ws_bytes,
                           void* stream);
-
-/* Variant that also returns the runner-up value of every match (match_val2, may be NULL) --
- * what RegTR.ratio_test needs (Lowe ratio, qk_regtr_full.py:370-384; cfg.use_ratio_test). */
-int spr_match_dualsoftmax2(const float* feat, int d, const int* cu,
-                           const int* cu_host, int npairs, float* match_val,
-                           float* match_val2, int* match_ind, void* ws, size_t ws_bytes,
-                           void* stream);
 
 /* ---- pose-hypothesis residuals (config-off refinements) -------
  * spr_pose_residuals: res[i] = || b_i - T_s a_i || with one pose per set s of pair_cu
@@ -541,7 +496,7 @@ int spr_sinkhorn_correspondences(const float* feat, int d, const float* xyz,
                                  int slack, float* out_w, float* out_that,
                                  void* ws, size_t ws_bytes, void* stream);
 
-/* spr_match_dualsoftmax2 + spr_sinkhorn_correspondences of the same features in one call -- RegTR's inference
+/* spr_match_dualsoftmax + spr_sinkhorn_correspondences of the same features in one call -- RegTR's inference
  * forward runs them back to back on the conditioned features (qk_regtr_full.py:453-479 then :525-536).  The scaled
  * correlation matrices are computed and stored once; the Sinkhorn passes evaluate the affinity as they read them.
  * Outputs bit for bit those of the two separate calls; match_val2 may be NULL; workspace:
@@ -603,12 +558,11 @@ int spr_sum_scaled(const float* values, int n, float scale, float* out,
  * spr_layernorm_bwd / spr_instnorm_bwd / spr_maxpool_bwd / spr_scatter_rows_add: gradients of
  *   spr_layernorm (both outputs), spr_instnorm (incl. fused add + LeakyReLU), spr_maxpool_gather,
  *   spr_gather_rows.
- * spr_kpconv_weighted_features_f: recomputes wf[n,p,c] = sum_k infl[n,p,k] x[idx[n,k],c]
+ * spr_kpconv_weighted_features: recomputes wf[n,p,c] = sum_k infl[n,p,k] x[idx[n,k],c]
  *   (kpconv_blocks.py:394) and the neighbour count (:409-411) from the per-support flags the
  *   forward computes (same kernel, same summation order; ws: spr_kpconv_weighted_features_workspace_bytes(ns)).
- *   spr_kpconv_weighted_features (no workspace) sums each row in an order of its own: on a row whose feature sum
- *   is ~0 its count can differ from the forward's -- kept for existing callers only.  spr_kpconv_bwd_dx scatters
- *   d wf back to d x.  Together with two spr_bgemm calls = KPConv backward.
+ *   spr_kpconv_bwd_dx scatters d wf back to d x; dwf_range: the max |dwf| partials published by the product
+ *   that wrote dwf (spr_linear out_range); NULL = measured.  Together with two spr_bgemm calls = KPConv backward.
  * spr_softmax_rows / spr_softmax_bwd_rows: row softmax of per-batch matrices (located by
  *   c_off, m rows, n columns of the same descriptor records) and its backward -- the
  *   non-GEMM steps of the attention backward.
@@ -621,7 +575,7 @@ int spr_bgemm(const float* A, const float* B, float* C, const void* desc_dev, in
  * dW = wf^T g over every point of the batch, kpconv_blocks.py:401-406 differentiated).  nl * nr <= 65536. */
 /* dW = dY^T X in the forward's arithmetic (range-scaled split-fp16 MFMA, fp32 accumulation): per-batch partial
  * products parts[b][nl][nr] over `chunk` rows each, summed by spr_reduce_parts (fixed order).  L [rows, nl],
- * R [rows, nr] row-major; nl, nr multiples of 4, chunk a multiple of 16; ranges as in spr_linear_r. */
+ * R [rows, nr] row-major; nl, nr multiples of 4, chunk a multiple of 16; ranges as in spr_linear. */
 size_t spr_tn_product_split_workspace_bytes(void);
 int spr_tn_product_split(const float* L, const float* R, long rows, int nl, int nr, int chunk,
                          const float* l_range, int l_range_n, const float* r_range, int r_range_n,
@@ -650,24 +604,15 @@ int spr_maxpool_bwd(const float* x, int ns, int c, const int* idx, int nq, int i
                     const float* dy, float* dx, void* ws, size_t ws_bytes, void* stream);
 int spr_scatter_rows_add(const float* dy, const int* idx, int n, int c, int n_src, float* dx,
                          void* ws, size_t ws_bytes, void* stream);
+size_t spr_kpconv_weighted_features_workspace_bytes(int ns);
 int spr_kpconv_weighted_features(const float* q_xyz, int nq, const float* s_xyz, int ns,
                                  const int* nbr, int nbr_stride, int kmax, const float* x, int cin,
                                  const float* kernel_points, int n_kp, float kp_extent,
-                                 float* wf, float* cnt, void* stream);
-int spr_kpconv_weighted_features_f(const float* q_xyz, int nq, const float* s_xyz, int ns,
-                                   const int* nbr, int nbr_stride, int kmax, const float* x, int cin,
-                                   const float* kernel_points, int n_kp, float kp_extent,
-                                   float* wf, float* cnt, void* ws, size_t ws_bytes, void* stream);
-size_t spr_kpconv_weighted_features_workspace_bytes(int ns);
+                                 float* wf, float* cnt, void* ws, size_t ws_bytes, void* stream);
 int spr_kpconv_bwd_dx(const float* q_xyz, int nq, const float* s_xyz, int ns, const int* nbr,
                       int nbr_stride, int kmax, int cin, const float* kernel_points, int n_kp,
-                      float kp_extent, const float* dwf, float* dx, void* ws, size_t ws_bytes,
-                      void* stream);
-/* dwf_range: the max |dwf| partials published by the product that wrote dwf (spr_linear_r out_range); NULL = measured */
-int spr_kpconv_bwd_dx_r(const float* q_xyz, int nq, const float* s_xyz, int ns, const int* nbr,
-                        int nbr_stride, int kmax, int cin, const float* kernel_points, int n_kp,
-                        float kp_extent, const float* dwf, const float* dwf_range, int dwf_range_n, float* dx,
-                        void* ws, size_t ws_bytes, void* stream);
+                      float kp_extent, const float* dwf, const float* dwf_range, int dwf_range_n, float* dx,
+                      void* ws, size_t ws_bytes, void* stream);
 int spr_softmax_rows(float* mat, const void* desc_dev, int nbatch, int max_m, void* stream);
 int spr_softmax_bwd_rows(const float* p, float* dp, const void* desc_dev, int nbatch, int max_m,
                          void* stream);

@@ -33,67 +33,49 @@ SIGNATURES = {
     "spr_radius_table_query_workspace_bytes": (_sz, [_i]),
     "spr_radius_table_slots": (_i, []),
     "spr_radius_table_build": (_i, [_vp, _vp, _i, _i, _f, _vp, _sz, _vp, _sz, _vp]),
-    "spr_radius_table_query": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "spr_radius_table_query_a": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    "spr_radius_table_query": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "spr_kpconv_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "spr_kpconv_fwd": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _f, _vp,
-                            _i, _vp, _sz, _vp]),
+    "spr_kpconv_fwd": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _f, _vp, _i, _vp, _i, _vp,
+                            _i, _vp, _vp, _vp, _sz, _vp]),
     "spr_instnorm_workspace_bytes": (_sz, [_i, _i, _i]),
-    "spr_instnorm": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _f, _vp, _vp, _sz, _vp]),
-    "spr_maxpool_gather": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _vp]),
+    "spr_instnorm": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _f, _vp, _vp, _i, _vp, _sz, _vp]),
+    "spr_maxpool_gather": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "spr_linear_workspace_bytes": (_sz, []),
-    "spr_linear": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
-    "spr_linear_r": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _sz, _vp]),
+    "spr_linear": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _sz, _vp]),
     "spr_range_parts": (_i, []),
     "spr_absmax_multi": (_i, [_vp, _i, _i, _vp, _vp]),
     "spr_absmax": (_i, [_vp, _l, _i, _l, _vp, _vp]),
-    "spr_kpconv_fwd_r": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _f, _vp,
-                              _i, _vp, _i, _vp, _i, _vp, _sz, _vp]),
     "spr_kpconv_plan_bytes": (_sz, [_i]),
     "spr_kpconv_plan": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "spr_kpconv_wplanes_bytes": (_sz, [_i, _i]),
     "spr_kpconv_prep_weights": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _sz, _vp]),
-    "spr_kpconv_fwd_p": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _f, _vp,
-                              _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
-    "spr_instnorm_r": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _f, _vp, _vp, _i, _vp, _sz, _vp]),
     "spr_block_tail_tile_rows": (_i, [_i, _i, _i]),
     "spr_block_tail_tiles_len": (_sz, [_i, _i, _i]),
     "spr_block_tail_tiles": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "spr_block_tail_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "spr_block_tail": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _i, _vp, _i,
-                            _vp, _i, _vp, _i, _vp, _i, _vp, _sz, _vp]),
-    "spr_block_tail_n": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _i, _vp, _i,
-                              _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _f, _vp, _sz, _vp]),
+                            _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _f, _vp, _sz, _vp]),
     "spr_instnorm_stats": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _sz, _vp]),
-    "spr_maxpool_gather_r": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp]),
-    "spr_maxpool_gather_o": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
     "spr_cell_order_workspace_bytes": (_sz, [_i]),
     "spr_cell_order": (_i, [_vp, _vp, _i, _i, _f, _vp, _vp, _sz, _vp]),
     "spr_layernorm_range_count": (_i, [_i]),
-    "spr_layernorm_r": (_i, [_vp, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "spr_attn_inproj_varlen_fwd_r": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _i, _vp, _i, _vp,
-                                          _i, _vp, _vp, _vp, _sz, _vp]),
     "spr_attn_inproj_prepare": (_i, [_vp, _i, _vp, _vp]),
     "spr_set_gemm_mode": (_i, [_i]),
-    "spr_layernorm": (_i, [_vp, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
+    "spr_layernorm": (_i, [_vp, _i, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     "spr_posemb_sine": (_i, [_vp, _i, _i, _f, _f, _vp, _vp]),
     "spr_attn_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "spr_attn_varlen_fwd": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _i,
-                                 _vp, _sz, _vp]),
-    "spr_attn_varlen_fwd_lse": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _i, _vp, _vp,
-                                     _vp, _sz, _vp]),
-    "spr_attn_varlen_bwd_lse": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i,
-                                     _i, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "spr_attn_varlen_fwd": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _i, _vp, _vp, _vp,
+                                 _sz, _vp]),
     "spr_attn_probs_workspace_bytes": (_sz, [_i, _i, _i]),
     "spr_attn_probs": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _i, _i, _vp, _sz,
                             _vp]),
-    "spr_attn_bwd_workspace_bytes": (_sz, [_i, _i]),
-    "spr_attn_bwd_workspace_bytes2": (_sz, [_i, _i, _i]),
-    "spr_attn_varlen_bwd": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f,
-                                 _vp, _vp, _vp, _vp, _sz, _vp]),
+    "spr_attn_bwd_workspace_bytes": (_sz, [_i, _i, _i]),
+    "spr_attn_bwd_min_workspace_bytes": (_sz, [_i, _i]),
+    "spr_attn_varlen_bwd": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i,
+                                 _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     "spr_attn_inproj_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "spr_attn_inproj_varlen_fwd": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _i, _vp,
-                                        _sz, _vp]),
+    "spr_attn_inproj_varlen_fwd": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _i, _vp, _i, _vp,
+                                        _i, _vp, _vp, _vp, _sz, _vp]),
     "spr_set_attn_mode": (_i, [_i]),
     "spr_xenc_prepared_bytes": (_sz, [_i, _i]),
     "spr_xenc_plan_bytes": (_sz, []),
@@ -101,8 +83,7 @@ SIGNATURES = {
     "spr_xenc_workspace_bytes": (_sz, [_i, _i]),
     "spr_xenc_forward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "spr_match_workspace_bytes": (_sz, [_vp, _i]),
-    "spr_match_dualsoftmax": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
-    "spr_match_dualsoftmax2": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "spr_match_dualsoftmax": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "spr_pose_residuals": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "spr_pose_scores": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp]),
     "spr_weighted_procrustes": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp]),
@@ -134,10 +115,9 @@ SIGNATURES = {
     "spr_maxpool_bwd": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "spr_scatter_rows_add": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "spr_kpconv_weighted_features_workspace_bytes": (_sz, [_i]),
-    "spr_kpconv_weighted_features": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _f, _vp, _vp, _vp]),
-    "spr_kpconv_weighted_features_f": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _f, _vp, _vp, _vp, _sz, _vp]),
-    "spr_kpconv_bwd_dx": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _f, _vp, _vp, _vp, _sz, _vp]),
-    "spr_kpconv_bwd_dx_r": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _f, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
+    "spr_kpconv_weighted_features": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _f, _vp, _vp, _vp, _sz,
+                                          _vp]),
+    "spr_kpconv_bwd_dx": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _f, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
     "spr_softmax_rows": (_i, [_vp, _vp, _i, _i, _vp]),
     "spr_softmax_bwd_rows": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     "spr_bce_logits_mean_bwd": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),

@@ -210,11 +210,11 @@ class KPConvFn(torch.autograd.Function):
         wf = torch.empty((nq, n_kp * cin), dtype=torch.float32, device=x.device)
         cnt = torch.empty((nq,), dtype=torch.float32, device=x.device)
         ws = _ops._workspace(L.spr_kpconv_weighted_features_workspace_bytes(ns), x.device)
-        _lib.check(L.spr_kpconv_weighted_features_f(_ops._ptr(q_pts), nq, _ops._ptr(s_pts), ns, _ops._ptr(nbr32), int(stride),
+        _lib.check(L.spr_kpconv_weighted_features(_ops._ptr(q_pts), nq, _ops._ptr(s_pts), ns, _ops._ptr(nbr32), int(stride),
                                                   kmax, _ops._ptr(xd), cin, _ops._ptr(kp.detach().contiguous()), n_kp,
                                                   ctx.kp_extent, _ops._ptr(wf), _ops._ptr(cnt), _ops._ptr(ws), ws.numel(),
                                                   _ops._stream(x)),
-                   "spr_kpconv_weighted_features_f")
+                   "spr_kpconv_weighted_features")
         g = (dout / cnt.unsqueeze(1)).contiguous()
         # |wf| <= kmax max|x| (every influence weight is <= 1): a bound within 2^3..2^5 of the true maximum, well
         # inside what the split arithmetic absorbs -- the 1 GB tensor is not scanned for its range
@@ -235,10 +235,10 @@ class KPConvFn(torch.autograd.Function):
             dx = torch.empty((ns, cin), dtype=torch.float32, device=x.device)
             ws = _ops._workspace(L.spr_scatter_workspace_bytes(ns, cin), x.device)
             dr, dr_n = _ops._get_range(dwf)          # published by the product that wrote dwf: no second scan of it
-            _lib.check(L.spr_kpconv_bwd_dx_r(_ops._ptr(q_pts), nq, _ops._ptr(s_pts), ns, _ops._ptr(nbr32), int(stride), kmax,
-                                             cin, _ops._ptr(kp.detach().contiguous()), n_kp, ctx.kp_extent,
-                                             _ops._ptr(dwf), _ops._ptr(dr), int(dr_n), _ops._ptr(dx), _ops._ptr(ws),
-                                             ws.numel(), _ops._stream(x)), "spr_kpconv_bwd_dx_r")
+            _lib.check(L.spr_kpconv_bwd_dx(_ops._ptr(q_pts), nq, _ops._ptr(s_pts), ns, _ops._ptr(nbr32), int(stride), kmax,
+                                           cin, _ops._ptr(kp.detach().contiguous()), n_kp, ctx.kp_extent,
+                                           _ops._ptr(dwf), _ops._ptr(dr), int(dr_n), _ops._ptr(dx), _ops._ptr(ws),
+                                           ws.numel(), _ops._stream(x)), "spr_kpconv_bwd_dx")
         if ctx.needs_input_grad[4]:
             # the first layer (cin = 1: constant input) is the ill-conditioned sum: float64 accumulation
             dw = _tn_product(wf, g, nq, n_kp * cin, cout, f64=(cin == 1)).view(n_kp, cin, cout)

@@ -839,18 +839,26 @@ int launch_core(const AttnPlanes& pl, int t, size_t tp, const int* cu, const int
 }
 }  // namespace
 
-static int attn_varlen_fwd_impl(const float* q, int q_stride, const float* k, int k_stride,
-                               const float* v, int v_stride, const int* cu,
-                               const int* kv_seg, int t, int nseg, int max_len_host, int nhead,
-                               int head_dim, float scale, float* out, int o_stride, float* lse_out, void* ws,
-                               size_t ws_bytes, void* stream_) {
+// lse (NULL = not wanted): receives [t, nhead] = log2 sum_j 2^(log2(e) q_i.k_j scale) per query and head for
+// spr_attn_varlen_bwd (the backward then skips its own pass over the keys).  *lse_written = 0 in
+// exact-f32 mode (attention mode 0, whose core does not produce it): lse is then untouched.
+extern "C" int spr_attn_varlen_fwd(const float* q, int q_stride, const float* k, int k_stride, const float* v,
+                                   int v_stride, const int* cu, const int* kv_seg, int t, int nseg,
+                                   int max_len_host, int nhead, int head_dim, float scale, float* out, int o_stride,
+                                   float* lse, int* lse_written, void* ws, size_t ws_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
+  SPR_REQUIRE(lse == nullptr || lse_written != nullptr, "attention: lse needs lse_written");
   SPR_REQUIRE(head_dim == HD, "attention: head_dim must be %d (got %d)", HD, head_dim);
   SPR_REQUIRE(t >= 1 && nseg >= 1 && nhead >= 1 && max_len_host >= 1, "attention: bad sizes");
   SPR_REQUIRE(q_stride % 4 == 0 && k_stride % 4 == 0 && v_stride % 4 == 0 && o_stride % 4 == 0,
               "attention: row strides must be multiples of 4 floats");
   SPR_REQUIRE((long)cdiv(max_len_host, QB) * nhead * nseg < (1l << 31), "attention: grid too large");
   const int mode = spr::g_attn_mode.load(std::memory_order_relaxed);
+  float* lse_out = nullptr;
+  if (lse != nullptr) {
+    *lse_written = attn_core_writes_lse(mode) ? 1 : 0;
+    if (*lse_written) lse_out = lse;
+  }
   if (mode == 0) {
     dim3 grid(cdiv(max_len_host, QB) * nhead * nseg);
     hipLaunchKernelGGL(k_attn, grid, dim3(256), 0, stream, q, q_stride, k, k_stride, v, v_stride, cu,
@@ -878,42 +886,11 @@ static int attn_varlen_fwd_impl(const float* q, int q_stride, const float* k, in
   return launch_core(pl, t, tp, cu, kv_seg, nseg, max_len_host, nhead, out, o_stride, mode, stream, lse_out);
 }
 
-extern "C" int spr_attn_varlen_fwd(const float* q, int q_stride, const float* k, int k_stride,
-                                   const float* v, int v_stride, const int* cu,
-                                   const int* kv_seg, int t, int nseg, int max_len_host, int nhead,
-                                   int head_dim, float scale, float* out, int o_stride, void* ws,
-                                   size_t ws_bytes, void* stream_) {
-  return attn_varlen_fwd_impl(q, q_stride, k, k_stride, v, v_stride, cu, kv_seg, t, nseg, max_len_host, nhead, head_dim,
-                              scale, out, o_stride, nullptr, ws, ws_bytes, stream_);
-}
-
-// The same, additionally handing out lse [t, nhead] = log2 sum_j 2^(log2(e) q_i.k_j scale) per query and head for
-// spr_attn_varlen_bwd_lse (the backward then skips its own pass over the keys).  *lse_written = 0 in
-// exact-f32 mode (attention mode 0, whose core does not produce it): lse is then untouched.
-extern "C" int spr_attn_varlen_fwd_lse(const float* q, int q_stride, const float* k, int k_stride, const float* v,
-                                       int v_stride, const int* cu, const int* kv_seg, int t, int nseg,
-                                       int max_len_host, int nhead, int head_dim, float scale, float* out, int o_stride,
-                                       float* lse, int* lse_written, void* ws, size_t ws_bytes, void* stream_) {
-  SPR_REQUIRE(lse != nullptr && lse_written != nullptr, "attention: lse / lse_written must not be null");
-  const bool can = attn_core_writes_lse(spr::g_attn_mode.load(std::memory_order_relaxed));
-  *lse_written = can ? 1 : 0;
-  return attn_varlen_fwd_impl(q, q_stride, k, k_stride, v, v_stride, cu, kv_seg, t, nseg, max_len_host, nhead, head_dim,
-                              scale, out, o_stride, can ? lse : nullptr, ws, ws_bytes, stream_);
-}
-
 extern "C" size_t spr_attn_inproj_workspace_bytes(int t, int nseg, int nhead, int head_dim) {
   if (t < 0 || nseg < 0 || nhead < 0 || head_dim < 0) return 0;
   // operand planes + (exact mode only) the fp32 [t, 3 d] projection
   return spr_attn_workspace_bytes(t, nseg, nhead, head_dim) +
          align_up((size_t)(t > 0 ? t : 1) * 3 * nhead * head_dim * sizeof(float), 256);
-}
-
-extern "C" int spr_attn_inproj_varlen_fwd(const float* x_qk, const float* x_v, int t, const float* w_in,
-                                          const float* b_in, const int* cu, const int* kv_seg, int nseg,
-                                          int max_len_host, int nhead, int head_dim, float scale, float* out,
-                                          int o_stride, void* ws, size_t ws_bytes, void* stream_) {
-  return spr_attn_inproj_varlen_fwd_r(x_qk, x_v, t, w_in, b_in, cu, kv_seg, nseg, max_len_host, nhead, head_dim, scale,
-                                      out, o_stride, nullptr, 0, nullptr, 0, nullptr, nullptr, ws, ws_bytes, stream_);
 }
 
 // Weight-side inputs of the fused in-projection, measured once per weight version:
@@ -927,12 +904,12 @@ extern "C" int spr_attn_inproj_prepare(const float* w_in, int d, float* out, voi
   return 0;
 }
 
-extern "C" int spr_attn_inproj_varlen_fwd_r(const float* x_qk, const float* x_v, int t, const float* w_in,
-                                            const float* b_in, const int* cu, const int* kv_seg, int nseg,
-                                            int max_len_host, int nhead, int head_dim, float scale, float* out,
-                                            int o_stride, const float* xqk_range, int xqk_range_n,
-                                            const float* xv_range, int xv_range_n, float* out_range,
-                                            const float* w_prep, void* ws, size_t ws_bytes, void* stream_) {
+extern "C" int spr_attn_inproj_varlen_fwd(const float* x_qk, const float* x_v, int t, const float* w_in,
+                                          const float* b_in, const int* cu, const int* kv_seg, int nseg,
+                                          int max_len_host, int nhead, int head_dim, float scale, float* out,
+                                          int o_stride, const float* xqk_range, int xqk_range_n,
+                                          const float* xv_range, int xv_range_n, float* out_range,
+                                          const float* w_prep, void* ws, size_t ws_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   SPR_REQUIRE(head_dim == HD, "attention: head_dim must be %d (got %d)", HD, head_dim);
   SPR_REQUIRE(nhead * head_dim == 256, "attention in-projection: d_model must be 256 (got %d)", nhead * head_dim);
@@ -978,10 +955,11 @@ extern "C" int spr_attn_inproj_varlen_fwd_r(const float* x_qk, const float* x_v,
       if (int rc = launch_linear_ranged(x_v, t, d, w_in + (size_t)2 * d * d, d, b_in + 2 * d, v, xvp, wp, stream))
         return rc;
       return spr_attn_varlen_fwd(qk, 2 * d, qk + d, 2 * d, v, d, cu, kv_seg, t, nseg, max_len_host, nhead,
-                                 head_dim, scale, out, o_stride, ws, planes_bytes, stream_);
+                                 head_dim, scale, out, o_stride, nullptr, nullptr, ws, planes_bytes, stream_);
     }
     return spr_attn_varlen_fwd(qkv, 3 * d, qkv + d, 3 * d, qkv + 2 * d, 3 * d, cu, kv_seg, t, nseg,
-                               max_len_host, nhead, head_dim, scale, out, o_stride, ws, planes_bytes, stream_);
+                               max_len_host, nhead, head_dim, scale, out, o_stride, nullptr, nullptr, ws, planes_bytes,
+                               stream_);
   }
   SPR_REQUIRE((long)cdiv(max_len_host, QB) * nhead * nseg < (1l << 31), "attention: grid too large");
   pl.cu = cu;

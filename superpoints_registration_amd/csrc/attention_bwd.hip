@@ -639,7 +639,7 @@ constexpr int DQ_BUF_HALVES = 4 * R_HALVES + 2 * C_HALVES;     // K: R + C plane
 constexpr int DKV_BUF_HALVES = 4 * R_HALVES + 4 * C_HALVES;    // Q and dO: R + C planes
 
 // grid (query tile, head, query segment)
-// HL: the per-query log-sum-exp comes from the forward (a.lse, spr_attn_varlen_fwd_lse): no sweep 1
+// HL: the per-query log-sum-exp comes from the forward (a.lse, spr_attn_varlen_fwd): no sweep 1
 template <bool PL, bool HL>
 __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void k_attn_bwd_dq_h(const AttnBwdArgs a, const float* __restrict__ scales,
                                                           const BwdPlanes pl) {
@@ -972,7 +972,8 @@ __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void k_attn_bwd_dkv_h(const A
 
 using namespace spr;
 
-static size_t attn_bwd_base_bytes(int t, int nhead) {
+// the least the backward runs with: its kernels then convert the fp32 tiles they stage themselves
+extern "C" size_t spr_attn_bwd_min_workspace_bytes(int t, int nhead) {
   // lse, dsum [t, nhead]; four max-|x| partial arrays and the four operand scales of the split-fp16 form
   return 2 * align_up((size_t)(t > 0 ? t : 1) * (size_t)(nhead > 0 ? nhead : 1) * sizeof(float), 256) +
          align_up((size_t)4 * kAmaxParts * sizeof(float), 256) + 256;
@@ -983,21 +984,20 @@ static size_t attn_bwd_plane_bytes(int t, int nseg, int nhead) {
   return 8 * align_up((size_t)(t > 0 ? t : 1) * d * 2, 256) + 6 * align_up(d * (size_t)attn_bwd_tc(t, nseg) * 2, 256) +
          align_up((size_t)(nseg + 2) * sizeof(int), 256);
 }
-extern "C" size_t spr_attn_bwd_workspace_bytes(int t, int nhead) { return attn_bwd_base_bytes(t, nhead); }
-// with room for the operand planes of the split-fp16 form (k_attn_bwd_pack); a workspace of only
-// spr_attn_bwd_workspace_bytes still works -- the kernels then convert the fp32 tiles they stage themselves
-extern "C" size_t spr_attn_bwd_workspace_bytes2(int t, int nseg, int nhead) {
-  return attn_bwd_base_bytes(t, nhead) + attn_bwd_plane_bytes(t, nseg, nhead);
+// with room for the operand planes of the split-fp16 form (k_attn_bwd_pack)
+extern "C" size_t spr_attn_bwd_workspace_bytes(int t, int nseg, int nhead) {
+  return spr_attn_bwd_min_workspace_bytes(t, nhead) + attn_bwd_plane_bytes(t, nseg, nhead);
 }
 
 // q, k, v, out (the forward's output), dout: [t, nhead * 32] with unit inner stride and the given row strides;
 // kv_seg: key segment of every query segment -- must be a permutation; q_seg: its inverse.
 // dq, dk, dv: [t, nhead * 32] contiguous, fully written.
-static int attn_varlen_bwd_impl(const float* q, int q_stride, const float* k, int k_stride, const float* v,
-                               int v_stride, const float* out, int o_stride, const float* dout, int do_stride,
-                               const float* lse_in, const int* cu, const int* kv_seg, const int* q_seg, int t, int nseg,
-                               int max_len_host, int nhead, int head_dim, float scale, float* dq, float* dk,
-                               float* dv, void* ws, size_t ws_bytes, void* stream_) {
+// lse_in [t, nhead]: what spr_attn_varlen_fwd handed out for the same q, k (NULL: computed here)
+extern "C" int spr_attn_varlen_bwd(const float* q, int q_stride, const float* k, int k_stride, const float* v,
+                                   int v_stride, const float* out, int o_stride, const float* dout, int do_stride,
+                                   const float* lse_in, const int* cu, const int* kv_seg, const int* q_seg, int t,
+                                   int nseg, int max_len_host, int nhead, int head_dim, float scale, float* dq,
+                                   float* dk, float* dv, void* ws, size_t ws_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   SPR_REQUIRE(head_dim == BHD, "attn_bwd: head_dim must be 32 (got %d)", head_dim);
   SPR_REQUIRE(q && k && v && out && dout && cu && kv_seg && q_seg && dq && dk && dv, "attn_bwd: null operand");
@@ -1006,7 +1006,7 @@ static int attn_varlen_bwd_impl(const float* q, int q_stride, const float* k, in
   SPR_REQUIRE(q_stride >= d && k_stride >= d && v_stride >= d && o_stride >= d && do_stride >= d &&
                   q_stride % 4 == 0 && k_stride % 4 == 0 && v_stride % 4 == 0 && o_stride % 4 == 0 && do_stride % 4 == 0,
               "attn_bwd: row strides must be multiples of 4 floats and >= nhead * 32");
-  SPR_REQUIRE(ws != nullptr && ws_bytes >= spr_attn_bwd_workspace_bytes(t, nhead), "attn_bwd: workspace too small");
+  SPR_REQUIRE(ws != nullptr && ws_bytes >= spr_attn_bwd_min_workspace_bytes(t, nhead), "attn_bwd: workspace too small");
   Workspace w(ws, ws_bytes);
   AttnBwdArgs a;
   a.lse = w.take<float>((size_t)t * nhead);
@@ -1035,7 +1035,7 @@ static int attn_varlen_bwd_impl(const float* q, int q_stride, const float* k, in
     constexpr size_t dkv_lds = (size_t)NB * DKV_BUF_HALVES * 2 + 4 * BT * sizeof(float);
     static_assert(dkv_lds >= sizeof(float) * 2 * 2 * 16 * 64, "the final reduction reuses the tile buffers");
     BwdPlanes pl{};
-    if (ws_bytes >= spr_attn_bwd_workspace_bytes2(t, nseg, nhead)) {
+    if (ws_bytes >= spr_attn_bwd_workspace_bytes(t, nseg, nhead)) {
       // operand planes written once (k_attn_bwd_pack), staged by 16-byte copies
       const int tc = attn_bwd_tc(t, nseg);
       _Float16** r[4] = {pl.rq, pl.rk, pl.rv, pl.ro};
@@ -1076,23 +1076,4 @@ static int attn_varlen_bwd_impl(const float* q, int q_stride, const float* k, in
   hipLaunchKernelGGL(k_attn_bwd_dkv, grid, dim3(256), 0, stream, a);
   SPR_LAUNCH_CHECK();
   return 0;
-}
-
-extern "C" int spr_attn_varlen_bwd(const float* q, int q_stride, const float* k, int k_stride, const float* v,
-                                   int v_stride, const float* out, int o_stride, const float* dout, int do_stride,
-                                   const int* cu, const int* kv_seg, const int* q_seg, int t, int nseg,
-                                   int max_len_host, int nhead, int head_dim, float scale, float* dq, float* dk,
-                                   float* dv, void* ws, size_t ws_bytes, void* stream_) {
-  return attn_varlen_bwd_impl(q, q_stride, k, k_stride, v, v_stride, out, o_stride, dout, do_stride, nullptr, cu, kv_seg,
-                              q_seg, t, nseg, max_len_host, nhead, head_dim, scale, dq, dk, dv, ws, ws_bytes, stream_);
-}
-
-// lse [t, nhead]: what spr_attn_varlen_fwd_lse handed out for the same q, k (NULL: computed here)
-extern "C" int spr_attn_varlen_bwd_lse(const float* q, int q_stride, const float* k, int k_stride, const float* v,
-                                       int v_stride, const float* out, int o_stride, const float* dout, int do_stride,
-                                       const float* lse, const int* cu, const int* kv_seg, const int* q_seg, int t,
-                                       int nseg, int max_len_host, int nhead, int head_dim, float scale, float* dq,
-                                       float* dk, float* dv, void* ws, size_t ws_bytes, void* stream_) {
-  return attn_varlen_bwd_impl(q, q_stride, k, k_stride, v, v_stride, out, o_stride, dout, do_stride, lse, cu, kv_seg,
-                              q_seg, t, nseg, max_len_host, nhead, head_dim, scale, dq, dk, dv, ws, ws_bytes, stream_);
 }

@@ -419,7 +419,7 @@ __global__ __launch_bounds__(256) void k_kpconv_aux2(const float* __restrict__ q
     }
     if (!DX) {   // neighbour count of the reference: rows whose feature sum is > 0
       bool pos = false;
-      if (flag != nullptr) {              // as the forward's kernel flagged them (spr_kpconv_weighted_features_f)
+      if (flag != nullptr) {              // as the forward's kernel flagged them (spr_kpconv_weighted_features)
         pos = ok && flag[id] != 0;
       } else if (ok) {                    // legacy entry: its own sequential sum (may differ at a sum of ~0)
         const float* xr = x + (size_t)id * cin;
@@ -681,10 +681,20 @@ extern "C" size_t spr_kpconv_weighted_features_workspace_bytes(int ns) {
   return align_up(n, 256) + align_up((n + 1) * 16, 256) + 256;
 }
 
-static int kpconv_weighted_features_impl(const float* q_xyz, int nq, const float* s_xyz, int ns, const int* nbr,
-                                         int nbr_stride, int kmax, const float* x, int cin, const float* kernel_points,
-                                         int n_kp, float kp_extent, float* wf, float* cnt, const unsigned char* flag,
-                                         hipStream_t stream) {
+// wf and cnt as the forward sums and counts them: same kernel, neighbours counted from the forward's per-support flags
+extern "C" int spr_kpconv_weighted_features(const float* q_xyz, int nq, const float* s_xyz, int ns, const int* nbr,
+                                            int nbr_stride, int kmax, const float* x, int cin,
+                                            const float* kernel_points, int n_kp, float kp_extent, float* wf,
+                                            float* cnt, void* ws, size_t ws_bytes, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SPR_REQUIRE(nq > 0 && ns > 0 && cin >= 1 && n_kp >= 1 && n_kp <= kKPmax && kp_extent > 0.f && kmax >= 1 &&
+                  kmax <= nbr_stride, "kpconv_weighted_features: bad arguments");
+  SPR_REQUIRE(ws && ws_bytes >= spr_kpconv_weighted_features_workspace_bytes(ns),
+              "kpconv_weighted_features: workspace too small");
+  unsigned char* flag = (unsigned char*)ws;
+  float4* sxf = (float4*)((char*)ws + align_up((size_t)ns, 256));
+  int* tile_ctr = (int*)((char*)sxf + align_up(((size_t)ns + 1) * 16, 256));
+  launch_rowflag(x, s_xyz, ns, cin, flag, sxf, tile_ctr, stream);
   if (cin == 32)
     hipLaunchKernelGGL((k_kpconv_aux2<false, true>), dim3(cdiv(nq, 4)), dim3(256), 0, stream, q_xyz, nq, s_xyz, ns, nbr,
                        nbr_stride, kmax, x, cin, kernel_points, n_kp, 1.0f / kp_extent, (const float*)nullptr, wf, cnt,
@@ -697,33 +707,6 @@ static int kpconv_weighted_features_impl(const float* q_xyz, int nq, const float
   return 0;
 }
 
-extern "C" int spr_kpconv_weighted_features(const float* q_xyz, int nq, const float* s_xyz, int ns, const int* nbr,
-                                            int nbr_stride, int kmax, const float* x, int cin,
-                                            const float* kernel_points, int n_kp, float kp_extent, float* wf,
-                                            float* cnt, void* stream_) {
-  SPR_REQUIRE(nq > 0 && ns > 0 && cin >= 1 && n_kp >= 1 && n_kp <= kKPmax && kp_extent > 0.f && kmax >= 1 &&
-                  kmax <= nbr_stride, "kpconv_weighted_features: bad arguments");
-  return kpconv_weighted_features_impl(q_xyz, nq, s_xyz, ns, nbr, nbr_stride, kmax, x, cin, kernel_points, n_kp,
-                                       kp_extent, wf, cnt, nullptr, (hipStream_t)stream_);
-}
-
-extern "C" int spr_kpconv_weighted_features_f(const float* q_xyz, int nq, const float* s_xyz, int ns, const int* nbr,
-                                              int nbr_stride, int kmax, const float* x, int cin,
-                                              const float* kernel_points, int n_kp, float kp_extent, float* wf,
-                                              float* cnt, void* ws, size_t ws_bytes, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  SPR_REQUIRE(nq > 0 && ns > 0 && cin >= 1 && n_kp >= 1 && n_kp <= kKPmax && kp_extent > 0.f && kmax >= 1 &&
-                  kmax <= nbr_stride, "kpconv_weighted_features: bad arguments");
-  SPR_REQUIRE(ws && ws_bytes >= spr_kpconv_weighted_features_workspace_bytes(ns),
-              "kpconv_weighted_features: workspace too small");
-  unsigned char* flag = (unsigned char*)ws;
-  float4* sxf = (float4*)((char*)ws + align_up((size_t)ns, 256));
-  int* tile_ctr = (int*)((char*)sxf + align_up(((size_t)ns + 1) * 16, 256));
-  launch_rowflag(x, s_xyz, ns, cin, flag, sxf, tile_ctr, stream);
-  return kpconv_weighted_features_impl(q_xyz, nq, s_xyz, ns, nbr, nbr_stride, kmax, x, cin, kernel_points, n_kp,
-                                       kp_extent, wf, cnt, flag, stream);
-}
-
 namespace {
 // an externally published range (n partials) as the kAmaxParts partials the fixed-point kernels read
 __global__ __launch_bounds__(256) void k_range_to_parts(const float* __restrict__ range, int n, float* __restrict__ parts) {
@@ -733,35 +716,15 @@ __global__ __launch_bounds__(256) void k_range_to_parts(const float* __restrict_
 }
 }  // namespace
 
-static int kpconv_bwd_dx_impl(const float* q_xyz, int nq, const float* s_xyz, int ns, const int* nbr,
-                              int nbr_stride, int kmax, int cin, const float* kernel_points, int n_kp,
-                              float kp_extent, const float* dwf, const float* dwf_range, int dwf_range_n, float* dx,
-                              void* ws, size_t ws_bytes, void* stream_);
-
-// dx [ns, cin] is fully written (ws: spr_scatter_workspace_bytes(ns, cin)); order-independent sums
+// dx [ns, cin] is fully written (ws: spr_scatter_workspace_bytes(ns, cin)); order-independent sums.
+// dwf_range: max |dwf| partials published by the product that wrote dwf (spr_linear's out_range): the 1 GB
+// tensor is then not scanned again for the fixed-point scale; NULL = measured here
 extern "C" int spr_kpconv_bwd_dx(const float* q_xyz, int nq, const float* s_xyz, int ns, const int* nbr,
                                  int nbr_stride, int kmax, int cin, const float* kernel_points, int n_kp,
-                                 float kp_extent, const float* dwf, float* dx, void* ws, size_t ws_bytes,
-                                 void* stream_) {
-  return kpconv_bwd_dx_impl(q_xyz, nq, s_xyz, ns, nbr, nbr_stride, kmax, cin, kernel_points, n_kp, kp_extent, dwf,
-                            nullptr, 0, dx, ws, ws_bytes, stream_);
-}
-// dwf_range: max |dwf| partials published by the product that wrote dwf (spr_linear_r's out_range): the 1 GB
-// tensor is then not scanned again for the fixed-point scale
-extern "C" int spr_kpconv_bwd_dx_r(const float* q_xyz, int nq, const float* s_xyz, int ns, const int* nbr,
-                                   int nbr_stride, int kmax, int cin, const float* kernel_points, int n_kp,
-                                   float kp_extent, const float* dwf, const float* dwf_range, int dwf_range_n, float* dx,
-                                   void* ws, size_t ws_bytes, void* stream_) {
-  SPR_REQUIRE(dwf_range == nullptr || dwf_range_n >= 1, "kpconv_bwd_dx: a range needs a count");
-  return kpconv_bwd_dx_impl(q_xyz, nq, s_xyz, ns, nbr, nbr_stride, kmax, cin, kernel_points, n_kp, kp_extent, dwf,
-                            dwf_range, dwf_range_n, dx, ws, ws_bytes, stream_);
-}
-
-static int kpconv_bwd_dx_impl(const float* q_xyz, int nq, const float* s_xyz, int ns, const int* nbr,
-                              int nbr_stride, int kmax, int cin, const float* kernel_points, int n_kp,
-                              float kp_extent, const float* dwf, const float* dwf_range, int dwf_range_n, float* dx,
-                              void* ws, size_t ws_bytes, void* stream_) {
+                                 float kp_extent, const float* dwf, const float* dwf_range, int dwf_range_n, float* dx,
+                                 void* ws, size_t ws_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
+  SPR_REQUIRE(dwf_range == nullptr || dwf_range_n >= 1, "kpconv_bwd_dx: a range needs a count");
   SPR_REQUIRE(nq > 0 && ns > 0 && cin >= 1 && n_kp >= 1 && n_kp <= kKPmax && kp_extent > 0.f && kmax >= 1 &&
                   kmax <= nbr_stride, "kpconv_bwd_dx: bad arguments");
   FxScratch f;

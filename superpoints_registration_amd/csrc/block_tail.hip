@@ -498,12 +498,15 @@ extern "C" size_t spr_block_tail_workspace_bytes(int n, int nb, int kb, int n_ou
          4 * align_up(kAmaxParts * sizeof(float), 256);
 }
 
-static int block_tail_impl(const float* xa, int ka, const float* wa, const float* xb, int kb, const float* wb,
-                           const float* add, const int* cu, const int* tiles, int n, int nb, int n_out, float eps,
-                           float slope, float* out, const float* xa_range, int xa_range_n, const float* wa_range,
-                           int wa_range_n, const float* xb_range, int xb_range_n, const float* wb_range,
-                           int wb_range_n, float* out_range, int out_range_n, const float* xa_mean,
-                           const float* xa_rstd, float xa_slope, void* ws, size_t ws_bytes, void* stream_) {
+// xa_mean / xa_rstd (both or neither): xa is the RAW input of a per-cloud InstanceNorm + LeakyReLU(xa_slope) whose
+// statistics the caller has (spr_instnorm_stats, [nb][ka]): lrelu(IN(lrelu(IN(xa)) wa^T) + ...).  xa_range must then
+// bound the NORMALISED values (sqrt(longest cloud) is always valid: |x - mean| <= sqrt(n - 1) sigma).
+extern "C" int spr_block_tail(const float* xa, int ka, const float* wa, const float* xb, int kb, const float* wb,
+                              const float* add, const int* cu, const int* tiles, int n, int nb, int n_out, float eps,
+                              float slope, float* out, const float* xa_range, int xa_range_n, const float* wa_range,
+                              int wa_range_n, const float* xb_range, int xb_range_n, const float* wb_range,
+                              int wb_range_n, float* out_range, int out_range_n, const float* xa_mean,
+                              const float* xa_rstd, float xa_slope, void* ws, size_t ws_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   SPR_REQUIRE(spr::gemm_mode() == 1, "block_tail: only in the split-fp16 product mode (spr_set_gemm_mode(1))");
   const TailShape sh = tail_shape(ka, kb, n_out);
@@ -561,30 +564,4 @@ static int block_tail_impl(const float* xa, int ka, const float* wa, const float
 #undef SPR_TAIL
   SPR_REQUIRE(false, "block_tail: no kernel for ka=%d kb=%d n_out=%d", ka, kb, n_out);
   return 1;
-}
-
-extern "C" int spr_block_tail(const float* xa, int ka, const float* wa, const float* xb, int kb, const float* wb,
-                              const float* add, const int* cu, const int* tiles, int n, int nb, int n_out, float eps,
-                              float slope, float* out, const float* xa_range, int xa_range_n, const float* wa_range,
-                              int wa_range_n, const float* xb_range, int xb_range_n, const float* wb_range,
-                              int wb_range_n, float* out_range, int out_range_n, void* ws, size_t ws_bytes,
-                              void* stream_) {
-  return block_tail_impl(xa, ka, wa, xb, kb, wb, add, cu, tiles, n, nb, n_out, eps, slope, out, xa_range, xa_range_n,
-                         wa_range, wa_range_n, xb_range, xb_range_n, wb_range, wb_range_n, out_range, out_range_n,
-                         nullptr, nullptr, 1.0f, ws, ws_bytes, stream_);
-}
-
-// The same with xa = the RAW input of a per-cloud InstanceNorm + LeakyReLU(xa_slope) whose statistics the caller
-// has (spr_instnorm_stats: xa_mean, xa_rstd [nb][ka]): lrelu(IN(lrelu(IN(xa)) wa^T) + ...).  xa_range must bound
-// the NORMALISED values (sqrt(longest cloud) is always valid: |x - mean| <= sqrt(n - 1) sigma).
-extern "C" int spr_block_tail_n(const float* xa, int ka, const float* wa, const float* xb, int kb, const float* wb,
-                                const float* add, const int* cu, const int* tiles, int n, int nb, int n_out, float eps,
-                                float slope, float* out, const float* xa_range, int xa_range_n, const float* wa_range,
-                                int wa_range_n, const float* xb_range, int xb_range_n, const float* wb_range,
-                                int wb_range_n, float* out_range, int out_range_n, const float* xa_mean,
-                                const float* xa_rstd, float xa_slope, void* ws, size_t ws_bytes, void* stream_) {
-  SPR_REQUIRE(xa_mean != nullptr && xa_rstd != nullptr, "block_tail_n: statistics missing");
-  return block_tail_impl(xa, ka, wa, xb, kb, wb, add, cu, tiles, n, nb, n_out, eps, slope, out, xa_range, xa_range_n,
-                         wa_range, wa_range_n, xb_range, xb_range_n, wb_range, wb_range_n, out_range, out_range_n,
-                         xa_mean, xa_rstd, xa_slope, ws, ws_bytes, stream_);
 }

@@ -216,7 +216,7 @@ extern "C" int spr_absmax_multi(const void* jobs_dev, int njobs, int parts_per_j
 }
 
 // Range of a tensor that does not change between calls (weights): measured once by the caller
-// and handed to spr_linear_r / spr_kpconv_fwd_r as w_range (spr_range_parts() floats).
+// and handed to spr_linear / spr_kpconv_fwd as w_range (spr_range_parts() floats).
 extern "C" int spr_range_parts(void) { return spr::kAmaxParts; }
 extern "C" int spr_absmax(const float* x, long rows, int cols, long stride, float* parts, void* stream_) {
   SPR_REQUIRE(x != nullptr && parts != nullptr && rows >= 1 && cols >= 1 && stride >= cols, "absmax: bad arguments");

@@ -1368,37 +1368,16 @@ extern "C" size_t spr_kpconv_workspace_bytes(int nq, int ns, int cin, int cout) 
          2 * align_up(kAmaxParts * sizeof(float), 256) + spr_kpconv_plan_bytes(nq) + 256;
 }
 
+// x_range / w_range: operand ranges handed in (see spr_linear); NULL = measured here.
+// plan / wplanes: spr_kpconv_plan of THIS neighbour matrix (same nq, ns, stride, kmax, rows_sorted) and
+// spr_kpconv_prep_weights of THESE weights with THIS w_range; NULL = built here, per call.
 extern "C" int spr_kpconv_fwd(const float* q_xyz, int nq, const float* s_xyz, int ns,
                               const int* nbr, int nbr_stride, int kmax, int rows_sorted,
                               const float* x, int cin, const float* weights, int cout,
                               const float* kernel_points, int n_kp, float kp_extent,
-                              float* out, int impl, void* ws, size_t ws_bytes,
+                              float* out, int impl, const float* x_range, int x_range_n, const float* w_range,
+                              int w_range_n, const void* plan, const void* wplanes, void* ws, size_t ws_bytes,
                               void* stream_) {
-  return spr_kpconv_fwd_r(q_xyz, nq, s_xyz, ns, nbr, nbr_stride, kmax, rows_sorted, x, cin, weights, cout, kernel_points,
-                          n_kp, kp_extent, out, impl, nullptr, 0, nullptr, 0, ws, ws_bytes, stream_);
-}
-
-// x_range / w_range: operand ranges handed in (see spr_linear_r); NULL = measured here.
-extern "C" int spr_kpconv_fwd_r(const float* q_xyz, int nq, const float* s_xyz, int ns,
-                                const int* nbr, int nbr_stride, int kmax, int rows_sorted,
-                                const float* x, int cin, const float* weights, int cout,
-                                const float* kernel_points, int n_kp, float kp_extent,
-                                float* out, int impl, const float* x_range, int x_range_n, const float* w_range,
-                                int w_range_n, void* ws, size_t ws_bytes, void* stream_) {
-  return spr_kpconv_fwd_p(q_xyz, nq, s_xyz, ns, nbr, nbr_stride, kmax, rows_sorted, x, cin, weights, cout, kernel_points,
-                          n_kp, kp_extent, out, impl, x_range, x_range_n, w_range, w_range_n, nullptr, nullptr, ws,
-                          ws_bytes, stream_);
-}
-
-// plan / wplanes: spr_kpconv_plan of THIS neighbour matrix (same nq, ns, stride, kmax, rows_sorted) and
-// spr_kpconv_prep_weights of THESE weights with THIS w_range; NULL = built here, per call.
-extern "C" int spr_kpconv_fwd_p(const float* q_xyz, int nq, const float* s_xyz, int ns,
-                                const int* nbr, int nbr_stride, int kmax, int rows_sorted,
-                                const float* x, int cin, const float* weights, int cout,
-                                const float* kernel_points, int n_kp, float kp_extent,
-                                float* out, int impl, const float* x_range, int x_range_n, const float* w_range,
-                                int w_range_n, const void* plan, const void* wplanes, void* ws, size_t ws_bytes,
-                                void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   SPR_REQUIRE((x_range == nullptr || x_range_n >= 1) && (w_range == nullptr || w_range_n >= 1),
               "kpconv: a range needs a count");

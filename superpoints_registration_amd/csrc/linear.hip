@@ -992,10 +992,10 @@ int spr::launch_gemm_grouped(const float* a, int k, const float* b, float* c, co
 
 extern "C" size_t spr_linear_workspace_bytes(void) { return 2 * align_up(kAmaxParts * sizeof(float), 256); }
 
-extern "C" int spr_linear_r(const float* x, int m, int k, const float* w, int n, const float* bias,
-                            const float* residual, int act, float* out, const float* x_range, int x_range_n,
-                            const float* w_range, int w_range_n, float* out_range, int out_range_cap,
-                            int* out_range_n_host, void* ws, size_t ws_bytes, void* stream_) {
+extern "C" int spr_linear(const float* x, int m, int k, const float* w, int n, const float* bias,
+                          const float* residual, int act, float* out, const float* x_range, int x_range_n,
+                          const float* w_range, int w_range_n, float* out_range, int out_range_cap,
+                          int* out_range_n_host, void* ws, size_t ws_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   if (out_range_n_host) *out_range_n_host = 0;
   SPR_REQUIRE(m > 0 && k > 0 && n > 0, "linear: bad sizes m=%d k=%d n=%d", m, k, n);
@@ -1046,13 +1046,6 @@ extern "C" int spr_linear_r(const float* x, int m, int k, const float* w, int n,
 #undef SPR_LG
 }
 
-extern "C" int spr_linear(const float* x, int m, int k, const float* w, int n, const float* bias,
-                          const float* residual, int act, float* out, void* ws, size_t ws_bytes,
-                          void* stream_) {
-  return spr_linear_r(x, m, k, w, n, bias, residual, act, out, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, ws, ws_bytes,
-                      stream_);
-}
-
 extern "C" int spr_set_gemm_mode(int mode) {
   SPR_REQUIRE(mode == 0 || mode == 1, "gemm mode must be 0 (exact f32 MFMA) or 1 (split-fp16)");
   spr::g_gemm_mode.store(mode);
@@ -1064,9 +1057,9 @@ extern "C" int spr_layernorm_range_count(int m) {
   return kLnRangeSlots;
 }
 
-extern "C" int spr_layernorm_r(const float* x, int m, int c, const float* gamma, const float* beta,
-                               float eps, const float* pos, float* out_norm, float* out_pos, float* range_norm,
-                               float* range_pos, void* stream_) {
+extern "C" int spr_layernorm(const float* x, int m, int c, const float* gamma, const float* beta,
+                             float eps, const float* pos, float* out_norm, float* out_pos, float* range_norm,
+                             float* range_pos, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   SPR_REQUIRE(m > 0 && c % 64 == 0 && c <= 1024, "layernorm: c must be a multiple of 64 and <= 1024 (c=%d)", c);
   SPR_REQUIRE(out_pos == nullptr || pos != nullptr, "layernorm: out_pos needs pos");
@@ -1082,12 +1075,6 @@ extern "C" int spr_layernorm_r(const float* x, int m, int c, const float* gamma,
                        pos, out_norm, out_pos, range_norm, range_pos);
   SPR_LAUNCH_CHECK();
   return 0;
-}
-
-extern "C" int spr_layernorm(const float* x, int m, int c, const float* gamma, const float* beta,
-                             float eps, const float* pos, float* out_norm, float* out_pos,
-                             void* stream_) {
-  return spr_layernorm_r(x, m, c, gamma, beta, eps, pos, out_norm, out_pos, nullptr, nullptr, stream_);
 }
 
 extern "C" int spr_posemb_sine(const float* xyz, int n, int d_model, float scale, float temperature,

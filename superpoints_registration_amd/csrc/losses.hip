@@ -361,8 +361,12 @@ extern "C" int spr_infonce_pair(const float* anchor_feat, int n, const float* po
   hipLaunchKernelGGL(k_wsym, dim3(cdiv(d * d, 256)), dim3(256), 0, stream, W, d, wsym);
   hipLaunchKernelGGL(k_transform, dim3(cdiv(n, 256)), dim3(256), 0, stream, pose_gt, anchor_xyz, n, axyz);
   // logits = (A W_sym) B^T : W_sym is symmetric, so the NT GEMM applies it as is
-  if (int rc = spr_linear(anchor_feat, n, d, wsym, d, nullptr, nullptr, SPR_ACT_NONE, t, lw1, lws, stream_)) return rc;
-  if (int rc = spr_linear(t, n, d, positive_feat, m, nullptr, nullptr, SPR_ACT_NONE, logits, lw2, lws, stream_)) return rc;
+  if (int rc = spr_linear(anchor_feat, n, d, wsym, d, nullptr, nullptr, SPR_ACT_NONE, t, nullptr, 0, nullptr, 0,
+                          nullptr, 0, nullptr, lw1, lws, stream_))
+    return rc;
+  if (int rc = spr_linear(t, n, d, positive_feat, m, nullptr, nullptr, SPR_ACT_NONE, logits, nullptr, 0, nullptr, 0,
+                          nullptr, 0, nullptr, lw2, lws, stream_))
+    return rc;
   hipLaunchKernelGGL(k_infonce_rows, dim3(cdiv((long)n * 64, 256)), dim3(256), 0, stream, logits, n, m, axyz,
                      positive_xyz, r_p, r_n, rl, rm);
   hipLaunchKernelGGL(k_pair_partial, dim3(nb), dim3(RB), 0, stream, rl, rm, n, pa, pb);
@@ -429,8 +433,12 @@ extern "C" int spr_infonce_pair_dlogits(const float* anchor_feat, int n, const f
   SPR_REQUIRE(lw2 != nullptr, "infonce_bwd: workspace carve failed");
   hipLaunchKernelGGL(k_wsym, dim3(cdiv(d * d, 256)), dim3(256), 0, stream, W, d, wsym_out);
   hipLaunchKernelGGL(k_transform, dim3(cdiv(n, 256)), dim3(256), 0, stream, pose_gt, anchor_xyz, n, axyz);
-  if (int rc = spr_linear(anchor_feat, n, d, wsym_out, d, nullptr, nullptr, SPR_ACT_NONE, t_out, lw1, lws, stream_)) return rc;
-  if (int rc = spr_linear(t_out, n, d, positive_feat, m, nullptr, nullptr, SPR_ACT_NONE, logits, lw2, lws, stream_)) return rc;
+  if (int rc = spr_linear(anchor_feat, n, d, wsym_out, d, nullptr, nullptr, SPR_ACT_NONE, t_out, nullptr, 0, nullptr, 0,
+                          nullptr, 0, nullptr, lw1, lws, stream_))
+    return rc;
+  if (int rc = spr_linear(t_out, n, d, positive_feat, m, nullptr, nullptr, SPR_ACT_NONE, logits, nullptr, 0, nullptr, 0,
+                          nullptr, 0, nullptr, lw2, lws, stream_))
+    return rc;
   hipLaunchKernelGGL(k_infonce_dlogits, dim3(cdiv((long)n * 64, 256)), dim3(256), 0, stream, logits, n, m, axyz,
                      positive_xyz, r_p, r_n, dlogits, row_mask);
   SPR_LAUNCH_CHECK();

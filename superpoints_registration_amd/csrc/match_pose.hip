@@ -1289,9 +1289,9 @@ int corr_gemm(const Corr& c, int g, int epi_mode, const float* epi, hipStream_t 
 }
 }  // namespace
 
-extern "C" int spr_match_dualsoftmax2(const float* feat, int d, const int* cu, const int* cu_host,
-                                      int npairs, float* match_val, float* match_val2, int* match_ind, void* ws,
-                                      size_t ws_bytes, void* stream_) {
+extern "C" int spr_match_dualsoftmax(const float* feat, int d, const int* cu, const int* cu_host,
+                                     int npairs, float* match_val, float* match_val2, int* match_ind, void* ws,
+                                     size_t ws_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   SPR_REQUIRE(npairs >= 1 && d % 32 == 0, "match: need npairs >= 1 and d %% 32 == 0");
   SPR_REQUIRE(ws_bytes >= match_ws_bytes(cu_host, npairs), "match: workspace too small");
@@ -1325,12 +1325,6 @@ extern "C" int spr_match_dualsoftmax2(const float* feat, int d, const int* cu, c
   }
   SPR_LAUNCH_CHECK();
   return 0;
-}
-
-extern "C" int spr_match_dualsoftmax(const float* feat, int d, const int* cu, const int* cu_host,
-                                     int npairs, float* match_val, int* match_ind, void* ws,
-                                     size_t ws_bytes, void* stream_) {
-  return spr_match_dualsoftmax2(feat, d, cu, cu_host, npairs, match_val, nullptr, match_ind, ws, ws_bytes, stream_);
 }
 
 extern "C" int spr_pose_residuals(const float* pose, const float* a, const float* b, const int* pair_cu,
@@ -1396,7 +1390,7 @@ extern "C" int spr_sinkhorn_correspondences(const float* feat, int d, const floa
   return 0;
 }
 
-// spr_match_dualsoftmax2 + spr_sinkhorn_correspondences of the SAME features in one call (what RegTR's inference
+// spr_match_dualsoftmax + spr_sinkhorn_correspondences of the SAME features in one call (what RegTR's inference
 // forward runs back to back, qk_regtr_full.py:453-479 and :525-536): the scaled correlation matrices are computed
 // and stored once; the Sinkhorn passes read them through the affinity view (struct Aff).  Outputs are bit for bit
 // those of the two separate calls.  match_val2 may be NULL.  Workspace: spr_match_workspace_bytes.

@@ -388,18 +388,12 @@ extern "C" size_t spr_instnorm_workspace_bytes(int max_len, int nb, int c) {
   return align_up(B * ns * 2 * C * sizeof(double), 256) + 2 * align_up(B * C * sizeof(float), 256);
 }
 
-extern "C" int spr_instnorm(const float* x, const int* cu, int n, int nb, int max_len_host, int c,
-                            float eps, int norm, const float* add, float slope, float* out,
-                            void* ws, size_t ws_bytes, void* stream_) {
-  return spr_instnorm_r(x, cu, n, nb, max_len_host, c, eps, norm, add, slope, out, nullptr, 0, ws, ws_bytes, stream_);
-}
-
 // out_range: NULL, or out_range_n (a power of two) zero-initialised floats that receive partial
 // maxima of |out| (operand-range hand-over to the consuming GEMM / KPConv); a few hundred slots
 // keep the atomic traffic per address low on the largest tensors.
-extern "C" int spr_instnorm_r(const float* x, const int* cu, int n, int nb, int max_len_host, int c,
-                              float eps, int norm, const float* add, float slope, float* out, float* out_range,
-                              int out_range_n, void* ws, size_t ws_bytes, void* stream_) {
+extern "C" int spr_instnorm(const float* x, const int* cu, int n, int nb, int max_len_host, int c,
+                            float eps, int norm, const float* add, float slope, float* out, float* out_range,
+                            int out_range_n, void* ws, size_t ws_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   SPR_REQUIRE(out_range == nullptr || (out_range_n >= 1 && (out_range_n & (out_range_n - 1)) == 0),
               "instnorm: out_range_n must be a power of two");
@@ -428,7 +422,7 @@ extern "C" int spr_instnorm_r(const float* x, const int* cu, int n, int nb, int 
 }
 
 // Statistics only: mean [nb][c] and rstd [nb][c] of a per-cloud InstanceNorm (the two passes k_in_stats / k_in_final
-// of spr_instnorm, bit for bit), for consumers that normalise on load (spr_block_tail_n).
+// of spr_instnorm, bit for bit), for consumers that normalise on load (spr_block_tail with xa_mean / xa_rstd).
 extern "C" int spr_instnorm_stats(const float* x, const int* cu, int n, int nb, int max_len_host, int c, float eps,
                                   float* mean, float* rstd, void* ws, size_t ws_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
@@ -491,27 +485,9 @@ extern "C" int spr_instnorm_bwd(const float* x, const float* out, const float* d
   return 0;
 }
 
-extern "C" int spr_maxpool_gather(const float* x, int ns, int c, const int* idx, int nq,
-                                  int idx_stride, int k, float* out, void* stream_) {
-  return spr_maxpool_gather_r(x, ns, c, idx, nq, idx_stride, k, out, nullptr, 0, stream_);
-}
-
-// out_range: as in spr_instnorm_r.
-extern "C" int spr_maxpool_gather_r(const float* x, int ns, int c, const int* idx, int nq, int idx_stride, int k,
-                                    float* out, float* out_range, int out_range_n, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  SPR_REQUIRE(out_range == nullptr || (out_range_n >= 1 && (out_range_n & (out_range_n - 1)) == 0),
-              "maxpool: out_range_n must be a power of two");
-  SPR_REQUIRE(nq > 0 && ns > 0 && c % 4 == 0 && k >= 1 && k <= idx_stride, "maxpool: bad arguments");
-  const long total = (long)nq * (c / 4);
-  hipLaunchKernelGGL(k_maxpool, dim3(cdiv(total, 256)), dim3(256), 0, stream, x, ns, c, idx, nq,
-                     idx_stride, k, out, out_range, out_range_n, (const int*)nullptr);
-  SPR_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int spr_maxpool_gather_o(const float* x, int ns, int c, const int* idx, int nq, int idx_stride, int k,
-                                    const int* order, float* out, float* out_range, int out_range_n, void* stream_) {
+// order: NULL, or the permutation of [0, nq) in which the queries are walked; out_range: as in spr_instnorm.
+extern "C" int spr_maxpool_gather(const float* x, int ns, int c, const int* idx, int nq, int idx_stride, int k,
+                                  const int* order, float* out, float* out_range, int out_range_n, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   SPR_REQUIRE(out_range == nullptr || (out_range_n >= 1 && (out_range_n & (out_range_n - 1)) == 0),
               "maxpool: out_range_n must be a power of two");

@@ -1093,29 +1093,18 @@ extern "C" int spr_radius_table_build(const float* s_xyz, const int* s_cu, int n
 // self != 0: the queries ARE the table's supports (same array, same cu) -> cell-order walk.  slot in
 // [0, spr_radius_table_slots()): one per query call against this table build (its max row count).
 // *max_count as in spr_radius_neighbors (-1 extent too large, -2 table overflow: use algo 1).
+// algo, the selection algorithm: 0 = one thread per query (scan of its 27 cells into a scratch row + rank sort in
+// registers: the cheaper one for sparse rows), 1 = one wave per query (one pass, the row in registers, no scratch: the
+// faster one when rows are dense -- more supports in range than `limit`), -1 = the library's choice.
 extern "C" int spr_radius_table_query(const float* q_xyz, const int* q_cu, int nq, int self, int ns, int nb,
                                       float radius, int limit, int slot, const void* table, int* out_idx,
-                                      int* max_count, void* ws, size_t ws_bytes, void* stream_) {
+                                      int* max_count, int algo, void* ws, size_t ws_bytes, void* stream_) {
   SPR_REQUIRE(q_xyz && q_cu && table && out_idx && max_count && nq > 0 && ns > 0 && nb >= 1, "radius_table_query: bad arguments");
   SPR_REQUIRE(limit >= 1 && limit <= 128, "radius_table_query: limit must be in [1,128], got %d", limit);
   SPR_REQUIRE(slot >= 0 && slot < kTableSlots, "radius_table_query: slot out of range");
   SPR_REQUIRE(!self || nq == ns, "radius_table_query: a self search has nq == ns");
-  SPR_REQUIRE(ws != nullptr && ws_bytes >= table_query_ws_bytes(nq), "radius_table_query: workspace too small");
-  return table_query(q_xyz, q_cu, nq, self ? 1 : 0, ns, nb, radius, limit, slot, table, out_idx, max_count, ws, ws_bytes,
-                     (hipStream_t)stream_);
-}
-
-// The same with the selection algorithm chosen by the caller: 0 = one thread per query (scan of its 27 cells into a
-// scratch row + rank sort in registers: the cheaper one for sparse rows), 1 = one wave per query (one pass, the row in
-// registers, no scratch: the faster one when rows are dense -- more supports in range than `limit`).
-extern "C" int spr_radius_table_query_a(const float* q_xyz, const int* q_cu, int nq, int self, int ns, int nb,
-                                        float radius, int limit, int slot, const void* table, int* out_idx,
-                                        int* max_count, int algo, void* ws, size_t ws_bytes, void* stream_) {
-  SPR_REQUIRE(q_xyz && q_cu && table && out_idx && max_count && nq > 0 && ns > 0 && nb >= 1, "radius_table_query: bad arguments");
-  SPR_REQUIRE(limit >= 1 && limit <= 128, "radius_table_query: limit must be in [1,128], got %d", limit);
-  SPR_REQUIRE(slot >= 0 && slot < kTableSlots, "radius_table_query: slot out of range");
-  SPR_REQUIRE(!self || nq == ns, "radius_table_query: a self search has nq == ns");
-  SPR_REQUIRE(algo == 0 || algo == 1, "radius_table_query: algo must be 0 (thread per query) or 1 (wave per query)");
+  SPR_REQUIRE(algo >= -1 && algo <= 1,
+              "radius_table_query: algo must be 0 (thread per query), 1 (wave per query) or -1 (the library's choice)");
   SPR_REQUIRE(ws != nullptr && ws_bytes >= table_query_ws_bytes(nq), "radius_table_query: workspace too small");
   return table_query(q_xyz, q_cu, nq, self ? 1 : 0, ns, nb, radius, limit, slot, table, out_idx, max_count, ws, ws_bytes,
                      (hipStream_t)stream_, algo);

@@ -325,15 +325,10 @@ class RadiusTable:
         out = torch.empty((nq, limit), dtype=torch.int32, device=queries.device)
         mc = torch.empty((1,), dtype=torch.int32, device=queries.device)
         slot, self._slot = self._slot, self._slot + 1
-        if dense is None:
-            _lib.check(L.spr_radius_table_query(_ptr(queries), _ptr(q_cu), nq, self_search, self.ns, self.nb, self.radius,
-                                                int(limit), slot, _ptr(self.blob), _ptr(out), _ptr(mc), _ptr(ws),
-                                                ws.numel(), _stream(queries)), "spr_radius_table_query")
-        else:
-            _lib.check(L.spr_radius_table_query_a(_ptr(queries), _ptr(q_cu), nq, self_search, self.ns, self.nb,
-                                                  self.radius, int(limit), slot, _ptr(self.blob), _ptr(out), _ptr(mc),
-                                                  1 if dense else 0, _ptr(ws), ws.numel(), _stream(queries)),
-                       "spr_radius_table_query_a")
+        _lib.check(L.spr_radius_table_query(_ptr(queries), _ptr(q_cu), nq, self_search, self.ns, self.nb, self.radius,
+                                            int(limit), slot, _ptr(self.blob), _ptr(out), _ptr(mc),
+                                            -1 if dense is None else int(bool(dense)), _ptr(ws), ws.numel(),
+                                            _stream(queries)), "spr_radius_table_query")
         m = int(mc.item())
         if m == -2:     # cell table too small for this geometry: exact same result, slower path
             return radius_neighbors(queries, self.supports, q_cu, self.s_cu, self.radius, limit, True, algo=1)
@@ -393,11 +388,11 @@ def kpconv_raw(q_pts, s_pts, nbr, x, weights, kernel_points, kp_extent: float, r
             plan = _kpconv_plan(nbr, nq, ns, int(stride), kmax, bool(rows_sorted), order)
         if wr is not None:
             wplanes = _kpconv_wplanes(weights, wr, wr_n)
-    _lib.check(L.spr_kpconv_fwd_p(_ptr(q_pts), nq, _ptr(s_pts), ns, _ptr(nbr), int(stride), kmax,
-                                  int(bool(rows_sorted)), _ptr(x), cin, _ptr(weights), cout,
-                                  _ptr(kernel_points), n_kp, float(kp_extent), _ptr(out), int(impl),
-                                  _ptr(xr), int(xr_n), _ptr(wr), int(wr_n), _ptr(plan), _ptr(wplanes),
-                                  _ptr(ws), ws.numel(), _stream(x)), "spr_kpconv_fwd_p")
+    _lib.check(L.spr_kpconv_fwd(_ptr(q_pts), nq, _ptr(s_pts), ns, _ptr(nbr), int(stride), kmax,
+                                int(bool(rows_sorted)), _ptr(x), cin, _ptr(weights), cout,
+                                _ptr(kernel_points), n_kp, float(kp_extent), _ptr(out), int(impl),
+                                _ptr(xr), int(xr_n), _ptr(wr), int(wr_n), _ptr(plan), _ptr(wplanes),
+                                _ptr(ws), ws.numel(), _stream(x)), "spr_kpconv_fwd")
     return out
 
 
@@ -482,11 +477,10 @@ def instnorm_raw(x, cu, eps: float = 1e-5, norm: bool = True, add=None, slope: f
     ws = _workspace(L.spr_instnorm_workspace_bytes(max_len, nb, c), x.device)
     cnt = _STREAM_SLOTS
     rng = _zero_slots(cnt, x.device)
-    _lib.check(L.spr_instnorm_r(_ptr(x), _ptr(cu), n, nb, max_len, c, float(eps), int(bool(norm)), _ptr(add),
-                                float(slope), _ptr(out), _ptr(rng), cnt, _ptr(ws), ws.numel(), _stream(x)),
-               "spr_instnorm_r")
-    if rng is not None:
-        _set_range(out, rng, cnt)
+    _lib.check(L.spr_instnorm(_ptr(x), _ptr(cu), n, nb, max_len, c, float(eps), int(bool(norm)), _ptr(add),
+                              float(slope), _ptr(out), _ptr(rng), cnt, _ptr(ws), ws.numel(), _stream(x)),
+               "spr_instnorm")
+    _set_range(out, rng, cnt)
     return out
 
 
@@ -553,7 +547,7 @@ def block_tail(xa, wa, cu, xb=None, wb=None, add=None, eps: float = 1e-5, slope:
     """a5, inference: lrelu(IN(xa wa^T) + (IN(xb wb^T) | add), slope) without the un-normalised
     projections ever being written (spr_block_tail).  The caller checks block_tail_tile_rows first.
     xa_stats = (mean, rstd) of instnorm_stats(xa): xa is then the RAW input of a per-cloud InstanceNorm +
-    LeakyReLU(xa_slope) that runs while the tiles are staged (spr_block_tail_n) -- the bottleneck block's norm
+    LeakyReLU(xa_slope) that runs while the tiles are staged -- the bottleneck block's norm
     behind its KPConv costs no pass of its own."""
     xa = _dev(xa, "xa", torch.float32)
     wa = _dev(wa, "wa", torch.float32)
@@ -589,21 +583,16 @@ def block_tail(xa, wa, cu, xb=None, wb=None, add=None, eps: float = 1e-5, slope:
         wbr, wbr_n = _static_range(wb)
     cnt = _STREAM_SLOTS
     rng = _zero_slots(cnt, xa.device)
+    mean = rstd = None
     if xa_stats is not None:
         mean, rstd = xa_stats
         assert mean.shape == (nb, ka) and rstd.shape == (nb, ka) and mean.is_contiguous() and rstd.is_contiguous()
-        _lib.check(L.spr_block_tail_n(_ptr(xa), ka, _ptr(wa), _ptr(xb), kb, _ptr(wb), _ptr(add), _ptr(cu), _ptr(tiles),
-                                      n, nb, n_out, float(eps), float(slope), _ptr(out), _ptr(xar), int(xar_n),
-                                      _ptr(war), int(war_n), _ptr(xbr), int(xbr_n), _ptr(wbr), int(wbr_n),
-                                      _ptr(rng), cnt, _ptr(mean), _ptr(rstd), float(xa_slope), _ptr(ws), ws.numel(),
-                                      _stream(xa)), "spr_block_tail_n")
-    else:
-        _lib.check(L.spr_block_tail(_ptr(xa), ka, _ptr(wa), _ptr(xb), kb, _ptr(wb), _ptr(add), _ptr(cu), _ptr(tiles),
-                                    n, nb, n_out, float(eps), float(slope), _ptr(out), _ptr(xar), int(xar_n),
-                                    _ptr(war), int(war_n), _ptr(xbr), int(xbr_n), _ptr(wbr), int(wbr_n),
-                                    _ptr(rng), cnt, _ptr(ws), ws.numel(), _stream(xa)), "spr_block_tail")
-    if rng is not None:
-        _set_range(out, rng, cnt)
+    _lib.check(L.spr_block_tail(_ptr(xa), ka, _ptr(wa), _ptr(xb), kb, _ptr(wb), _ptr(add), _ptr(cu), _ptr(tiles),
+                                n, nb, n_out, float(eps), float(slope), _ptr(out), _ptr(xar), int(xar_n),
+                                _ptr(war), int(war_n), _ptr(xbr), int(xbr_n), _ptr(wbr), int(wbr_n),
+                                _ptr(rng), cnt, _ptr(mean), _ptr(rstd), float(xa_slope), _ptr(ws), ws.numel(),
+                                _stream(xa)), "spr_block_tail")
+    _set_range(out, rng, cnt)
     return out
 
 
@@ -642,16 +631,11 @@ def maxpool_raw(x, idx, order=None) -> torch.Tensor:
     L = _lib.lib()
     cnt = _STREAM_SLOTS
     rng = _zero_slots(cnt, x.device)
-    if order is not None:
-        if order.dtype != torch.int32 or order.numel() != nq or not order.is_contiguous():
-            raise ValueError("maxpool: order must be a contiguous int32 permutation of the query rows")
-        _lib.check(L.spr_maxpool_gather_o(_ptr(x), ns, c, _ptr(idx), nq, int(stride), k, _ptr(order), _ptr(out),
-                                          _ptr(rng), cnt, _stream(x)), "spr_maxpool_gather_o")
-    else:
-        _lib.check(L.spr_maxpool_gather_r(_ptr(x), ns, c, _ptr(idx), nq, int(stride), k, _ptr(out), _ptr(rng), cnt,
-                                          _stream(x)), "spr_maxpool_gather_r")
-    if rng is not None:
-        _set_range(out, rng, cnt)
+    if order is not None and (order.dtype != torch.int32 or order.numel() != nq or not order.is_contiguous()):
+        raise ValueError("maxpool: order must be a contiguous int32 permutation of the query rows")
+    _lib.check(L.spr_maxpool_gather(_ptr(x), ns, c, _ptr(idx), nq, int(stride), k, _ptr(order), _ptr(out),
+                                    _ptr(rng), cnt, _stream(x)), "spr_maxpool_gather")
+    _set_range(out, rng, cnt)
     return out
 
 
@@ -682,10 +666,10 @@ def linear_raw(x, weight, bias=None, residual=None, act: int = ACT_NONE) -> torc
     # outputs that go on into another GEMM (no residual: FFN hidden, projections) publish their range
     orng = torch.empty((_RANGE_CAP,), dtype=torch.float32, device=x.device) if residual is None else None
     on = ctypes.c_int(0)
-    _lib.check(L.spr_linear_r(_ptr(x), m, k, _ptr(weight), n, _ptr(bias), _ptr(residual), int(act), _ptr(out),
-                              _ptr(xr), int(xr_n), _ptr(wr), int(wr_n), _ptr(orng),
-                              _RANGE_CAP if orng is not None else 0, ctypes.byref(on),
-                              _ptr(ws), ws.numel(), _stream(x)), "spr_linear_r")
+    _lib.check(L.spr_linear(_ptr(x), m, k, _ptr(weight), n, _ptr(bias), _ptr(residual), int(act), _ptr(out),
+                            _ptr(xr), int(xr_n), _ptr(wr), int(wr_n), _ptr(orng),
+                            _RANGE_CAP if orng is not None else 0, ctypes.byref(on),
+                            _ptr(ws), ws.numel(), _stream(x)), "spr_linear")
     if orng is not None:
         _set_range(out, orng, on.value)
     return out
@@ -726,9 +710,9 @@ def layernorm_raw(x, gamma, beta, eps: float = 1e-5, pos=None, want_norm: bool =
     cnt = L.spr_layernorm_range_count(m)
     rn = _zero_slots(cnt, x.device) if out_norm is not None else None
     rp = _zero_slots(cnt, x.device) if out_pos is not None else None
-    _lib.check(L.spr_layernorm_r(_ptr(x), m, c, _ptr(_dev(gamma, "gamma", torch.float32)),
-                                 _ptr(_dev(beta, "beta", torch.float32)), float(eps), _ptr(pos),
-                                 _ptr(out_norm), _ptr(out_pos), _ptr(rn), _ptr(rp), _stream(x)), "spr_layernorm_r")
+    _lib.check(L.spr_layernorm(_ptr(x), m, c, _ptr(_dev(gamma, "gamma", torch.float32)),
+                               _ptr(_dev(beta, "beta", torch.float32)), float(eps), _ptr(pos),
+                               _ptr(out_norm), _ptr(out_pos), _ptr(rn), _ptr(rp), _stream(x)), "spr_layernorm")
     if out_norm is not None:
         _set_range(out_norm, rn, cnt)
     if out_pos is not None:
@@ -765,7 +749,7 @@ def attention(q, k, v, cu, kv_seg, max_len: int, nhead: int, out=None, lens_host
 
 def attention_raw(q, k, v, cu, kv_seg, max_len: int, nhead: int, out=None, want_lse: bool = False):
     """want_lse: returns (out, lse) with lse [T, nhead] = the per-query log2-sum-exp the backward can reuse
-    (spr_attn_varlen_fwd_lse), or (out, None) when the configured core does not produce it."""
+    (spr_attn_varlen_fwd's lse), or (out, None) when the configured core does not produce it."""
     for t, nm in ((q, "q"), (k, "k"), (v, "v")):
         if not t.is_cuda or t.dtype != torch.float32 or t.stride(1) != 1:
             raise RuntimeError(f"attention: {nm} must be a float32 device tensor with unit inner stride")
@@ -778,19 +762,15 @@ def attention_raw(q, k, v, cu, kv_seg, max_len: int, nhead: int, out=None, want_
         out = torch.empty((T, d), dtype=torch.float32, device=q.device)
     L = _lib.lib()
     ws = _workspace(L.spr_attn_workspace_bytes(T, nseg, nhead, hd), q.device)
-    if want_lse:
-        lse = torch.empty((T, nhead), dtype=torch.float32, device=q.device)
-        written = ctypes.c_int(0)
-        _lib.check(L.spr_attn_varlen_fwd_lse(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0),
-                                             _ptr(cu), _ptr(kv_seg), T, nseg, int(max_len), nhead, hd,
-                                             1.0 / math.sqrt(hd), _ptr(out), out.stride(0), _ptr(lse),
-                                             ctypes.byref(written), _ptr(ws), ws.numel(), _stream(q)),
-                   "spr_attn_varlen_fwd_lse")
-        return out, (lse if written.value else None)
+    lse = torch.empty((T, nhead), dtype=torch.float32, device=q.device) if want_lse else None
+    written = ctypes.c_int(0)
     _lib.check(L.spr_attn_varlen_fwd(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0),
                                      _ptr(cu), _ptr(kv_seg), T, nseg, int(max_len), nhead, hd,
-                                     1.0 / math.sqrt(hd), _ptr(out), out.stride(0), _ptr(ws), ws.numel(),
-                                     _stream(q)), "spr_attn_varlen_fwd")
+                                     1.0 / math.sqrt(hd), _ptr(out), out.stride(0), _ptr(lse),
+                                     ctypes.byref(written), _ptr(ws), ws.numel(), _stream(q)),
+               "spr_attn_varlen_fwd")
+    if want_lse:
+        return out, (lse if written.value else None)
     return out
 
 
@@ -887,11 +867,11 @@ def attention_bwd(q, k, v, out, dout, cu, kv_seg_host, max_len: int, nhead: int,
     dk = torch.empty_like(dq)
     dv = torch.empty_like(dq)
     L = _lib.lib()
-    ws = _workspace(L.spr_attn_bwd_workspace_bytes2(T, nseg, nhead), q.device)      # with room for the operand planes
-    _lib.check(L.spr_attn_varlen_bwd_lse(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(out),
-                                         out.stride(0), _ptr(dout), dout.stride(0), _ptr(lse), _ptr(cu), _ptr(kv),
-                                         _ptr(inv), T, nseg, int(max_len), nhead, hd, 1.0 / math.sqrt(hd), _ptr(dq),
-                                         _ptr(dk), _ptr(dv), _ptr(ws), ws.numel(), _stream(q)), "spr_attn_varlen_bwd_lse")
+    ws = _workspace(L.spr_attn_bwd_workspace_bytes(T, nseg, nhead), q.device)      # with room for the operand planes
+    _lib.check(L.spr_attn_varlen_bwd(_ptr(q), q.stride(0), _ptr(k), k.stride(0), _ptr(v), v.stride(0), _ptr(out),
+                                     out.stride(0), _ptr(dout), dout.stride(0), _ptr(lse), _ptr(cu), _ptr(kv),
+                                     _ptr(inv), T, nseg, int(max_len), nhead, hd, 1.0 / math.sqrt(hd), _ptr(dq),
+                                     _ptr(dk), _ptr(dv), _ptr(ws), ws.numel(), _stream(q)), "spr_attn_varlen_bwd")
     return dq, dk, dv
 
 
@@ -931,12 +911,12 @@ def attention_inproj(x_qk, x_v, w_in, b_in, cu, kv_seg, max_len: int, nhead: int
     qr, qn = _get_range(x_qk) if fused else (None, 0)
     vr, vn = (qr, qn) if x_v is x_qk else (_get_range(x_v) if fused else (None, 0))
     orng = torch.empty((1,), dtype=torch.float32, device=x_qk.device) if fused else None
-    _lib.check(L.spr_attn_inproj_varlen_fwd_r(_ptr(x_qk), _ptr(x_v), T, _ptr(w_in), _ptr(b_in), _ptr(cu),
-                                              _ptr(kv_seg), nseg, int(max_len), nhead, hd, 1.0 / math.sqrt(hd),
-                                              _ptr(out), out.stride(0), _ptr(qr), int(qn), _ptr(vr), int(vn),
-                                              _ptr(orng), _ptr(w_prep if fused else None), _ptr(ws), ws.numel(),
-                                              _stream(x_qk)),
-               "spr_attn_inproj_varlen_fwd_r")
+    _lib.check(L.spr_attn_inproj_varlen_fwd(_ptr(x_qk), _ptr(x_v), T, _ptr(w_in), _ptr(b_in), _ptr(cu),
+                                            _ptr(kv_seg), nseg, int(max_len), nhead, hd, 1.0 / math.sqrt(hd),
+                                            _ptr(out), out.stride(0), _ptr(qr), int(qn), _ptr(vr), int(vn),
+                                            _ptr(orng), _ptr(w_prep if fused else None), _ptr(ws), ws.numel(),
+                                            _stream(x_qk)),
+               "spr_attn_inproj_varlen_fwd")
     if orng is not None:
         _set_range(out, orng, 1)
     return out
@@ -1057,8 +1037,8 @@ def match_dualsoftmax_top2(feat, cu, cu_host: Sequence[int], npairs: int):
     val = torch.zeros((T,), dtype=torch.float32, device=feat.device)
     val2 = torch.zeros((T,), dtype=torch.float32, device=feat.device)
     ind = torch.zeros((T,), dtype=torch.int32, device=feat.device)
-    _lib.check(L.spr_match_dualsoftmax2(_ptr(feat), d, _ptr(cu), arr, npairs, _ptr(val), _ptr(val2), _ptr(ind),
-                                        _ptr(ws), ws.numel(), _stream(feat)), "spr_match_dualsoftmax2")
+    _lib.check(L.spr_match_dualsoftmax(_ptr(feat), d, _ptr(cu), arr, npairs, _ptr(val), _ptr(val2), _ptr(ind),
+                                       _ptr(ws), ws.numel(), _stream(feat)), "spr_match_dualsoftmax")
     return val, val2, ind
 
 
@@ -1096,7 +1076,7 @@ def match_dualsoftmax_raw(feat, cu, cu_host: Sequence[int], npairs: int):
     ws = _workspace(L.spr_match_workspace_bytes(arr, npairs), feat.device)
     val = torch.zeros((T,), dtype=torch.float32, device=feat.device)
     ind = torch.zeros((T,), dtype=torch.int32, device=feat.device)
-    _lib.check(L.spr_match_dualsoftmax(_ptr(feat), d, _ptr(cu), arr, npairs, _ptr(val), _ptr(ind),
+    _lib.check(L.spr_match_dualsoftmax(_ptr(feat), d, _ptr(cu), arr, npairs, _ptr(val), None, _ptr(ind),
                                        _ptr(ws), ws.numel(), _stream(feat)), "spr_match_dualsoftmax")
     return val, ind
 

@@ -188,8 +188,8 @@ def test_attention_backward_split_operand_ranges(device, qs, ks, vs, gs):
 
 def test_attention_backward_operand_planes_and_small_workspace_agree(device, monkeypatch):
     """spr_attn_varlen_bwd writes the split operand planes once per call when the workspace has room for them
-    (spr_attn_bwd_workspace_bytes2) and lets its kernels convert the fp32 tiles themselves when it has not
-    (spr_attn_bwd_workspace_bytes): the same values reach the same LDS tiles, so the gradients agree bit for bit."""
+    (spr_attn_bwd_workspace_bytes) and lets its kernels convert the fp32 tiles themselves when it has not
+    (spr_attn_bwd_min_workspace_bytes): the same values reach the same LDS tiles, so the gradients agree bit for bit."""
     from superpoints_registration_amd import _lib
     lens, kv_seg = [130, 64, 1, 257], [1, 0, 3, 2]
     tot = sum(lens)
@@ -205,11 +205,11 @@ def test_attention_backward_operand_planes_and_small_workspace_agree(device, mon
 
     with_planes = grads()
     L = _lib.lib()
-    small = L.spr_attn_bwd_workspace_bytes
+    small = L.spr_attn_bwd_min_workspace_bytes
 
     class Patched:
         def __getattr__(self, name):
-            if name == "spr_attn_bwd_workspace_bytes2":
+            if name == "spr_attn_bwd_workspace_bytes":
                 return lambda t, nseg, nhead: small(t, nhead)
             return getattr(L, name)
 

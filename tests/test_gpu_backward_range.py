@@ -476,7 +476,7 @@ def test_kpconv_backward_counts_like_the_forward(device, cin):
 
 @pytest.mark.parametrize("mag", [1e-30, 1e-16, 1.0, 1e18])
 def test_kpconv_dx_published_range_gives_the_same_bits(device, mag):
-    """spr_kpconv_bwd_dx_r with the range published by the d wf product equals the measured-range form bit for bit."""
+    """spr_kpconv_bwd_dx with the range published by the d wf product equals the measured-range form bit for bit."""
     q, s, nb, kp, ext = _kp_cloud(720)
     ns, nq, cin = s.shape[0], q.shape[0], 32
     dwf = (synthetic.rand((nq, 15 * cin), 721) * mag).to(device)
@@ -490,9 +490,9 @@ def test_kpconv_dx_published_range_gives_the_same_bits(device, mag):
     for rr, n in ((r, rn), (None, 0)):
         dx = torch.empty((ns, cin), dtype=torch.float32, device=device)
         ws = torch.empty(L.spr_scatter_workspace_bytes(ns, cin), dtype=torch.uint8, device=device)
-        _lib.check(L.spr_kpconv_bwd_dx_r(ops._ptr(dq), nq, ops._ptr(ds), ns, ops._ptr(nbd), nbd.shape[1], nbd.shape[1],
-                                         cin, ops._ptr(dkp), 15, ext, ops._ptr(dwf), ops._ptr(rr), n, ops._ptr(dx),
-                                         ops._ptr(ws), ws.numel(), ops._stream(dwf)), "spr_kpconv_bwd_dx_r")
+        _lib.check(L.spr_kpconv_bwd_dx(ops._ptr(dq), nq, ops._ptr(ds), ns, ops._ptr(nbd), nbd.shape[1], nbd.shape[1],
+                                       cin, ops._ptr(dkp), 15, ext, ops._ptr(dwf), ops._ptr(rr), n, ops._ptr(dx),
+                                       ops._ptr(ws), ws.numel(), ops._stream(dwf)), "spr_kpconv_bwd_dx")
         outs.append(dx.cpu())
     assert torch.equal(outs[0], outs[1])
     assert float(outs[0].abs().max()) > 0
@@ -601,9 +601,9 @@ def test_layernorm_backward_unaligned_storage(device):
         assert e <= 2e-5, f"layernorm unaligned {nm}: {e:.2e}"
 
 
-def test_kpconv_weighted_features_legacy_entry_agrees_off_zero_sums(device):
-    """spr_kpconv_weighted_features (no workspace, its own row sums) and spr_kpconv_weighted_features_f (the forward's
-    flags) write the same weighted features bit for bit, and the same counts wherever no row sum is near 0."""
+def test_kpconv_weighted_features_counts_off_zero_sums(device):
+    """spr_kpconv_weighted_features (counting from the forward's flags) gives the neighbour count computed from x on
+    the host wherever no row sum is near 0."""
     q, s, nb, kp, ext = _kp_cloud(730)
     ns, nq, cin = s.shape[0], q.shape[0], 64
     x = synthetic.rand((ns, cin), 731)
@@ -611,20 +611,12 @@ def test_kpconv_weighted_features_legacy_entry_agrees_off_zero_sums(device):
     dq, ds, dx, dkp = q.to(device), s.to(device), x.to(device), kp.to(device)
     nbd = nb.to(torch.int32).to(device).contiguous()
     L = _lib.lib()
-    res = []
-    for with_flags in (False, True):
-        wf = torch.empty((nq, 15 * cin), dtype=torch.float32, device=device)
-        cnt = torch.empty((nq,), dtype=torch.float32, device=device)
-        args = (ops._ptr(dq), nq, ops._ptr(ds), ns, ops._ptr(nbd), nbd.shape[1], nbd.shape[1], ops._ptr(dx), cin,
-                ops._ptr(dkp), 15, ext, ops._ptr(wf), ops._ptr(cnt))
-        if with_flags:
-            ws = torch.empty(L.spr_kpconv_weighted_features_workspace_bytes(ns), dtype=torch.uint8, device=device)
-            _lib.check(L.spr_kpconv_weighted_features_f(*args, ops._ptr(ws), ws.numel(), ops._stream(dx)),
-                       "spr_kpconv_weighted_features_f")
-        else:
-            _lib.check(L.spr_kpconv_weighted_features(*args, ops._stream(dx)), "spr_kpconv_weighted_features")
-        res.append((wf.cpu(), cnt.cpu()))
-    assert torch.equal(res[0][0], res[1][0])
-    assert torch.equal(res[0][1], res[1][1])
+    wf = torch.empty((nq, 15 * cin), dtype=torch.float32, device=device)
+    cnt = torch.empty((nq,), dtype=torch.float32, device=device)
+    ws = torch.empty(L.spr_kpconv_weighted_features_workspace_bytes(ns), dtype=torch.uint8, device=device)
+    _lib.check(L.spr_kpconv_weighted_features(ops._ptr(dq), nq, ops._ptr(ds), ns, ops._ptr(nbd), nbd.shape[1],
+                                              nbd.shape[1], ops._ptr(dx), cin, ops._ptr(dkp), 15, ext, ops._ptr(wf),
+                                              ops._ptr(cnt), ops._ptr(ws), ws.numel(), ops._stream(dx)),
+               "spr_kpconv_weighted_features")
     ref = (torch.cat([x, torch.zeros(1, cin)])[nb].sum(-1) > 0).sum(1).clamp_min(1).float()
-    assert torch.equal(res[1][1], ref)
+    assert torch.equal(cnt.cpu(), ref)

@@ -1,6 +1,6 @@
 """GPU: the fused tail of the ResNet bottleneck block (spr_block_tail; kpconv_blocks.py:733-741) against
 a float64 evaluation of the reference's expression and against the separate operators it replaces
-(spr_linear_r + spr_instnorm_r), on ragged batches with clouds shorter than, equal to and not a
+(spr_linear + spr_instnorm), on ragged batches with clouds shorter than, equal to and not a
 multiple of the 64-row statistics tile.  Tolerances are written next to each check."""
 import numpy as np
 import pytest
@@ -142,7 +142,7 @@ def test_block_tail_rejects_unsupported_shape(device):
 
 @pytest.mark.parametrize("shape", SHAPES)
 def test_block_tail_normalises_its_input_on_load(device, shape):
-    """Round 5 (spr_block_tail_n): xa handed over RAW with the statistics of the per-cloud InstanceNorm +
+    """spr_block_tail with xa_mean / xa_rstd: xa handed over RAW with the statistics of the per-cloud InstanceNorm +
     LeakyReLU(0.1) that precedes the tail in a bottleneck block (kpconv_blocks.py:717-719 of the reference).  Against
     the float64 expression lrelu(IN(lrelu(IN(xa)) wa^T) + ...) at 5e-6 of the output scale, and against the two
     separate operators (instnorm, then the plain tail) at 2e-6: the only difference between the two GPU routes is
