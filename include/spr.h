@@ -111,6 +111,31 @@ int spr_radius_table_query(const float* q_xyz, const int* q_cu, int nq, int self
                            float radius, int limit, int slot, const void* table, int* out_idx,
                            int* max_count, int algo, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- 8f-5: ground-truth overlap masks and mutual correspondences ---------------
+ * Replaces compute_overlap(src, tgt, search_voxel_size) (utils/pointcloud.py:8-65: one Open3D kd-tree radius query
+ * per point), called per pair by the loaders (data_loaders/threedmatch.py:78-84) and by
+ * data_processing/compute_overlap_3dmatch.py / compute_overlap_kitti.py.  One call labels all nb pairs, both
+ * directions.  Contract (float64 on the exactly converted float32 inputs, one rounding per operation):
+ *   s'_i = ((R0 x + R1 y) + R2 z) + t per output coordinate, pose [nb,3,4] f32 maps src -> tgt;
+ *   d2(a, b) = ((ax-bx)^2 + (ay-by)^2) + (az-bz)^2;
+ *   src_corr[i] = the LOCAL target index j minimising (d2(s'_i, tgt_j), j) if that d2 < radius * radius (strict),
+ *   else -1; tgt_corr[j] likewise over the transformed sources; masks = corr >= 0;
+ *   corr [2, ns] i32: the mutual pairs (i, src_corr[i]) with src_corr[i] > 0 -- the reference's `> 0`
+ *   (utils/pointcloud.py:57-58) drops a source whose mutual partner is target 0 -- and tgt_corr[src_corr[i]] == i,
+ *   local indices, ascending i; pair c owns columns [src_cu[c], src_cu[c] + corr_count[c]) of both rows.
+ * Outputs are identical to a float64 evaluation of these rules, whatever the batch composition.  Empty clouds and
+ * clouds that do not overlap are legal (all -1).  Geometry never overflows the cell table (a cloud whose box needs
+ * more than 16 n + 4096 cells gets coarser cells, same result); non-finite coordinates or poses give
+ * corr_count[c] = -1 for every pair.
+ *   src_xyz [ns,3] f32, src_cu [nb+1] i32, tgt_xyz [nt,3] f32, tgt_cu [nb+1] i32
+ *   src_corr [ns] i32, tgt_corr [nt] i32, src_mask [ns] u8, tgt_mask [nt] u8, corr [2,ns] i32, corr_count [nb] i32
+ */
+size_t spr_gt_overlap_workspace_bytes(int ns, int nt, int nb);
+int spr_gt_overlap(const float* src_xyz, const int* src_cu, int ns, const float* tgt_xyz, const int* tgt_cu,
+                   int nt, const float* pose, int nb, double radius, int* src_corr, int* tgt_corr,
+                   unsigned char* src_mask, unsigned char* tgt_mask, int* corr, int* corr_count, void* ws,
+                   size_t ws_bytes, void* stream);
+
 /* ---- a4: KPConv forward ---------------------------------------------------
  * Replaces KPConv.forward(q_pts, s_pts, neighb_inds, x)
  * (models/backbone_kpconv/kpconv_blocks.py:269-414; rigid kernel, linear

@@ -281,6 +281,40 @@ def radius_neighbors(queries: torch.Tensor, supports: torch.Tensor, q_cu: torch.
     return out[:, :min(m, limit)], m
 
 
+def gt_overlap(src_xyz: torch.Tensor, src_cu: torch.Tensor, tgt_xyz: torch.Tensor, tgt_cu: torch.Tensor,
+               pose: torch.Tensor, radius: float):
+    """8f-5.  Ground-truth overlap labels of all pairs of a batch in one call (spr_gt_overlap; the reference's
+    compute_overlap, utils/pointcloud.py:8-65, as a float64 definition -- see include/spr.h).
+    src_xyz [sum N,3] / tgt_xyz [sum M,3] packed, src_cu / tgt_cu int32 [B+1], pose [B,3,4] (src -> tgt).
+    Returns (src_corr [sum N] i32, tgt_corr [sum M] i32, src_mask [sum N] bool, tgt_mask [sum M] bool,
+    corr [2, sum N] i32, corr_count: list of B ints): corr indices are local to the pair, pair b owns columns
+    [src_cu[b], src_cu[b] + corr_count[b]).  One device->host read (the counts)."""
+    src_xyz = _dev(src_xyz, "src_xyz", torch.float32)
+    tgt_xyz = _dev(tgt_xyz, "tgt_xyz", torch.float32)
+    src_cu = _dev(src_cu, "src_cu", torch.int32)
+    tgt_cu = _dev(tgt_cu, "tgt_cu", torch.int32)
+    pose = _dev(pose, "pose", torch.float32)
+    ns, nt, nb = src_xyz.shape[0], tgt_xyz.shape[0], src_cu.numel() - 1
+    if tgt_cu.numel() - 1 != nb or tuple(pose.shape) != (nb, 3, 4):
+        raise ValueError(f"gt_overlap: {nb} source clouds, {tgt_cu.numel() - 1} target clouds, pose {tuple(pose.shape)}")
+    dev = src_xyz.device
+    L = _lib.lib()
+    ws = _workspace(L.spr_gt_overlap_workspace_bytes(ns, nt, nb), dev)
+    src_corr = torch.empty((ns,), dtype=torch.int32, device=dev)
+    tgt_corr = torch.empty((nt,), dtype=torch.int32, device=dev)
+    src_mask = torch.empty((ns,), dtype=torch.uint8, device=dev)
+    tgt_mask = torch.empty((nt,), dtype=torch.uint8, device=dev)
+    corr = torch.empty((2, ns), dtype=torch.int32, device=dev)
+    count = torch.zeros((max(nb, 1),), dtype=torch.int32, device=dev)
+    _lib.check(L.spr_gt_overlap(_ptr(src_xyz), _ptr(src_cu), ns, _ptr(tgt_xyz), _ptr(tgt_cu), nt, _ptr(pose), nb,
+                                float(radius), _ptr(src_corr), _ptr(tgt_corr), _ptr(src_mask), _ptr(tgt_mask),
+                                _ptr(corr), _ptr(count), _ptr(ws), ws.numel(), _stream(src_xyz)), "spr_gt_overlap")
+    counts = count[:nb].tolist()
+    if any(c < 0 for c in counts):
+        raise RuntimeError("spr_gt_overlap: non-finite coordinates or pose")
+    return src_corr, tgt_corr, src_mask.view(torch.bool), tgt_mask.view(torch.bool), corr, counts
+
+
 class RadiusTable:
     """Cell table of one support set at one radius (spr_radius_table_build), queried by several neighbour
     searches.  The pyramid builds one per level: the conv search, the pool search and the previous level's

@@ -35,6 +35,7 @@ from typing import Callable, Dict, Iterable, List, Optional
 
 import torch
 
+from .overlap import label_batch
 from .se3 import se3_compare
 
 _log = logging.getLogger("spr.training")
@@ -377,10 +378,18 @@ class Trainer:
             self.sync = GradientSync(model.parameters(), self.group, self.bucket_bytes)
         return self
 
+    def _ensure_labels(self, batch) -> None:
+        """A batch of clouds and poses that comes without ground-truth overlap masks (all a dataset gives) is
+        labelled on the device; the reference's loaders do this per pair on the CPU (threedmatch.py:78-84).
+        Batches of another shape (a stand-in model's) pass through untouched."""
+        if 'src_overlap' not in batch and all(k in batch for k in ('src_xyz', 'tgt_xyz', 'pose')):
+            label_batch(batch, self.cfg.overlap_radius)
+
     def train_step(self, model, batch) -> dict:
         """trainer.py:107-146 for one batch."""
         self.global_step += 1
         model.train()
+        self._ensure_labels(batch)
         with torch.enable_grad():
             pred = model(batch)                                  # training_step:
             losses = model.compute_loss(pred, batch)             #   forward + compute_loss
@@ -412,6 +421,7 @@ class Trainer:
         model.eval()
         losses, metrics = [], []
         for batch in batches:
+            self._ensure_labels(batch)
             pred = model(batch)
             losses.append({k: v.detach() for k, v in model.compute_loss(pred, batch).items()})
             metrics.append(compute_metrics(pred, batch))
