@@ -617,20 +617,27 @@ __global__ __launch_bounds__(64 * P1W) void k_kpconv_mfma(
   }  // persistent tile loop
 }
 
+// LDS bytes of one k_kpconv_mfma workgroup: the split weighted-feature tile + the staged neighbour rows
+static inline size_t mfma_lds_bytes(int cc, int tq, int p1w, int kmax) {
+  const int sh = kKP * cc + 16, qpw = tq / p1w, nblk = (kmax + 15) / 16;
+  return 2 * sizeof(_Float16) * (size_t)tq * sh + sizeof(int) * (tq + p1w) + sizeof(int) * (size_t)p1w * qpw * nblk +
+         sizeof(int) * (size_t)tq * nblk * 16;
+}
+constexpr size_t kMfmaLdsMax = 160 * 1024;
+// queries per tile and waves of the two tile shapes spr_kpconv_fwd launches (64- and 32-channel chunks)
+constexpr int kTile64TQ = 32, kTile32TQ = 64, kTileWaves = 8;
+
 template <int CC, int TQ, int NTW, int NW, int SK, int P1W = NW>
 int launch_mfma(const float* q_xyz, int nq, const float* s_xyz, int ns, const int* nbr,
                 int nbr_stride, int kmax, int rows_sorted, const float* x, int cin,
                 const _Float16* Wh, const _Float16* Wl, int cout, const float* kpts,
                 float inv_extent, const float4* sxf, const float* x_parts, const float* w_parts, int n_xparts,
                 int n_wparts, float* out, hipStream_t stream) {
-  constexpr int SH = kKP * CC + 16;
-  constexpr int QPW = TQ / P1W;
-  const int nblk = (kmax + 15) / 16;
-  const size_t lds = 2 * sizeof(_Float16) * (size_t)TQ * SH + sizeof(int) * (TQ + P1W) +
-                     sizeof(int) * (size_t)P1W * QPW * nblk + sizeof(int) * (size_t)TQ * nblk * 16;
+  const size_t lds = mfma_lds_bytes(CC, TQ, P1W, kmax);
   auto kern = k_kpconv_mfma<CC, TQ, NTW, NW, SK, P1W>;
   ProfScope prof(stream, cin * 100000 + cout, nq);
-  SPR_REQUIRE(lds <= 160 * 1024, "kpconv: neighbour rows too wide for the LDS tile (kmax=%d)", kmax);
+  // (spr_kpconv_fwd routes such shapes to the generic kernel; kept for any other caller)
+  SPR_REQUIRE(lds <= kMfmaLdsMax, "kpconv: neighbour rows too wide for the LDS tile (kmax=%d)", kmax);
   if (lds > 64 * 1024)
     if (int rc = ensure_dyn_lds((const void*)kern, 160 * 1024)) return rc;
   const int n_cu = device_cu_count();
@@ -1413,7 +1420,11 @@ extern "C" int spr_kpconv_fwd(const float* q_xyz, int nq, const float* s_xyz, in
   launch_rowflag(x, s_xyz, ns, cin, flag, sxf, tile_ctr, stream);
   SPR_LAUNCH_CHECK();
 
-  if ((impl == 0 || impl == 2) && n_kp == kKP && cin % 32 == 0 && cout % 32 == 0 && cout <= 256) {
+  // Neighbour rows too wide for the tile kernel's LDS (kmax > 128 at 32-channel chunks, > 272 at 64; the ring kernel
+  // stops at 128 anyway) go to the generic kernel below, before any operand preparation is launched for the tile.
+  const bool tile_fits = cin % 64 == 0 ? mfma_lds_bytes(64, kTile64TQ, kTileWaves, kmax) <= kMfmaLdsMax
+                                       : mfma_lds_bytes(32, kTile32TQ, kTileWaves, kmax) <= kMfmaLdsMax;
+  if ((impl == 0 || impl == 2) && n_kp == kKP && cin % 32 == 0 && cout % 32 == 0 && cout <= 256 && tile_fits) {
     const int ktot = n_kp * cin;
     const float* xp = x_range != nullptr ? x_range : x_parts;
     const float* wp = w_range != nullptr ? w_range : w_parts;
@@ -1454,14 +1465,14 @@ extern "C" int spr_kpconv_fwd(const float* q_xyz, int nq, const float* s_xyz, in
       kernel_points, inv_extent, sxf, xp, wp, n_xp, n_wp, out, stream
     if (cin % 64 == 0) {
       // TQ = 32 (MT = 2), 8 waves: 4 n-groups x 2 k-halves, every wave both m-tiles
-      if (cout == 64) return launch_mfma<64, 32, 1, 8, 2>(SPR_KP_ARGS);
-      if (cout == 128) return launch_mfma<64, 32, 2, 8, 2>(SPR_KP_ARGS);
-      if (cout == 256) return launch_mfma<64, 32, 4, 8, 2>(SPR_KP_ARGS);
+      if (cout == 64) return launch_mfma<64, kTile64TQ, 1, kTileWaves, 2>(SPR_KP_ARGS);
+      if (cout == 128) return launch_mfma<64, kTile64TQ, 2, kTileWaves, 2>(SPR_KP_ARGS);
+      if (cout == 256) return launch_mfma<64, kTile64TQ, 4, kTileWaves, 2>(SPR_KP_ARGS);
     } else {
       // TQ = 64 (MT = 4), 8 waves: 2 n-groups
-      if (cout == 32) return launch_mfma<32, 64, 1, 8, 1>(SPR_KP_ARGS);
-      if (cout == 64) return launch_mfma<32, 64, 2, 8, 1>(SPR_KP_ARGS);
-      if (cout == 128) return launch_mfma<32, 64, 4, 8, 1>(SPR_KP_ARGS);
+      if (cout == 32) return launch_mfma<32, kTile32TQ, 1, kTileWaves, 1>(SPR_KP_ARGS);
+      if (cout == 64) return launch_mfma<32, kTile32TQ, 2, kTileWaves, 1>(SPR_KP_ARGS);
+      if (cout == 128) return launch_mfma<32, kTile32TQ, 4, kTileWaves, 1>(SPR_KP_ARGS);
     }
 #undef SPR_KP_ARGS
   }

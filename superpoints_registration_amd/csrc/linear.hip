@@ -708,7 +708,15 @@ __global__ void k_layernorm(const float* __restrict__ x, int m, int c,
     v[i] = (i < nv) ? x[(size_t)row * c + i * 64 + lane] : 0.f;
     s += v[i];
   }
-  const float mean = wave_sum(s) / (float)c;
+  // The float32 row sum carries an error of a few ulp of c * |mean|, which a row of large centre and small
+  // spread (1e3 +- 1e-2) turns into percents of its spread.  v - mean0 is exact for such a row, so the mean of the
+  // residuals repairs the mean to an ulp of the spread at the price of one more wave reduction.
+  // (k_layernorm_bwd in backward.hip recomputes its mean the same way.)
+  const float mean0 = wave_sum(s) / (float)c;
+  float sd = 0.f;
+#pragma unroll
+  for (int i = 0; i < MAXV; ++i) sd += (i < nv) ? v[i] - mean0 : 0.f;
+  const float mean = mean0 + wave_sum(sd) / (float)c;
   float ss = 0.f;
 #pragma unroll
   for (int i = 0; i < MAXV; ++i) {
@@ -782,7 +790,9 @@ __global__ __launch_bounds__(256) void k_layernorm256(const float* __restrict__ 
   for (int r = 0; r < kLnRows; ++r) {
     if (row0 + r >= m) continue;
     const size_t o = (size_t)(row0 + r) * 256 + 4 * lane;
-    const float mean = wave_sum((v[r].x + v[r].y) + (v[r].z + v[r].w)) / 256.0f;
+    // mean of the residuals around the float32 mean: see k_layernorm
+    const float mean0 = wave_sum((v[r].x + v[r].y) + (v[r].z + v[r].w)) / 256.0f;
+    const float mean = mean0 + wave_sum(((v[r].x - mean0) + (v[r].y - mean0)) + ((v[r].z - mean0) + (v[r].w - mean0))) / 256.0f;
     const float dx = v[r].x - mean, dy = v[r].y - mean, dz = v[r].z - mean, dw = v[r].w - mean;
     const float rstd = 1.0f / sqrtf(wave_sum((dx * dx + dy * dy) + (dz * dz + dw * dw)) / 256.0f + eps);
     float4 y;

@@ -331,7 +331,9 @@ __global__ void k_maxpool(const float* __restrict__ x, int ns, int c, const int*
   const int q = (int)(gid % c4);
   const int row = order != nullptr ? order[gid / c4] : (int)(gid / c4);
   gid = (long)row * c4 + q;
-  float4 m = make_float4(-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f);
+  // minus infinity, not a large finite value: a row whose true maximum is below -3.0e38 (or -inf) is a selection
+  // like any other and must come out as that value
+  float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
   const int* ir = idx + (size_t)row * idx_stride;
   int j = 0;
   // four gathers in flight per thread (the serial one-load-per-iteration loop was latency bound)

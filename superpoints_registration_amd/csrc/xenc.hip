@@ -200,8 +200,8 @@ __device__ __forceinline__ void split_block(const f32x16& v, float scale, f16x8&
 }
 
 // LayerNorm over the 256 features of the lane's token (two half rows: lanes l and l ^ 32).  Same
-// operations as k_layernorm256 (two-pass mean / variance, (d rstd) gamma + beta); only the order of the
-// two sums differs.  v is left untouched (it is also the residual).
+// operations as k_layernorm256 (mean, mean of the residuals around it, variance of the residuals,
+// (d rstd) gamma + beta); only the order of the sums differs.  v is left untouched (it is also the residual).
 __device__ __forceinline__ void ln_stats(const f32x16 (&v)[8], float eps, float& mean, float& rstd) {
   float s = 0.f;
 #pragma unroll
@@ -209,7 +209,14 @@ __device__ __forceinline__ void ln_stats(const f32x16 (&v)[8], float eps, float&
 #pragma unroll
     for (int e = 0; e < 16; ++e) s += v[b][e];
   s += __shfl_xor(s, 32, 64);
-  mean = s / 256.0f;
+  const float mean0 = s / 256.0f;
+  float sd = 0.f;   // the float32 row sum is a few ulp of 256 |mean| off: repair it as linear.hip's k_layernorm does
+#pragma unroll
+  for (int b = 0; b < 8; ++b)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) sd += v[b][e] - mean0;
+  sd += __shfl_xor(sd, 32, 64);
+  mean = mean0 + sd / 256.0f;
   float ss = 0.f;
 #pragma unroll
   for (int b = 0; b < 8; ++b)
