@@ -136,6 +136,87 @@ int spr_gt_overlap(const float* src_xyz, const int* src_cu, int ns, const float*
                    unsigned char* src_mask, unsigned char* tgt_mask, int* corr, int* corr_count, void* ws,
                    size_t ws_bytes, void* stream);
 
+/* ---- 8f-6: training augmentation (perturb, jitter, shuffle, swap) -----------------
+ * Replaces the per-pair CPU chain RigidPerturb -> Jitter -> ShufflePoints -> RandomSwap of the 3DMatch and KITTI
+ * training loaders (data_loaders/transforms.py:15-179, composed in data_loaders/__init__.py:17-54).  One call
+ * augments all nb pairs.  The reference draws from the global numpy / random / torch generators; here every draw is a
+ * pure function of (seed, pair_key, side, element, stream tag): a pair is augmented identically whatever batch,
+ * position, grid or rank it lands in.
+ *
+ * Draw contract.  Philox4x32-10 (multipliers D2511F53 / CD9E8D57, key increments 9E3779B9 / BB67AE85):
+ *   key     = (seed & 0xffffffff, seed >> 32)
+ *   counter = (element, q & 0xffffffff, tag, q >> 32)  with q = 2 * pair_key + side (pair_key < 2^63; side 0 = source,
+ *             1 = target; pair decisions use side 0) -- i.e. (element, 2 pair_key + side, tag, 0) for keys below 2^31
+ *   tag     = 0 pair decisions, 1 jitter noise (element = ORIGINAL local point index), 2 shuffle keys (same)
+ *   uniform u(w) = ((w >> 9) + 0.5) * 2^-23, in (0, 1), exact in float32 and float64 (24 significant bits)
+ *   normal  from two words (a, b): r = sqrt(-2 ln u(a)), (r cos(2 pi u(b)), r sin(2 pi u(b))).
+ * Jitter noise is float32 on the device: r = sqrtf(-2.f * logf(u(a))), angle = 6.2831855f * u(b), sincosf -- the
+ * accurate library functions, one rounding per operation.  Point i gets, from the four words w0..w3 of its tag-1
+ * block: (r(w0) cos(w1), r(w0) sin(w1), r(w2) cos(w3)).  Its shuffle key is word 0 of its tag-2 block.
+ * Pair decisions are float64 on the host, from the tag-0 blocks of elements 0, 1, 2 (words e.w):
+ *   perturb the source iff u(0.0) > 0.5, else the target; swap iff u(0.1) > 0.5   (random.random() > 0.5)
+ *   SPR_AUG_SMALL (SE3.sample_small, std = 0.1): axis = (s cos phi, s sin phi, z) with z = 2 u(1.0) - 1,
+ *     s = sqrt(1 - z^2), phi = 2 pi u(1.1); angle = n(1.2, 1.3).cos * std * pi / sqrt(3); rotation by Rodrigues'
+ *     formula; translation = (n(2.0, 2.1).cos, n(2.0, 2.1).sin, n(2.2, 2.3).cos) * std / sqrt(3)
+ *   SPR_AUG_LARGE: Euler angles (z, y, x) = 2 pi (u(1.0), u(1.1), u(1.2)), R = Rx Ry Rz (the extrinsic
+ *     'zyx' of scipy.spatial.transform.Rotation.from_euler); translation = -4 + 8 (u(2.0), u(2.1), u(2.2))
+ *   SPR_AUG_NONE: identity (and spr_augment_pairs applies no perturbation whatever it is handed).
+ *   The [3,4] result is rounded to float32.
+ *
+ * spr_philox4x32_host: one block on the host (the known-answer entry).
+ * spr_augment_draw: the decisions of nb pairs into HOST arrays (perturb_src_host [nb] u8, swap_host [nb] u8,
+ *   perturb_host [nb,3,4] f32; each may be NULL) and, when `noise` / `keys` are given, the device buffers
+ *   noise [ns+nt,3] f32 and keys [ns+nt] u32 of a batch with the given src_cu / tgt_cu and DEVICE pair_key [nb] u64,
+ *   in the stacked order [all sources, all targets].  These are the values spr_augment_pairs generates inline when it
+ *   is handed NULL for them: inline and explicit agree bit for bit.
+ *
+ * spr_augment_pairs.  Contract (float64 on the exactly converted float32 inputs, one rounding per operation, sums of
+ * three products as ((a0 b0 + a1 b1) + a2 b2); every named intermediate is rounded to float32):
+ *   cat(A, B) = [A_R B_R | A_R B_t + A_t],  inv(A) = [A_R^T | -(A_R^T A_t)]
+ *   centroid c = f32(sum_f64(points of the perturbed cloud) / n)             (mode SMALL only; n = 0 -> 0)
+ *   P' = f32([R | (R (-c)) + (t + c)])   (= C^-1 P C, C the translation by -c)   SMALL;   P' = P   LARGE
+ *   pose' = f32(cat(pose, inv(P'))) when the source is perturbed, f32(cat(P', pose)) when the target is
+ *   x' = f32(((R'0 x + R'1 y) + R'2 z) + t') for the points of the perturbed cloud, x' = x for the other
+ *   x'' = x' + f32(noise * scale)   in float32, both clouds, noise indexed by the ORIGINAL point index
+ *   shuffle: per cloud the stable ascending order of its 32-bit keys, cut to the first max_pts; masks are gathered
+ *     with the points; perm = the original local index of every output point
+ *   correspondences are remapped through the inverse permutation; those with an end cut away (or out of range) are
+ *     dropped, the survivors keep their relative order
+ *   swap: the pair's clouds, masks, permutations and correspondence rows change sides, pose_out = f32(inv(pose')).
+ * flags [nb] u8: bit 0 = perturb the source (else the target), bit 1 = swap.  mode: SPR_AUG_*.
+ * Output lengths are known to the caller: min(len, max_pts) per cloud, sides exchanged where the pair swaps;
+ * out_src_cu / out_tgt_cu [nb+1] i32 are written on the device.  Only the number of surviving correspondences is data
+ * dependent: pair c owns columns [corr_off[c], corr_off[c] + corr_count[c]) of both rows of corr [2, corr_stride]
+ * (corr_off ascending, runs disjoint -- spr_gt_overlap's layout with corr_off = src_cu, corr_stride = ns) and the same
+ * columns, from corr_off[c], of out_corr; out_corr_count [nb] i32.
+ * status [nb] i32: 0, or 1 when the pair has a non-finite coordinate, pose or perturbation (its outputs are then
+ * unspecified but every index is in range; other pairs are unaffected).
+ * Empty clouds, SPR_AUG_NONE, scale = 0, max_pts above every length and pairs without correspondences are legal.
+ *   src_xyz [ns,3] f32, tgt_xyz [nt,3] f32, src_cu / tgt_cu [nb+1] i32, pose [nb,3,4] f32, perturb [nb,3,4] f32,
+ *   src_mask [ns] / tgt_mask [nt] u8 (both or neither; NULL: no masks, out masks untouched),
+ *   corr NULL: no correspondences (corr_off, corr_count, out_corr, out_corr_count unused),
+ *   noise / keys: NULL = generated inline from (seed, pair_key); pair_key [nb] u64 is then required,
+ *   out_src_xyz / out_tgt_xyz [.,3] f32, out_*_mask u8 and out_*_perm i32 hold the sum of that side's output lengths
+ *   (ns + nt rows always suffice); out_pose [nb,3,4] f32; out_corr [2,corr_stride] i32.
+ */
+#define SPR_AUG_NONE 0
+#define SPR_AUG_SMALL 1
+#define SPR_AUG_LARGE 2
+int spr_philox4x32_host(const uint32_t* ctr_host, const uint32_t* key_host, uint32_t* out_host);
+int spr_augment_draw(uint64_t seed, const uint64_t* pair_key_host, int nb, int mode, unsigned char* perturb_src_host,
+                     unsigned char* swap_host, float* perturb_host, const uint64_t* pair_key, const int* src_cu,
+                     int ns, const int* tgt_cu, int nt, float* noise, unsigned int* keys, void* stream);
+size_t spr_augment_workspace_bytes(int ns, int nt, int nb, int corr_stride);
+int spr_augment_pairs(const float* src_xyz, const int* src_cu, int ns, const float* tgt_xyz, const int* tgt_cu,
+                      int nt, const float* pose, int nb, const unsigned char* src_mask,
+                      const unsigned char* tgt_mask, const int* corr, int corr_stride, const int* corr_off,
+                      const int* corr_count, const float* perturb, const unsigned char* flags, int mode, float scale,
+                      int max_pts, uint64_t seed, const uint64_t* pair_key, const float* noise,
+                      const unsigned int* keys, float* out_src_xyz, float* out_tgt_xyz, int* out_src_cu,
+                      int* out_tgt_cu, float* out_pose, unsigned char* out_src_mask, unsigned char* out_tgt_mask,
+                      int* out_src_perm, int* out_tgt_perm, int* out_corr, int* out_corr_count, int* status, void* ws,
+                      size_t ws_bytes, void* stream);
+
 /* ---- a4: KPConv forward ---------------------------------------------------
  * Replaces KPConv.forward(q_pts, s_pts, neighb_inds, x)
  * (models/backbone_kpconv/kpconv_blocks.py:269-414; rigid kernel, linear

@@ -17,6 +17,7 @@ _i = ctypes.c_int
 _f = ctypes.c_float
 _sz = ctypes.c_size_t
 _l = ctypes.c_long
+_u64 = ctypes.c_uint64
 
 # name -> (restype, argtypes); mirrors include/spr.h exactly
 SIGNATURES = {
@@ -37,6 +38,12 @@ SIGNATURES = {
     "spr_gt_overlap_workspace_bytes": (_sz, [_i, _i, _i]),
     "spr_gt_overlap": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                             _sz, _vp]),
+    "spr_philox4x32_host": (_i, [_vp, _vp, _vp]),
+    "spr_augment_draw": (_i, [_u64, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "spr_augment_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "spr_augment_pairs": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _f, _i,
+                               _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                               _sz, _vp]),
     "spr_kpconv_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "spr_kpconv_fwd": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _f, _vp, _i, _vp, _i, _vp,
                             _i, _vp, _vp, _vp, _sz, _vp]),

@@ -53,6 +53,7 @@ CONFIGS = {
         first_feats_dim=128, conv_radius=2.5, architecture=['simple'] + _RESNET,
         use_sinkhorn=True, sinkhorn_itr=3, slack=True, r_p=0.2, r_n=0.4, val_threshold=0.15,
         num_refinement_steps=4, acceptance_radius=0.1, overlap_radius=0.0375,
+        augment_noise=0.005, perturb_pose='small',
     ),
     # conf/qk_regtr_full_kitti.yaml
     'kitti': dict(
@@ -62,6 +63,7 @@ CONFIGS = {
         use_sinkhorn=False, sinkhorn_itr=3, slack=True, r_p=1.6, r_n=3.2, val_threshold=0.25,
         num_refinement_steps=10, acceptance_radius=0.6, overlap_radius=0.3,
         scheduler_param=[135800, 0.5], reg_success_thresh_rot=5, reg_success_thresh_trans=2,
+        augment_noise=0.01, perturb_pose='large',
     ),
     # conf/qk_regtr_full_modelnet.yaml
     'modelnet': dict(
@@ -70,6 +72,7 @@ CONFIGS = {
         architecture=['simple', 'resnetb', 'resnetb', 'resnetb_strided', 'resnetb', 'resnetb'],
         use_sinkhorn=False, sinkhorn_itr=1, slack=False, r_p=0.12, r_n=0.24,
         num_refinement_steps=5, acceptance_radius=0.05, overlap_radius=0.04,
+        augment_noise=0.005, perturb_pose='small',
     ),
 }
 

@@ -315,6 +315,153 @@ def gt_overlap(src_xyz: torch.Tensor, src_cu: torch.Tensor, tgt_xyz: torch.Tenso
     return src_corr, tgt_corr, src_mask.view(torch.bool), tgt_mask.view(torch.bool), corr, counts
 
 
+AUG_MODES = {'none': 0, 'small': 1, 'large': 2}
+
+
+def philox4x32(counter, key) -> np.ndarray:
+    """One Philox4x32-10 block through the library's host path (spr_philox4x32_host): uint32 [4]."""
+    c = np.ascontiguousarray(counter, dtype=np.uint32).reshape(4)
+    k = np.ascontiguousarray(key, dtype=np.uint32).reshape(2)
+    out = np.zeros(4, dtype=np.uint32)
+    _lib.check(_lib.lib().spr_philox4x32_host(c.ctypes.data, k.ctypes.data, out.ctypes.data), "spr_philox4x32_host")
+    return out
+
+
+def augment_draw(seed: int, pair_keys, mode: str, src_cu: Optional[torch.Tensor] = None,
+                 tgt_cu: Optional[torch.Tensor] = None, ns: int = 0, nt: int = 0):
+    """8f-6.  The augmentation draws of pairs `pair_keys` under `seed` (spr_augment_draw; contract in include/spr.h).
+    Returns (perturb_src [nb] bool, swap [nb] bool, perturb [nb,3,4] f32) as numpy arrays -- the per-pair
+    decisions are host data and need no device.  With src_cu / tgt_cu (device int32 [nb+1]) and the packed sizes ns,
+    nt it also returns the device buffers (noise [ns+nt,3] f32, keys [ns+nt] int32 holding the uint32 bit patterns)
+    that augment_pairs generates inline when it is not handed them."""
+    pk = np.ascontiguousarray(pair_keys, dtype=np.uint64).reshape(-1)
+    nb = pk.size
+    psrc = np.zeros(nb, dtype=np.uint8)
+    swap = np.zeros(nb, dtype=np.uint8)
+    perturb = np.zeros((nb, 3, 4), dtype=np.float32)
+    L = _lib.lib()
+    if src_cu is None:
+        _lib.check(L.spr_augment_draw(int(seed), pk.ctypes.data, nb, AUG_MODES[mode], psrc.ctypes.data, swap.ctypes.data,
+                                      perturb.ctypes.data, None, None, 0, None, 0, None, None, None), "spr_augment_draw")
+        return psrc.astype(bool), swap.astype(bool), perturb
+    src_cu = _dev(src_cu, "src_cu", torch.int32)
+    tgt_cu = _dev(tgt_cu, "tgt_cu", torch.int32)
+    if src_cu.numel() - 1 != nb or tgt_cu.numel() - 1 != nb:
+        raise ValueError(f"augment_draw: {nb} pair keys, cu arrays of {src_cu.numel() - 1} / {tgt_cu.numel() - 1} clouds")
+    dev = src_cu.device
+    pk_dev = torch.from_numpy(pk.view(np.int64)).to(dev)
+    noise = torch.empty((ns + nt, 3), dtype=torch.float32, device=dev)
+    keys = torch.empty((ns + nt,), dtype=torch.int32, device=dev)
+    _lib.check(L.spr_augment_draw(int(seed), pk.ctypes.data, nb, AUG_MODES[mode], psrc.ctypes.data, swap.ctypes.data,
+                                  perturb.ctypes.data, _ptr(pk_dev), _ptr(src_cu), int(ns), _ptr(tgt_cu), int(nt),
+                                  _ptr(noise), _ptr(keys), _stream(src_cu)), "spr_augment_draw")
+    return psrc.astype(bool), swap.astype(bool), perturb, noise, keys
+
+
+def augment_pairs(src_xyz: torch.Tensor, src_cu: torch.Tensor, tgt_xyz: torch.Tensor, tgt_cu: torch.Tensor,
+                  pose: torch.Tensor, perturb_src, swap, perturb, mode: str, scale: float, max_pts: int = 30000,
+                  seed: int = 0, pair_keys=None, src_mask: Optional[torch.Tensor] = None,
+                  tgt_mask: Optional[torch.Tensor] = None, corr: Optional[torch.Tensor] = None, corr_off=None,
+                  corr_count=None, noise: Optional[torch.Tensor] = None, keys: Optional[torch.Tensor] = None,
+                  out_lens=None) -> dict:
+    """8f-6.  RigidPerturb -> Jitter -> ShufflePoints -> RandomSwap of all pairs of a batch in one call
+    (spr_augment_pairs; the float64 contract is in include/spr.h).
+    src_xyz [sum N,3] / tgt_xyz [sum M,3] packed with src_cu / tgt_cu int32 [B+1]; pose [B,3,4]; the decisions
+    perturb_src / swap ([B] bool) and perturb ([B,3,4] f32) as augment_draw returns them (host arrays or tensors);
+    optional masks (bool or uint8, both or neither) and corr [2, W] int32 with per-pair column offsets corr_off and
+    counts corr_count ([B] ints; ops.gt_overlap's layout is corr_off = src_cu[:-1]).  noise [sum N + sum M, 3] f32 and
+    keys [sum N + sum M] (uint32 patterns in an int32 tensor) are generated inline from (seed, pair_keys) when None.
+    out_lens = (src_lens, tgt_lens) of the OUTPUT when the caller has them on the host (see augment.output_lengths).
+    Returns a dict of device tensors: src_xyz, tgt_xyz, src_cu, tgt_cu, pose, src_perm, tgt_perm, status [B] and, when
+    given, src_mask, tgt_mask (bool), corr [2, W], corr_count [B] (device: the only data-dependent sizes).  No
+    device-to-host read happens here."""
+    src_xyz = _dev(src_xyz, "src_xyz", torch.float32)
+    tgt_xyz = _dev(tgt_xyz, "tgt_xyz", torch.float32)
+    src_cu = _dev(src_cu, "src_cu", torch.int32)
+    tgt_cu = _dev(tgt_cu, "tgt_cu", torch.int32)
+    pose = _dev(pose, "pose", torch.float32)
+    dev = src_xyz.device
+    ns, nt, nb = src_xyz.shape[0], tgt_xyz.shape[0], src_cu.numel() - 1
+    if tgt_cu.numel() - 1 != nb or tuple(pose.shape) != (nb, 3, 4):
+        raise ValueError(f"augment_pairs: {nb} source clouds, {tgt_cu.numel() - 1} target clouds, pose {tuple(pose.shape)}")
+    flags_h = (np.asarray(perturb_src, dtype=bool).reshape(-1).astype(np.uint8)
+               | (np.asarray(swap, dtype=bool).reshape(-1).astype(np.uint8) << 1))
+    if flags_h.size != nb:
+        raise ValueError(f"augment_pairs: {flags_h.size} decisions for {nb} pairs")
+    flags = torch.from_numpy(flags_h).to(dev)
+    if isinstance(perturb, torch.Tensor):
+        perturb_d = perturb.to(device=dev, dtype=torch.float32).contiguous()
+    else:
+        perturb_d = torch.from_numpy(np.ascontiguousarray(perturb, dtype=np.float32)).to(dev)
+    if tuple(perturb_d.shape) != (nb, 3, 4):
+        raise ValueError(f"augment_pairs: perturb {tuple(perturb_d.shape)} for {nb} pairs")
+    pk_dev = None
+    if pair_keys is not None:
+        pk = np.ascontiguousarray(pair_keys, dtype=np.uint64).reshape(-1)
+        if pk.size != nb:
+            raise ValueError(f"augment_pairs: {pk.size} pair keys for {nb} pairs")
+        pk_dev = torch.from_numpy(pk.view(np.int64)).to(dev)
+    elif noise is None or keys is None:
+        raise ValueError("augment_pairs: pair_keys are needed when noise or keys are generated inline")
+    if (src_mask is None) != (tgt_mask is None):
+        raise ValueError("augment_pairs: masks come for both clouds or for neither")
+    if src_mask is not None:
+        src_mask = _dev(src_mask, "src_mask").to(torch.uint8).contiguous()
+        tgt_mask = _dev(tgt_mask, "tgt_mask").to(torch.uint8).contiguous()
+        if src_mask.numel() != ns or tgt_mask.numel() != nt:
+            raise ValueError("augment_pairs: mask length differs from the cloud's")
+    if noise is not None:
+        noise = _dev(noise, "noise", torch.float32)
+        if tuple(noise.shape) != (ns + nt, 3):
+            raise ValueError(f"augment_pairs: noise {tuple(noise.shape)}, expected {(ns + nt, 3)}")
+    if keys is not None:
+        keys = _dev(keys, "keys", torch.int32)
+        if keys.numel() != ns + nt:
+            raise ValueError(f"augment_pairs: {keys.numel()} keys for {ns + nt} points")
+    stride = 0
+    off_d = cnt_d = out_corr = out_cnt = None
+    if corr is not None:
+        corr = _dev(corr, "corr", torch.int32)
+        stride = int(corr.shape[1])
+        off_d = torch.from_numpy(np.ascontiguousarray(corr_off, dtype=np.int32).reshape(-1)).to(dev) \
+            if not isinstance(corr_off, torch.Tensor) else _dev(corr_off, "corr_off", torch.int32)
+        cnt_d = torch.from_numpy(np.ascontiguousarray(corr_count, dtype=np.int32).reshape(-1)).to(dev) \
+            if not isinstance(corr_count, torch.Tensor) else _dev(corr_count, "corr_count", torch.int32)
+        if off_d.numel() != nb or cnt_d.numel() != nb:
+            raise ValueError("augment_pairs: corr_off / corr_count need one entry per pair")
+        out_corr = torch.empty((2, stride), dtype=torch.int32, device=dev)
+        out_cnt = torch.zeros((nb,), dtype=torch.int32, device=dev)
+    if out_lens is not None:
+        n_os, n_ot = int(sum(out_lens[0])), int(sum(out_lens[1]))
+    else:
+        n_os = n_ot = ns + nt
+    L = _lib.lib()
+    ws = _workspace(L.spr_augment_workspace_bytes(ns, nt, nb, stride), dev)
+    o_src = torch.empty((n_os, 3), dtype=torch.float32, device=dev)
+    o_tgt = torch.empty((n_ot, 3), dtype=torch.float32, device=dev)
+    o_scu = torch.empty((nb + 1,), dtype=torch.int32, device=dev)
+    o_tcu = torch.empty((nb + 1,), dtype=torch.int32, device=dev)
+    o_pose = torch.empty((nb, 3, 4), dtype=torch.float32, device=dev)
+    o_sperm = torch.empty((n_os,), dtype=torch.int32, device=dev)
+    o_tperm = torch.empty((n_ot,), dtype=torch.int32, device=dev)
+    o_smask = torch.empty((n_os,), dtype=torch.uint8, device=dev) if src_mask is not None else None
+    o_tmask = torch.empty((n_ot,), dtype=torch.uint8, device=dev) if src_mask is not None else None
+    status = torch.zeros((max(nb, 1),), dtype=torch.int32, device=dev)
+    _lib.check(L.spr_augment_pairs(
+        _ptr(src_xyz), _ptr(src_cu), ns, _ptr(tgt_xyz), _ptr(tgt_cu), nt, _ptr(pose), nb, _ptr(src_mask), _ptr(tgt_mask),
+        _ptr(corr), stride, _ptr(off_d), _ptr(cnt_d), _ptr(perturb_d), _ptr(flags), AUG_MODES[mode], float(scale),
+        int(max_pts), int(seed), _ptr(pk_dev), _ptr(noise), _ptr(keys), _ptr(o_src), _ptr(o_tgt), _ptr(o_scu),
+        _ptr(o_tcu), _ptr(o_pose), _ptr(o_smask), _ptr(o_tmask), _ptr(o_sperm), _ptr(o_tperm), _ptr(out_corr),
+        _ptr(out_cnt), _ptr(status), _ptr(ws), ws.numel(), _stream(src_xyz)), "spr_augment_pairs")
+    out = {'src_xyz': o_src, 'tgt_xyz': o_tgt, 'src_cu': o_scu, 'tgt_cu': o_tcu, 'pose': o_pose, 'src_perm': o_sperm,
+           'tgt_perm': o_tperm, 'status': status[:nb]}
+    if src_mask is not None:
+        out['src_mask'], out['tgt_mask'] = o_smask.view(torch.bool), o_tmask.view(torch.bool)
+    if corr is not None:
+        out['corr'], out['corr_count'] = out_corr, out_cnt
+    return out
+
+
 class RadiusTable:
     """Cell table of one support set at one radius (spr_radius_table_build), queried by several neighbour
     searches.  The pyramid builds one per level: the conv search, the pool search and the previous level's

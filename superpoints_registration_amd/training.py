@@ -35,6 +35,7 @@ from typing import Callable, Dict, Iterable, List, Optional
 
 import torch
 
+from .augment import TrainAugmentation
 from .overlap import label_batch
 from .se3 import se3_compare
 
@@ -357,11 +358,16 @@ class CheckpointManager:
 class Trainer:
     """fit() / validate() with the reference's step order.  `batches` are dicts as produced by the
     reference's collate_pair (src_xyz / tgt_xyz lists, pose, src_overlap / tgt_overlap) already on
-    the device; data loading itself is out of the hot-path scope."""
+    the device; data loading itself is out of the hot-path scope.  augment=True applies the reference's training
+    augmentation (augment.py: cfg.perturb_pose, cfg.augment_noise, shuffle, swap) to every training batch on the
+    device, with draws keyed on (seed, global_step, rank, position in the batch); validate() never augments."""
 
     def __init__(self, cfg, ckpt_dir: Optional[str] = None, grad_clip: Optional[float] = None, rank: int = 0,
-                 world: int = 1, process_group=None, bucket_bytes: int = 16 << 20):
+                 world: int = 1, process_group=None, bucket_bytes: int = 16 << 20, augment: bool = False,
+                 seed: int = 0):
         self.cfg = cfg
+        self.augment, self.seed = bool(augment), int(seed)
+        self.augmentation = TrainAugmentation(cfg) if self.augment else None
         self.grad_clip = cfg.get('grad_clip', 0.0) if grad_clip is None else grad_clip
         self.rank, self.world, self.group = rank, world, process_group
         self.bucket_bytes = bucket_bytes
@@ -385,11 +391,21 @@ class Trainer:
         if 'src_overlap' not in batch and all(k in batch for k in ('src_xyz', 'tgt_xyz', 'pose')):
             label_batch(batch, self.cfg.overlap_radius)
 
+    def _pair_keys(self, n: int) -> List[int]:
+        """One key per pair of this step, distinct across steps, ranks and batch positions (up to 65536 pairs per
+        rank and step)."""
+        return [((self.global_step * self.world + self.rank) << 16) + i for i in range(n)]
+
     def train_step(self, model, batch) -> dict:
         """trainer.py:107-146 for one batch."""
         self.global_step += 1
         model.train()
-        self._ensure_labels(batch)
+        augment = self.augment and all(k in batch for k in ('src_xyz', 'tgt_xyz', 'pose'))
+        if augment:
+            batch = dict(batch)          # labels and augmented clouds go into a copy: the caller's batch stays as it is
+        self._ensure_labels(batch)       # on the clean geometry, as the reference's loaders do
+        if augment:
+            batch = self.augmentation(batch, self.seed, self._pair_keys(len(batch['src_xyz'])))
         with torch.enable_grad():
             pred = model(batch)                                  # training_step:
             losses = model.compute_loss(pred, batch)             #   forward + compute_loss
