@@ -173,9 +173,7 @@ class LinearFn(torch.autograd.Function):
                 bgemm(g, w.detach().contiguous(), dx, [(0, 0, 0, m, k, n)], (n, 1), (k, 1), (k, 1))
         if ctx.needs_input_grad[1]:
             xd = x.detach().contiguous()
-            r = getattr(x, '_spr_range', None)
-            if r is not None and xd is not x:
-                xd._spr_range = r             # same storage and version counter: the forward's measurement still holds
+            _ops.share_range(x, xd)           # same storage and version counter: the forward's measurement still holds
             dw = _tn_product(g, xd, m, n, k)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             db = _colsum(g)

@@ -54,28 +54,49 @@ def invalidate_ranges() -> None:
     _range_epoch[0] += 1
 
 
+def _ident(t: torch.Tensor):
+    """What everything derived from a tensor is keyed on: the derived value holds while the tensor keeps its
+    storage pointer and version counter and invalidate_ranges() has not been called."""
+    return (t.data_ptr(), t._version, _range_epoch[0])
+
+
 def _set_range(t: torch.Tensor, parts: torch.Tensor, n: int, guard=None) -> None:
     if n > 0:     # ONE attribute store: a reader on another thread sees the range and its guard together
-        t._spr_range = (parts, int(n), t._version, t.data_ptr(), _range_epoch[0], guard)
+        ptr, version, epoch = _ident(t)
+        t._spr_range = (parts, int(n), version, ptr, epoch, guard)
 
 
 def _get_range(t):
     r = getattr(t, '_spr_range', None)
-    if r is None or r[2] != t._version or r[3] != t.data_ptr() or r[4] != _range_epoch[0]:
+    if r is None or (r[3], r[2], r[4]) != _ident(t):
         return None, 0
     if r[5] is not None:
         r[5].acquire()
     return r[0], r[1]
+
+
+def share_range(src: torch.Tensor, alias: torch.Tensor) -> None:
+    """Hands the range attached to src to `alias`, a detached view of it: with the same storage and version
+    counter the measurement still holds, and _get_range(alias) drops it like src's own once either is edited."""
+    r = getattr(src, '_spr_range', None)
+    if r is not None and alias is not src:
+        alias._spr_range = r
+
 
 _RANGE_CAP = 4096   # partials a GEMM may publish (one per workgroup)
 _STREAM_SLOTS = 512  # atomic-max slots of the streaming producers (InstanceNorm apply, max-pool)
 _zero_pool = {}
 
 
+def _stream_key(device):
+    """Key of the per-(device, current stream) pools: their buffers are reused in stream order."""
+    return (device, torch.cuda.current_stream(device).cuda_stream)
+
+
 def _zero_slots(n: int, device) -> torch.Tensor:
     """n zero-initialised floats from a per-(device, stream) pool: one memset per 256 K slots instead
     of one per LayerNorm call (its range slots are combined with atomic max and must start at 0)."""
-    key = (device, torch.cuda.current_stream(device).cuda_stream)
+    key = _stream_key(device)
     pool = _zero_pool.get(key)
     if pool is None or pool[1] + n > pool[0].numel():
         pool = [torch.zeros(1 << 18, dtype=torch.float32, device=device), 0]
@@ -107,21 +128,40 @@ class _StreamGuard:
             self.seen.add(cur.cuda_stream)
 
 
+def _derived(src: torch.Tensor, slot: str, extra, build):
+    """The one cache rule of this file.  The value derived from `src` and kept on it as attribute `slot` is returned
+    while `src` is untouched (_ident) and `extra`, the call arguments it depends on, is the same; otherwise build()
+    launches it on the current stream and returns (value, tensor to guard).  Readers on other streams wait for that
+    launch (_StreamGuard).  Stored as (key, value, guard) in ONE attribute store, like _set_range."""
+    key = (_ident(src), extra)
+    c = getattr(src, slot, None)
+    if c is not None and c[0] == key:
+        c[2].acquire()
+        return c[1]
+    value, buf = build()
+    setattr(src, slot, (key, value, _StreamGuard(buf)))
+    return value
+
+
+def _measure_range(t: torch.Tensor, guarded: bool):
+    """Measures max |t| over the rows of t (spr_absmax) and attaches it like a published range; guarded for readers
+    on other streams when t outlives the call on a shared object (a weight)."""
+    L = _lib.lib()
+    n = L.spr_range_parts()
+    flat = t.reshape(-1, t.shape[-1])
+    parts = torch.empty((n,), dtype=torch.float32, device=t.device)
+    _lib.check(L.spr_absmax(_ptr(flat), flat.shape[0], flat.shape[1], flat.shape[1], _ptr(parts), _stream(t)),
+               "spr_absmax")
+    _set_range(t, parts, n, _StreamGuard(parts) if guarded else None)
+    return parts, n
+
+
 def _static_range(w: torch.Tensor):
     """Range partials of a tensor that rarely changes (weights): measured once per (storage,
     version) with spr_absmax and kept on the tensor like a published range -- an optimizer step
     bumps the version counter and the next call measures again."""
     r, n = _get_range(w)
-    if r is not None:
-        return r, n
-    L = _lib.lib()
-    n = L.spr_range_parts()
-    flat = w.reshape(-1, w.shape[-1])
-    parts = torch.empty((n,), dtype=torch.float32, device=w.device)
-    _lib.check(L.spr_absmax(_ptr(flat), flat.shape[0], flat.shape[1], flat.shape[1], _ptr(parts), _stream(w)),
-               "spr_absmax")
-    _set_range(w, parts, n, _StreamGuard(parts))
-    return parts, n
+    return (r, n) if r is not None else _measure_range(w, True)
 
 
 _PRIME_PARTS = 16
@@ -155,37 +195,27 @@ def prime_weight_ranges(params) -> int:
 def weight_transposed(w: torch.Tensor) -> torch.Tensor:
     """Contiguous W^T of a [n, k] weight, kept on the tensor per (storage, version) like its range (the
     backward's dX = g W runs as the forward's NT product on it); guarded for readers on other streams."""
-    c = getattr(w, '_spr_wt', None)
-    if c is not None and c[1] == w._version and c[2] == w.data_ptr() and c[3] == _range_epoch[0]:
-        c[4].acquire()
-        return c[0]
-    wt = w.detach().t().contiguous()
-    # max |W^T| = max |W|: the transposed copy shares the weight's measured range instead of being scanned itself
-    r, n = _static_range(w)
-    if r is not None:
-        rw = getattr(w, '_spr_range', None)
-        _set_range(wt, r, n, rw[5] if rw is not None else None)
-    w._spr_wt = (wt, w._version, w.data_ptr(), _range_epoch[0], _StreamGuard(wt))
-    return wt
+    def build():
+        wt = w.detach().t().contiguous()
+        # max |W^T| = max |W|: the copy shares the weight's measured range, and that measurement's guard, unscanned
+        r, n = _static_range(w)
+        _set_range(wt, r, n, w._spr_range[5])
+        return wt, wt
+    return _derived(w, '_spr_wt', None, build)
 
 
 def ensure_range(t: torch.Tensor) -> torch.Tensor:
     """Measures max |t| once (spr_absmax) and publishes it on the tensor like a producer kernel would, unless a
     valid range is already attached: a gradient that feeds two products (dX and dW of a projection) is then
     scanned once instead of once per product."""
-    if t.dim() != 2 or not t.is_contiguous() or _get_range(t)[0] is not None:
-        return t
-    L = _lib.lib()
-    n = L.spr_range_parts()
-    parts = torch.empty((n,), dtype=torch.float32, device=t.device)
-    _lib.check(L.spr_absmax(_ptr(t), t.shape[0], t.shape[1], t.shape[1], _ptr(parts), _stream(t)), "spr_absmax")
-    _set_range(t, parts, n)
+    if t.dim() == 2 and t.is_contiguous() and _get_range(t)[0] is None:
+        _measure_range(t, False)
     return t
 
 
 def _workspace(nbytes: int, device) -> torch.Tensor:
     """Grow-only scratch buffer per device+stream (stream-ordered reuse)."""
-    key = (device, torch.cuda.current_stream(device).cuda_stream)
+    key = _stream_key(device)
     buf = _ws_cache.get(key)
     if buf is None or buf.numel() < nbytes:
         buf = torch.empty(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=device)
@@ -480,16 +510,14 @@ class RadiusTable:
                                             _stream(self.supports)), "spr_radius_table_build")
         self._slot = 0
         self._slots = L.spr_radius_table_slots()
-        self._versions = (self.supports._version, self.s_cu._version)   # the table is stale after an in-place edit
+        self._built = (_ident(self.supports), _ident(self.s_cu))        # the table is stale after an in-place edit
 
     def matches(self, supports: torch.Tensor, s_cu: torch.Tensor, radius: float) -> bool:
         """True when this table was built from exactly these tensors (same storage, shape AND content: an
         in-place update of the supports bumps their version counter) at this radius and has a result slot left."""
-        return (supports.data_ptr() == self.supports.data_ptr() and supports.shape[0] == self.ns
-                and s_cu.data_ptr() == self.s_cu.data_ptr() and float(radius) == self.radius
-                and (self.supports._version, self.s_cu._version) == self._versions
-                and supports._version == self.supports._version and s_cu._version == self.s_cu._version
-                and self._slot < self._slots)
+        return ((_ident(supports), _ident(s_cu)) == self._built
+                and (_ident(self.supports), _ident(self.s_cu)) == self._built
+                and supports.shape[0] == self.ns and float(radius) == self.radius and self._slot < self._slots)
 
     def query(self, queries: torch.Tensor, q_cu: torch.Tensor, limit: int,
               dense: Optional[bool] = None) -> Tuple[torch.Tensor, int]:
@@ -586,19 +614,16 @@ def _kpconv_plan(nbr: torch.Tensor, nq: int, ns: int, stride: int, kmax: int, ro
     if order is not None:
         order = _dev(order, "order", torch.int32)
         assert order.shape == (nq,)
-    key = (nbr.data_ptr(), nbr._version, nq, ns, stride, kmax, rows_sorted, _range_epoch[0],
-           None if order is None else (order.data_ptr(), order._version))
-    c = getattr(nbr, '_spr_kp_plan', None)
-    if c is not None and c[0] == key:
-        c[2].acquire()
-        return c[1]
-    L = _lib.lib()
-    nbytes = L.spr_kpconv_plan_bytes(nq)
-    plan = torch.empty((nbytes,), dtype=torch.uint8, device=nbr.device)
-    _lib.check(L.spr_kpconv_plan(_ptr(nbr), nq, ns, stride, kmax, int(rows_sorted), _ptr(order), _ptr(plan), nbytes,
-                                 _stream(nbr)), "spr_kpconv_plan")
-    nbr._spr_kp_plan = (key, plan, _StreamGuard(plan))
-    return plan
+
+    def build():
+        L = _lib.lib()
+        nbytes = L.spr_kpconv_plan_bytes(nq)
+        plan = torch.empty((nbytes,), dtype=torch.uint8, device=nbr.device)
+        _lib.check(L.spr_kpconv_plan(_ptr(nbr), nq, ns, stride, kmax, int(rows_sorted), _ptr(order), _ptr(plan),
+                                     nbytes, _stream(nbr)), "spr_kpconv_plan")
+        return plan, plan
+    return _derived(nbr, '_spr_kp_plan', (nq, ns, stride, kmax, rows_sorted, None if order is None else _ident(order)),
+                    build)
 
 
 def kpconv_plan_prefetch(nbr: torch.Tensor, ns: int, rows_sorted: bool = True) -> None:
@@ -615,19 +640,15 @@ def kpconv_plan_prefetch(nbr: torch.Tensor, ns: int, rows_sorted: bool = True) -
 def _kpconv_wplanes(weights: torch.Tensor, wr: torch.Tensor, wr_n: int) -> torch.Tensor:
     """Split-fp16 fragment-order planes of a KPConv weight tensor (spr_kpconv_prep_weights), cached per
     weight version next to its range."""
-    key = (weights.data_ptr(), weights._version, wr.data_ptr(), _range_epoch[0])
-    c = getattr(weights, '_spr_kp_wplanes', None)
-    if c is not None and c[0] == key:
-        c[2].acquire()
-        return c[1]
-    L = _lib.lib()
-    n_kp, cin, cout = weights.shape
-    nbytes = L.spr_kpconv_wplanes_bytes(cin, cout)
-    planes = torch.empty((nbytes,), dtype=torch.uint8, device=weights.device)
-    _lib.check(L.spr_kpconv_prep_weights(_ptr(weights), n_kp, cin, cout, _ptr(wr), int(wr_n), _ptr(planes), nbytes,
-                                         _stream(weights)), "spr_kpconv_prep_weights")
-    weights._spr_kp_wplanes = (key, planes, _StreamGuard(planes))
-    return planes
+    def build():
+        L = _lib.lib()
+        n_kp, cin, cout = weights.shape
+        nbytes = L.spr_kpconv_wplanes_bytes(cin, cout)
+        planes = torch.empty((nbytes,), dtype=torch.uint8, device=weights.device)
+        _lib.check(L.spr_kpconv_prep_weights(_ptr(weights), n_kp, cin, cout, _ptr(wr), int(wr_n), _ptr(planes),
+                                             nbytes, _stream(weights)), "spr_kpconv_prep_weights")
+        return planes, planes
+    return _derived(weights, '_spr_kp_wplanes', wr.data_ptr(), build)
 
 
 def instnorm(x, cu, eps: float = 1e-5, norm: bool = True, add=None, slope: float = 1.0,
@@ -677,20 +698,12 @@ def _tail_tiles(cu: torch.Tensor, n: int, tr: int) -> torch.Tensor:
     """tile table of spr_block_tail for a cu_seqlens tensor, cached on it (one per pyramid level and tile
     height; the pyramid hands the same cu tensor to every block of a level) and guarded for readers on
     other streams like the KPConv plans."""
-    key = (cu.data_ptr(), cu._version, n, tr, _range_epoch[0])
-    cache = getattr(cu, '_spr_tail_tiles', None)
-    if cache is None:
-        cache = {}
-        cu._spr_tail_tiles = cache
-    c = cache.get(tr)
-    if c is not None and c[0] == key:
-        c[2].acquire()
-        return c[1]
-    L = _lib.lib()
-    t = torch.empty((L.spr_block_tail_tiles_len(n, cu.numel() - 1, tr),), dtype=torch.int32, device=cu.device)
-    _lib.check(L.spr_block_tail_tiles(_ptr(cu), n, cu.numel() - 1, tr, _ptr(t), _stream(cu)), "spr_block_tail_tiles")
-    cache[tr] = (key, t, _StreamGuard(t))
-    return t
+    def build():
+        L = _lib.lib()
+        t = torch.empty((L.spr_block_tail_tiles_len(n, cu.numel() - 1, tr),), dtype=torch.int32, device=cu.device)
+        _lib.check(L.spr_block_tail_tiles(_ptr(cu), n, cu.numel() - 1, tr, _ptr(t), _stream(cu)), "spr_block_tail_tiles")
+        return t, t
+    return _derived(cu, f'_spr_tail_tiles_{tr}', (n, tr), build)       # one slot per tile height
 
 
 def instnorm_stats(x, cu, eps: float = 1e-5, max_len: Optional[int] = None):
@@ -1059,16 +1072,13 @@ def attention_bwd(q, k, v, out, dout, cu, kv_seg_host, max_len: int, nhead: int,
 def inproj_prepare(w_in: torch.Tensor):
     """Weight-side inputs of the fused in-projection (max |w| partials + row L1 norms), measured
     once per weight version and cached on the tensor like _static_range."""
-    r = getattr(w_in, '_spr_inproj', None)
-    if r is not None and r[1] == w_in._version and r[2] == w_in.data_ptr() and r[3] == _range_epoch[0]:
-        r[4].acquire()
-        return r[0]
-    L = _lib.lib()
-    d = w_in.shape[1]
-    buf = torch.empty((L.spr_range_parts() + 3 * d,), dtype=torch.float32, device=w_in.device)
-    _lib.check(L.spr_attn_inproj_prepare(_ptr(w_in), d, _ptr(buf), _stream(w_in)), "spr_attn_inproj_prepare")
-    w_in._spr_inproj = (buf, w_in._version, w_in.data_ptr(), _range_epoch[0], _StreamGuard(buf))
-    return buf
+    def build():
+        L = _lib.lib()
+        d = w_in.shape[1]
+        buf = torch.empty((L.spr_range_parts() + 3 * d,), dtype=torch.float32, device=w_in.device)
+        _lib.check(L.spr_attn_inproj_prepare(_ptr(w_in), d, _ptr(buf), _stream(w_in)), "spr_attn_inproj_prepare")
+        return buf, buf
+    return _derived(w_in, '_spr_inproj', None, build)
 
 
 def attention_inproj(x_qk, x_v, w_in, b_in, cu, kv_seg, max_len: int, nhead: int, w_prep=None) -> torch.Tensor:
@@ -1138,8 +1148,8 @@ def xenc_prepare(layer_params, layer_eps, final, nhead: int, d_ff: int, pos_boun
     (SPR_XENC_PTRS_PER_LAYER); layer_eps: per layer (eps1, eps2, eps3); final: (weight, bias, eps) of
     the stack's last LayerNorm or None.  `cached`: a previous XencPlan, returned as is when nothing changed."""
     flat = [t for lp in layer_params for t in lp] + ([final[0], final[1]] if final is not None else [])
-    key = (tuple((t.data_ptr(), t._version) for t in flat), tuple(float(e) for le in layer_eps for e in le),
-           None if final is None else float(final[2]), int(nhead), int(d_ff), float(pos_bound), _range_epoch[0])
+    key = (tuple(_ident(t) for t in flat), tuple(float(e) for le in layer_eps for e in le),
+           None if final is None else float(final[2]), int(nhead), int(d_ff), float(pos_bound))
     if cached is not None and cached.key == key:
         return cached
     with _xenc_lock:
