@@ -617,6 +617,21 @@ int spr_match_sinkhorn(const float* feat, int d, const float* xyz, const int* cu
 int spr_gather_rows(const float* x, int n_src, int c, const int* idx, int n,
                     float* out, void* stream);
 
+/* ---- pair assembly: encoded clouds -> the token layout of a list of pairs ---------
+ * RegTR.register (regtr.py): a cloud is encoded once (pyramid, KPConv encoder, feat_proj) and used by
+ * any number of pairs.  x [t_in, c] holds the packed rows of n_clouds clouds (cu [n_clouds + 1]);
+ * y [t_out, c] receives 2 * npairs segments stacked [src_0..src_{P-1}, tgt_0..tgt_{P-1}]: segment s is a
+ * copy of cloud src_idx[s] for s < npairs and of cloud tgt_idx[s - npairs] otherwise.  cu_out
+ * [2 * npairs + 1] is the exclusive prefix of the output segment lengths, built by the caller from the
+ * host-side cloud lengths (t_out = cu_out[2 * npairs]); src_idx / tgt_idx [npairs] i32.  One launch,
+ * whatever the number of pairs; 16-byte accesses when c % 4 == 0 and x, y are 16-byte aligned (tokens),
+ * 4-byte accesses otherwise (c = 3: the superpoint coordinates).  Rows whose source would lie outside
+ * the indexed cloud (an index outside [0, n_clouds), a cu_out that does not match the clouds) are zeros.
+ */
+int spr_pair_gather(const float* x, int t_in, int c, const int* cu, int n_clouds,
+                    const int* src_idx, const int* tgt_idx, int npairs, const int* cu_out,
+                    int t_out, float* y, void* stream);
+
 /* ---- losses (forward) of RegTR.compute_loss -- SURVEY 8f row 1 --------------
  * models/qk_regtr_full.py:313-368.  Deterministic reductions (fixed partition,
  * float64 accumulation).  Scalars are written to device memory (out[0]).

@@ -1529,3 +1529,31 @@ def gather_rows_raw(x, idx) -> torch.Tensor:
     _lib.check(_lib.lib().spr_gather_rows(_ptr(x), n_src, c, _ptr(idx), n, _ptr(out), _stream(x)),
                "spr_gather_rows")
     return out
+
+
+def pair_gather(x, cu, src_idx, tgt_idx, cu_out, out=None, rows: Optional[int] = None) -> torch.Tensor:
+    """Pair assembly (spr_pair_gather): x [T, C] holds the packed rows of the clouds described by cu [U+1]; the result
+    [T_out, C] stacks 2P segments [src_0..src_{P-1}, tgt_0..tgt_{P-1}], segment s a copy of cloud src_idx[s] (s < P) or
+    tgt_idx[s - P].  cu_out [2P+1]: the prefix of the output segment lengths, built on the host from the host-side
+    cloud lengths (lengths_to_cu).  T_out is taken from `out`, else from `rows`; only when neither is given is it read
+    back from cu_out (a device->host read).  One launch for all pairs, any C (tokens: 256, coordinates: 3)."""
+    x = _dev(x, "x", torch.float32)
+    cu = _dev(cu, "cu", torch.int32)
+    src_idx = _dev(src_idx, "src_idx", torch.int32)
+    tgt_idx = _dev(tgt_idx, "tgt_idx", torch.int32)
+    cu_out = _dev(cu_out, "cu_out", torch.int32)
+    npairs = src_idx.numel()
+    if x.dim() != 2 or tgt_idx.numel() != npairs or cu_out.numel() != 2 * npairs + 1 or cu.numel() < 2:
+        raise ValueError("pair_gather: x [T, C], cu [U+1], src_idx [P], tgt_idx [P], cu_out [2P+1]")
+    t_in, c = x.shape
+    if out is not None:
+        t_out = int(out.shape[0])
+    else:
+        t_out = int(rows) if rows is not None else int(cu_out[-1])
+        out = torch.empty((t_out, c), dtype=torch.float32, device=x.device)
+    if (not out.is_cuda or out.device != x.device or out.dtype != torch.float32 or not out.is_contiguous()
+            or tuple(out.shape) != (t_out, c)):
+        raise ValueError("pair_gather: out must be a contiguous float32 [T_out, C] tensor on x's device")
+    _lib.check(_lib.lib().spr_pair_gather(_ptr(x), t_in, c, _ptr(cu), cu.numel() - 1, _ptr(src_idx), _ptr(tgt_idx),
+                                          npairs, _ptr(cu_out), t_out, _ptr(out), _stream(x)), "spr_pair_gather")
+    return out

@@ -61,6 +61,49 @@ def _meta_tensors(meta):
                 yield t
 
 
+class EncodedClouds:
+    """What RegTR.encode leaves of a list of clouds and RegTR.register reads: the projected superpoint tokens and the
+    coarsest-level points, both packed cloud after cloud, with the per-cloud superpoint counts on the host (`lens`)
+    and as a device prefix (`cu`), plus the kpconv_meta of the encode call (None once encodings were concatenated)."""
+
+    def __init__(self, tokens, points, lens, cu=None, kpconv_meta=None):
+        lens = [int(n) for n in lens]
+        if tokens.shape[0] != sum(lens) or points.shape[0] != sum(lens):
+            raise ValueError(f"EncodedClouds: {tokens.shape[0]} token rows, {points.shape[0]} points, counts sum to {sum(lens)}")
+        self.tokens, self.points, self.lens = tokens, points, lens
+        self.cu = cu if cu is not None else ops.lengths_to_cu(lens, tokens.device)
+        self.kpconv_meta = kpconv_meta
+
+    def __len__(self):
+        return len(self.lens)
+
+    def _check(self, i):
+        if isinstance(i, bool) or not isinstance(i, (int, np.integer)) or not 0 <= i < len(self.lens):
+            raise ValueError(f"cloud index {i!r} is not an index in range({len(self.lens)})")
+        return int(i)
+
+    def select(self, indices):
+        """The encodings of clouds `indices` (any order, repeats allowed): host bookkeeping and one concatenation of
+        row ranges per tensor.  The pyramid metadata describes the whole encode call and stays with it."""
+        indices = [self._check(i) for i in indices]
+        if not indices:
+            raise ValueError("select: empty index list")
+        start = np.concatenate([[0], np.cumsum(self.lens)])
+        rows = [slice(int(start[i]), int(start[i + 1])) for i in indices]
+        return EncodedClouds(torch.cat([self.tokens[r] for r in rows]), torch.cat([self.points[r] for r in rows]),
+                             [self.lens[i] for i in indices])
+
+    @staticmethod
+    def cat(encodings):
+        """Several encodings as one (a sequence keeps frame t and appends frame t+1): one concatenation per tensor.
+        kpconv_meta does not survive: it describes one encode call."""
+        encodings = list(encodings)
+        if not encodings:
+            raise ValueError("cat: empty list of encodings")
+        return EncodedClouds(torch.cat([e.tokens for e in encodings]), torch.cat([e.points for e in encodings]),
+                             [n for e in encodings for n in e.lens])
+
+
 class RegTR(nn.Module):
     def __init__(self, cfg, *args, compute_upsamples=True, order=ops.ORDER_REFERENCE,
                  return_attn=False, record_attn=False, **kwargs):
@@ -115,15 +158,20 @@ class RegTR(nn.Module):
         return self._forward(batch)
 
     def _forward(self, batch):
-        cfg = self.cfg
         B = len(batch['src_xyz'])
+        tokens, xyz_c, lens_c, meta = self._encode(list(batch['src_xyz']) + list(batch['tgt_xyz']))
+        batch['kpconv_meta'] = meta                      # qk_regtr_full.py:153
+        return self._register(tokens, xyz_c, lens_c[:B], lens_c[B:])
+
+    def _encode(self, clouds):
+        """The per-cloud half of the forward: pyramid, KPConv encoder, feat_proj.  Nothing here looks across clouds.
+        Returns (tokens [sum L, d_embed], coarsest points [sum L, 3], host superpoint counts, kpconv_meta)."""
         # Pyramid (index work, never differentiated: qk_regtr_full.py:152) and KPConv encoder on a
         # column of ones (:157-166).  The pyramid is built on a SIDE stream and the blocks of a
         # level are launched on the caller's stream as soon as their part exists: the searches of
         # the deeper levels -- small latency-bound kernels, each followed by a device->host read of
         # a size -- run beside the big convolutions of the shallower ones instead of in front of
         # them (SPR_NO_SIDE_STREAM=1: one stream, pyramid first).
-        clouds = list(batch['src_xyz']) + list(batch['tgt_xyz'])
         device = clouds[0].device
         feats0 = torch.ones((sum(int(c.shape[0]) for c in clouds), 1), dtype=torch.float32, device=device)
         if _concurrency.active(device):
@@ -151,15 +199,19 @@ class RegTR(nn.Module):
             with torch.no_grad():
                 meta = self.preprocessor(clouds)
             feats_un, _ = self.kpf_encoder(feats0, meta)
-        batch['kpconv_meta'] = meta                      # qk_regtr_full.py:153
-        lens_c = meta['_lens_host'][-1]
-        src_lens, tgt_lens = lens_c[:B], lens_c[B:]
-        xyz_c = meta['points'][-1]
         tokens = ops.linear(feats_un, self.feat_proj.weight, self.feat_proj.bias)
+        return tokens, meta['points'][-1], meta['_lens_host'][-1], meta
+
+    def _register(self, tokens, xyz_c, src_lens, tgt_lens, segments=None):
+        """The per-pair half: position embedding, cross-encoder, overlap head, matching + pose on tokens / points
+        packed [src_0..src_{B-1}, tgt_0..tgt_{B-1}].  segments: make_segments(src_lens, tgt_lens) if the caller has it."""
+        cfg = self.cfg
+        B = len(src_lens)
+        device = tokens.device
 
         # superpoint attention on packed tokens (qk_regtr_full.py:199-230)
         pe = self.pos_embed(xyz_c) if cfg.transformer_encoder_has_pos_emb else None
-        cu, seg_self, seg_cross, max_len = make_segments(src_lens, tgt_lens, device)
+        cu, seg_self, seg_cross, max_len = segments if segments is not None else make_segments(src_lens, tgt_lens, device)
         seg_host = ([int(n) for n in list(src_lens) + list(tgt_lens)], list(range(2 * B)),
                     list(range(B, 2 * B)) + list(range(B)))
         cond = self.transformer_encoder.forward_packed(tokens, cu, seg_self, seg_cross, max_len, pos=pe,
@@ -251,6 +303,50 @@ class RegTR(nn.Module):
             'src_overlap': src_ov, 'tgt_overlap': tgt_ov,
             'overlap_prob_list': vals, 'ind_list': inds,
         }
+
+    # ------------------------------------------------------------------ #
+    # Encode each cloud once, register any list of pairs over the encodings (inference only).
+    def _inference_only(self, what):
+        if self.training:
+            raise RuntimeError(f"RegTR.{what} is an inference path: call model.eval() first (training goes through forward)")
+
+    def encode(self, clouds) -> EncodedClouds:
+        """Pyramid, KPConv encoder and feat_proj of a list of [N_i, 3] float32 device clouds -- the part of forward()
+        that never looks across clouds -- kept for any number of register() calls."""
+        self._inference_only("encode")
+        clouds = list(clouds)
+        if not clouds:
+            raise ValueError("encode: empty cloud list")
+        clouds = [ops._dev(c, f"clouds[{i}]", torch.float32) for i, c in enumerate(clouds)]   # CPU tensor: raises
+        if any(c.dim() != 2 or c.shape[1] != 3 or c.shape[0] == 0 for c in clouds):
+            raise ValueError("encode: every cloud must be a non-empty [N, 3] tensor")
+        with torch.no_grad():
+            tokens, xyz_c, lens_c, meta = self._encode(clouds)
+        return EncodedClouds(tokens, xyz_c, lens_c, cu=meta['_cu'][len(meta['points']) - 1], kpconv_meta=meta)
+
+    def register(self, enc: EncodedClouds, pairs) -> dict:
+        """forward()'s output dict for the pairs (src_index, tgt_index) into `enc`: one ops.pair_gather per tensor
+        lays tokens and points out as [src_0..src_{P-1}, tgt_0..tgt_{P-1}], then the unchanged second half of
+        forward() runs (position embedding of the gathered points, cross-encoder, overlap head, matching + pose)."""
+        self._inference_only("register")
+        pairs = [tuple(p) for p in pairs]
+        if not pairs:
+            raise ValueError("register: empty pair list")
+        if any(len(p) != 2 for p in pairs):
+            raise ValueError("register: pairs are (src_index, tgt_index)")
+        src = [enc._check(p[0]) for p in pairs]
+        tgt = [enc._check(p[1]) for p in pairs]
+        tokens = ops._dev(enc.tokens, "enc.tokens", torch.float32)
+        points = ops._dev(enc.points, "enc.points", torch.float32)
+        P = len(pairs)
+        src_lens, tgt_lens = [enc.lens[i] for i in src], [enc.lens[i] for i in tgt]
+        with torch.no_grad():
+            segments = make_segments(src_lens, tgt_lens, tokens.device)      # cu_out from the host counts: no read-back
+            idx = torch.from_numpy(np.asarray(src + tgt, dtype=np.int32)).to(tokens.device)
+            rows = sum(src_lens) + sum(tgt_lens)
+            tok = ops.pair_gather(tokens, enc.cu, idx[:P], idx[P:], segments[0], rows=rows)
+            xyz = ops.pair_gather(points, enc.cu, idx[:P], idx[P:], segments[0], rows=rows)
+            return self._register(tok, xyz, src_lens, tgt_lens, segments)
 
     # ------------------------------------------------------------------ #
     def compute_loss(self, pred, batch):
