@@ -394,6 +394,29 @@ int spr_layernorm(const float* x, int m, int c, const float* gamma, const float*
 int spr_posemb_sine(const float* xyz, int n, int d_model, float scale,
                     float temperature, float* out, void* stream);
 
+/* ---- a7: learned positional embedding ----------------------------------------
+ * Replaces PositionEmbeddingLearned.forward (transformer/position_embedding.py:53-72; pos_emb_type: learned,
+ * qk_regtr_full.py:55-56): the MLP 3 -> 32 -> 64 -> 128 -> 256 -> d_model with a ReLU behind each of the first four
+ * layers.  xyz [t,3] -> pe [t,d_model]; d_model must be 256 (anything else is a status error, like spr_xenc_prepare).
+ *   params_host: a HOST array of the ten DEVICE pointers mlp.{0,2,4,6,8}.{weight,bias} in that order
+ *   (weight [out,in] row-major as nn.Linear keeps it, 16-byte aligned).
+ * One fused kernel: a workgroup carries a tile of 64 tokens through all five layers in LDS, the weights stream from
+ * L2; no intermediate goes to memory.  Exact f32 arithmetic (layers 2-5 on v_mfma_f32_32x32x2_f32): no operand is
+ * scaled, no coordinate or weight magnitude needs a bound, and spr_set_gemm_mode does not change the result.
+ * t = 0 returns 0 and writes nothing.
+ * spr_posemb_mlp_bwd: the ten parameter gradients (grads_host: HOST array of ten DEVICE pointers, shapes and order of
+ *   params_host; fully written, t = 0 writes zeros) of sum(pe * dpe), dpe [t,256] 16-byte aligned.  Nothing is kept
+ *   from the forward: one kernel recomputes the activations from xyz, runs the deltas back down
+ *   (delta_l = (delta_{l+1} W_{l+1}) relu'(h_l), relu'(0) = 0) and leaves both in ws; the weight gradients are
+ *   spr_bgemm products over fixed 256-token records summed by spr_reduce_parts, the bias gradients spr_colsum.
+ *   No atomics: two calls on the same inputs give the same bits.  There is no d xyz (coordinates are never
+ *   differentiated).  ws: spr_posemb_mlp_bwd_workspace_bytes(t) bytes, 256-byte aligned.
+ */
+int spr_posemb_mlp(const float* xyz, const float* const* params_host, int t, int d_model, float* pe, void* stream);
+size_t spr_posemb_mlp_bwd_workspace_bytes(int t);
+int spr_posemb_mlp_bwd(const float* xyz, const float* const* params_host, const float* dpe, int t, int d_model,
+                       float* const* grads_host, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- a9: varlen multi-head attention core -----------------------------------
  * Replaces the scaled-dot-product core of the four nn.MultiheadAttention
  * calls per layer (transformers.py:198-227) on packed tokens: segment s

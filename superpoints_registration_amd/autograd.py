@@ -312,7 +312,28 @@ class LayerNormFn(torch.autograd.Function):
         _lib.check(L.spr_layernorm_bwd(_ops._ptr(x.detach()), m, c, _ops._ptr(gamma.detach().contiguous()), ctx.eps,
                                        _ops._ptr(dn), _ops._ptr(dp), _ops._ptr(dx), _ops._ptr(dg), _ops._ptr(db),
                                        _ops._ptr(ws), ws.numel(), _ops._stream(x)), "spr_layernorm_bwd")
-        return dx, dg, db, None, None, None
+        # pos enters as out_pos = LN(x) + pos: its gradient is the one arriving at out_pos (a learned embedding;
+        # the sine table never requires one)
+        dpos = dp if (ctx.has[1] and ctx.needs_input_grad[4]) else None
+        return dx, dg, db, None, dpos, None
+
+
+class PosEmbMLPFn(torch.autograd.Function):
+    """pe = MLP(xyz) of PositionEmbeddingLearned (spr_posemb_mlp).  Only xyz is kept: spr_posemb_mlp_bwd recomputes the
+    activations and returns the ten parameter gradients.  No gradient for xyz."""
+
+    @staticmethod
+    def forward(ctx, xyz, *params):
+        with torch.no_grad():
+            pe = _ops.posemb_mlp_raw(xyz, params)
+        ctx.save_for_backward(xyz, *params)
+        return pe
+
+    @staticmethod
+    def backward(ctx, dpe):
+        xyz, *params = ctx.saved_tensors
+        grads = _ops.posemb_mlp_bwd(xyz.detach(), params, dpe.contiguous())
+        return (None,) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[1:]))
 
 
 class MaxPoolFn(torch.autograd.Function):

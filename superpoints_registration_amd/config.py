@@ -77,9 +77,15 @@ CONFIGS = {
 }
 
 
-def get_config(name: str) -> Config:
+def get_config(name: str, **overrides) -> Config:
+    """The shipped experiment `name`; keyword arguments override single keys (get_config('3dmatch',
+    pos_emb_type='learned')).  Only keys the configs already carry can be overridden: a misspelt one raises."""
     cfg = Config(copy.deepcopy(_COMMON))
     cfg.update(copy.deepcopy(CONFIGS[name]))
+    unknown = sorted(k for k in overrides if k not in cfg)
+    if unknown:
+        raise KeyError(f"get_config: unknown keys {unknown}")
+    cfg.update(copy.deepcopy(overrides))
     return cfg
 
 

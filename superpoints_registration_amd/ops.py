@@ -883,9 +883,9 @@ def set_gemm_mode(mode: int) -> None:
 
 
 def layernorm(x, gamma, beta, eps: float = 1e-5, pos=None, want_norm: bool = True):
-    """Returns (LN(x) or None, LN(x)+pos or None).  Differentiable in x, gamma, beta
+    """Returns (LN(x) or None, LN(x)+pos or None).  Differentiable in x, gamma, beta and pos
     (autograd.LayerNormFn)."""
-    if _wants_grad(x, gamma, beta):
+    if _wants_grad(x, gamma, beta, pos):
         from .autograd import LayerNormFn
         n, p = LayerNormFn.apply(_dev(x, "x", torch.float32), gamma, beta, float(eps), pos, bool(want_norm))
         return (n if (want_norm or pos is None) else None), (p if pos is not None else None)
@@ -922,6 +922,68 @@ def posemb_sine(xyz, d_model: int, scale: float = 1.0, temperature: float = 1000
                                           float(temperature), _ptr(out), _stream(xyz)),
                "spr_posemb_sine")
     return out
+
+
+POSEMB_MLP_WIDTHS = (3, 32, 64, 128, 256, 256)   # PositionEmbeddingLearned: fixed in the kernel (csrc/posemb_mlp.hip)
+
+
+def _posemb_mlp_params(params, device):
+    """The ten tensors mlp.{0,2,4,6,8}.{weight,bias} checked against the fixed widths, as a ctypes pointer array
+    (plus the tensors themselves, which must stay alive across the call)."""
+    params = list(params)
+    if len(params) != 10:
+        raise ValueError(f"posemb_mlp: ten parameters (five weights and biases) expected, got {len(params)}")
+    keep = []
+    for i, t in enumerate(params):
+        t = _dev(t.detach() if isinstance(t, torch.Tensor) else t, f"params[{i}]", torch.float32)
+        l = i // 2
+        want = (POSEMB_MLP_WIDTHS[l + 1], POSEMB_MLP_WIDTHS[l]) if i % 2 == 0 else (POSEMB_MLP_WIDTHS[l + 1],)
+        if tuple(t.shape) != want:
+            raise ValueError(f"posemb_mlp: params[{i}] has shape {tuple(t.shape)}, the kernel is built for {want} "
+                             "(n_dim 3, d_model 256)")
+        if t.device != device:
+            raise RuntimeError(f"posemb_mlp: params[{i}] is on {t.device}, xyz on {device}")
+        keep.append(t)
+    return (ctypes.c_void_p * 10)(*[t.data_ptr() for t in keep]), keep
+
+
+def posemb_mlp(xyz, params) -> torch.Tensor:
+    """a7, pos_emb_type 'learned': the MLP 3 -> 32 -> 64 -> 128 -> 256 -> 256 (ReLU between the layers) of xyz [T, 3] in
+    one fused kernel.  params: mlp.{0,2,4,6,8}.{weight,bias} in that order.  Differentiable in the parameters
+    (autograd.PosEmbMLPFn); coordinates are never differentiated."""
+    params = list(params)
+    if _wants_grad(*params):
+        from .autograd import PosEmbMLPFn
+        return PosEmbMLPFn.apply(_dev(xyz, "xyz", torch.float32), *params)
+    return posemb_mlp_raw(xyz, params)
+
+
+def posemb_mlp_raw(xyz, params) -> torch.Tensor:
+    xyz = _dev(xyz, "xyz", torch.float32)
+    if xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise ValueError(f"posemb_mlp: xyz must be [T, 3], got {tuple(xyz.shape)}")
+    ptrs, keep = _posemb_mlp_params(params, xyz.device)
+    t = xyz.shape[0]
+    out = torch.empty((t, 256), dtype=torch.float32, device=xyz.device)
+    _lib.check(_lib.lib().spr_posemb_mlp(_ptr(xyz), ptrs, t, 256, _ptr(out), _stream(xyz)), "spr_posemb_mlp")
+    return out
+
+
+def posemb_mlp_bwd(xyz, params, dpe):
+    """The ten parameter gradients of sum(posemb_mlp(xyz, params) * dpe), in the order of params."""
+    xyz = _dev(xyz, "xyz", torch.float32)
+    dpe = _dev(dpe, "dpe", torch.float32)
+    t = xyz.shape[0]
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or tuple(dpe.shape) != (t, 256):
+        raise ValueError(f"posemb_mlp_bwd: xyz [T, 3] and dpe [T, 256] expected, got {tuple(xyz.shape)}, {tuple(dpe.shape)}")
+    ptrs, keep = _posemb_mlp_params(params, xyz.device)
+    grads = [torch.empty_like(p) for p in keep]
+    gptrs = (ctypes.c_void_p * 10)(*[g.data_ptr() for g in grads])
+    L = _lib.lib()
+    ws = _workspace(L.spr_posemb_mlp_bwd_workspace_bytes(t), xyz.device)
+    _lib.check(L.spr_posemb_mlp_bwd(_ptr(xyz), ptrs, _ptr(dpe), t, 256, gptrs, _ptr(ws), ws.numel(), _stream(xyz)),
+               "spr_posemb_mlp_bwd")
+    return grads
 
 
 def attention(q, k, v, cu, kv_seg, max_len: int, nhead: int, out=None, lens_host=None,

@@ -30,7 +30,7 @@ import torch.nn as nn
 
 from . import _concurrency, ops
 from .kpconv import KPFEncoder, Preprocessor
-from .transformers import (PositionEmbeddingCoordsSine, TransformerCrossEncoder,
+from .transformers import (PositionEmbeddingCoordsSine, PositionEmbeddingLearned, TransformerCrossEncoder,
                            TransformerCrossEncoderLayer, make_segments)
 
 
@@ -120,14 +120,20 @@ class RegTR(nn.Module):
             if cfg.get(flag, False):
                 raise NotImplementedError(f"cfg.{flag}=True is not supported (use_attn_affinity raises "
                                           "ValueError in the reference itself, qk_regtr_full.py:505-511)")
-        if cfg.get('pos_emb_type', 'sine') != 'sine':
-            raise NotImplementedError("only pos_emb_type='sine'")
+        if cfg.get('pos_emb_type', 'sine') not in ('sine', 'learned'):
+            raise NotImplementedError("pos_emb_type must be 'sine' or 'learned' (qk_regtr_full.py:52-58)")
 
         self.preprocessor = Preprocessor(cfg, compute_upsamples=compute_upsamples, order=order)
         self.kpf_encoder = KPFEncoder(cfg, cfg.d_embed)
         self.feat_proj = nn.Linear(self.kpf_encoder.encoder_skip_dims[-1], cfg.d_embed, bias=True)
-        self.pos_embed = PositionEmbeddingCoordsSine(3, cfg.d_embed,
-                                                     scale=cfg.get('pos_emb_scaling', 1.0))
+        if cfg.get('pos_emb_type', 'sine') == 'sine':
+            self.pos_embed = PositionEmbeddingCoordsSine(3, cfg.d_embed,
+                                                         scale=cfg.get('pos_emb_scaling', 1.0))
+            self._pos_bound = 1.0                           # |sin|, |cos| <= 1
+        else:
+            self.pos_embed = PositionEmbeddingLearned(3, cfg.d_embed)
+            # max |MLP(xyz)| depends on the coordinates: no static bound, the cross-encoder runs operator by operator
+            self._pos_bound = None
         encoder_layer = TransformerCrossEncoderLayer(
             cfg.d_embed, cfg.nhead, cfg.d_feedforward, cfg.dropout,
             activation=cfg.transformer_act, normalize_before=cfg.pre_norm,
@@ -215,7 +221,7 @@ class RegTR(nn.Module):
         seg_host = ([int(n) for n in list(src_lens) + list(tgt_lens)], list(range(2 * B)),
                     list(range(B, 2 * B)) + list(range(B)))
         cond = self.transformer_encoder.forward_packed(tokens, cu, seg_self, seg_cross, max_len, pos=pe,
-                                                       seg_host=seg_host, pos_bound=1.0)   # |sin|, |cos| <= 1
+                                                       seg_host=seg_host, pos_bound=self._pos_bound)
 
         # overlap head (qk_regtr_full.py:248-249)
         overlap = ops.linear(cond, self.overlap_predictor.weight, self.overlap_predictor.bias,

@@ -56,6 +56,29 @@ class PositionEmbeddingCoordsSine(nn.Module):
         return out.view(*lead, self.d_model)
 
 
+class PositionEmbeddingLearned(nn.Module):
+    """position_embedding.py:53-72 (pos_emb_type: learned): the MLP n_dim -> 32 -> 64 -> 128 -> 256 -> d_model with a
+    ReLU behind each of the first four layers.  `mlp` is the reference's nn.Sequential and only holds the parameters
+    (state-dict names mlp.{0,2,4,6,8}.{weight,bias}, shapes, default init); its forward() is never called -- the
+    embedding runs as one fused kernel (ops.posemb_mlp), training through autograd.PosEmbMLPFn."""
+
+    def __init__(self, n_dim: int = 1, d_model: int = 256):
+        super().__init__()
+        if n_dim != 3:
+            raise NotImplementedError("the hot path embeds 3-D coordinates")
+        if d_model != 256:
+            raise NotImplementedError("the learned embedding kernel is built for d_model 256 (d_embed of every config)")
+        self.n_dim, self.d_model = n_dim, d_model
+        self.mlp = nn.Sequential(nn.Linear(n_dim, 32), nn.ReLU(), nn.Linear(32, 64), nn.ReLU(), nn.Linear(64, 128),
+                                 nn.ReLU(), nn.Linear(128, 256), nn.ReLU(), nn.Linear(256, d_model))
+
+    def forward(self, xyz: torch.Tensor) -> torch.Tensor:
+        assert xyz.shape[-1] == self.n_dim
+        lead = xyz.shape[:-1]
+        params = [p for i in (0, 2, 4, 6, 8) for p in (self.mlp[i].weight, self.mlp[i].bias)]
+        return ops.posemb_mlp(xyz.reshape(-1, 3), params).view(*lead, self.d_model)
+
+
 def _pack(padded: Tensor, key_padding_mask: Optional[Tensor]):
     """(L,B,D) + mask (B,L) [True = pad]  ->  packed [sum L_b, D], lengths."""
     L, B, D = padded.shape
