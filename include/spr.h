@@ -605,6 +605,54 @@ int spr_weighted_procrustes(const float* a, const float* b, const float* w,
                             const int* pair_cu, int npairs, float* out_pose,
                             void* stream);
 
+/* ---- the config-off refinements for all pairs in one call -------------------
+ * Replaces the per-pair tail of RegTR.softmax_correlation (qk_regtr_full.py:370-398 ratio_test / recompute_weights /
+ * local_global_registration, :465-553 and :573-658): one launch, one workgroup per pair.
+ * Inputs: val / val2 / ind [t_total] as spr_match_dualsoftmax writes them (val2 may be NULL without
+ * SPR_REFINE_RATIO), overlap [t_total] f32, xyz [t_total,3] f32, cu [2*npairs+1] i32 (cu[2*npairs] = t_total);
+ * k_b [npairs] i32 entries kept per pair and out_cu [npairs+1] i32 their exclusive prefix (device; the caller
+ * computes both on the host and uploads them in one copy; out_cu[b+1] - out_cu[b] = k_b[b] <= n_b).
+ * Per pair, N / M the src / tgt counts, in this order:
+ *   1. the "own" side carries the matches: the tgt tokens when N > M, else the src tokens; n = min(N, M) entries
+ *   2. RATIO:    v = (val2 / v < lowe_thres) ? v : 0     correctly rounded f32 divide; 0/0 fails the test
+ *   3. MEDIAN:   v = (v > med) ? v : 0,  med = the element at sorted (ascending) position (n-1)/2, exact
+ *   4. OVERLAP:  ov = overlap_src * overlap_tgt of (entry, partner ind);  v *= ov unless OVERLAP_W
+ *   5. TOPK:     the k_b largest v in descending order, ties to the lower position; without TOPK k_b = n and the
+ *                order is the token order
+ *      outputs in that order at out_cu[b]: val_out f32, src_pts / tgt_pts [.,3] f32 (the entry's own point and its
+ *      partner's; SINKHORN: the src and the tgt point at the entry's position, no partner gather), ind_out i64 =
+ *      the partner index, or with TOPK the entry's position (what the reference's ind_list holds after its topk)
+ *   6. pose = the solve of spr_weighted_procrustes on the output points, weights ov (OVERLAP_W) else v; with
+ *      pose_in [npairs,3,4] (required by SINKHORN) no solve: pose = pose_in
+ *   7. LGR: n_steps x { res = ||b - (R a + t)|| in spr_pose_residuals' arithmetic; w *= (res < acceptance_radius)
+ *      (w starts as v); pose = solve(w) }
+ * pose [npairs,3,4].  A pair's outputs depend on that pair's inputs only: fixed reduction order, no atomics -- the
+ * same bits alone or at any place in any batch.
+ * status [npairs] i32 (device, no host read here): 0; SPR_REFINE_BAD_INDEX when an ind of the own side lies outside
+ * the partner cloud (the entry is then treated as matched to partner 0: never a wild read); SPR_REFINE_BAD_LAYOUT
+ * when cu / k_b / out_cu contradict each other or n_b > max_n (pose zeros, nothing else written).
+ * max_n: the largest n_b (host).  Up to 4 096 entries a pair's working set (20 bytes per entry) stays in LDS; above,
+ * it lives in `ws` (spr_refine_pairs_workspace_bytes, 0 when max_n <= 4 096); max_n > SPR_REFINE_MAX_N is refused
+ * with a status return.  OVERLAP_W needs OVERLAP, RATIO needs val2, SINKHORN needs pose_in (status return).
+ */
+#define SPR_REFINE_RATIO 1
+#define SPR_REFINE_MEDIAN 2
+#define SPR_REFINE_OVERLAP 4
+#define SPR_REFINE_OVERLAP_W 8
+#define SPR_REFINE_TOPK 16
+#define SPR_REFINE_LGR 32
+#define SPR_REFINE_SINKHORN 64
+#define SPR_REFINE_ALL_FLAGS 127
+#define SPR_REFINE_MAX_N 16384
+#define SPR_REFINE_BAD_INDEX 1
+#define SPR_REFINE_BAD_LAYOUT 2
+size_t spr_refine_pairs_workspace_bytes(int npairs, int max_n);
+int spr_refine_pairs(const float* val, const float* val2, const int* ind, const float* overlap, const float* xyz,
+                     const int* cu, int npairs, int t_total, const int* k_b, const int* out_cu, int flags,
+                     float lowe_thres, float acceptance_radius, int n_steps, const float* pose_in, int max_n,
+                     float* pose, float* val_out, long long* ind_out, float* src_pts, float* tgt_pts, int* status,
+                     void* ws, size_t ws_bytes, void* stream);
+
 /* ---- a13: Sinkhorn (slack) soft correspondences -----------------------------
  * Replaces the Sinkhorn branch of softmax_correlation
  * (qk_regtr_full.py:525-536 / :635-647) + sinkhorn() and the weighted target

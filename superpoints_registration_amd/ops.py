@@ -1320,6 +1320,88 @@ def pose_scores(poses, a, b) -> torch.Tensor:
     return out
 
 
+REFINE_FLAGS = {'ratio': 1, 'median': 2, 'overlap': 4, 'overlap_as_weights': 8, 'topk': 16, 'lgr': 32, 'sinkhorn': 64}
+REFINE_MAX_N = 16384          # SPR_REFINE_MAX_N of include/spr.h
+REFINE_BAD_INDEX, REFINE_BAD_LAYOUT = 1, 2
+
+
+def refine_pairs(val, val2, ind, overlap, xyz, cu, cu_host: Sequence[int], npairs: int, k=None, *, ratio: bool = False,
+                 median: bool = False, overlap_prune: bool = False, overlap_as_weights: bool = False,
+                 lgr_steps: int = 0, lowe_thres: float = 0.0, acceptance_radius: float = 0.0, pose_in=None,
+                 sinkhorn: bool = False) -> dict:
+    """8f-3.  The config-off refinements of RegTR.softmax_correlation (ratio test, median threshold, overlap weighting,
+    top-k pruning, pose, LGR) for all pairs in one call (spr_refine_pairs; the order of operations is in include/spr.h).
+    val / val2 / ind [T] as match_dualsoftmax(_top2) returns them (val2 None unless `ratio`), overlap [T] or [T,1],
+    xyz [T,3], cu int32 [2B+1] with its host copy cu_host.  k: entries kept per pair ([B] ints, top-k pruning), None
+    keeps all min(N, M) entries in token order.  pose_in [B,3,4]: the pose stands (no solve) and LGR starts from it;
+    `sinkhorn`: the point sets are the src / tgt points at the entry's position (needs pose_in).
+    Returns a dict: pose [B,3,4]; val, ind (int64), src_pts, tgt_pts packed at out_cu (host list, [B+1]); status [B]
+    int32 on the device (0, REFINE_BAD_INDEX, REFINE_BAD_LAYOUT) -- nothing here reads it back."""
+    B = int(npairs)
+    cu_h = [int(c) for c in cu_host]
+    if B < 1 or len(cu_h) != 2 * B + 1 or cu_h[0] != 0 or any(b < a for a, b in zip(cu_h, cu_h[1:])):
+        raise ValueError(f"refine_pairs: cu_host of {len(cu_h)} entries does not describe {B} pairs")
+    n_own = [min(cu_h[b + 1] - cu_h[b], cu_h[B + b + 1] - cu_h[B + b]) for b in range(B)]
+    k_h = list(n_own) if k is None else [int(x) for x in k]
+    if len(k_h) != B or any(not 0 <= kk <= n for kk, n in zip(k_h, n_own)):
+        raise ValueError(f"refine_pairs: k {k_h} for pairs of {n_own} entries")
+    if overlap_as_weights and not overlap_prune:
+        raise ValueError("refine_pairs: overlap_as_weights needs overlap_prune")
+    if max(n_own) > REFINE_MAX_N:
+        raise ValueError(f"refine_pairs: a pair of {max(n_own)} entries, the cap is {REFINE_MAX_N}")
+    if sinkhorn and pose_in is None:
+        raise ValueError("refine_pairs: sinkhorn needs pose_in")
+    if ratio and val2 is None:
+        raise ValueError("refine_pairs: the ratio test needs val2")
+    val = _dev(val, "val", torch.float32)
+    val2 = _dev(val2, "val2", torch.float32) if ratio else None
+    ind = _dev(ind, "ind", torch.int32)
+    overlap = _dev(overlap, "overlap", torch.float32).reshape(-1)
+    xyz = _dev(xyz, "xyz", torch.float32)
+    cu = _dev(cu, "cu", torch.int32)
+    if pose_in is not None:
+        pose_in = _dev(pose_in, "pose_in", torch.float32)
+    T = cu_h[-1]
+    sizes = (val.numel(), ind.numel(), overlap.numel(), xyz.shape[0], T if val2 is None else val2.numel())
+    if any(n != T for n in sizes) or xyz.dim() != 2 or xyz.shape[1] != 3 or cu.numel() != 2 * B + 1:
+        raise ValueError(f"refine_pairs: val / ind / overlap / xyz rows / val2 = {sizes}, cu {cu.numel()}; expected {T} "
+                         f"tokens and {2 * B + 1} prefix entries")
+    if pose_in is not None and tuple(pose_in.shape) != (B, 3, 4):
+        raise ValueError(f"refine_pairs: pose_in {tuple(pose_in.shape)} for {B} pairs")
+    dev = val.device
+    out_cu = [0]
+    for kk in k_h:
+        out_cu.append(out_cu[-1] + kk)
+
+    def build():    # k_b and out_cu: one upload, kept on cu while the same pairs are refined again
+        t = torch.from_numpy(np.asarray(k_h + out_cu, dtype=np.int32)).to(dev)
+        return t, t
+    meta = _derived(cu, '_spr_refine_meta', tuple(k_h), build)
+    flags = ((REFINE_FLAGS['ratio'] if ratio else 0) | (REFINE_FLAGS['median'] if median else 0)
+             | (REFINE_FLAGS['overlap'] if overlap_prune else 0)
+             | (REFINE_FLAGS['overlap_as_weights'] if overlap_as_weights else 0)
+             | (REFINE_FLAGS['topk'] if k is not None else 0) | (REFINE_FLAGS['lgr'] if lgr_steps > 0 else 0)
+             | (REFINE_FLAGS['sinkhorn'] if sinkhorn else 0))
+    S = out_cu[-1]
+    L = _lib.lib()
+    need = L.spr_refine_pairs_workspace_bytes(B, max(n_own))
+    ws = _workspace(need, dev) if need else None
+    pose = torch.empty((B, 3, 4), dtype=torch.float32, device=dev)
+    rows = max(S, 1)              # k = 0 everywhere is legal; the library wants real pointers
+    o_val = torch.empty((rows,), dtype=torch.float32, device=dev)
+    o_ind = torch.empty((rows,), dtype=torch.int64, device=dev)
+    o_src = torch.empty((rows, 3), dtype=torch.float32, device=dev)
+    o_tgt = torch.empty((rows, 3), dtype=torch.float32, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    _lib.check(L.spr_refine_pairs(_ptr(val), _ptr(val2), _ptr(ind), _ptr(overlap), _ptr(xyz), _ptr(cu), B, T,
+                                  _ptr(meta[:B]), _ptr(meta[B:]), flags, float(lowe_thres), float(acceptance_radius),
+                                  int(lgr_steps), _ptr(pose_in), max(n_own), _ptr(pose), _ptr(o_val), _ptr(o_ind),
+                                  _ptr(o_src), _ptr(o_tgt), _ptr(status), _ptr(ws), ws.numel() if ws is not None else 0,
+                                  _stream(val)), "spr_refine_pairs")
+    return {'pose': pose, 'val': o_val[:S], 'ind': o_ind[:S], 'src_pts': o_src[:S], 'tgt_pts': o_tgt[:S],
+            'out_cu': out_cu, 'status': status}
+
+
 def match_dualsoftmax_raw(feat, cu, cu_host: Sequence[int], npairs: int):
     feat = _dev(feat, "feat", torch.float32)
     cu = _dev(cu, "cu", torch.int32)

@@ -15,7 +15,7 @@ Differences by design (documented in DESIGN.md):
     (num_layers, B, L, S) maps, padded to the longest src / tgt cloud with zeros;
   * the config-off refinements of softmax_correlation (ratio test, median threshold, overlap
     weighting, top-k pruning, LGR, RANSAC -- qk_regtr_full.py:370-421, :465-556) are available
-    on the inference path (`_refined_pose`); the two dead "affinity" switches
+    on the inference path (`_refined_pose`: one library call for all pairs); the two dead "affinity" switches
     (use_attn_affinity raises in the reference itself, use_corr_affinity) stay unsupported;
   * training: with gradients enabled every operator runs through its explicit HIP backward
     (autograd.py), so `compute_loss(model(batch), batch)['total'].backward()` fills the
@@ -411,68 +411,45 @@ class RegTR(nn.Module):
         return losses
 
     def _refined_pose(self, xyz_c, overlap, val, val2, ind, cu, cu_host, B, cond):
-        """The config-off refinements of RegTR.softmax_correlation, pair by pair like the reference
-        (qk_regtr_full.py:445-668): Lowe ratio test (:370-384), median threshold (:471-473),
-        overlap weighting (:484-494), top-k pruning (:499-502), then the pose, then LGR
-        (:386-398) and RANSAC (:400-421).  Selection logic is index glue on per-pair vectors of
-        a few hundred entries; every pose solve, residual and score runs in the HIP library --
-        RANSAC's 500 hypotheses as ONE batched Procrustes launch + one scoring launch instead of
-        the reference's 500 sequential solves."""
+        """The config-off refinements of RegTR.softmax_correlation (qk_regtr_full.py:445-668) for all pairs in ONE
+        library call (ops.refine_pairs): Lowe ratio test (:370-384), median threshold (:471-473), overlap weighting
+        (:484-494), top-k pruning (:499-502), then the pose, then LGR (:386-398).  With use_sinkhorn the Sinkhorn solve
+        goes first and its pose stands (:525-536); RANSAC (:400-421) follows per pair, only when use_ransac -- its 500
+        hypotheses as ONE batched Procrustes launch + one scoring launch.  The per-pair tensors returned are views
+        of the packed outputs."""
         cfg = self.cfg
-        dev = xyz_c.device
-        out = {k: [] for k in ('pose', 'val', 'ind', 'src_pts', 'tgt_pts')}
+        on = lambda f: bool(cfg.get(f, False))
+        sink, topk, lgr = bool(cfg.use_sinkhorn), on('remove_points_from_val'), on('use_lgr')
+        n_src = [cu_host[b + 1] - cu_host[b] for b in range(B)]
+        n_tgt = [cu_host[B + b + 1] - cu_host[B + b] for b in range(B)]
+        if on('use_overlap_as_weights') and not on('remove_outliers_overlap') and not sink:
+            raise ValueError("use_overlap_as_weights needs remove_outliers_overlap (as in the reference)")
+        if sink and lgr and not topk and any(n != m for n, m in zip(n_src, n_tgt)):
+            raise ValueError("use_lgr over the Sinkhorn point sets needs src and tgt clouds of equal length "
+                             "(or remove_points_from_val), as in the reference")
         sk_pose = None
-        if cfg.use_sinkhorn:   # the Sinkhorn pose ignores the pruned correspondences (:525-536)
+        if sink:   # the Sinkhorn pose ignores the pruned correspondences (:525-536)
             w, t_hat = ops.sinkhorn_correspondences(cond, xyz_c, cu, cu_host, B, self.alpha, self.beta,
                                                     int(cfg.sinkhorn_itr), bool(cfg.slack))
             sk_pose = ops.weighted_procrustes(xyz_c[:cu_host[B]], t_hat, w, cu[:B + 1].contiguous())
-        for b in range(B):
-            s0, s1, t0, t1 = cu_host[b], cu_host[b + 1], cu_host[B + b], cu_host[B + b + 1]
-            N, M = s1 - s0, t1 - t0
-            src_xyz, tgt_xyz = xyz_c[s0:s1], xyz_c[t0:t1]
-            ov_s, ov_t = overlap[s0:s1, 0], overlap[t0:t1, 0]
-            own = slice(t0, t1) if N > M else slice(s0, s1)
-            v, i = val[own].clone(), ind[own].long()
-            if cfg.get('use_ratio_test', False):
-                v = torch.where(val2[own] / v < cfg.lowe_thres, v, torch.zeros_like(v))
-            if cfg.get('threshold_corr', False):
-                v = torch.where(v > torch.median(v), v, torch.zeros_like(v))
-            if N > M:
-                src_pts = src_xyz if cfg.use_sinkhorn else src_xyz[i]
-                tgt_pts = tgt_xyz
-            else:
-                src_pts = src_xyz
-                tgt_pts = tgt_xyz if cfg.use_sinkhorn else tgt_xyz[i]
-            ov = None
-            if cfg.get('remove_outliers_overlap', False):
-                ov = (ov_s[i] * ov_t) if N > M else (ov_s * ov_t[i])
-                if not cfg.get('use_overlap_as_weights', False):
-                    v = v * ov
-            if cfg.get('remove_points_from_val', False):
-                k = int(cfg.val_threshold * (M if N > M else N))
-                v, i = torch.topk(v, k)
-                src_pts, tgt_pts = src_pts[i], tgt_pts[i]
-                if ov is not None:
-                    ov = ov[i]
-            one = torch.tensor([0, src_pts.shape[0]], dtype=torch.int32, device=dev)
-            if cfg.use_sinkhorn:
-                T = sk_pose[b]
-            else:
-                wts = ov if cfg.get('use_overlap_as_weights', False) else v
-                if wts is None:
-                    raise ValueError("use_overlap_as_weights needs remove_outliers_overlap (as in the reference)")
-                T = ops.weighted_procrustes(src_pts.contiguous(), tgt_pts.contiguous(), wts.contiguous(), one)[0]
-            if cfg.get('use_lgr', False):
-                wl = v
-                for _ in range(int(cfg.num_refinement_steps)):
-                    res = ops.pose_residuals(T[None].contiguous(), src_pts.contiguous(), tgt_pts.contiguous(), one)
-                    wl = wl * (res < cfg.acceptance_radius).float()
-                    T = ops.weighted_procrustes(src_pts.contiguous(), tgt_pts.contiguous(), wl.contiguous(), one)[0]
-            if cfg.get('use_ransac', False):
-                T = self._ransac(src_pts.contiguous(), tgt_pts.contiguous(), v.contiguous())
-            for k_, v_ in (('pose', T), ('val', v), ('ind', i), ('src_pts', src_pts), ('tgt_pts', tgt_pts)):
-                out[k_].append(v_)
-        out['pose'] = torch.stack(out['pose'])
+        k = [int(cfg.val_threshold * min(n, m)) for n, m in zip(n_src, n_tgt)] if topk else None
+        r = ops.refine_pairs(val, val2, ind, overlap, xyz_c, cu, cu_host, B, k,
+                             ratio=on('use_ratio_test'), median=on('threshold_corr'),
+                             overlap_prune=on('remove_outliers_overlap'),
+                             overlap_as_weights=on('use_overlap_as_weights') and on('remove_outliers_overlap'),
+                             lgr_steps=int(cfg.num_refinement_steps) if lgr else 0,
+                             lowe_thres=float(cfg.lowe_thres) if on('use_ratio_test') else 0.0,
+                             acceptance_radius=float(cfg.acceptance_radius) if lgr else 0.0,
+                             pose_in=sk_pose, sinkhorn=sink)
+        oc = r['out_cu']
+        out = {k_: [r[k_][oc[b]:oc[b + 1]] for b in range(B)] for k_ in ('val', 'ind', 'src_pts', 'tgt_pts')}
+        if sink and not topk:      # the unpruned Sinkhorn sets are the clouds themselves
+            out['src_pts'] = [xyz_c[cu_host[b]:cu_host[b + 1]] for b in range(B)]
+            out['tgt_pts'] = [xyz_c[cu_host[B + b]:cu_host[B + b + 1]] for b in range(B)]
+        out['pose'] = r['pose']
+        if on('use_ransac'):
+            out['pose'] = torch.stack([self._ransac(out['src_pts'][b].contiguous(), out['tgt_pts'][b].contiguous(),
+                                                    out['val'][b].contiguous()) for b in range(B)])
         return out
 
     @staticmethod
