@@ -665,6 +665,8 @@ int spr_refine_pairs(const float* val, const float* val2, const int* ind, const 
  * (qk_regtr_full.py:77-78) -- read by the kernel, no host round trip.
  * Outputs per src token: w [Tsrc], t_hat [Tsrc,3] (packed like the src
  * segments).  Feed (src_xyz, t_hat, w) to spr_weighted_procrustes.
+ * The scratch holds the scaled correlation (the same matrices as
+ * spr_match_dualsoftmax); the affinity is evaluated as the passes read it.
  */
 size_t spr_sinkhorn_workspace_bytes(const int* cu_host, int npairs);
 int spr_sinkhorn_correspondences(const float* feat, int d, const float* xyz,

@@ -39,17 +39,6 @@ constexpr int CK = 32;        // D slab staged in LDS
 constexpr int LDT = CT + 1;   // padded LDS row
 constexpr int CB = 256;       // threads per tile workgroup
 
-__device__ __forceinline__ double block_sum_d(double v, double* sh) {
-  v = wave_sum_d(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) sh[wave] = v;
-  __syncthreads();
-  double t = 0.0;
-  for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += sh[i];
-  __syncthreads();
-  return t;   // valid in every thread
-}
-
 // torch.nn.functional.softplus (beta 1, threshold 20) and its derivative
 __device__ __forceinline__ double softplus_d(double s) { return s > 20.0 ? s : log1p(exp(s)); }
 __device__ __forceinline__ double softplus_grad_d(double s) { return s > 20.0 ? 1.0 : 1.0 / (1.0 + exp(-s)); }

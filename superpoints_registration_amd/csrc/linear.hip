@@ -56,13 +56,9 @@ __device__ __forceinline__ float store_tile(const f32x16& acc, int row0, int col
     if (RES) v += res[r];
     if (ACT == SPR_ACT_RELU) v = fmaxf(v, 0.f);
     if (ACT == SPR_ACT_SIGMOID) v = 1.f / (1.f + expf(-v));
-    // matching-head epilogues (match_pose.hip): same float operations, in the same order, as
-    // the separate k_scale / k_affinity passes over the score matrix they replace
+    // matching-head epilogue (match_pose.hip): the same float operation as the separate k_scale
+    // pass over the score matrix it replaces
     if (ACT == kEpiScale) v = v * epi[0];
-    if (ACT == kEpiAffinity) {
-      const float sc = fmaxf(v * epi[0], 0.f);
-      v = -(sc - epi[1]) * epi[2];
-    }
     if (row < M) {
       out[(size_t)row * N + col] = v;
       vmax = fmaxf(vmax, fabsf(v));
@@ -980,8 +976,7 @@ int launch_grouped_act(const float* a, int k, const float* b, float* c, const sp
 }
 }  // namespace
 
-// epi_mode: 0 none, kEpiScale (out = v * epi[0]), kEpiAffinity (out = -(max(v epi[0], 0) - epi[1]) epi[2]);
-// epi = device parameters of the epilogue.
+// epi_mode: 0 none, kEpiScale (out = v * epi[0]); epi = device parameters of the epilogue.
 int spr::launch_gemm_grouped(const float* a, int k, const float* b, float* c, const GemmGroup* groups_dev,
                              int total_tiles, int max_n, const float* a_parts, const float* w_parts,
                              int epi_mode, const float* epi, hipStream_t stream) {
@@ -993,8 +988,6 @@ int spr::launch_gemm_grouped(const float* a, int k, const float* b, float* c, co
                                                     nullptr, stream);
     case kEpiScale: return launch_grouped_act<kEpiScale>(a, k, b, c, groups_dev, total_tiles, max_n, a_parts,
                                                          w_parts, epi, stream);
-    case kEpiAffinity: return launch_grouped_act<kEpiAffinity>(a, k, b, c, groups_dev, total_tiles, max_n, a_parts,
-                                                               w_parts, epi, stream);
   }
   SPR_REQUIRE(false, "grouped gemm: unknown epilogue %d", epi_mode);
   return 1;

@@ -42,18 +42,6 @@ __global__ void k_overlap_pool(const float* __restrict__ ov, int ns, const int* 
   out[q] = v != v ? v : fminf(fmaxf(v, 0.f), 1.f);
 }
 
-__device__ __forceinline__ double block_sum(double v, double* sh) {
-  v = wave_sum_d(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) sh[wave] = v;
-  __syncthreads();
-  double t = 0.0;
-  if (threadIdx.x == 0)
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += sh[i];
-  __syncthreads();
-  return t;   // valid in thread 0
-}
-
 // partial[b] = sum over the block's slice of  max(x,0) - x y + log1p(exp(-|x|))
 __global__ void k_bce_partial(const float* __restrict__ x, const float* __restrict__ y, int n,
                               double* __restrict__ partial) {
@@ -64,7 +52,7 @@ __global__ void k_bce_partial(const float* __restrict__ x, const float* __restri
     const float xi = x[i], yi = y[i];
     v = (double)(fmaxf(xi, 0.f) - xi * yi + log1pf(expf(-fabsf(xi))));
   }
-  const double t = block_sum(v, sh);
+  const double t = block_sum_d(v, sh);
   if (threadIdx.x == 0) partial[blockIdx.x] = t;
 }
 
@@ -77,8 +65,8 @@ __global__ void k_finish(const double* __restrict__ partial, const double* __res
     a += partial[i];
     if (den) b += den[i];
   }
-  const double ta = block_sum(a, sh);
-  const double tb = block_sum(b, sh);
+  const double ta = block_sum_d(a, sh);
+  const double tb = block_sum_d(b, sh);
   if (threadIdx.x == 0) out[0] = (float)(den ? ta / tb : ta * scale);
 }
 
@@ -162,8 +150,8 @@ __global__ void k_pair_partial(const float* __restrict__ a, const float* __restr
   __shared__ double sh[RB / 64];
   const int i = blockIdx.x * RB + threadIdx.x;
   const double va = i < n ? (double)a[i] : 0.0, vb = i < n ? (double)b[i] : 0.0;
-  const double ta = block_sum(va, sh);
-  const double tb = block_sum(vb, sh);
+  const double ta = block_sum_d(va, sh);
+  const double tb = block_sum_d(vb, sh);
   if (threadIdx.x == 0) {
     pa[blockIdx.x] = ta;
     pb[blockIdx.x] = tb;
@@ -185,7 +173,7 @@ __global__ void k_tloss_partial(const float* __restrict__ pose_gt, const float* 
       v += (double)fabsf(g - p);
     }
   }
-  const double t = block_sum(v, sh);
+  const double t = block_sum_d(v, sh);
   if (threadIdx.x == 0) partial[blockIdx.x] = t;
 }
 
@@ -288,7 +276,7 @@ __global__ __launch_bounds__(RB) void k_tloss_bwd(const float* __restrict__ pose
     }
   }
   for (int k = 0; k < 12; ++k) {
-    const double t = block_sum(acc[k], sh);
+    const double t = block_sum_d(acc[k], sh);
     if (threadIdx.x == 0) dpose[k] = (float)(t * (double)gout[0] / (3.0 * (double)n));
   }
 }

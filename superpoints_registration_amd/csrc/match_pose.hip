@@ -12,10 +12,16 @@
 //
 // The reference loops over pairs in Python, materialises softmax copies of the
 // N x M matrix and calls LAPACK through torch.svd (plus a device->host sync in
-// an assert, se3_torch.py:132).  Here: one GEMM per pair (spr_linear's arithmetic:
-// range-scaled split-fp16 MFMA by default, exact f32 in gemm mode 0) writes
-// the score matrix once into scratch; row / column log-sum-exp passes stream
-// it (wave per row, 64 columns x 4 row-lanes per workgroup for columns); the
+// an assert, se3_torch.py:132).  Here ONE routine, match_head, serves the three
+// forward entry points (matches, Sinkhorn correspondences, both): a grouped GEMM
+// (spr_linear's arithmetic: range-scaled split-fp16 MFMA by default, exact f32
+// in gemm mode 0) writes the scaled score matrices of a group of pairs once into
+// scratch (layout: next_pair_off); row / column log-sum-exp sweeps stream them
+// (k_row_lse_v: wave per row; k_col_lse_v: 64 columns x 32 row lanes per
+// workgroup; with RAW they also reduce the raw matrix in the same read;
+// k_row_lse / k_col_lse for the shapes those do not take), the
+// Sinkhorn ones through the affinity view (struct Aff) -- the affinity itself is
+// stored only by the backward; the
 // slack Sinkhorn is carried as two potential vectors
 //     u_i = log(1 + sum_j exp(A_ij - v_j)),  v_j = log(1 + sum_i exp(A_ij - u_i))
 // (algebraically identical to normalising the zero-padded (N+1)x(M+1) matrix,
@@ -35,6 +41,11 @@ struct PairDesc {
   int src_beg, n, tgt_beg, m;
   long long off;  // offset (floats) of this pair's N x M matrix in the scratch
 };
+// THE layout rule of the scratch: the matrices follow each other, every one starting on a multiple of 64 floats.
+// Offset of the matrix after an n x m one at `off`.
+__host__ __device__ inline long long next_pair_off(long long off, int n, int m) {
+  return (off + (long long)n * m + 63) / 64 * 64;
+}
 
 // ---- row / column log-sum-exp over the scaled correlation ------------------
 // lse over j of (c[i][j]*scale - sub[j])   (sub may be NULL); optionally +1
@@ -45,8 +56,8 @@ struct PairDesc {
 // float: their rounding errors are independent and average out).
 // Optional elementwise view of the stored matrix: the Sinkhorn affinity -(max(x, 0) - softplus(alpha)) / (e^beta +
 // 0.02) of the scaled correlation x, evaluated as the passes read it (aff = {scale, softplus alpha, 1 / den} from
-// k_epi_params; the same float operations as the GEMM epilogue kEpiAffinity, so a matrix stored with kEpiScale and read
-// through this view gives bit for bit the values of one stored with kEpiAffinity).  aff == nullptr: identity.
+// k_epi_params; the same float operations as k_affinity, which the backward uses to store the affinity: bit for bit the
+// same values).  The forward never stores the affinity.  aff == nullptr: identity.
 struct Aff {
   bool on;
   float sp, inv_den;
@@ -139,11 +150,15 @@ __device__ __forceinline__ float exp_neg(float x) {
 
 typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
 
-// one wave per row, the whole row (M <= 256 RV) held in registers between the max and the sum
-template <int RV, typename PT>
+// one wave per row, the whole row (M <= 256 RV) held in registers between the max and the sum.
+// RAW: the same read of the row also gives the plain log-sum-exp of the raw matrix (no sub, no view, no slack) in
+// raw_out -- the head's first sweep computes the dual softmax's reduction and the first Sinkhorn pass together.  The
+// operations of either quantity and their order do not depend on RAW, so neither do the bits.
+template <int RV, typename PT, bool RAW>
 __global__ __launch_bounds__(256) void k_row_lse_v(const float* __restrict__ mat, const PairDesc* __restrict__ pd,
                                                    PT* __restrict__ row_out, const PT* __restrict__ col_sub,
-                                                   int slack, const float* __restrict__ aff) {
+                                                   int slack, const float* __restrict__ aff,
+                                                   PT* __restrict__ raw_out) {
   const PairDesc p = pd[blockIdx.y];
   const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int lane = threadIdx.x & 63;
@@ -152,7 +167,8 @@ __global__ __launch_bounds__(256) void k_row_lse_v(const float* __restrict__ mat
   const float* r = mat + p.off + (size_t)row * p.m;
   const PT* cs = col_sub ? col_sub + p.tgt_beg : nullptr;
   PT v[RV][4];
-  float mx = slack ? 0.f : -INFINITY;
+  PT vr[RAW ? RV : 1][4];
+  float mx = slack ? 0.f : -INFINITY, mxr = -INFINITY;
 #pragma unroll
   for (int i = 0; i < RV; ++i) {
     const int j = 4 * (lane + 64 * i);
@@ -162,44 +178,68 @@ __global__ __launch_bounds__(256) void k_row_lse_v(const float* __restrict__ mat
       pt4u b = {0, 0, 0, 0};
       if (cs) b = *reinterpret_cast<const pt4u*>(cs + j);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v[i][e] = (PT)af(a[e]) - b[e];
+      for (int e = 0; e < 4; ++e) {
+        if constexpr (RAW) vr[i][e] = a[e] - 0.f;
+        v[i][e] = (PT)af(a[e]) - b[e];
+      }
     } else {
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v[i][e] = j + e < p.m ? (PT)af(r[j + e]) - (cs ? cs[j + e] : (PT)0) : (PT)-INFINITY;
+      for (int e = 0; e < 4; ++e) {
+        if constexpr (RAW) vr[i][e] = j + e < p.m ? r[j + e] - 0.f : -INFINITY;
+        v[i][e] = j + e < p.m ? (PT)af(r[j + e]) - (cs ? cs[j + e] : (PT)0) : (PT)-INFINITY;
+      }
     }
+    if constexpr (RAW)
+      mxr = fmaxf(mxr, fmaxf(fmaxf((float)vr[i][0], (float)vr[i][1]), fmaxf((float)vr[i][2], (float)vr[i][3])));
     mx = fmaxf(mx, fmaxf(fmaxf((float)v[i][0], (float)v[i][1]), fmaxf((float)v[i][2], (float)v[i][3])));
   }
+  if constexpr (RAW) mxr = wave_max(mxr);
   mx = wave_max(mx);
-  PT s = 0;
+  PT sr = 0, s = 0;
+  if constexpr (RAW) {
+#pragma unroll
+    for (int i = 0; i < RV; ++i)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) sr += (PT)exp_neg((float)(vr[i][e] - (PT)mxr));
+  }
 #pragma unroll
   for (int i = 0; i < RV; ++i)
 #pragma unroll
     for (int e = 0; e < 4; ++e) s += (PT)exp_neg((float)(v[i][e] - (PT)mx));      // columns past the end: e^-inf = 0
+  if constexpr (RAW) sr = wave_sum_t(sr);
   s = wave_sum_t(s);
   if (slack) s += (PT)expf(0.f - mx);
-  if (lane == 0) row_out[p.src_beg + row] = (PT)mx + lse_log(s);
+  if (lane == 0) {
+    if constexpr (RAW) raw_out[p.src_beg + row] = (PT)mxr + lse_log(sr);
+    row_out[p.src_beg + row] = (PT)mx + lse_log(s);
+  }
 }
 
 // block = 512 threads: 16 column quads (64 columns) x 32 row lanes; four rows in flight per thread, one
-// running maximum per column that moves at most once per four rows
+// running maximum per column that moves at most once per four rows.  RAW as in k_row_lse_v: quantity 0 is then the
+// raw matrix's reduction, the last one (index NQ - 1) the one with sub, slack and view.
 constexpr int kColLanesV = 32;
-template <typename PT>
+template <typename PT, bool RAW>
 __global__ __launch_bounds__(512) void k_col_lse_v(const float* __restrict__ mat, const PairDesc* __restrict__ pd,
                                                   PT* __restrict__ col_out, const PT* __restrict__ row_sub,
-                                                  int slack, const float* __restrict__ aff) {
+                                                  int slack, const float* __restrict__ aff,
+                                                  PT* __restrict__ raw_out) {
+  constexpr int NQ = RAW ? 2 : 1;
   const PairDesc p = pd[blockIdx.y];
   const Aff af(aff);
   const int cl = threadIdx.x & 15, rl = threadIdx.x >> 4;
   const int col = blockIdx.x * 64 + 4 * cl;
-  __shared__ float smx[kColLanesV][64];
-  __shared__ PT ssum[kColLanesV][64];
-  float mx[4];
-  PT s[4];
+  __shared__ float smx[NQ][kColLanesV][64];
+  __shared__ PT ssum[NQ][kColLanesV][64];
+  float mx[NQ][4];
+  PT s[NQ][4];
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    mx[e] = -INFINITY;
-    s[e] = 0;
-  }
+  for (int w = 0; w < NQ; ++w)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      mx[w][e] = -INFINITY;
+      s[w][e] = 0;
+    }
   if (col < p.m) {
     // branch-free loads (four rows in flight need their loads back to back): the row index is clamped and masked
     // afterwards; the last, partial column quad reads the row's last four columns and shifts
@@ -215,223 +255,104 @@ __global__ __launch_bounds__(512) void k_col_lse_v(const float* __restrict__ mat
         a[q] = *reinterpret_cast<const f4u*>(base + (size_t)i * p.m);
         sub[q] = rs ? rs[i] : (PT)0;
       }
-      PT v[4][4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const bool rok = i0 + q * kColLanesV < p.n;
-        const float a0 = af(a[q][0]), a1 = af(a[q][1]), a2 = af(a[q][2]), a3 = af(a[q][3]);
-        const float t0 = shift == 0 ? a0 : shift == 1 ? a1 : shift == 2 ? a2 : a3;
-        const float t1 = shift == 0 ? a1 : shift == 1 ? a2 : shift == 2 ? a3 : INFINITY;
-        const float t2 = shift == 0 ? a2 : shift == 1 ? a3 : INFINITY;
-        const float t3 = shift == 0 ? a3 : INFINITY;
-        v[q][0] = rok ? (PT)t0 - sub[q] : (PT)-INFINITY;
-        v[q][1] = rok && t1 < INFINITY ? (PT)t1 - sub[q] : (PT)-INFINITY;
-        v[q][2] = rok && t2 < INFINITY ? (PT)t2 - sub[q] : (PT)-INFINITY;
-        v[q][3] = rok && t3 < INFINITY ? (PT)t3 - sub[q] : (PT)-INFINITY;
-      }
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float m4 = fmaxf(fmaxf((float)v[0][e], (float)v[1][e]), fmaxf((float)v[2][e], (float)v[3][e]));
-        if (m4 > mx[e]) {
-          s[e] *= (PT)exp_neg(mx[e] - m4);        // first time: 0 * exp(-inf) = 0
-          mx[e] = m4;
-        }
-        if (mx[e] > -INFINITY) {
-          const PT m = (PT)mx[e];
-          s[e] += ((PT)exp_neg((float)(v[0][e] - m)) + (PT)exp_neg((float)(v[1][e] - m))) +
-                  ((PT)exp_neg((float)(v[2][e] - m)) + (PT)exp_neg((float)(v[3][e] - m)));
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    smx[rl][4 * cl + e] = mx[e];
-    ssum[rl][4 * cl + e] = s[e];
-  }
-  __syncthreads();
-  if (threadIdx.x < 64) {
-    const int c = blockIdx.x * 64 + threadIdx.x;
-    if (c < p.m) {
-      float M = slack ? 0.f : -INFINITY;
-      for (int k = 0; k < kColLanesV; ++k) M = fmaxf(M, smx[k][threadIdx.x]);
-      PT S = slack ? (PT)expf(0.f - M) : (PT)0;
-      for (int k = 0; k < kColLanesV; ++k)
-        if (smx[k][threadIdx.x] > -INFINITY) S += ssum[k][threadIdx.x] * (PT)expf(smx[k][threadIdx.x] - M);
-      col_out[p.tgt_beg + c] = (PT)M + lse_log(S);
-    }
-  }
-}
-
-// ---- two reductions per sweep (round 5) ---------------------------------------------------------------
-// The head of spr_match_sinkhorn reads every correlation matrix for four independent reductions: row / column
-// log-sum-exp of the dual softmax (raw x) and the first Sinkhorn row / column pass (affinity view, slack).  The two
-// row passes share one read of the row, the two column passes one read of the column block: per quantity the SAME
-// operations in the same order as k_row_lse_v / k_col_lse_v, so the results are bit for bit those of the separate
-// launches -- two sweeps of each matrix instead of four.
-template <int RV>
-__global__ __launch_bounds__(256) void k_row_lse_v2(const float* __restrict__ mat, const PairDesc* __restrict__ pd,
-                                                    float* __restrict__ row_out1, float* __restrict__ row_out2,
-                                                    const float* __restrict__ col_sub2, const float* __restrict__ aff2) {
-  const PairDesc p = pd[blockIdx.y];
-  const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int lane = threadIdx.x & 63;
-  if (row >= p.n) return;
-  const Aff af(aff2);
-  const float* r = mat + p.off + (size_t)row * p.m;
-  const float* cs = col_sub2 + p.tgt_beg;
-  float v1[RV][4], v2[RV][4];
-  float mx1 = -INFINITY, mx2 = 0.f;      // (the Sinkhorn pass carries the slack entry: exp(0))
-#pragma unroll
-  for (int i = 0; i < RV; ++i) {
-    const int j = 4 * (lane + 64 * i);
-    if (j + 3 < p.m) {
-      const f4u a = *reinterpret_cast<const f4u*>(r + j);
-      const f4u b = *reinterpret_cast<const f4u*>(cs + j);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        v1[i][e] = a[e] - 0.f;
-        v2[i][e] = af(a[e]) - b[e];
-      }
-    } else {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        v1[i][e] = j + e < p.m ? r[j + e] - 0.f : -INFINITY;
-        v2[i][e] = j + e < p.m ? af(r[j + e]) - cs[j + e] : -INFINITY;
-      }
-    }
-    mx1 = fmaxf(mx1, fmaxf(fmaxf(v1[i][0], v1[i][1]), fmaxf(v1[i][2], v1[i][3])));
-    mx2 = fmaxf(mx2, fmaxf(fmaxf(v2[i][0], v2[i][1]), fmaxf(v2[i][2], v2[i][3])));
-  }
-  mx1 = wave_max(mx1);
-  mx2 = wave_max(mx2);
-  float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-  for (int i = 0; i < RV; ++i)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) s1 += exp_neg(v1[i][e] - mx1);
-#pragma unroll
-  for (int i = 0; i < RV; ++i)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) s2 += exp_neg(v2[i][e] - mx2);
-  s1 = wave_sum_t(s1);
-  s2 = wave_sum_t(s2);
-  s2 += expf(0.f - mx2);
-  if (lane == 0) {
-    row_out1[p.src_beg + row] = mx1 + lse_log(s1);
-    row_out2[p.src_beg + row] = mx2 + lse_log(s2);
-  }
-}
-
-__global__ __launch_bounds__(512) void k_col_lse_v2(const float* __restrict__ mat, const PairDesc* __restrict__ pd,
-                                                   float* __restrict__ col_out1, float* __restrict__ col_out2,
-                                                   const float* __restrict__ row_sub2, const float* __restrict__ aff2) {
-  const PairDesc p = pd[blockIdx.y];
-  const Aff af(aff2);
-  const int cl = threadIdx.x & 15, rl = threadIdx.x >> 4;
-  const int col = blockIdx.x * 64 + 4 * cl;
-  __shared__ float smx[2][kColLanesV][64];
-  __shared__ float ssum[2][kColLanesV][64];
-  float mx[2][4], s[2][4];
-#pragma unroll
-  for (int w = 0; w < 2; ++w)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      mx[w][e] = -INFINITY;
-      s[w][e] = 0.f;
-    }
-  if (col < p.m) {
-    const int shift = col + 3 < p.m ? 0 : col - (p.m - 4);
-    const float* base = mat + p.off + (col - shift);
-    const float* rs = row_sub2 + p.src_beg;
-    for (int i0 = rl; i0 < p.n; i0 += 4 * kColLanesV) {
-      f4u a[4];
-      float sub[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int i = min(i0 + q * kColLanesV, p.n - 1);
-        a[q] = *reinterpret_cast<const f4u*>(base + (size_t)i * p.m);
-        sub[q] = rs[i];
-      }
-      float v[2][4][4];
+      PT v[NQ][4][4];
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const bool rok = i0 + q * kColLanesV < p.n;
 #pragma unroll
-        for (int w = 0; w < 2; ++w) {
-          const float a0 = w ? af(a[q][0]) : a[q][0], a1 = w ? af(a[q][1]) : a[q][1], a2 = w ? af(a[q][2]) : a[q][2],
-                      a3 = w ? af(a[q][3]) : a[q][3];
-          const float sb = w ? sub[q] : 0.f;
+        for (int w = 0; w < NQ; ++w) {
+          const bool raw = w + 1 < NQ;
+          const float a0 = raw ? a[q][0] : af(a[q][0]), a1 = raw ? a[q][1] : af(a[q][1]),
+                      a2 = raw ? a[q][2] : af(a[q][2]), a3 = raw ? a[q][3] : af(a[q][3]);
+          const PT sb = raw ? (PT)0 : sub[q];
           const float t0 = shift == 0 ? a0 : shift == 1 ? a1 : shift == 2 ? a2 : a3;
           const float t1 = shift == 0 ? a1 : shift == 1 ? a2 : shift == 2 ? a3 : INFINITY;
           const float t2 = shift == 0 ? a2 : shift == 1 ? a3 : INFINITY;
           const float t3 = shift == 0 ? a3 : INFINITY;
-          v[w][q][0] = rok ? t0 - sb : -INFINITY;
-          v[w][q][1] = rok && t1 < INFINITY ? t1 - sb : -INFINITY;
-          v[w][q][2] = rok && t2 < INFINITY ? t2 - sb : -INFINITY;
-          v[w][q][3] = rok && t3 < INFINITY ? t3 - sb : -INFINITY;
+          v[w][q][0] = rok ? (PT)t0 - sb : (PT)-INFINITY;
+          v[w][q][1] = rok && t1 < INFINITY ? (PT)t1 - sb : (PT)-INFINITY;
+          v[w][q][2] = rok && t2 < INFINITY ? (PT)t2 - sb : (PT)-INFINITY;
+          v[w][q][3] = rok && t3 < INFINITY ? (PT)t3 - sb : (PT)-INFINITY;
         }
       }
 #pragma unroll
-      for (int w = 0; w < 2; ++w)
+      for (int w = 0; w < NQ; ++w)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const float m4 = fmaxf(fmaxf(v[w][0][e], v[w][1][e]), fmaxf(v[w][2][e], v[w][3][e]));
+          const float m4 = fmaxf(fmaxf((float)v[w][0][e], (float)v[w][1][e]), fmaxf((float)v[w][2][e], (float)v[w][3][e]));
           if (m4 > mx[w][e]) {
-            s[w][e] *= exp_neg(mx[w][e] - m4);
+            s[w][e] *= (PT)exp_neg(mx[w][e] - m4);        // first time: 0 * exp(-inf) = 0
             mx[w][e] = m4;
           }
           if (mx[w][e] > -INFINITY) {
-            const float m = mx[w][e];
-            s[w][e] += (exp_neg(v[w][0][e] - m) + exp_neg(v[w][1][e] - m)) + (exp_neg(v[w][2][e] - m) + exp_neg(v[w][3][e] - m));
+            const PT m = (PT)mx[w][e];
+            s[w][e] += ((PT)exp_neg((float)(v[w][0][e] - m)) + (PT)exp_neg((float)(v[w][1][e] - m))) +
+                       ((PT)exp_neg((float)(v[w][2][e] - m)) + (PT)exp_neg((float)(v[w][3][e] - m)));
           }
         }
     }
   }
 #pragma unroll
-  for (int w = 0; w < 2; ++w)
+  for (int w = 0; w < NQ; ++w)
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       smx[w][rl][4 * cl + e] = mx[w][e];
       ssum[w][rl][4 * cl + e] = s[w][e];
     }
   __syncthreads();
-  if (threadIdx.x < 128) {
-    const int w = threadIdx.x >> 6, t = threadIdx.x & 63;
+  if (threadIdx.x < 64 * NQ) {   // wave w finishes quantity w
+    const int w = NQ > 1 ? threadIdx.x >> 6 : 0, t = threadIdx.x & 63;
     const int c = blockIdx.x * 64 + t;
     if (c < p.m) {
-      float M = w ? 0.f : -INFINITY;
+      const bool sl = w + 1 == NQ && slack;
+      float M = sl ? 0.f : -INFINITY;
       for (int k = 0; k < kColLanesV; ++k) M = fmaxf(M, smx[w][k][t]);
-      float S = w ? expf(0.f - M) : 0.f;
+      PT S = sl ? (PT)expf(0.f - M) : (PT)0;
       for (int k = 0; k < kColLanesV; ++k)
-        if (smx[w][k][t] > -INFINITY) S += ssum[w][k][t] * expf(smx[w][k][t] - M);
-      (w ? col_out2 : col_out1)[p.tgt_beg + c] = M + lse_log(S);
+        if (smx[w][k][t] > -INFINITY) S += ssum[w][k][t] * (PT)expf(smx[w][k][t] - M);
+      (w + 1 == NQ ? col_out : raw_out)[p.tgt_beg + c] = (PT)M + lse_log(S);
     }
   }
 }
 
-// launches of the two passes for `np` pairs starting at descriptor pg
+// The only launch sites of the sweeps, for `np` pairs starting at descriptor pg.  raw_out != NULL: the same sweep also
+// writes the plain log-sum-exp of the raw matrix there -- float potentials and the shapes of lse_raw_ok only.
+inline bool lse_raw_ok(int max_m, int min_m) { return max_m <= 2048 && min_m >= 4; }
 template <typename PT>
-void launch_row_lse(const float* mat, const PairDesc* pg, int np, int max_n, int max_m, PT* out, const PT* col_sub,
-                    int slack, hipStream_t stream, const float* aff = nullptr) {
+int launch_row_lse(const float* mat, const PairDesc* pg, int np, int max_n, int max_m, PT* out, const PT* col_sub,
+                   int slack, hipStream_t stream, const float* aff = nullptr, PT* raw_out = nullptr) {
   const dim3 grid(cdiv((long)max_n * 64, 256), np);
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, stream, mat, pg, out, col_sub, slack, aff, raw_out);
+  };
+  if constexpr (sizeof(PT) == 4) {   // (no double instantiation of these: the rows would not fit the register file)
+    if (raw_out != nullptr && max_m <= 1024) return go(k_row_lse_v<4, PT, true>), 0;
+    if (raw_out != nullptr && max_m <= 2048) return go(k_row_lse_v<8, PT, true>), 0;
+    if (raw_out == nullptr && max_m > 2048 && max_m <= 4096) return go(k_row_lse_v<16, PT, false>), 0;
+  }
+  SPR_REQUIRE(raw_out == nullptr, "row sweep: no two-quantity kernel for this shape or type");
   if (max_m <= 1024)
-    hipLaunchKernelGGL((k_row_lse_v<4, PT>), grid, dim3(256), 0, stream, mat, pg, out, col_sub, slack, aff);
+    go(k_row_lse_v<4, PT, false>);
   else if (max_m <= 2048)
-    hipLaunchKernelGGL((k_row_lse_v<8, PT>), grid, dim3(256), 0, stream, mat, pg, out, col_sub, slack, aff);
-  else if (max_m <= 4096 && sizeof(PT) == 4)
-    hipLaunchKernelGGL((k_row_lse_v<16, float>), grid, dim3(256), 0, stream, mat, pg, (float*)out, (const float*)col_sub, slack, aff);
+    go(k_row_lse_v<8, PT, false>);
   else
     hipLaunchKernelGGL(k_row_lse<PT>, grid, dim3(256), 0, stream, mat, pg, out, col_sub, slack, aff);
+  return 0;
 }
 template <typename PT>
-void launch_col_lse(const float* mat, const PairDesc* pg, int np, int max_m, PT* out, const PT* row_sub, int slack,
-                    hipStream_t stream, int min_m, const float* aff = nullptr) {
-  if (min_m < 4) {   // (a pair with fewer than four target tokens: the one-column-per-thread form)
-    hipLaunchKernelGGL(k_col_lse<PT>, dim3(cdiv(max_m, 64), np), dim3(1024), 0, stream, mat, pg, out, row_sub, slack, aff);
-    return;
+int launch_col_lse(const float* mat, const PairDesc* pg, int np, int max_m, PT* out, const PT* row_sub, int slack,
+                   hipStream_t stream, int min_m, const float* aff = nullptr, PT* raw_out = nullptr) {
+  const dim3 grid(cdiv(max_m, 64), np);
+  if (raw_out != nullptr) {
+    SPR_REQUIRE(sizeof(PT) == 4 && min_m >= 4, "column sweep: no two-quantity kernel for this shape or type");
+    if constexpr (sizeof(PT) == 4)
+      hipLaunchKernelGGL((k_col_lse_v<PT, true>), grid, dim3(16 * kColLanesV), 0, stream, mat, pg, out, row_sub, slack, aff, raw_out);
+  } else if (min_m < 4) {   // (a pair with fewer than four target tokens: the one-column-per-thread form)
+    hipLaunchKernelGGL(k_col_lse<PT>, grid, dim3(1024), 0, stream, mat, pg, out, row_sub, slack, aff);
+  } else {
+    hipLaunchKernelGGL((k_col_lse_v<PT, false>), grid, dim3(16 * kColLanesV), 0, stream, mat, pg, out, row_sub, slack, aff, raw_out);
   }
-  hipLaunchKernelGGL(k_col_lse_v<PT>, dim3(cdiv(max_m, 64), np), dim3(16 * kColLanesV), 0, stream, mat, pg, out, row_sub, slack, aff);
+  return 0;
 }
 
 // ---- dual softmax arg-max ---------------------------------------------------
@@ -576,8 +497,8 @@ __global__ void k_scale(float* __restrict__ mat, long long total, float s) {
 // affinity = -(max(c*scale, 0) - sp_alpha) * inv_den      (qk_regtr_full.py:532-535)
 // alpha, beta: the model's learnable scalars, read from DEVICE memory (no host round trip);
 // softplus with threshold 20 like torch.nn.Softplus, evaluated in float64.
-// parameters of the fused epilogues: [0] = scale, [1] = softplus(alpha), [2] = 1 / (exp(beta) + 0.02)
-// (the same double-precision expressions as k_affinity)
+// parameters of the epilogues and of the affinity view: [0] = scale, [1] = softplus(alpha),
+// [2] = 1 / (exp(beta) + 0.02)
 __global__ void k_epi_params(float scale, const float* __restrict__ alpha_p, const float* __restrict__ beta_p,
                              float* __restrict__ out) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -589,15 +510,12 @@ __global__ void k_epi_params(float scale, const float* __restrict__ alpha_p, con
   }
 }
 
-__global__ void k_affinity(float* __restrict__ mat, long long total, float scale,
-                           const float* __restrict__ alpha_p, const float* __restrict__ beta_p) {
+// in place, epi = {scale, softplus alpha, 1 / den} from k_epi_params
+__global__ void k_affinity(float* __restrict__ mat, long long total, const float* __restrict__ epi) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const float alpha = alpha_p[0], beta = beta_p[0];
-  const float sp_alpha = (float)(alpha > 20.f ? (double)alpha : log1p(exp((double)alpha)));
-  const float inv_den = (float)(1.0 / (exp((double)beta) + 0.02));
   if (i < total) {
-    const float sc = fmaxf(mat[i] * scale, 0.f);
-    mat[i] = -(sc - sp_alpha) * inv_den;
+    const float sc = fmaxf(mat[i] * epi[0], 0.f);
+    mat[i] = -(sc - epi[1]) * epi[2];
   }
 }
 
@@ -926,15 +844,12 @@ __global__ __launch_bounds__(256) void k_affinity_bwd(const float* __restrict__ 
     if (dA != 0.f) s2 += (double)dA * (double)amat[i];
     dmat[i] = corr[i] * scale > 0.f ? -dA * inv_den * scale : 0.f;
   }
-  s1 = wave_sum_d(s1);
-  s2 = wave_sum_d(s2);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s1;
-  __syncthreads();
-  if (threadIdx.x == 0) parts[2 * blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s2;
-  __syncthreads();
-  if (threadIdx.x == 0) parts[2 * blockIdx.x + 1] = sh[0] + sh[1] + sh[2] + sh[3];
+  s1 = block_sum_d(s1, sh);
+  s2 = block_sum_d(s2, sh);
+  if (threadIdx.x == 0) {
+    parts[2 * blockIdx.x] = s1;
+    parts[2 * blockIdx.x + 1] = s2;
+  }
 }
 // d alpha = (sum dA) inv_den sigmoid(alpha);  d beta = (sum dA A) (-e^beta / den)
 __global__ void k_affinity_bwd_final(const double* __restrict__ parts, int nparts, const float* __restrict__ alpha_p,
@@ -967,31 +882,30 @@ __global__ void k_build_grad_recs(const PairDesc* __restrict__ pd, int npairs, i
   rt[b] = GemmRec{p.off, (long long)p.src_beg * d, (long long)p.tgt_beg * d, p.m, d, p.n, p.m};
 }
 
-int build_pairs(const int* cu_host, int npairs, PairDesc* h, long long* total) {
+// descriptors of all pairs on the host; returns the scratch's size in floats
+long long build_pairs(const int* cu_host, int npairs, PairDesc* h) {
   long long off = 0;
   for (int b = 0; b < npairs; ++b) {
-    h[b].src_beg = cu_host[b];
-    h[b].n = cu_host[b + 1] - cu_host[b];
-    h[b].tgt_beg = cu_host[npairs + b];
-    h[b].m = cu_host[npairs + b + 1] - cu_host[npairs + b];
-    h[b].off = off;
-    off += (long long)h[b].n * h[b].m;
-    off = (off + 63) / 64 * 64;
+    h[b] = PairDesc{cu_host[b], cu_host[b + 1] - cu_host[b], cu_host[npairs + b],
+                    cu_host[npairs + b + 1] - cu_host[npairs + b], off};
+    off = next_pair_off(off, h[b].n, h[b].m);
   }
-  *total = off;
-  return 0;
+  return off;
 }
 
-size_t match_ws_bytes(const int* cu_host, int npairs) {
+// bytes of the scratch, and of everything corr_setup carves around it
+size_t pair_mat_bytes(const int* cu_host, int npairs) {
   long long off = 0;
-  int tmax = cu_host[2 * npairs];
-  for (int b = 0; b < npairs; ++b) {
-    off += (long long)(cu_host[b + 1] - cu_host[b]) *
-           (cu_host[npairs + b + 1] - cu_host[npairs + b]);
-    off = (off + 63) / 64 * 64;
-  }
-  return align_up((size_t)off * 4, 256) + align_up(sizeof(PairDesc) * npairs, 256) +
-         align_up(sizeof(GemmGroup) * npairs, 256) + 4 * align_up((size_t)tmax * 4, 256) + 2 * align_up(kAmaxParts * sizeof(float), 256) + 2048;
+  for (int b = 0; b < npairs; ++b)
+    off = next_pair_off(off, cu_host[b + 1] - cu_host[b], cu_host[npairs + b + 1] - cu_host[npairs + b]);
+  return align_up((size_t)off * 4, 256);
+}
+size_t corr_ws_bytes(const int* cu_host, int npairs) {
+  return pair_mat_bytes(cu_host, npairs) + align_up(sizeof(PairDesc) * npairs, 256) +
+         align_up(sizeof(GemmGroup) * npairs, 256) + 2 * align_up(kAmaxParts * sizeof(float), 256);
+}
+size_t match_ws_bytes(const int* cu_host, int npairs) {
+  return corr_ws_bytes(cu_host, npairs) + 4 * align_up((size_t)cu_host[2 * npairs] * 4, 256) + 2048;
 }
 
 }  // namespace
@@ -1036,8 +950,7 @@ __global__ void k_build_pairs(const int* __restrict__ cu, int npairs, PairDesc* 
       g.pad = 0;
       gg[b] = g;
     }
-    off += (long long)p.n * p.m;
-    off = (off + 63) / 64 * 64;
+    off = next_pair_off(off, p.n, p.m);
     pd[b] = p;
   }
 }
@@ -1048,7 +961,7 @@ __global__ void k_build_pairs(const int* __restrict__ cu, int npairs, PairDesc* 
 // the 256 MB Infinity Cache.  Group budget 250 MB = 16 of the bench's pairs (measured: 96 MB groups leave the chip
 // under-filled -- 3.9 ms of matching kernels per forward; 250 MB: 2.6 ms; one group of 477 MB: 3.0 ms).  corr_setup builds the descriptors of all pairs, corr_gemm launches the
 // product of one group.
-// epi_mode / epi: optional elementwise epilogue of the grouped GEMM (kEpiScale, kEpiAffinity; parameters on the
+// epi_mode / epi: optional elementwise epilogue of the grouped GEMM (kEpiScale; parameters on the
 // device); applied = whether it ran (split-fp16 mode) or the separate pass over the matrix is still needed
 // (exact-f32 mode: one GEMM per pair).
 struct Corr {
@@ -1077,7 +990,7 @@ int corr_setup(Corr& c, const float* feat, int d, const int* cu_dev, const int* 
   c.d = d;
   c.npairs = npairs;
   c.h.resize(npairs);
-  build_pairs(cu_host, npairs, c.h.data(), &c.total);
+  c.total = build_pairs(cu_host, npairs, c.h.data());
   c.mat = w.take<float>((size_t)c.total);
   c.pd = w.take<PairDesc>(npairs);
   SPR_REQUIRE(c.mat && c.pd, "match: workspace carve failed");
@@ -1140,44 +1053,119 @@ int corr_gemm(const Corr& c, int g, int epi_mode, const float* epi, hipStream_t 
   }
   return 0;
 }
+
+// The matching head: dual-softmax matches (want_match) and / or Sinkhorn correspondences (want_sinkhorn) of one set
+// of features.  The scaled correlation matrices are stored once per group (GEMM epilogue kEpiScale, or k_scale after
+// the exact-f32 GEMMs); the Sinkhorn passes read them through the affinity view (struct Aff).  With both wanted, the
+// dual softmax's row / column reduction and the first Sinkhorn iteration share a sweep where the two-quantity
+// kernels (k_row_lse_v / k_col_lse_v with RAW) take the shape (same bits as the separate sweeps).  Every output is therefore bit for bit the same
+// whichever entry point asked for it.
+struct HeadArgs {
+  const char* name;
+  const float* feat;
+  int d;
+  const int *cu, *cu_host;
+  int npairs;
+  void* ws;
+  size_t ws_bytes;
+  hipStream_t stream;
+  // what only one of the two heads reads (set by name in the entry points)
+  const float* xyz = nullptr;
+  const float *alpha = nullptr, *beta = nullptr;
+  int n_iters = 0;
+  float *match_val = nullptr, *match_val2 = nullptr;
+  int* match_ind = nullptr;
+  float *out_w = nullptr, *out_that = nullptr;
+};
+HeadArgs head_args(const char* name, const float* feat, int d, const int* cu, const int* cu_host, int npairs, void* ws,
+                   size_t ws_bytes, void* stream) {
+  HeadArgs a;
+  a.name = name;
+  a.feat = feat;
+  a.d = d;
+  a.cu = cu;
+  a.cu_host = cu_host;
+  a.npairs = npairs;
+  a.ws = ws;
+  a.ws_bytes = ws_bytes;
+  a.stream = (hipStream_t)stream;
+  return a;
+}
+int match_head(const HeadArgs& a, bool want_match, bool want_sinkhorn) {
+  hipStream_t stream = a.stream;
+  SPR_REQUIRE(a.npairs >= 1 && a.d % 32 == 0 && a.n_iters >= 0, "%s: need npairs >= 1, d %% 32 == 0, n_iters >= 0",
+              a.name);
+  SPR_REQUIRE(a.ws_bytes >= match_ws_bytes(a.cu_host, a.npairs), "%s: workspace too small", a.name);
+  Workspace w(a.ws, a.ws_bytes);
+  const float scale = 1.0f / sqrtf((float)a.d);
+  float* epi = w.take<float>(4);       // {scale, softplus alpha, 1 / (e^beta + 0.02)}: the epilogue reads [0], the view all
+  SPR_REQUIRE(epi != nullptr, "%s: workspace carve failed", a.name);
+  hipLaunchKernelGGL(k_epi_params, dim3(1), dim3(64), 0, stream, scale, want_sinkhorn ? a.alpha : nullptr,
+                     want_sinkhorn ? a.beta : nullptr, epi);
+  const float* aff = want_sinkhorn ? epi : nullptr;
+  Corr c;
+  if (corr_setup(c, a.feat, a.d, a.cu, a.cu_host, a.npairs, w, stream, false)) return 1;
+  const int T = a.cu_host[2 * a.npairs];
+  float *row_lse = nullptr, *col_lse = nullptr, *u = nullptr, *v = nullptr;
+  if (want_match) {
+    row_lse = w.take<float>(T);
+    col_lse = w.take<float>(T);
+    SPR_REQUIRE(col_lse != nullptr, "%s: workspace carve failed", a.name);
+  }
+  if (want_sinkhorn) {
+    u = w.take<float>(T);
+    v = w.take<float>(T);
+    SPR_REQUIRE(v != nullptr, "%s: workspace carve failed", a.name);
+    SPR_HIP_CHECK(hipMemsetAsync(u, 0, sizeof(float) * T, stream));
+    SPR_HIP_CHECK(hipMemsetAsync(v, 0, sizeof(float) * T, stream));
+  }
+  // with both heads wanted the dual softmax's reductions and the first Sinkhorn iteration share their sweeps
+  const bool fuse = want_match && want_sinkhorn && a.n_iters >= 1 && lse_raw_ok(c.max_m, c.min_m);
+  for (int g = 0; g < c.ngroups; ++g) {
+    bool scaled = false;
+    if (corr_gemm(c, g, kEpiScale, epi, stream, &scaled)) return 1;
+    const int np = c.count(g);
+    const PairDesc* pg = c.pd + c.first(g);
+    if (!scaled) {
+      const long long cnt = c.end(g) - c.beg(g);
+      hipLaunchKernelGGL(k_scale, dim3(cdiv(cnt, 256)), dim3(256), 0, stream, c.mat + c.beg(g), cnt, scale);
+    }
+    const dim3 grow(cdiv((long)c.max_n * 64, 256), np), gcol(cdiv(c.max_m, 64), np);
+    if (fuse) {
+      if (launch_row_lse<float>(c.mat, pg, np, c.max_n, c.max_m, u, (const float*)v, 1, stream, aff, row_lse)) return 1;
+      if (launch_col_lse<float>(c.mat, pg, np, c.max_m, v, (const float*)u, 1, stream, c.min_m, aff, col_lse)) return 1;
+    } else if (want_match) {
+      launch_row_lse<float>(c.mat, pg, np, c.max_n, c.max_m, row_lse, nullptr, 0, stream);
+      launch_col_lse<float>(c.mat, pg, np, c.max_m, col_lse, nullptr, 0, stream, c.min_m);
+    }
+    if (want_match) {
+      hipLaunchKernelGGL(k_match_cols, gcol, dim3(1024), 0, stream, c.mat, pg, row_lse, col_lse, a.match_val,
+                         a.match_ind, a.match_val2);
+      hipLaunchKernelGGL(k_match_rows, grow, dim3(256), 0, stream, c.mat, pg, row_lse, col_lse, a.match_val,
+                         a.match_ind, a.match_val2);
+    }
+    if (want_sinkhorn) {
+      for (int it = fuse ? 1 : 0; it < a.n_iters; ++it) {
+        launch_row_lse<float>(c.mat, pg, np, c.max_n, c.max_m, u, (const float*)v, 1, stream, aff);
+        launch_col_lse<float>(c.mat, pg, np, c.max_m, v, (const float*)u, 1, stream, c.min_m, aff);
+      }
+      hipLaunchKernelGGL(k_sinkhorn_final, grow, dim3(256), 0, stream, c.mat, pg, u, v, a.xyz, a.out_w, a.out_that,
+                         aff);
+    }
+  }
+  SPR_LAUNCH_CHECK();
+  return 0;
+}
 }  // namespace
 
 extern "C" int spr_match_dualsoftmax(const float* feat, int d, const int* cu, const int* cu_host,
                                      int npairs, float* match_val, float* match_val2, int* match_ind, void* ws,
                                      size_t ws_bytes, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  SPR_REQUIRE(npairs >= 1 && d % 32 == 0, "match: need npairs >= 1 and d %% 32 == 0");
-  SPR_REQUIRE(ws_bytes >= match_ws_bytes(cu_host, npairs), "match: workspace too small");
-  Workspace w(ws, ws_bytes);
-  const float scale = 1.0f / sqrtf((float)d);
-  float* epi = w.take<float>(4);
-  SPR_REQUIRE(epi != nullptr, "match: workspace carve failed");
-  hipLaunchKernelGGL(k_epi_params, dim3(1), dim3(64), 0, stream, scale, (const float*)nullptr,
-                     (const float*)nullptr, epi);
-  Corr c;
-  if (corr_setup(c, feat, d, cu, cu_host, npairs, w, stream, false)) return 1;
-  const int T = cu_host[2 * npairs];
-  float* row_lse = w.take<float>(T);
-  float* col_lse = w.take<float>(T);
-  SPR_REQUIRE(col_lse != nullptr, "match: workspace carve failed");
-  for (int g = 0; g < c.ngroups; ++g) {
-    bool scaled = false;
-    if (corr_gemm(c, g, kEpiScale, epi, stream, &scaled)) return 1;
-    const int np = c.count(g);
-    PairDesc* pg = c.pd + c.first(g);
-    if (!scaled) {
-      const long long cnt = c.end(g) - c.beg(g);
-      hipLaunchKernelGGL(k_scale, dim3(cdiv(cnt, 256)), dim3(256), 0, stream, c.mat + c.beg(g), cnt, scale);
-    }
-    launch_row_lse<float>(c.mat, pg, np, c.max_n, c.max_m, row_lse, nullptr, 0, stream);
-    launch_col_lse<float>(c.mat, pg, np, c.max_m, col_lse, nullptr, 0, stream, c.min_m);
-    hipLaunchKernelGGL(k_match_cols, dim3(cdiv(c.max_m, 64), np), dim3(1024), 0, stream, c.mat, pg, row_lse, col_lse,
-                       match_val, match_ind, match_val2);
-    hipLaunchKernelGGL(k_match_rows, dim3(cdiv((long)c.max_n * 64, 256), np), dim3(256), 0, stream, c.mat, pg, row_lse,
-                       col_lse, match_val, match_ind, match_val2);
-  }
-  SPR_LAUNCH_CHECK();
-  return 0;
+  HeadArgs a = head_args("match", feat, d, cu, cu_host, npairs, ws, ws_bytes, stream_);
+  a.match_val = match_val;
+  a.match_val2 = match_val2;
+  a.match_ind = match_ind;
+  return match_head(a, true, false);
 }
 
 extern "C" int spr_pose_residuals(const float* pose, const float* a, const float* b, const int* pair_cu,
@@ -1204,112 +1192,38 @@ extern "C" int spr_sinkhorn_correspondences(const float* feat, int d, const floa
                                             const float* beta, int n_iters, int slack, float* out_w,
                                             float* out_that,
                                             void* ws, size_t ws_bytes, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
   (void)slack;  // the reference's sinkhorn() always pads the slack row/col (se3_torch.py:182-184)
-  SPR_REQUIRE(npairs >= 1 && d % 32 == 0 && n_iters >= 0, "sinkhorn: bad arguments");
-  SPR_REQUIRE(ws_bytes >= match_ws_bytes(cu_host, npairs), "sinkhorn: workspace too small");
-  Workspace w(ws, ws_bytes);
-  const float scale = 1.0f / sqrtf((float)d);
   SPR_REQUIRE(alpha != nullptr && beta != nullptr, "sinkhorn: alpha / beta must be device pointers");
-  float* epi = w.take<float>(4);
-  SPR_REQUIRE(epi != nullptr, "sinkhorn: workspace carve failed");
-  hipLaunchKernelGGL(k_epi_params, dim3(1), dim3(64), 0, stream, scale, alpha, beta, epi);
-  Corr c;
-  if (corr_setup(c, feat, d, cu, cu_host, npairs, w, stream, false)) return 1;
-  const int T = cu_host[2 * npairs];
-  float* u = w.take<float>(T);
-  float* v = w.take<float>(T);
-  SPR_REQUIRE(v != nullptr, "sinkhorn: workspace carve failed");
-  SPR_HIP_CHECK(hipMemsetAsync(u, 0, sizeof(float) * T, stream));
-  SPR_HIP_CHECK(hipMemsetAsync(v, 0, sizeof(float) * T, stream));
-  for (int g = 0; g < c.ngroups; ++g) {
-    bool fused = false;
-    if (corr_gemm(c, g, kEpiAffinity, epi, stream, &fused)) return 1;
-    const int np = c.count(g);
-    PairDesc* pg = c.pd + c.first(g);
-    if (!fused) {
-      const long long cnt = c.end(g) - c.beg(g);
-      hipLaunchKernelGGL(k_affinity, dim3(cdiv(cnt, 256)), dim3(256), 0, stream, c.mat + c.beg(g), cnt, scale, alpha,
-                         beta);
-    }
-    for (int it = 0; it < n_iters; ++it) {
-      launch_row_lse<float>(c.mat, pg, np, c.max_n, c.max_m, u, v, 1, stream);
-      launch_col_lse<float>(c.mat, pg, np, c.max_m, v, (const float*)u, 1, stream, c.min_m);
-    }
-    hipLaunchKernelGGL(k_sinkhorn_final, dim3(cdiv((long)c.max_n * 64, 256), np), dim3(256), 0, stream, c.mat, pg, u, v,
-                       xyz, out_w, out_that, (const float*)nullptr);
-  }
-  SPR_LAUNCH_CHECK();
-  return 0;
+  HeadArgs a = head_args("sinkhorn", feat, d, cu, cu_host, npairs, ws, ws_bytes, stream_);
+  a.xyz = xyz;
+  a.alpha = alpha;
+  a.beta = beta;
+  a.n_iters = n_iters;
+  a.out_w = out_w;
+  a.out_that = out_that;
+  return match_head(a, false, true);
 }
 
 // spr_match_dualsoftmax + spr_sinkhorn_correspondences of the SAME features in one call (what RegTR's inference
-// forward runs back to back, qk_regtr_full.py:453-479 and :525-536): the scaled correlation matrices are computed
-// and stored once; the Sinkhorn passes read them through the affinity view (struct Aff).  Outputs are bit for bit
-// those of the two separate calls.  match_val2 may be NULL.  Workspace: spr_match_workspace_bytes.
+// forward runs back to back, qk_regtr_full.py:453-479 and :525-536).  Outputs are bit for bit those of the two
+// separate calls.  match_val2 may be NULL.  Workspace: spr_match_workspace_bytes.
 extern "C" int spr_match_sinkhorn(const float* feat, int d, const float* xyz, const int* cu, const int* cu_host,
                                   int npairs, const float* alpha, const float* beta, int n_iters, float* match_val,
                                   float* match_val2, int* match_ind, float* out_w, float* out_that, void* ws,
                                   size_t ws_bytes, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  SPR_REQUIRE(npairs >= 1 && d % 32 == 0 && n_iters >= 0, "match_sinkhorn: bad arguments");
   SPR_REQUIRE(feat && xyz && cu && cu_host && alpha && beta && match_val && match_ind && out_w && out_that,
               "match_sinkhorn: null argument");
-  SPR_REQUIRE(ws_bytes >= match_ws_bytes(cu_host, npairs), "match_sinkhorn: workspace too small");
-  Workspace w(ws, ws_bytes);
-  const float scale = 1.0f / sqrtf((float)d);
-  float* epi = w.take<float>(4);       // {scale}: the GEMM epilogue
-  float* aff = w.take<float>(4);       // {scale, softplus alpha, 1 / (e^beta + 0.02)}: the view of the Sinkhorn passes
-  SPR_REQUIRE(aff != nullptr, "match_sinkhorn: workspace carve failed");
-  hipLaunchKernelGGL(k_epi_params, dim3(1), dim3(64), 0, stream, scale, (const float*)nullptr, (const float*)nullptr, epi);
-  hipLaunchKernelGGL(k_epi_params, dim3(1), dim3(64), 0, stream, scale, alpha, beta, aff);
-  Corr c;
-  if (corr_setup(c, feat, d, cu, cu_host, npairs, w, stream, false)) return 1;
-  const int T = cu_host[2 * npairs];
-  float* row_lse = w.take<float>(T);
-  float* col_lse = w.take<float>(T);
-  float* u = w.take<float>(T);
-  float* v = w.take<float>(T);
-  SPR_REQUIRE(v != nullptr, "match_sinkhorn: workspace carve failed");
-  SPR_HIP_CHECK(hipMemsetAsync(u, 0, sizeof(float) * T, stream));
-  SPR_HIP_CHECK(hipMemsetAsync(v, 0, sizeof(float) * T, stream));
-  for (int g = 0; g < c.ngroups; ++g) {
-    bool scaled = false;
-    if (corr_gemm(c, g, kEpiScale, epi, stream, &scaled)) return 1;
-    const int np = c.count(g);
-    PairDesc* pg = c.pd + c.first(g);
-    if (!scaled) {
-      const long long cnt = c.end(g) - c.beg(g);
-      hipLaunchKernelGGL(k_scale, dim3(cdiv(cnt, 256)), dim3(256), 0, stream, c.mat + c.beg(g), cnt, scale);
-    }
-    const dim3 grow(cdiv((long)c.max_n * 64, 256), np), gcol(cdiv(c.max_m, 64), np);
-    // the dual softmax's row / column pass and the first Sinkhorn iteration's in two sweeps instead of four
-    // (k_row_lse_v2 / k_col_lse_v2: same bits); the separate launches for the shapes the fused sweeps do not take
-    const bool fuse = n_iters >= 1 && c.max_m <= 2048 && c.min_m >= 4;
-    if (fuse) {
-      if (c.max_m <= 1024)
-        hipLaunchKernelGGL(k_row_lse_v2<4>, grow, dim3(256), 0, stream, c.mat, pg, row_lse, u, (const float*)v, (const float*)aff);
-      else
-        hipLaunchKernelGGL(k_row_lse_v2<8>, grow, dim3(256), 0, stream, c.mat, pg, row_lse, u, (const float*)v, (const float*)aff);
-      hipLaunchKernelGGL(k_col_lse_v2, gcol, dim3(16 * kColLanesV), 0, stream, c.mat, pg, col_lse, v, (const float*)u,
-                         (const float*)aff);
-    } else {
-      launch_row_lse<float>(c.mat, pg, np, c.max_n, c.max_m, row_lse, nullptr, 0, stream);
-      launch_col_lse<float>(c.mat, pg, np, c.max_m, col_lse, nullptr, 0, stream, c.min_m);
-    }
-    hipLaunchKernelGGL(k_match_cols, gcol, dim3(1024), 0, stream, c.mat, pg, row_lse, col_lse, match_val, match_ind,
-                       match_val2);
-    hipLaunchKernelGGL(k_match_rows, grow, dim3(256), 0, stream, c.mat, pg, row_lse, col_lse, match_val, match_ind,
-                       match_val2);
-    for (int it = fuse ? 1 : 0; it < n_iters; ++it) {
-      launch_row_lse<float>(c.mat, pg, np, c.max_n, c.max_m, u, (const float*)v, 1, stream, aff);
-      launch_col_lse<float>(c.mat, pg, np, c.max_m, v, (const float*)u, 1, stream, c.min_m, aff);
-    }
-    hipLaunchKernelGGL(k_sinkhorn_final, grow, dim3(256), 0, stream, c.mat, pg, u, v, xyz, out_w, out_that,
-                       (const float*)aff);
-  }
-  SPR_LAUNCH_CHECK();
-  return 0;
+  HeadArgs a = head_args("match_sinkhorn", feat, d, cu, cu_host, npairs, ws, ws_bytes, stream_);
+  a.xyz = xyz;
+  a.alpha = alpha;
+  a.beta = beta;
+  a.n_iters = n_iters;
+  a.match_val = match_val;
+  a.match_val2 = match_val2;
+  a.match_ind = match_ind;
+  a.out_w = out_w;
+  a.out_that = out_that;
+  return match_head(a, true, true);
 }
 
 extern "C" int spr_weighted_procrustes(const float* a, const float* b, const float* w,
@@ -1335,16 +1249,11 @@ extern "C" int spr_weighted_procrustes_bwd(const float* a, const float* b, const
 }
 
 extern "C" size_t spr_sinkhorn_bwd_workspace_bytes(const int* cu_host, int npairs, int n_iters) {
-  long long off = 0;
   const int tmax = cu_host[2 * npairs];
-  for (int b = 0; b < npairs; ++b) {
-    off += (long long)(cu_host[b + 1] - cu_host[b]) * (cu_host[npairs + b + 1] - cu_host[npairs + b]);
-    off = (off + 63) / 64 * 64;
-  }
   const int it = n_iters > 0 ? n_iters : 1;
-  return 3 * align_up((size_t)off * 4, 256) + align_up(sizeof(PairDesc) * npairs, 256) +
+  return corr_ws_bytes(cu_host, npairs) + 2 * pair_mat_bytes(cu_host, npairs) +
          2 * align_up(sizeof(GemmRec) * npairs, 256) + (size_t)(4 * it + 5) * align_up((size_t)tmax * 4, 256) + 1024 +
-         2 * align_up(kAmaxParts * sizeof(float), 256) + align_up(2 * 1024 * sizeof(double), 256) + 2048;
+         align_up(2 * 1024 * sizeof(double), 256) + 2048;
 }
 
 // Gradient of (w, t_hat) = spr_sinkhorn_correspondences(feat, ...) w.r.t. feat, alpha, beta.
@@ -1359,23 +1268,12 @@ extern "C" int spr_sinkhorn_bwd(const float* feat, int d, const float* xyz, cons
               "sinkhorn_bwd: null operand");
   SPR_REQUIRE(ws_bytes >= spr_sinkhorn_bwd_workspace_bytes(cu_host, npairs, n_iters), "sinkhorn_bwd: workspace too small");
   Workspace w(ws, ws_bytes);
-  float* mat;
-  PairDesc* pd;
-  std::vector<PairDesc> h;
-  long long total;
-  int max_n, max_m;
-  Corr cc;
-  if (corr_setup(cc, feat, d, cu, cu_host, npairs, w, stream, true)) return 1;     // the backward keeps every matrix
-  if (corr_gemm(cc, 0, 0, nullptr, stream, nullptr)) return 1;
-  mat = cc.mat;
-  pd = cc.pd;
-  h = cc.h;
-  total = cc.total;
-  max_n = cc.max_n;
-  max_m = cc.max_m;
+  Corr c;
+  if (corr_setup(c, feat, d, cu, cu_host, npairs, w, stream, true)) return 1;     // the backward keeps every matrix
+  if (corr_gemm(c, 0, 0, nullptr, stream, nullptr)) return 1;
   const int T = cu_host[2 * npairs];
-  float* corr = w.take<float>((size_t)total);
-  float* dmat = w.take<float>((size_t)total);
+  float* corr = w.take<float>((size_t)c.total);
+  float* dmat = w.take<float>((size_t)c.total);
   GemmRec* rs = w.take<GemmRec>(npairs);
   GemmRec* rt = w.take<GemmRec>(npairs);
   const int it_n = n_iters > 0 ? n_iters : 1;
@@ -1386,35 +1284,37 @@ extern "C" int spr_sinkhorn_bwd(const float* feat, int d, const float* xyz, cons
   float* dvb = w.take<float>(T);
   double* zero = w.take<double>(T);
   double* parts = w.take<double>(2 * 1024);
-  SPR_REQUIRE(parts != nullptr, "sinkhorn_bwd: workspace carve failed");
+  float* epi = w.take<float>(4);
+  SPR_REQUIRE(epi != nullptr, "sinkhorn_bwd: workspace carve failed");
   const float scale = 1.0f / sqrtf((float)d);
-  SPR_HIP_CHECK(hipMemsetAsync(dmat, 0, sizeof(float) * (size_t)total, stream));
-  SPR_HIP_CHECK(hipMemcpyAsync(corr, mat, sizeof(float) * (size_t)total, hipMemcpyDeviceToDevice, stream));
-  hipLaunchKernelGGL(k_affinity, dim3(cdiv(total, 256)), dim3(256), 0, stream, mat, total, scale, alpha, beta);
+  SPR_HIP_CHECK(hipMemsetAsync(dmat, 0, sizeof(float) * (size_t)c.total, stream));
+  SPR_HIP_CHECK(hipMemcpyAsync(corr, c.mat, sizeof(float) * (size_t)c.total, hipMemcpyDeviceToDevice, stream));
+  hipLaunchKernelGGL(k_epi_params, dim3(1), dim3(64), 0, stream, scale, alpha, beta, epi);
+  hipLaunchKernelGGL(k_affinity, dim3(cdiv(c.total, 256)), dim3(256), 0, stream, c.mat, c.total, (const float*)epi);
   SPR_HIP_CHECK(hipMemsetAsync(zero, 0, sizeof(double) * T, stream));
-  const dim3 grow(cdiv((long)max_n * 64, 256), npairs), gcol(cdiv(max_m, 64), npairs);
+  const dim3 grow(cdiv((long)c.max_n * 64, 256), npairs), gcol(cdiv(c.max_m, 64), npairs);
   // forward potentials, every iteration kept
   for (int it = 0; it < n_iters; ++it) {
+    double* ut = U + (size_t)it * T;
     const double* vprev = it == 0 ? zero : V + (size_t)(it - 1) * T;
-    launch_row_lse<double>(mat, pd, npairs, max_n, max_m, U + (size_t)it * T, vprev, 1, stream);
-    launch_col_lse<double>(mat, pd, npairs, max_m, V + (size_t)it * T, (const double*)(U + (size_t)it * T), 1, stream,
-                           cc.min_m);
+    launch_row_lse<double>(c.mat, c.pd, npairs, c.max_n, c.max_m, ut, vprev, 1, stream);
+    launch_col_lse<double>(c.mat, c.pd, npairs, c.max_m, V + (size_t)it * T, (const double*)ut, 1, stream, c.min_m);
   }
   const double* un = n_iters > 0 ? U + (size_t)(n_iters - 1) * T : zero;
   const double* vn = n_iters > 0 ? V + (size_t)(n_iters - 1) * T : zero;
   // final step: dA = gP * P, du_n, dv_n
-  hipLaunchKernelGGL(k_sk_bwd_final, grow, dim3(256), 0, stream, mat, dmat, pd, un, vn, xyz, dw, dthat, du);
-  hipLaunchKernelGGL(k_sk_colsum_neg, gcol, dim3(1024), 0, stream, dmat, pd, dva);
+  hipLaunchKernelGGL(k_sk_bwd_final, grow, dim3(256), 0, stream, c.mat, dmat, c.pd, un, vn, xyz, dw, dthat, du);
+  hipLaunchKernelGGL(k_sk_colsum_neg, gcol, dim3(1024), 0, stream, dmat, c.pd, dva);
   float* dv_cur = dva;
   float* dv_prev = dvb;
   for (int it = n_iters - 1; it >= 0; --it) {
     const double* ut = U + (size_t)it * T;
     const double* vt = V + (size_t)it * T;
     // v_t = colLSE(A - u_t): adds to dA and to du_t
-    hipLaunchKernelGGL(k_sk_bwd_col, grow, dim3(256), 0, stream, mat, dmat, pd, ut, vt, (const float*)dv_cur, du);
+    hipLaunchKernelGGL(k_sk_bwd_col, grow, dim3(256), 0, stream, c.mat, dmat, c.pd, ut, vt, (const float*)dv_cur, du);
     // u_t = rowLSE(A - v_{t-1}): adds to dA, produces dv_{t-1} (v_0 = 0 is a constant)
     const double* vprev = it == 0 ? nullptr : V + (size_t)(it - 1) * T;
-    hipLaunchKernelGGL(k_sk_bwd_row, gcol, dim3(1024), 0, stream, mat, dmat, pd, ut, vprev, (const float*)du,
+    hipLaunchKernelGGL(k_sk_bwd_row, gcol, dim3(1024), 0, stream, c.mat, dmat, c.pd, ut, vprev, (const float*)du,
                        it == 0 ? (float*)nullptr : dv_prev);
     if (it > 0) {
       // du_{t-1} starts from zero: only v_{t-1} depends on it
@@ -1426,14 +1326,14 @@ extern "C" int spr_sinkhorn_bwd(const float* feat, int d, const float* xyz, cons
   }
   // affinity -> correlation, alpha, beta
   const int nparts = 1024;
-  hipLaunchKernelGGL(k_affinity_bwd, dim3(nparts), dim3(256), 0, stream, corr, mat, dmat, total, scale, beta, parts);
+  hipLaunchKernelGGL(k_affinity_bwd, dim3(nparts), dim3(256), 0, stream, corr, c.mat, dmat, c.total, scale, beta, parts);
   hipLaunchKernelGGL(k_affinity_bwd_final, dim3(1), dim3(64), 0, stream, parts, nparts, alpha, beta, dalpha, dbeta);
   // correlation -> features: dFs = dcorr Ft, dFt = dcorr^T Fs (exact-f32 batched GEMM)
-  hipLaunchKernelGGL(k_build_grad_recs, dim3(cdiv(npairs, 64)), dim3(64), 0, stream, pd, npairs, d, rs, rt);
+  hipLaunchKernelGGL(k_build_grad_recs, dim3(cdiv(npairs, 64)), dim3(64), 0, stream, c.pd, npairs, d, rs, rt);
   SPR_LAUNCH_CHECK();
   // all pairs in one launch per product: the records carry each pair's own leading dimension (BgemmDesc.pad), a
   // pair alone is 38 tiles of 128 x 128
-  if (int rc = spr_bgemm(dmat, feat, dfeat, rs, npairs, max_n, d, max_m, 1, d, 1, d, 1, 1.0f, 0.0f, stream_)) return rc;
-  if (int rc = spr_bgemm(dmat, feat, dfeat, rt, npairs, max_m, d, 1, max_m, d, 1, d, 1, 1.0f, 0.0f, stream_)) return rc;
+  if (int rc = spr_bgemm(dmat, feat, dfeat, rs, npairs, c.max_n, d, c.max_m, 1, d, 1, d, 1, 1.0f, 0.0f, stream_)) return rc;
+  if (int rc = spr_bgemm(dmat, feat, dfeat, rt, npairs, c.max_m, d, 1, c.max_m, d, 1, d, 1, 1.0f, 0.0f, stream_)) return rc;
   return 0;
 }

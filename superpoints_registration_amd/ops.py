@@ -1281,17 +1281,8 @@ def match_dualsoftmax(feat, cu, cu_host: Sequence[int], npairs: int):
 def match_dualsoftmax_top2(feat, cu, cu_host: Sequence[int], npairs: int):
     """(val, val2, ind): the best and the runner-up dual-softmax value of every match (Lowe ratio
     test of RegTR.ratio_test, qk_regtr_full.py:370-384).  Inference only."""
-    feat = _dev(feat, "feat", torch.float32)
-    cu = _dev(cu, "cu", torch.int32)
-    T, d = feat.shape
-    arr = _cu_host_arr(cu_host)
-    L = _lib.lib()
-    ws = _workspace(L.spr_match_workspace_bytes(arr, npairs), feat.device)
-    val = torch.zeros((T,), dtype=torch.float32, device=feat.device)
-    val2 = torch.zeros((T,), dtype=torch.float32, device=feat.device)
-    ind = torch.zeros((T,), dtype=torch.int32, device=feat.device)
-    _lib.check(L.spr_match_dualsoftmax(_ptr(feat), d, _ptr(cu), arr, npairs, _ptr(val), _ptr(val2), _ptr(ind),
-                                       _ptr(ws), ws.numel(), _stream(feat)), "spr_match_dualsoftmax")
+    val, val2, ind, _, _ = _match_head(feat, None, cu, cu_host, npairs, None, None, 0, match=True, top2=True,
+                                       sinkhorn=False)
     return val, val2, ind
 
 
@@ -1402,17 +1393,46 @@ def refine_pairs(val, val2, ind, overlap, xyz, cu, cu_host: Sequence[int], npair
             'out_cu': out_cu, 'status': status}
 
 
-def match_dualsoftmax_raw(feat, cu, cu_host: Sequence[int], npairs: int):
+def _match_head(feat, xyz, cu, cu_host: Sequence[int], npairs: int, alpha, beta, n_iters: int, *, match: bool,
+                top2: bool, sinkhorn: bool):
+    """The one marshalling of the matching head's three entry points (csrc/match_pose.hip, match_head).
+    Returns (val, val2, ind, w, t_hat) with None for what was not asked for."""
     feat = _dev(feat, "feat", torch.float32)
     cu = _dev(cu, "cu", torch.int32)
+    dev = feat.device
     T, d = feat.shape
     arr = _cu_host_arr(cu_host)
     L = _lib.lib()
-    ws = _workspace(L.spr_match_workspace_bytes(arr, npairs), feat.device)
-    val = torch.zeros((T,), dtype=torch.float32, device=feat.device)
-    ind = torch.zeros((T,), dtype=torch.int32, device=feat.device)
-    _lib.check(L.spr_match_dualsoftmax(_ptr(feat), d, _ptr(cu), arr, npairs, _ptr(val), None, _ptr(ind),
-                                       _ptr(ws), ws.numel(), _stream(feat)), "spr_match_dualsoftmax")
+    ws = _workspace(L.spr_match_workspace_bytes(arr, npairs), dev)
+    val = val2 = ind = w = that = None
+    if match:
+        val = torch.zeros((T,), dtype=torch.float32, device=dev)
+        val2 = torch.zeros((T,), dtype=torch.float32, device=dev) if top2 else None
+        ind = torch.zeros((T,), dtype=torch.int32, device=dev)
+    if sinkhorn:
+        alpha_t, beta_t = _dev_scalar(alpha, dev), _dev_scalar(beta, dev)
+        xyz = _dev(xyz, "xyz", torch.float32)
+        tsrc = int(cu_host[npairs])
+        w = torch.empty((tsrc,), dtype=torch.float32, device=dev)
+        that = torch.empty((tsrc, 3), dtype=torch.float32, device=dev)
+    tail = (_ptr(ws), ws.numel(), _stream(feat))
+    if not sinkhorn:
+        _lib.check(L.spr_match_dualsoftmax(_ptr(feat), d, _ptr(cu), arr, npairs, _ptr(val), _ptr(val2), _ptr(ind),
+                                           *tail), "spr_match_dualsoftmax")
+    elif not match:
+        _lib.check(L.spr_sinkhorn_correspondences(_ptr(feat), d, _ptr(xyz), _ptr(cu), arr, npairs, _ptr(alpha_t),
+                                                  _ptr(beta_t), int(n_iters), 1, _ptr(w), _ptr(that), *tail),
+                   "spr_sinkhorn_correspondences")
+    else:
+        _lib.check(L.spr_match_sinkhorn(_ptr(feat), d, _ptr(xyz), _ptr(cu), arr, npairs, _ptr(alpha_t), _ptr(beta_t),
+                                        int(n_iters), _ptr(val), _ptr(val2), _ptr(ind), _ptr(w), _ptr(that), *tail),
+                   "spr_match_sinkhorn")
+    return val, val2, ind, w, that
+
+
+def match_dualsoftmax_raw(feat, cu, cu_host: Sequence[int], npairs: int):
+    val, _, ind, _, _ = _match_head(feat, None, cu, cu_host, npairs, None, None, 0, match=True, top2=False,
+                                    sinkhorn=False)
     return val, ind
 
 
@@ -1442,22 +1462,9 @@ def sinkhorn_correspondences(feat, xyz, cu, cu_host: Sequence[int], npairs: int,
 
 def sinkhorn_correspondences_raw(feat, xyz, cu, cu_host: Sequence[int], npairs: int, alpha,
                                  beta, n_iters: int, slack: bool = True):
-    feat = _dev(feat, "feat", torch.float32)
-    alpha_t, beta_t = _dev_scalar(alpha, feat.device), _dev_scalar(beta, feat.device)
-    xyz = _dev(xyz, "xyz", torch.float32)
-    cu = _dev(cu, "cu", torch.int32)
-    T, d = feat.shape
-    tsrc = int(cu_host[npairs])
-    arr = _cu_host_arr(cu_host)
-    L = _lib.lib()
-    ws = _workspace(L.spr_sinkhorn_workspace_bytes(arr, npairs), feat.device)
-    w = torch.empty((tsrc,), dtype=torch.float32, device=feat.device)
-    that = torch.empty((tsrc, 3), dtype=torch.float32, device=feat.device)
-    _lib.check(L.spr_sinkhorn_correspondences(_ptr(feat), d, _ptr(xyz), _ptr(cu), arr, npairs,
-                                              _ptr(alpha_t), _ptr(beta_t), int(n_iters), int(bool(slack)),
-                                              _ptr(w), _ptr(that), _ptr(ws), ws.numel(), _stream(feat)),
-               "spr_sinkhorn_correspondences")
-    return w, that
+    # (slack: the library always pads the slack row / column, like the reference's sinkhorn())
+    return _match_head(feat, xyz, cu, cu_host, npairs, alpha, beta, n_iters, match=False, top2=False,
+                       sinkhorn=True)[3:]
 
 
 def match_and_sinkhorn(feat, xyz, cu, cu_host: Sequence[int], npairs: int, alpha, beta, n_iters: int,
@@ -1467,24 +1474,7 @@ def match_and_sinkhorn(feat, xyz, cu, cu_host: Sequence[int], npairs: int, alpha
     wanted use the two operators.  Returns (val, val2 or None, ind, w, t_hat), bit for bit the separate results."""
     if _wants_grad(feat, alpha, beta):
         raise RuntimeError("match_and_sinkhorn is an inference operator (use match_dualsoftmax + sinkhorn_correspondences)")
-    feat = _dev(feat, "feat", torch.float32)
-    alpha_t, beta_t = _dev_scalar(alpha, feat.device), _dev_scalar(beta, feat.device)
-    xyz = _dev(xyz, "xyz", torch.float32)
-    cu = _dev(cu, "cu", torch.int32)
-    T, d = feat.shape
-    tsrc = int(cu_host[npairs])
-    arr = _cu_host_arr(cu_host)
-    L = _lib.lib()
-    ws = _workspace(L.spr_match_workspace_bytes(arr, npairs), feat.device)
-    val = torch.zeros((T,), dtype=torch.float32, device=feat.device)
-    val2 = torch.zeros((T,), dtype=torch.float32, device=feat.device) if top2 else None
-    ind = torch.zeros((T,), dtype=torch.int32, device=feat.device)
-    w = torch.empty((tsrc,), dtype=torch.float32, device=feat.device)
-    that = torch.empty((tsrc, 3), dtype=torch.float32, device=feat.device)
-    _lib.check(L.spr_match_sinkhorn(_ptr(feat), d, _ptr(xyz), _ptr(cu), arr, npairs, _ptr(alpha_t), _ptr(beta_t),
-                                    int(n_iters), _ptr(val), _ptr(val2), _ptr(ind), _ptr(w), _ptr(that), _ptr(ws),
-                                    ws.numel(), _stream(feat)), "spr_match_sinkhorn")
-    return val, val2, ind, w, that
+    return _match_head(feat, xyz, cu, cu_host, npairs, alpha, beta, n_iters, match=True, top2=top2, sinkhorn=True)
 
 
 def weighted_procrustes(a, b, w, pair_cu) -> torch.Tensor:
