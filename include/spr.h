@@ -529,6 +529,7 @@ int spr_xenc_forward(const void* plan_host, const float* x, const float* pos, co
  * keys); NULL = computed here.
  * ws: spr_attn_bwd_workspace_bytes has room for the pre-split operand planes of the split-fp16 form (faster);
  * with at least spr_attn_bwd_min_workspace_bytes the kernels convert the fp32 tiles they stage themselves.
+ * t rounded up to whole 64-row tiles + 64 * nseg must stay below 2^31 (the padded plane width is an int).
  */
 size_t spr_attn_bwd_workspace_bytes(int t, int nseg, int nhead);
 size_t spr_attn_bwd_min_workspace_bytes(int t, int nhead);
@@ -717,7 +718,8 @@ int spr_pair_gather(const float* x, int t_in, int c, const int* cu, int n_clouds
  *   transformed by pose_gt [3,4] inside (se3_transform, :341-345).
  * spr_transform_l1_pair: mean |T_gt x - T_pred x| over one pair's keypoints
  *   (:349-355).   spr_sum_scaled: out[0] = scale * sum(values[0..n)).
- * ws: spr_loss_workspace_bytes(max anchors, max positives, d) covers all four.
+ * ws: spr_loss_workspace_bytes(max anchors, max positives, d) covers all four.  spr_infonce_pair and its backward
+ *   accept d <= 46 336 (d * d is an int in their launches; the query cannot wrap size_t inside that range).
  */
 size_t spr_loss_workspace_bytes(int n_max, int m_max, int d);
 int spr_overlap_pool(const float* ov_prev, int ns_prev, const int* pool,

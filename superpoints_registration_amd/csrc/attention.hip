@@ -806,7 +806,7 @@ int carve(void* ws, size_t ws_bytes, int t, int nseg, int d, size_t tp, AttnPlan
   sm.p2 = w.take<float>(kAmaxParts);
   sm.rowl1 = w.take<float>(1024);
   sm.scales = w.take<float>(4);
-  SPR_REQUIRE(sm.scales != nullptr, "attention: workspace carve failed");
+  SPR_REQUIRE(w.ok() && sm.scales != nullptr, "attention: workspace carve failed");
   pl.scales = sm.scales;
   return 0;
 }

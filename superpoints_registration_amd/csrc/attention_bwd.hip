@@ -978,11 +978,15 @@ extern "C" size_t spr_attn_bwd_min_workspace_bytes(int t, int nhead) {
   return 2 * align_up((size_t)(t > 0 ? t : 1) * (size_t)(nhead > 0 ? nhead : 1) * sizeof(float), 256) +
          align_up((size_t)4 * kAmaxParts * sizeof(float), 256) + 256;
 }
-static int attn_bwd_tc(int t, int nseg) { return (t + BT - 1) / BT * BT + BT * (nseg > 0 ? nseg : 1); }
+// columns of the transposed operand planes: every segment padded to whole BT-column tiles.  size_t from the first
+// factor: the size query must not wrap where t + BT * nseg leaves int (the entry point refuses such sizes)
+static size_t attn_bwd_tc(int t, int nseg) {
+  return ((size_t)(t > 0 ? t : 1) + BT - 1) / BT * BT + (size_t)BT * (size_t)(nseg > 0 ? nseg : 1);
+}
 static size_t attn_bwd_plane_bytes(int t, int nseg, int nhead) {
   const size_t d = (size_t)(nhead > 0 ? nhead : 1) * BHD;
-  return 8 * align_up((size_t)(t > 0 ? t : 1) * d * 2, 256) + 6 * align_up(d * (size_t)attn_bwd_tc(t, nseg) * 2, 256) +
-         align_up((size_t)(nseg + 2) * sizeof(int), 256);
+  return 8 * align_up((size_t)(t > 0 ? t : 1) * d * 2, 256) + 6 * align_up(d * attn_bwd_tc(t, nseg) * 2, 256) +
+         align_up(((size_t)(nseg > 0 ? nseg : 1) + 2) * sizeof(int), 256);
 }
 // with room for the operand planes of the split-fp16 form (k_attn_bwd_pack)
 extern "C" size_t spr_attn_bwd_workspace_bytes(int t, int nseg, int nhead) {
@@ -1006,12 +1010,34 @@ extern "C" int spr_attn_varlen_bwd(const float* q, int q_stride, const float* k,
   SPR_REQUIRE(q_stride >= d && k_stride >= d && v_stride >= d && o_stride >= d && do_stride >= d &&
                   q_stride % 4 == 0 && k_stride % 4 == 0 && v_stride % 4 == 0 && o_stride % 4 == 0 && do_stride % 4 == 0,
               "attn_bwd: row strides must be multiples of 4 floats and >= nhead * 32");
+  SPR_REQUIRE(attn_bwd_tc(t, nseg) < (1ul << 31), "attn_bwd: too many tokens or segments (t=%d nseg=%d)", t, nseg);
   SPR_REQUIRE(ws != nullptr && ws_bytes >= spr_attn_bwd_min_workspace_bytes(t, nhead), "attn_bwd: workspace too small");
+  // the whole carve, checked once, in front of the first launch
+  const bool split = attn_mode() != 0;
+  const bool planes = split && ws_bytes >= spr_attn_bwd_workspace_bytes(t, nseg, nhead);
   Workspace w(ws, ws_bytes);
   AttnBwdArgs a;
   a.lse = w.take<float>((size_t)t * nhead);
   a.dsum = w.take<float>((size_t)t * nhead);
-  SPR_REQUIRE(a.dsum != nullptr, "attn_bwd: workspace carve failed");
+  float *parts = nullptr, *scales = nullptr;
+  BwdPlanes pl{};
+  if (split) {
+    parts = w.take<float>((size_t)4 * kAmaxParts);
+    scales = w.take<float>(4);
+  }
+  if (planes) {
+    const int tc = (int)attn_bwd_tc(t, nseg);
+    _Float16** r[4] = {pl.rq, pl.rk, pl.rv, pl.ro};
+    for (auto& rp : r)
+      for (int i = 0; i < 2; ++i) rp[i] = w.take<_Float16>((size_t)t * d);
+    _Float16** cpl[3] = {pl.cq, pl.ck, pl.co};
+    for (auto& cp : cpl)
+      for (int i = 0; i < 2; ++i) cp[i] = w.take<_Float16>((size_t)d * tc);
+    pl.cst = w.take<int>(nseg + 1);
+    pl.t = t;
+    pl.tc = tc;
+  }
+  SPR_REQUIRE(w.ok(), "attn_bwd: workspace carve failed");
   // the forward's log-sum-exp (split-fp16 forms only: the exact-f32 kernels keep their own sweep)
   const bool have_lse = lse_in != nullptr && attn_mode() != 0;
   if (have_lse) a.lse = const_cast<float*>(lse_in);
@@ -1022,11 +1048,8 @@ extern "C" int spr_attn_varlen_bwd(const float* q, int q_stride, const float* k,
   hipLaunchKernelGGL(k_attn_bwd_rowdot, dim3(cdiv((long)t * nhead, 256)), dim3(256), 0, stream, out, o_stride, dout,
                      do_stride, t, nhead, a.dsum);
   const dim3 grid(cdiv(max_len_host, BT), nhead, nseg);
-  if (attn_mode() != 0) {
+  if (split) {
     // split-fp16 form: operand scales from the measured maxima of q, k, v, dO
-    float* parts = w.take<float>((size_t)4 * kAmaxParts);
-    float* scales = w.take<float>(4);
-    SPR_REQUIRE(scales != nullptr, "attn_bwd: workspace carve failed");
     if (int rc = launch_absmax2(q, t, d, q_stride, parts, k, t, d, k_stride, parts + kAmaxParts, stream)) return rc;
     if (int rc = launch_absmax2(v, t, d, v_stride, parts + 2 * kAmaxParts, dout, t, d, do_stride, parts + 3 * kAmaxParts,
                                 stream))
@@ -1034,20 +1057,8 @@ extern "C" int spr_attn_varlen_bwd(const float* q, int q_stride, const float* k,
     hipLaunchKernelGGL(k_attn_bwd_scales, dim3(1), dim3(256), 0, stream, parts, scales);
     constexpr size_t dkv_lds = (size_t)NB * DKV_BUF_HALVES * 2 + 4 * BT * sizeof(float);
     static_assert(dkv_lds >= sizeof(float) * 2 * 2 * 16 * 64, "the final reduction reuses the tile buffers");
-    BwdPlanes pl{};
-    if (ws_bytes >= spr_attn_bwd_workspace_bytes(t, nseg, nhead)) {
+    if (planes) {
       // operand planes written once (k_attn_bwd_pack), staged by 16-byte copies
-      const int tc = attn_bwd_tc(t, nseg);
-      _Float16** r[4] = {pl.rq, pl.rk, pl.rv, pl.ro};
-      for (auto& rp : r)
-        for (int i = 0; i < 2; ++i) rp[i] = w.take<_Float16>((size_t)t * d);
-      _Float16** cpl[3] = {pl.cq, pl.ck, pl.co};
-      for (auto& cp : cpl)
-        for (int i = 0; i < 2; ++i) cp[i] = w.take<_Float16>((size_t)d * tc);
-      pl.cst = w.take<int>(nseg + 1);
-      pl.t = t;
-      pl.tc = tc;
-      SPR_REQUIRE(pl.cst != nullptr, "attn_bwd: workspace carve failed");
       hipLaunchKernelGGL(k_attn_bwd_cst, dim3(1), dim3(64), 0, stream, cu, nseg, pl.cst);
       hipLaunchKernelGGL(k_attn_bwd_pack, dim3(cdiv(max_len_host, BT), nhead, 4 * nseg), dim3(256), 0, stream, a, pl, scales);
       if (have_lse)

@@ -305,7 +305,7 @@ int carve_probs(void* ws, size_t ws_bytes, int t, int nhead, ProbsWs& w) {
   w.qparts = a.take<float>(kAmaxParts);
   w.kparts = a.take<float>(kAmaxParts);
   w.scales = a.take<float>(4);
-  SPR_REQUIRE(w.scales != nullptr, "attention probs: workspace carve failed");
+  SPR_REQUIRE(a.ok() && w.scales != nullptr, "attention probs: workspace carve failed");
   return 0;
 }
 }  // namespace

@@ -539,7 +539,7 @@ extern "C" int spr_augment_pairs(const float* src_xyz, const int* src_cu, int ns
   int* rb = w.take<int>((size_t)stride + 1);
   const size_t temp_bytes = aug_temp_bytes(P, (size_t)stride, nb);
   void* temp = w.take<char>(temp_bytes);
-  SPR_REQUIRE(temp != nullptr, "augment_pairs: workspace carve failed");
+  SPR_REQUIRE(w.ok() && temp != nullptr, "augment_pairs: workspace carve failed");
 
   const int TB = 256;
   hipLaunchKernelGGL(k_aug_layout, dim3(1), dim3(64), 0, stream, nb, max_pts, src_cu, tgt_cu, flags, out_src_cu,

@@ -628,7 +628,7 @@ int fx_scratch(void* ws, size_t ws_bytes, long rows, int c, hipStream_t stream, 
   Workspace w(ws, ws_bytes);
   out->acc = w.take<unsigned long long>((size_t)rows * c);
   out->parts = w.take<float>(kAmaxParts);
-  SPR_REQUIRE(out->parts != nullptr, "scatter: workspace carve failed");
+  SPR_REQUIRE(w.ok() && out->parts != nullptr, "scatter: workspace carve failed");
   SPR_HIP_CHECK(hipMemsetAsync(out->acc, 0, (size_t)rows * c * sizeof(unsigned long long), stream));
   return 0;
 }

@@ -312,7 +312,8 @@ __global__ void k_tn_f64_final(const double* __restrict__ part, int nslab, int n
 using namespace spr;
 
 extern "C" size_t spr_tn_product_f64_workspace_bytes(long rows, int nl, int nr) {
-  return (size_t)cdiv(rows > 0 ? rows : 1, kTnSlab) * (size_t)nl * nr * sizeof(double) + 256;
+  const size_t out = (size_t)(nl > 0 ? nl : 0) * (size_t)(nr > 0 ? nr : 0);
+  return (size_t)cdiv(rows > 0 ? rows : 1, kTnSlab) * out * sizeof(double) + 256;
 }
 
 extern "C" int spr_tn_product_f64(const float* Lm, const float* Rm, long rows, int nl, int nr, float* out,
@@ -460,6 +461,7 @@ extern "C" int spr_tn_product_split(const float* Lm, const float* Rm, long rows,
   Workspace w(ws, ws_bytes);
   float* lp = w.take<float>(kAmaxParts);
   float* rp = w.take<float>(kAmaxParts);
+  SPR_REQUIRE(w.ok(), "tn_product_split: workspace carve failed");
   const float* lparts = l_range;
   const float* rparts = r_range;
   int nlp = l_range_n, nrp = r_range_n;

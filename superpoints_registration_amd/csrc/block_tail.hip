@@ -474,7 +474,7 @@ extern "C" int spr_block_tail_tile_rows(int ka, int kb, int n_out) { return tail
 
 // tiles: int32 [spr_block_tail_tiles_len(n, nb, tile_rows)] = tile_cu [nb + 1], padding to a multiple of 4,
 // then one {first row, valid rows, cloud, 0} record per tile
-static size_t tiles_desc_offset(int nb) { return align_up((size_t)nb + 1, 4); }
+static size_t tiles_desc_offset(int nb) { return align_up((size_t)(nb > 0 ? nb : 0) + 1, 4); }
 extern "C" size_t spr_block_tail_tiles_len(int n, int nb, int tile_rows) {
   return tiles_desc_offset(nb) + 4 * ((size_t)cdiv(n > 0 ? n : 1, tile_rows > 0 ? tile_rows : 64) + (size_t)(nb > 0 ? nb : 1));
 }
@@ -493,8 +493,9 @@ extern "C" int spr_block_tail_tiles(const int* cu, int n, int nb, int tile_rows,
 extern "C" size_t spr_block_tail_workspace_bytes(int n, int nb, int kb, int n_out, int tile_rows) {
   const size_t nbr = kb > 0 ? 2 : 1;
   const size_t tiles = (size_t)cdiv(n > 0 ? n : 1, tile_rows > 0 ? tile_rows : 64) + (size_t)(nb > 0 ? nb : 1);
-  return align_up(tiles * nbr * 2 * (size_t)n_out * sizeof(double), 256) +
-         align_up((size_t)(nb > 0 ? nb : 1) * nbr * 2 * (size_t)n_out * sizeof(float), 256) +
+  const size_t no = (size_t)(n_out > 0 ? n_out : 0);
+  return align_up(tiles * nbr * 2 * no * sizeof(double), 256) +
+         align_up((size_t)(nb > 0 ? nb : 1) * nbr * 2 * no * sizeof(float), 256) +
          4 * align_up(kAmaxParts * sizeof(float), 256);
 }
 
@@ -525,7 +526,7 @@ extern "C" int spr_block_tail(const float* xa, int ka, const float* wa, const fl
   a.stats = w.take<float>((size_t)nb * nbr * 2 * n_out);
   float* mp[4];
   for (int i = 0; i < 4; ++i) mp[i] = w.take<float>(kAmaxParts);
-  SPR_REQUIRE(mp[3] != nullptr, "block_tail: workspace carve failed");
+  SPR_REQUIRE(w.ok() && mp[3] != nullptr, "block_tail: workspace carve failed");
   a.xa = xa; a.xb = xb; a.wa = wa; a.wb = wb; a.add = add; a.cu = cu; a.tile_cu = tiles;
   a.tile_desc = reinterpret_cast<const int4*>(tiles + tiles_desc_offset(nb));
   a.nb = nb; a.n = n; a.n_total = n_out; a.slope = slope; a.out = out; a.out_range = out_range; a.nslots = out_range_n;

@@ -405,7 +405,7 @@ bool carve(void* ws, size_t ws_bytes, int nbatch, int max_n, int max_m, CircleWs
   c.ccoef = w.take<float>(C);
   c.rgpart = w.take<float>(R * tm);
   c.cgpart = w.take<float>(C * tn);
-  return c.cgpart != nullptr;
+  return w.ok() && c.cgpart != nullptr;
 }
 
 // the launches shared by the forward and the backward: transform, tile partials, merged statistics

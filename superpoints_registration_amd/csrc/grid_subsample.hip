@@ -433,7 +433,7 @@ extern "C" int spr_grid_subsample(const float* xyz, const int* cu, int n, int nb
   SPR_REQUIRE(nb < (1 << 23), "grid_subsample: too many clouds");
   // reference: subsampling an empty batch is an error (wrapper.cpp:266-270)
   SPR_REQUIRE(n > 0, "grid_subsample: empty input");
-  SPR_REQUIRE(ws_bytes >= spr_grid_subsample_workspace_bytes(n, nb),
+  SPR_REQUIRE(ws != nullptr && ws_bytes >= spr_grid_subsample_workspace_bytes(n, nb),
               "grid_subsample: workspace too small");
   Workspace w(ws, ws_bytes);
   const size_t N = (size_t)n;
@@ -464,7 +464,7 @@ extern "C" int spr_grid_subsample(const float* xyz, const int* cu, int n, int nb
   int* scalars = w.take<int>(64);  // [0]=nvox [1]=err
   size_t temp_bytes = sort_temp_bytes(n);
   void* temp = w.take<char>(temp_bytes);
-  SPR_REQUIRE(temp != nullptr, "grid_subsample: workspace carve failed");
+  SPR_REQUIRE(w.ok() && temp != nullptr, "grid_subsample: workspace carve failed");
   int* nvox = scalars;
   int* err = scalars + 1;
 
@@ -570,14 +570,14 @@ extern "C" int spr_cell_order(const float* xyz, const int* cu, int n, int nb, fl
                               size_t ws_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   SPR_REQUIRE(n >= 1 && nb >= 1 && nb < (1 << 30) && cell > 0.f, "cell_order: bad arguments");
-  SPR_REQUIRE(ws_bytes >= spr_cell_order_workspace_bytes(n), "cell_order: workspace too small");
+  SPR_REQUIRE(ws != nullptr && ws_bytes >= spr_cell_order_workspace_bytes(n), "cell_order: workspace too small");
   Workspace w(ws, ws_bytes);
   unsigned long long* keys = w.take<unsigned long long>(n);
   unsigned long long* keys2 = w.take<unsigned long long>(n);
   int* vals = w.take<int>(n);
   size_t tb = sort_temp_bytes(n);
   void* temp = w.take<char>(tb);
-  SPR_REQUIRE(temp != nullptr, "cell_order: workspace carve failed");
+  SPR_REQUIRE(w.ok() && temp != nullptr, "cell_order: workspace carve failed");
   hipLaunchKernelGGL(k_order_keys, dim3(cdiv(n, 256)), dim3(256), 0, stream, xyz, cu, n, nb, 1.0f / cell, keys, vals);
   SPR_LAUNCH_CHECK();
   int bits = 31;
@@ -657,7 +657,7 @@ extern "C" int spr_voxel_downsample(const float* xyz, int n, double voxel_size, 
   int* err = w.take<int>(1);
   const size_t temp_bytes = vox_temp_bytes(n);
   void* temp = w.take<char>(temp_bytes);
-  SPR_REQUIRE(temp != nullptr, "voxel_downsample: workspace carve failed");
+  SPR_REQUIRE(w.ok() && temp != nullptr, "voxel_downsample: workspace carve failed");
   SPR_HIP_CHECK(hipMemsetAsync(err, 0, sizeof(int), stream));
   SPR_HIP_CHECK(hipMemsetAsync(out_count, 0, sizeof(int), stream));
   const int TBk = 256;

@@ -397,7 +397,7 @@ extern "C" int spr_gt_overlap(const float* src_xyz, const int* src_cu, int ns, c
   int* pos = w.take<int>((size_t)ns + 1);
   size_t temp_bytes = ov_scan_temp_bytes(cells + 1 > (size_t)ns + 1 ? cells + 1 : (size_t)ns + 1);
   void* temp = w.take<char>(temp_bytes);
-  SPR_REQUIRE(temp != nullptr, "gt_overlap: workspace carve failed");
+  SPR_REQUIRE(w.ok() && temp != nullptr, "gt_overlap: workspace carve failed");
 
   const double h0 = radius * (1.0 + 1.0 / 256.0);
   const double r2 = radius * radius;

@@ -1350,7 +1350,9 @@ extern "C" int spr_kpconv_plan(const int* nbr, int nq, int ns, int nbr_stride, i
   return 0;
 }
 
-extern "C" size_t spr_kpconv_wplanes_bytes(int cin, int cout) { return 2 * align_up((size_t)32 * cin * cout * 2, 256); }
+extern "C" size_t spr_kpconv_wplanes_bytes(int cin, int cout) {
+  return 2 * align_up((size_t)32 * (size_t)(cin > 0 ? cin : 0) * (size_t)(cout > 0 ? cout : 0) * 2, 256);
+}
 
 extern "C" int spr_kpconv_prep_weights(const float* weights, int n_kp, int cin, int cout, const float* w_range,
                                        int w_range_n, void* wplanes, size_t bytes, void* stream_) {
@@ -1392,7 +1394,7 @@ extern "C" int spr_kpconv_fwd(const float* q_xyz, int nq, const float* s_xyz, in
   SPR_REQUIRE(kmax >= 1 && kmax <= nbr_stride, "kpconv: bad kmax=%d stride=%d", kmax, nbr_stride);
   SPR_REQUIRE(cin >= 1 && cout >= 1 && n_kp >= 1 && n_kp <= 32, "kpconv: bad dims");
   SPR_REQUIRE(kp_extent > 0.f, "kpconv: KP_extent must be > 0");
-  SPR_REQUIRE(ws_bytes >= spr_kpconv_workspace_bytes(nq, ns, cin, cout), "kpconv: workspace too small");
+  SPR_REQUIRE(ws != nullptr && ws_bytes >= spr_kpconv_workspace_bytes(nq, ns, cin, cout), "kpconv: workspace too small");
   unsigned char* flag = (unsigned char*)ws;
   float4* sxf = (float4*)((char*)ws + align_up((size_t)ns, 256));
   _Float16* wh = (_Float16*)((char*)sxf + align_up(((size_t)ns + 1) * 16, 256));

@@ -1021,6 +1021,7 @@ extern "C" int spr_linear(const float* x, int m, int k, const float* w, int n, c
     Workspace wk(ws, ws_bytes);
     float* ap = wk.take<float>(kAmaxParts);
     float* wp = wk.take<float>(kAmaxParts);
+    SPR_REQUIRE(wk.ok(), "linear: workspace carve failed");
     // ranges handed in (x: published by its producer; w: measured once per weight version by
     // the caller, spr_absmax) are not measured again -- with both there is no pre-pass at all
     a_parts = x_range != nullptr ? x_range : ap;

@@ -304,6 +304,10 @@ extern "C" int spr_overlap_pool(const float* ov_prev, int ns_prev, const int* po
   return 0;
 }
 
+// widest feature the InfoNCE entry points accept: d * d (the W_sym launches) stays an int, and the size query below
+// cannot wrap size_t inside it
+static constexpr int kLossMaxD = 46336;
+
 extern "C" size_t spr_loss_workspace_bytes(int n_max, int m_max, int d) {
   if (n_max < 0 || m_max < 0 || d < 0) return 0;
   const size_t n = (size_t)(n_max > 0 ? n_max : 1), m = (size_t)(m_max > 0 ? m_max : 1);
@@ -331,6 +335,7 @@ extern "C" int spr_infonce_pair(const float* anchor_feat, int n, const float* po
                                 void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   SPR_REQUIRE(n >= 1 && m >= 1 && d >= 32 && d % 32 == 0, "infonce: bad sizes n=%d m=%d d=%d", n, m, d);
+  SPR_REQUIRE(d <= kLossMaxD, "infonce: d=%d, at most %d (d * d is an int in the launches)", d, kLossMaxD);
   SPR_REQUIRE(ws != nullptr && ws_bytes >= spr_loss_workspace_bytes(n, m, d), "infonce: workspace too small");
   Workspace w(ws, ws_bytes);
   float* logits = w.take<float>((size_t)n * m);
@@ -345,7 +350,7 @@ extern "C" int spr_infonce_pair(const float* anchor_feat, int n, const float* po
   const size_t lws = spr_linear_workspace_bytes();
   char* lw1 = w.take<char>(lws);
   char* lw2 = w.take<char>(lws);
-  SPR_REQUIRE(pb != nullptr && lw2 != nullptr, "infonce: workspace carve failed");
+  SPR_REQUIRE(w.ok() && pb != nullptr && lw2 != nullptr, "infonce: workspace carve failed");
   hipLaunchKernelGGL(k_wsym, dim3(cdiv(d * d, 256)), dim3(256), 0, stream, W, d, wsym);
   hipLaunchKernelGGL(k_transform, dim3(cdiv(n, 256)), dim3(256), 0, stream, pose_gt, anchor_xyz, n, axyz);
   // logits = (A W_sym) B^T : W_sym is symmetric, so the NT GEMM applies it as is
@@ -404,6 +409,7 @@ extern "C" int spr_infonce_pair_dlogits(const float* anchor_feat, int n, const f
                                         float* wsym_out, float* t_out, void* ws, size_t ws_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   SPR_REQUIRE(n >= 1 && m >= 1 && d >= 32 && d % 32 == 0, "infonce_bwd: bad sizes n=%d m=%d d=%d", n, m, d);
+  SPR_REQUIRE(d <= kLossMaxD, "infonce_bwd: d=%d, at most %d (d * d is an int in the launches)", d, kLossMaxD);
   SPR_REQUIRE(ws != nullptr && ws_bytes >= spr_loss_workspace_bytes(n, m, d), "infonce_bwd: workspace too small");
   Workspace w(ws, ws_bytes);
   float* logits = w.take<float>((size_t)n * m);
@@ -418,7 +424,7 @@ extern "C" int spr_infonce_pair_dlogits(const float* anchor_feat, int n, const f
   const size_t lws = spr_linear_workspace_bytes();
   char* lw1 = w.take<char>(lws);
   char* lw2 = w.take<char>(lws);
-  SPR_REQUIRE(lw2 != nullptr, "infonce_bwd: workspace carve failed");
+  SPR_REQUIRE(w.ok() && lw2 != nullptr, "infonce_bwd: workspace carve failed");
   hipLaunchKernelGGL(k_wsym, dim3(cdiv(d * d, 256)), dim3(256), 0, stream, W, d, wsym_out);
   hipLaunchKernelGGL(k_transform, dim3(cdiv(n, 256)), dim3(256), 0, stream, pose_gt, anchor_xyz, n, axyz);
   if (int rc = spr_linear(anchor_feat, n, d, wsym_out, d, nullptr, nullptr, SPR_ACT_NONE, t_out, nullptr, 0, nullptr, 0,

@@ -993,7 +993,7 @@ int corr_setup(Corr& c, const float* feat, int d, const int* cu_dev, const int* 
   c.total = build_pairs(cu_host, npairs, c.h.data());
   c.mat = w.take<float>((size_t)c.total);
   c.pd = w.take<PairDesc>(npairs);
-  SPR_REQUIRE(c.mat && c.pd, "match: workspace carve failed");
+  SPR_REQUIRE(w.ok() && c.mat && c.pd, "match: workspace carve failed");
   c.max_n = 0;
   c.max_m = 0;
   c.min_m = 1 << 30;
@@ -1013,7 +1013,7 @@ int corr_setup(Corr& c, const float* feat, int d, const int* cu_dev, const int* 
   int bm = 1, bn = 1;
   if (c.grouped) {
     c.gg = w.take<GemmGroup>(npairs);
-    SPR_REQUIRE(c.gg != nullptr, "match: workspace carve failed");
+    SPR_REQUIRE(w.ok() && c.gg != nullptr, "match: workspace carve failed");
     gemm_group_tile(c.max_m, &bm, &bn);
   }
   // descriptors are rebuilt on the device from cu (no pageable host copy)
@@ -1023,7 +1023,7 @@ int corr_setup(Corr& c, const float* feat, int d, const int* cu_dev, const int* 
   if (gemm_mode() == 1) {
     float* ps = w.take<float>(kAmaxParts);
     float* pt = w.take<float>(kAmaxParts);
-    SPR_REQUIRE(pt != nullptr, "match: workspace carve failed");
+    SPR_REQUIRE(w.ok() && pt != nullptr, "match: workspace carve failed");
     const int nsrc = cu_host[npairs], ntot = cu_host[2 * npairs];
     if (int rc = launch_absmax2(feat, nsrc, d, d, ps, feat + (size_t)nsrc * d, ntot - nsrc, d, d, pt, stream))
       return rc;
@@ -1099,7 +1099,7 @@ int match_head(const HeadArgs& a, bool want_match, bool want_sinkhorn) {
   Workspace w(a.ws, a.ws_bytes);
   const float scale = 1.0f / sqrtf((float)a.d);
   float* epi = w.take<float>(4);       // {scale, softplus alpha, 1 / (e^beta + 0.02)}: the epilogue reads [0], the view all
-  SPR_REQUIRE(epi != nullptr, "%s: workspace carve failed", a.name);
+  SPR_REQUIRE(w.ok() && epi != nullptr, "%s: workspace carve failed", a.name);
   hipLaunchKernelGGL(k_epi_params, dim3(1), dim3(64), 0, stream, scale, want_sinkhorn ? a.alpha : nullptr,
                      want_sinkhorn ? a.beta : nullptr, epi);
   const float* aff = want_sinkhorn ? epi : nullptr;
@@ -1110,12 +1110,12 @@ int match_head(const HeadArgs& a, bool want_match, bool want_sinkhorn) {
   if (want_match) {
     row_lse = w.take<float>(T);
     col_lse = w.take<float>(T);
-    SPR_REQUIRE(col_lse != nullptr, "%s: workspace carve failed", a.name);
+    SPR_REQUIRE(w.ok() && col_lse != nullptr, "%s: workspace carve failed", a.name);
   }
   if (want_sinkhorn) {
     u = w.take<float>(T);
     v = w.take<float>(T);
-    SPR_REQUIRE(v != nullptr, "%s: workspace carve failed", a.name);
+    SPR_REQUIRE(w.ok() && v != nullptr, "%s: workspace carve failed", a.name);
     SPR_HIP_CHECK(hipMemsetAsync(u, 0, sizeof(float) * T, stream));
     SPR_HIP_CHECK(hipMemsetAsync(v, 0, sizeof(float) * T, stream));
   }
@@ -1285,7 +1285,7 @@ extern "C" int spr_sinkhorn_bwd(const float* feat, int d, const float* xyz, cons
   double* zero = w.take<double>(T);
   double* parts = w.take<double>(2 * 1024);
   float* epi = w.take<float>(4);
-  SPR_REQUIRE(epi != nullptr, "sinkhorn_bwd: workspace carve failed");
+  SPR_REQUIRE(w.ok() && epi != nullptr, "sinkhorn_bwd: workspace carve failed");
   const float scale = 1.0f / sqrtf((float)d);
   SPR_HIP_CHECK(hipMemsetAsync(dmat, 0, sizeof(float) * (size_t)c.total, stream));
   SPR_HIP_CHECK(hipMemcpyAsync(corr, c.mat, sizeof(float) * (size_t)c.total, hipMemcpyDeviceToDevice, stream));

@@ -404,13 +404,14 @@ extern "C" int spr_instnorm(const float* x, const int* cu, int n, int nb, int ma
   float* rstd = nullptr;
   if (norm) {
     SPR_REQUIRE(max_len_host >= 1 && max_len_host <= n, "instnorm: bad max_len_host=%d", max_len_host);
-    SPR_REQUIRE(ws_bytes >= spr_instnorm_workspace_bytes(max_len_host, nb, c), "instnorm: workspace too small");
+    SPR_REQUIRE(ws != nullptr && ws_bytes >= spr_instnorm_workspace_bytes(max_len_host, nb, c),
+                "instnorm: workspace too small");
     Workspace w(ws, ws_bytes);
     const int nsplit = in_nsplit(max_len_host);
     double* part = w.take<double>((size_t)nb * nsplit * 2 * c);
     mean = w.take<float>((size_t)nb * c);
     rstd = w.take<float>((size_t)nb * c);
-    SPR_REQUIRE(rstd != nullptr, "instnorm: workspace carve failed");
+    SPR_REQUIRE(w.ok() && rstd != nullptr, "instnorm: workspace carve failed");
     hipLaunchKernelGGL(k_in_stats, dim3(nb, nsplit, cdiv(c, 64)), dim3(256), 0, stream, x, cu, c, nsplit, part);
     hipLaunchKernelGGL(k_in_final, dim3(cdiv((long)nb * c, 256)), dim3(256), 0, stream, part, cu,
                        nb, c, nsplit, eps, mean, rstd);
@@ -430,11 +431,12 @@ extern "C" int spr_instnorm_stats(const float* x, const int* cu, int n, int nb, 
   hipStream_t stream = (hipStream_t)stream_;
   SPR_REQUIRE(x && cu && mean && rstd && n > 0 && nb >= 1 && c >= 4 && c % 4 == 0, "instnorm_stats: bad arguments (c=%d)", c);
   SPR_REQUIRE(max_len_host >= 1 && max_len_host <= n, "instnorm_stats: bad max_len_host=%d", max_len_host);
-  SPR_REQUIRE(ws_bytes >= spr_instnorm_workspace_bytes(max_len_host, nb, c), "instnorm_stats: workspace too small");
+  SPR_REQUIRE(ws != nullptr && ws_bytes >= spr_instnorm_workspace_bytes(max_len_host, nb, c),
+              "instnorm_stats: workspace too small");
   Workspace w(ws, ws_bytes);
   const int nsplit = in_nsplit(max_len_host);
   double* part = w.take<double>((size_t)nb * nsplit * 2 * c);
-  SPR_REQUIRE(part != nullptr, "instnorm_stats: workspace carve failed");
+  SPR_REQUIRE(w.ok() && part != nullptr, "instnorm_stats: workspace carve failed");
   hipLaunchKernelGGL(k_in_stats, dim3(nb, nsplit, cdiv(c, 64)), dim3(256), 0, stream, x, cu, c, nsplit, part);
   hipLaunchKernelGGL(k_in_final, dim3(cdiv((long)nb * c, 256)), dim3(256), 0, stream, part, cu, nb, c, nsplit, eps, mean,
                      rstd);
@@ -459,7 +461,8 @@ extern "C" int spr_instnorm_bwd(const float* x, const float* out, const float* d
   double *m1 = nullptr, *m2 = nullptr;
   if (norm) {
     SPR_REQUIRE(max_len_host >= 1 && max_len_host <= n, "instnorm_bwd: bad max_len_host=%d", max_len_host);
-    SPR_REQUIRE(ws_bytes >= spr_instnorm_bwd_workspace_bytes(max_len_host, nb, c), "instnorm_bwd: workspace too small");
+    SPR_REQUIRE(ws != nullptr && ws_bytes >= spr_instnorm_bwd_workspace_bytes(max_len_host, nb, c),
+                "instnorm_bwd: workspace too small");
     Workspace w(ws, ws_bytes);
     const int nsplit = in_nsplit(max_len_host);
     double* part = w.take<double>((size_t)nb * nsplit * 2 * c);
@@ -467,7 +470,7 @@ extern "C" int spr_instnorm_bwd(const float* x, const float* out, const float* d
     rstd = w.take<float>((size_t)nb * c);
     m1 = w.take<double>((size_t)nb * c);
     m2 = w.take<double>((size_t)nb * c);
-    SPR_REQUIRE(m2 != nullptr, "instnorm_bwd: workspace carve failed");
+    SPR_REQUIRE(w.ok() && m2 != nullptr, "instnorm_bwd: workspace carve failed");
     hipLaunchKernelGGL(k_in_stats, dim3(nb, nsplit, cdiv(c, 64)), dim3(256), 0, stream, x, cu, c, nsplit, part);
     hipLaunchKernelGGL(k_in_final, dim3(cdiv((long)nb * c, 256)), dim3(256), 0, stream, part, cu, nb, c, nsplit,
                        eps, mean, rstd);

@@ -910,7 +910,7 @@ int table_build(const float* s_xyz, const int* s_cu, int ns, int nb, float radiu
   int* rank = w.take<int>((size_t)ns);
   const int nblk = (int)(table_cells_alloc(ns) / kScanBlock);
   int* bsum = w.take<int>((size_t)nblk);
-  SPR_REQUIRE(bsum != nullptr, "radius table: workspace carve failed");
+  SPR_REQUIRE(w.ok() && bsum != nullptr, "radius table: workspace carve failed");
   const float inv_cell = 1.0f / (radius * (1.0f + 1.0f / 256.0f));
   const int TB = 256;
   SPR_HIP_CHECK(hipMemsetAsync(t.hdr, 0, 8 * sizeof(int), stream));
@@ -942,7 +942,7 @@ int table_query(const float* q_xyz, const int* q_cu, int nq, int self, int ns, i
   unsigned long long* tmp_key = w.take<unsigned long long>((size_t)nq * rcap);
   int* kept = w.take<int>((size_t)nq);
   int* qid = w.take<int>((size_t)nq);
-  SPR_REQUIRE(qid != nullptr, "radius query: workspace carve failed");
+  SPR_REQUIRE(w.ok() && qid != nullptr, "radius query: workspace carve failed");
   const float r2 = radius * radius;  // neighbors.cpp:226 (float32)
   const float inv_cell = 1.0f / (radius * (1.0f + 1.0f / 256.0f));
   if (algo == 1) {   // the one-pass wave-per-query selection instead of scan + rank sort
@@ -1017,7 +1017,7 @@ extern "C" int spr_radius_neighbors(const float* q_xyz, const int* q_cu, int nq,
   SPR_REQUIRE(nb < 65536, "radius_neighbors: at most 65535 clouds per call");
   SPR_REQUIRE(radius > 0.f, "radius_neighbors: radius must be > 0");
   SPR_REQUIRE(limit >= 1 && limit <= 128, "radius_neighbors: limit must be in [1,128], got %d", limit);
-  SPR_REQUIRE(ws_bytes >= spr_radius_neighbors_workspace_bytes(nq, ns, nb),
+  SPR_REQUIRE(ws != nullptr && ws_bytes >= spr_radius_neighbors_workspace_bytes(nq, ns, nb),
               "radius_neighbors: workspace too small");
   Workspace w(ws, ws_bytes);
   const size_t N = (size_t)ns;
@@ -1030,7 +1030,7 @@ extern "C" int spr_radius_neighbors(const float* q_xyz, const int* q_cu, int nq,
   int* err = w.take<int>(16);
   size_t temp_bytes = nbr_sort_temp_bytes(ns);
   void* temp = w.take<char>(temp_bytes);
-  SPR_REQUIRE(temp != nullptr, "radius_neighbors: workspace carve failed");
+  SPR_REQUIRE(w.ok() && temp != nullptr, "radius_neighbors: workspace carve failed");
 
   const int TB = 256;
   if (algo == 0) {
@@ -1038,7 +1038,7 @@ extern "C" int spr_radius_neighbors(const float* q_xyz, const int* q_cu, int nq,
     const size_t bws = table_build_ws_bytes(ns), qws = table_query_ws_bytes(nq);
     void* build_ws = w.take<char>(bws);
     void* query_ws = w.take<char>(qws);
-    SPR_REQUIRE(query_ws != nullptr, "radius_neighbors: workspace carve failed (table)");
+    SPR_REQUIRE(w.ok() && query_ws != nullptr, "radius_neighbors: workspace carve failed (table)");
     if (int rc = table_build(s_xyz, s_cu, ns, nb, radius, blob, build_ws, bws, stream)) return rc;
     return table_query(q_xyz, q_cu, nq, (q_xyz == s_xyz && q_cu == s_cu && nq == ns) ? 1 : 0, ns, nb, radius, limit, 0,
                        blob, out_idx, max_count, query_ws, qws, stream);

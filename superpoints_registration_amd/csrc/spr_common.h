@@ -46,16 +46,23 @@ void set_error(const char* fmt, ...);
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
-// Bump allocator over a caller supplied workspace.
+// Bump allocator over a caller supplied workspace.  A take that does not fit returns nullptr and leaves the
+// allocator marked: every entry point checks ok() behind its last take and before its first launch, so a carve
+// that asks for more than the size query promised comes back as an error code, never as a null pointer in a kernel.
 struct Workspace {
   char* base;
   size_t size;
   size_t off;
-  Workspace(void* p, size_t n) : base((char*)p), size(n), off(0) {}
+  bool failed;
+  Workspace(void* p, size_t n) : base((char*)p), size(n), off(0), failed(false) {}
+  bool ok() const { return !failed; }
   template <typename T>
   T* take(size_t count) {
     size_t bytes = align_up(count * sizeof(T), 256);
-    if (off + bytes > size) return nullptr;
+    if (off + bytes > size) {
+      failed = true;
+      return nullptr;
+    }
     T* r = (T*)(base + off);
     off += bytes;
     return r;
