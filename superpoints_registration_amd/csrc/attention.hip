@@ -370,6 +370,14 @@ __device__ __forceinline__ float half_swap_max(float x) {
 // can contribute is bounded by 2^-10 sqrt(sum w_j^2) <= 2^-10 sqrt(2^-5) = 1.7e-4 of the value spread in the worst
 // case (32 keys of exactly that weight) and is ~5e-6 for flat rows of 2 000 keys -- the peaked rows mode 3 is
 // inaccurate on (few keys with large weights) are exact here.
+// The key loop carries no tile bookkeeping in vector registers ("the key loop"): a tile's
+// position is in the scalar base of its four DMA instructions, the LDS destinations are scalars, full tiles never
+// clamp a row (only the fetch of the tail tile does), and the loop is unrolled by two so that the buffer index is
+// static and every fragment read is a loop-invariant lane base plus an immediate offset.  Mode 4, a tile with two
+// non-significant halves: 110 vector instructions for 20 MFMAs (was 142).
+// A wave whose 32 queries all lie past the cloud's end runs the same loop WITHOUT the tile work (a second instance of
+// the loop, not a branch inside it: a branch around the tile body moves the compiler's waits for the staged tiles
+// into the loop); it writes nothing, except zeros for its 32 padding rows of the tiled output.
 template <bool H3, bool PLO, int WPS, bool ADAPT = false>
 __global__ __launch_bounds__(256, WPS) void k_attn_s(
     const _Float16* __restrict__ qh_g, const _Float16* __restrict__ ql_g,
@@ -386,8 +394,11 @@ __global__ __launch_bounds__(256, WPS) void k_attn_s(
   // fragment reads (16 lanes = 16 rows, one chunk) conflict-free without row padding.
   // V^T tiles the same way: 32 feature rows of 128 bytes (64 keys in the planes' fragment order, attn_vperm); chunk c of
   // row d at position c ^ ((d >> 1) & 7).
-  __shared__ __align__(16) _Float16 Kh[2][KT2 * HD], Kl[2][KT2 * HD];
-  __shared__ __align__(16) _Float16 Vth[2][HD * KT2], Vtl[2][HD * KT2];
+  // ONE LDS object for all planes: a lane's fragment reads of the hi and lo plane and of both buffers then share a base
+  // register and differ in the instruction's immediate offset only.
+  __shared__ __align__(16) _Float16 lds[H3 ? 4 : 2][2][KT2 * HD];   // [Kh, Vth, Kl, Vtl][buffer][tile image]
+  _Float16(*const Kh)[KT2 * HD] = lds[0], (*const Vth)[KT2 * HD] = lds[1];
+  _Float16(*const Kl)[KT2 * HD] = lds[H3 ? 2 : 0], (*const Vtl)[KT2 * HD] = lds[H3 ? 3 : 1];   // (!H3: never used)
   int seg, head, qt;
   {
     const int nqt = gridDim.x / (nhead * nseg);
@@ -411,12 +422,16 @@ __global__ __launch_bounds__(256, WPS) void k_attn_s(
   const int ks = kv_seg[seg];
   const int kbeg = cu[ks], klen = cu[ks + 1] - kbeg;
   const int vbeg = vstart(cu, ks);
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // a scalar: LDS-DMA destinations, the empty-wave branch
   const int l31 = lane & 31, lh = lane >> 5;
   const int hoff = head * HD;
+  // A wave whose 32 queries all lie past the cloud's end (the workgroup itself has q0 < qlen) takes its part in every
+  // K / V^T DMA, wait and barrier -- the other waves' tiles depend on them -- and nothing else: no Q loads, no tile().
+  const bool has_q = q0 + wave * 32 < qlen;
 
-  h16x8 qh[2], ql[2];
-  {
+  h16x8 qh[2] = {}, ql[2] = {};
+  if (has_q) {
     const int qi = min(q0 + wave * 32 + l31, qlen - 1);
     const size_t row = ((size_t)head * t_total + qbeg + qi) * HD + 8 * lh;
 #pragma unroll
@@ -440,24 +455,38 @@ __global__ __launch_bounds__(256, WPS) void k_attn_s(
 
   const int skr = tid >> 2, skc = ((tid & 3) ^ ((tid >> 4) & 3)) * 8;   // K: row, SOURCE chunk of this lane's position
   const int svr = tid >> 3, svc = ((tid & 7) ^ ((tid >> 4) & 7)) * 8;   // V^T: row, SOURCE chunk of this lane's position
+  // No address arithmetic per tile in vector registers: a tile's position goes into the SCALAR base of the DMA (K planes:
+  // 64 rows of 64 bytes per tile; blocked V^T planes: four 16-column blocks, vbeg is 16-aligned and kt a multiple of
+  // 64), the lane's offset inside a tile is the same for every tile, and the four LDS destinations are scalars (wave).
+  // Only the fetch of a TAIL tile (kt + 64 > klen) clamps its K rows to the segment's last key.
   const unsigned kdst_h = (unsigned)(uintptr_t)(&Kh[0][0]) + (unsigned)wave * 1024u;   // + buf * 4096
   const unsigned kdst_l = (unsigned)(uintptr_t)(&Kl[0][0]) + (unsigned)wave * 1024u;
   const unsigned vdst_h = (unsigned)(uintptr_t)(&Vth[0][0]) + (unsigned)wave * 1024u;
   const unsigned vdst_l = (unsigned)(uintptr_t)(&Vtl[0][0]) + (unsigned)wave * 1024u;
-  auto dma16 = [&](const void* base, unsigned off, unsigned dst) __attribute__((always_inline)) {
-    const unsigned d = __builtin_amdgcn_readfirstlane(dst);
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(off), "s"(base), "s"(d)
+  const size_t kbase = ((size_t)head * t_total + kbeg) * HD;                                   // halves, tile 0
+  const size_t vbase = attn_v_off(hoff, (size_t)vbeg, nhead * HD);
+  const unsigned vstep = (unsigned)(nhead * HD * KT2);                                          // halves per tile
+  const unsigned koff = (unsigned)(skr * HD + skc) * 2u;                                        // bytes inside a tile
+  const unsigned voff = (unsigned)attn_v_off(svr, (size_t)svc, nhead * HD) * 2u;
+  auto dma16 = [&](const _Float16* base, unsigned off, unsigned dst) __attribute__((always_inline)) {
+    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(off), "s"(base), "s"(dst)
                  : "memory", "m0");
   };
-  auto fetch = [&](int kt, int nbuf) {     // nbuf: the buffer tile kt will be read from
-    const unsigned koff = (unsigned)((((size_t)head * t_total + kbeg + min(kt + skr, klen - 1)) * HD + skc) * 2);
-    const unsigned voff = (unsigned)(attn_v_off(hoff + svr, (size_t)(vbeg + kt + svc), nhead * HD) * 2);
-    dma16(kh_g, koff, kdst_h + (unsigned)nbuf * 4096u);
-    if constexpr (H3) dma16(kl_g, koff, kdst_l + (unsigned)nbuf * 4096u);
-    dma16(vth_g, voff, vdst_h + (unsigned)nbuf * 4096u);
-    if constexpr (H3) dma16(vtl_g, voff, vdst_l + (unsigned)nbuf * 4096u);
+  auto fetch = [&](int kt, int nbuf, auto tail_tag) __attribute__((always_inline)) {   // nbuf: the buffer tile kt will be read from
+    const size_t kel = kbase + (size_t)(unsigned)kt * HD, vel = vbase + (size_t)((unsigned)kt / KT2) * vstep;
+    const _Float16 *kh_t = kh_g + kel, *kl_t = kl_g + kel, *vth_t = vth_g + vel, *vtl_t = vtl_g + vel;
+    const unsigned ko = decltype(tail_tag)::value ? (unsigned)(min(skr, klen - 1 - kt) * HD + skc) * 2u : koff;
+    dma16(kh_t, ko, kdst_h + (unsigned)nbuf * 4096u);
+    if constexpr (H3) dma16(kl_t, ko, kdst_l + (unsigned)nbuf * 4096u);
+    dma16(vth_t, voff, vdst_h + (unsigned)nbuf * 4096u);
+    if constexpr (H3) dma16(vtl_t, voff, vdst_l + (unsigned)nbuf * 4096u);
   };
-  auto stash = [&](int) {
+  // the fetch of the tile at kt, if there is one: full tiles never clamp
+  auto fetch_next = [&](int kt, int nbuf) __attribute__((always_inline)) {
+    if (kt + KT2 <= klen) fetch(kt, nbuf, std::false_type{});
+    else if (kt < klen) fetch(kt, nbuf, std::true_type{});
+  };
+  auto stash = [&]() {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's pieces of the next tile have landed
   };
 
@@ -465,7 +494,8 @@ __global__ __launch_bounds__(256, WPS) void k_attn_s(
   constexpr float kSumMax = 32768.f;  // a lane's tile sum below this: every probability inside fp16's range
   const float kSig = sig_thr;         // ADAPT: a probability below kSig x the lane's running sum needs no lo plane
 
-  auto tile = [&](int kt, int buf, auto tail_tag) {
+  // buf: an integral_constant in the steady state (LDS reads at immediate offsets); l31, lh: the lane's query and half
+  auto tile = [&](int kt, auto buf, auto tail_tag, int l31, int lh) {
     constexpr bool TAIL = decltype(tail_tag)::value;
     f32x16 sc[2];
     unsigned int ph_u[2][8], pl_u[2][8];
@@ -641,24 +671,56 @@ __global__ __launch_bounds__(256, WPS) void k_attn_s(
     }
   };
 
-  if (klen > 0) {
-    fetch(0, 0);
-    stash(0);
-  }
-  __syncthreads();
-  int buf = 0, kt = 0;
-  for (; kt + KT2 <= klen; kt += KT2, buf ^= 1) {
-    const bool more = kt + KT2 < klen;
-    // (the barrier at the end of the previous iteration: every wave has finished reading buffer buf ^ 1)
-    if (more) fetch(kt + KT2, buf ^ 1);
-    __builtin_amdgcn_sched_barrier(0);
-    tile(kt, buf, std::false_type{});
-    __builtin_amdgcn_sched_barrier(0);
-    if (more) stash(buf ^ 1);
+  // The key loop, unrolled by two so that the buffer index is a compile-time constant in the steady state: step(B) runs
+  // the full tile at kt out of buffer B while the DMA brings the next tile into buffer B ^ 1.  One barrier per tile: at
+  // the end of a step every wave has finished reading buffer B and has seen its own pieces of the next tile land.
+  auto key_loop = [&](auto work_tag) __attribute__((always_inline)) {
+    constexpr bool WORK = decltype(work_tag)::value;
+    int kt = 0;
+    fetch_next(0, 0);
+    stash();
     __syncthreads();
-  }
-  if (kt < klen) tile(kt, buf, std::true_type{});
+    auto step = [&](auto buf_tag) __attribute__((always_inline)) {
+      constexpr int B = decltype(buf_tag)::value;
+      if (kt + KT2 > klen) return false;
+      fetch_next(kt + KT2, B ^ 1);
+      __builtin_amdgcn_sched_barrier(0);
+      if constexpr (WORK) tile(kt, buf_tag, std::false_type{}, l31, lh);
+      __builtin_amdgcn_sched_barrier(0);
+      stash();
+      __syncthreads();
+      kt += KT2;
+      return true;
+    };
+    int buf = 0;
+    for (;;) {
+      if (!step(std::integral_constant<int, 0>{})) break;
+      buf = 1;
+      if (!step(std::integral_constant<int, 1>{})) break;
+      buf = 0;
+    }
+    if constexpr (WORK) {
+      if (kt < klen) {
+        // The tail tile reads its buffer through a run-time index.  Its lane id is opaque: the LDS read positions are
+        // formed again here, once -- otherwise the compiler forms a second set in front of the loop and spills it.
+        int tl = lane;
+        asm volatile("" : "+v"(tl));
+        tile(kt, buf, std::true_type{}, tl & 31, tl >> 5);
+      }
+    }
+  };
+  if (has_q) key_loop(std::true_type{});
+  else key_loop(std::false_type{});
 
+  if (!has_q) {
+    // tiled output (below): zeros for the wave's 32 padding rows -- finite, the chains compute on them and drop them
+    if (o_tiles != nullptr) {
+      float4* op = reinterpret_cast<float4*>(out) + ((size_t)(o_tiles[seg] + qt) * 4 + wave) * 2048 + lane;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) op[(4 * head + g) * 64] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    return;
+  }
   float l_run = psum;
   l_run += __shfl_xor(l_run, 32, 64);
   const int qi = q0 + wave * 32 + l31;
