@@ -39,6 +39,10 @@ extern "C" {
 #define SPR_ORDER_REFERENCE 0 /* libstdc++ unordered_map iteration order     */
 #define SPR_ORDER_CANONICAL 1 /* ascending (cloud, voxel key)                 */
 
+/* a2 selection rule: which `limit` of a query's supports in range a row keeps */
+#define SPR_SELECT_NEAREST 0 /* smallest (d2, index), ascending: cpp_neighbors */
+#define SPR_SELECT_INDEX 1   /* smallest indices, ascending: pytorch3d ball_query */
+
 int spr_version(void);
 const char* spr_last_error(void);
 
@@ -81,11 +85,22 @@ int spr_voxel_downsample(const float* xyz, int n, double voxel_size, int* out_id
  *   bounding boxes need more cells than the table holds -> retry with algo 1);
  * algo 1: sorted cell keys + binary search (no geometry limit besides 8191
  *   cells per axis, *max_count = -1).  Results are identical.
+ * select: the rule that cuts a row with more than `limit` supports in range.
+ *   SPR_SELECT_NEAREST keeps the `limit` nearest as described above (the
+ *   reference's CPU Preprocessor).  SPR_SELECT_INDEX keeps the `limit` LOWEST
+ *   support indices in range, ascending, padded with ns: the rows of the
+ *   reference's PreprocessorGPU (batch_neighbors_kpconv_gpu, kpconv.py:265-292
+ *   -> pytorch3d.ops.ball_query, the first K supports in index order).  The
+ *   candidates are the same under both rules -- the same float32 d2, the same
+ *   strict d2 < r*r -- and so is *max_count (the untruncated count, with its
+ *   -1 / -2 codes); rows with at most `limit` supports in range hold the same
+ *   set under both.  Any other value is an error.  Both algos and every algo
+ *   of spr_radius_table_query give identical rows under either rule.
  */
 size_t spr_radius_neighbors_workspace_bytes(int nq, int ns, int nb);
 int spr_radius_neighbors(const float* q_xyz, const int* q_cu, int nq,
                          const float* s_xyz, const int* s_cu, int ns, int nb,
-                         float radius, int limit, int algo, int* out_idx,
+                         float radius, int limit, int algo, int select, int* out_idx,
                          int* max_count, void* ws, size_t ws_bytes, void* stream);
 
 /* Cell table of spr_radius_neighbors (algo 0) as an object: built once per (supports, radius),
@@ -100,6 +115,7 @@ int spr_radius_neighbors(const float* q_xyz, const int* q_cu, int nq,
  *   row + rank sort in registers; cheaper for sparse rows), 1: one wave per query (one pass over the coalesced
  *   record runs, the row kept sorted in the wave's registers, no scratch, no sort kernel; faster when more
  *   supports lie in range than `limit`: LiDAR-shaped clouds), -1: the library's choice.  Identical rows.
+ *   select as in spr_radius_neighbors; one table serves queries under either rule.
  */
 size_t spr_radius_table_bytes(int ns, int nb);
 size_t spr_radius_table_build_workspace_bytes(int ns, int nb);
@@ -109,7 +125,7 @@ int spr_radius_table_build(const float* s_xyz, const int* s_cu, int ns, int nb, 
                            void* table, size_t table_bytes, void* ws, size_t ws_bytes, void* stream);
 int spr_radius_table_query(const float* q_xyz, const int* q_cu, int nq, int self, int ns, int nb,
                            float radius, int limit, int slot, const void* table, int* out_idx,
-                           int* max_count, int algo, void* ws, size_t ws_bytes, void* stream);
+                           int* max_count, int algo, int select, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- 8f-5: ground-truth overlap masks and mutual correspondences ---------------
  * Replaces compute_overlap(src, tgt, search_voxel_size) (utils/pointcloud.py:8-65: one Open3D kd-tree radius query

@@ -39,6 +39,9 @@ _COMMON = dict(
     transformer_encoder_has_pos_emb=True, sa_val_has_pos_emb=True, ca_val_has_pos_emb=True,
     pos_emb_type='sine', feature_loss_type='infonce', wt_feature=0.1, wt_feature_un=0.0,
     wt_overlap=1.0, wt_corr=1.0,
+    # which supports a neighbour row keeps when more than the level's limit lie in range: 'nearest' (the reference's
+    # CPU Preprocessor, cpp_neighbors) or 'index' (its PreprocessorGPU: pytorch3d ball_query, lowest indices first)
+    neighbor_select='nearest',
     # solver section of the YAML files (read by training.configure_optimizers / Trainer)
     optimizer='AdamW', base_lr=0.0001, weight_decay=0.0001, grad_clip=0.1, scheduler='step',
     scheduler_param=[127800, 0.5], reg_success_thresh_rot=10, reg_success_thresh_trans=0.1,

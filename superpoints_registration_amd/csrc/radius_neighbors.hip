@@ -25,6 +25,14 @@
 // scan + sort kernel pair -- see "Fast path" below.  Both give identical rows.
 // Ties: the reference's std::sort leaves equal-d2 runs in kd-tree visit order;
 // this kernel orders them by index (documented; tests canonicalise tie runs).
+//
+// Selection rule (template parameter SEL of every selecting kernel).  The candidates of a query are always the
+// supports with d2 < r2 above; the rule only decides which `limit` of them a row keeps and in what order:
+//   SPR_SELECT_NEAREST  the `limit` smallest (d2, index), ascending -- the contract above;
+//   SPR_SELECT_INDEX    the `limit` smallest indices, ascending: the rows of the reference's PreprocessorGPU
+//                       (kpconv.py:265-292, pytorch3d.ops.ball_query: the first K supports in index order).
+// Records arrive in cell order, so the index rule is a selection like the other one: the same kernels run with the
+// support index alone as the ordered part of the packed u64 key (sel_key).  The default instantiations are unchanged.
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -106,8 +114,9 @@ __device__ __forceinline__ bool nbr_less(float d2a, int ia, float d2b, int ib) {
   return (d2a < d2b) || (d2a == d2b && ia < ib);
 }
 
-// Dynamic LDS: float d2[limit][BLOCK], int id[limit][BLOCK].
-template <int BLOCK>
+// Dynamic LDS: float d2[limit][BLOCK], int id[limit][BLOCK].  SEL != 0 (index rule): every entry ranks with
+// d2 = 0, so nbr_less orders by index alone.
+template <int BLOCK, int SEL>
 __global__ __launch_bounds__(BLOCK) void k_query(
     const float* __restrict__ q_xyz, const int* __restrict__ q_cu, int nq,
     const int* __restrict__ s_cu, int ns, int nb, const NbrCloud* __restrict__ info,
@@ -159,6 +168,7 @@ __global__ __launch_bounds__(BLOCK) void k_query(
             d2 = __fadd_rn(d2, __fmul_rn(dzz, dzz));
             if (d2 < r2) {  // strict, nanoflann.hpp:249
               total++;
+              if (SEL) d2 = 0.f;   // in range is decided; from here d2 is only the ranking key
               const int sid = __float_as_int(s.w);
               int pos;
               if (kept < limit) {
@@ -215,6 +225,7 @@ struct GridCloud {
   float mn[3];
   int dim[3];
   long long off;  // first cell of this cloud in the table
+  int beg, len;   // the cloud's supports are [beg, beg + len): the index rule's histogram bins span them
 };
 
 __global__ __launch_bounds__(256) void k_grid_dims(const float* __restrict__ xyz,
@@ -259,6 +270,8 @@ __global__ __launch_bounds__(256) void k_grid_dims(const float* __restrict__ xyz
       g.dim[d] = n;
     }
     g.off = 0;
+    g.beg = beg;
+    g.len = end - beg;
     info[c] = g;
   }
 }
@@ -428,9 +441,16 @@ __device__ __forceinline__ unsigned long long nbr_key(float d2, int id) {
   return ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)id;
 }
 
+// the key a selection rule ranks by; its low word is the support index under either rule
+template <int SEL>
+__device__ __forceinline__ unsigned long long sel_key(float d2, int id) {
+  return SEL ? (unsigned long long)(unsigned)id : nbr_key(d2, id);
+}
+
 // scratch-row capacity: twice the row width, at most 128 (LDS of k_sort_rows)
 static inline int nbr_row_cap(int limit) { return limit * 2 < 128 ? limit * 2 : 128; }
 
+template <int SEL>
 __global__ __launch_bounds__(256) void k_scan_table(
     const float* __restrict__ q_xyz, const int* __restrict__ q_cu, int nq, int nb,
     const GridCloud* __restrict__ info, const int* __restrict__ start,
@@ -483,6 +503,9 @@ __global__ __launch_bounds__(256) void k_scan_table(
     // in-range candidates in kBins equal bins (per-thread counters in LDS); the bin in which the
     // cumulative count reaches `limit` gives a radius that still contains the `limit` nearest, and
     // the second pass collects only what lies inside it.
+    // Index rule: the bins are over the support's index inside its cloud instead (kBins equal ranges of
+    // [0, len)): monotone in the key, so the bin in which the cumulative count reaches `limit` still bounds
+    // the `limit` smallest keys.
     // slot-major scratch: entry k of thread t at tmp_key[k * nq + t] -- the lanes of a wave append to
     // neighbouring addresses, and k_sort_rows reads every slot as one coalesced line per wave
     // (row-major rows of cap * 8 bytes cost one cache line per lane and load)
@@ -491,7 +514,7 @@ __global__ __launch_bounds__(256) void k_scan_table(
     int kept = 0;
     unsigned long long worst = 0;   // largest key among the kept entries
     int w_pos = 0;
-    const float bin_scale = (float)kBins / r2;
+    const float bin_scale = SEL ? (float)kBins / (float)max(g.len, 1) : (float)kBins / r2;
     unsigned short* my_hist = l_hist + threadIdx.x;          // [kBins][256] u16, one column per thread
 #pragma unroll
     for (int b = 0; b < kBins; ++b) my_hist[b * 256] = 0;
@@ -504,7 +527,7 @@ __global__ __launch_bounds__(256) void k_scan_table(
       d2 = __fadd_rn(d2, __fmul_rn(dy, dy));
       d2 = __fadd_rn(d2, __fmul_rn(dz, dz));
       if (!(d2 < r2)) return;  // strict, nanoflann.hpp:249
-      const int bin = min((int)(d2 * bin_scale), kBins - 1);
+      const int bin = min((int)((SEL ? (float)(__float_as_int(s.w) - g.beg) : d2) * bin_scale), kBins - 1);
       if (!second) {
         total++;
         // saturating 16-bit counter: the cut below only asks whether the cumulative count reaches
@@ -512,11 +535,11 @@ __global__ __launch_bounds__(256) void k_scan_table(
         // (tens of thousands of returns inside one radius) must not wrap it
         const unsigned short h = my_hist[bin * 256];
         my_hist[bin * 256] = h == 65535 ? h : (unsigned short)(h + 1);
-        if (kept < cap) row[rs * kept++] = nbr_key(d2, __float_as_int(s.w));
+        if (kept < cap) row[rs * kept++] = sel_key<SEL>(d2, __float_as_int(s.w));
         return;
       }
       if (bin > cut_bin) return;
-      const unsigned long long key = nbr_key(d2, __float_as_int(s.w));
+      const unsigned long long key = sel_key<SEL>(d2, __float_as_int(s.w));
       if (kept < cap) {
         row[rs * kept] = key;
         if (kept == 0 || key > worst) {
@@ -671,7 +694,7 @@ __device__ __forceinline__ unsigned long long readlane_u64(unsigned long long v,
   return ((unsigned long long)hi << 32) | lo;
 }
 
-template <bool BIG>
+template <bool BIG, int SEL>
 __global__ __launch_bounds__(256) void k_knn_wave(
     const float* __restrict__ q_xyz, const int* __restrict__ q_cu, int nq, int nb,
     const GridCloud* __restrict__ info, const int* __restrict__ start, const float4* __restrict__ rec,
@@ -764,7 +787,7 @@ __global__ __launch_bounds__(256) void k_knn_wave(
         d2 = __fadd_rn(d2, __fmul_rn(dy, dy));
         d2 = __fadd_rn(d2, __fmul_rn(dz, dz));
         bool in = valid && d2 < r2;       // strict, nanoflann.hpp:249
-        const unsigned long long key = nbr_key(d2, __float_as_int(sp.w));
+        const unsigned long long key = sel_key<SEL>(d2, __float_as_int(sp.w));
         unsigned long long m = __builtin_amdgcn_ballot_w64(in);
         total += __popcll(m);
         if (cnt == limit) {               // full: only what beats the current last entry can enter
@@ -931,7 +954,7 @@ int table_build(const float* s_xyz, const int* s_cu, int ns, int nb, float radiu
 // identical either way.
 int table_query(const float* q_xyz, const int* q_cu, int nq, int self, int ns, int nb, float radius, int limit,
                 int slot, const void* blob, int* out_idx, int* max_count, void* ws, size_t ws_bytes,
-                hipStream_t stream, int algo = -1) {
+                hipStream_t stream, int algo = -1, int select = SPR_SELECT_NEAREST) {
   const TableView t = table_view(const_cast<void*>(blob), ns, nb);
   Workspace w(ws, ws_bytes);
   // limits up to kRegRows: the scratch rows are capped there and sorted in registers (k_sort_rows_reg); a query with
@@ -948,17 +971,18 @@ int table_query(const float* q_xyz, const int* q_cu, int nq, int self, int ns, i
   if (algo == 1) {   // the one-pass wave-per-query selection instead of scan + rank sort
     SPR_HIP_CHECK(hipMemsetAsync(qid, 0, sizeof(int), stream));
     const int nblk = min(cdiv(nq, 4 * kKnnChunk), 8 * device_cu_count());
-    if (limit <= 64)
-      hipLaunchKernelGGL(k_knn_wave<false>, dim3(nblk), dim3(256), 0, stream, q_xyz, q_cu, nq, nb, t.ginfo, t.start, t.rec,
-                         t.hdr + kHdrErr, r2, inv_cell, limit, self, ns, out_idx, t.hdr + kHdrSlot0 + slot, qid);
-    else
-      hipLaunchKernelGGL(k_knn_wave<true>, dim3(nblk), dim3(256), 0, stream, q_xyz, q_cu, nq, nb, t.ginfo, t.start, t.rec,
-                         t.hdr + kHdrErr, r2, inv_cell, limit, self, ns, out_idx, t.hdr + kHdrSlot0 + slot, qid);
+    const bool idx = select == SPR_SELECT_INDEX;
+    const auto knn = limit <= 64 ? (idx ? k_knn_wave<false, 1> : k_knn_wave<false, 0>)
+                                 : (idx ? k_knn_wave<true, 1> : k_knn_wave<true, 0>);
+    hipLaunchKernelGGL(knn, dim3(nblk), dim3(256), 0, stream, q_xyz, q_cu, nq, nb, t.ginfo, t.start, t.rec,
+                       t.hdr + kHdrErr, r2, inv_cell, limit, self, ns, out_idx, t.hdr + kHdrSlot0 + slot, qid);
     hipLaunchKernelGGL(k_nbr_err2, dim3(1), dim3(1), 0, stream, t.hdr, slot, max_count);
     SPR_LAUNCH_CHECK();
     return 0;
   }
-  hipLaunchKernelGGL(k_scan_table, dim3(cdiv(nq, 256)), dim3(256), 0, stream, q_xyz, q_cu, nq, nb, t.ginfo, t.start,
+  // the rank sorts below order whatever keys the scan packed: they serve both rules as they are
+  const auto scan = select == SPR_SELECT_INDEX ? k_scan_table<1> : k_scan_table<0>;
+  hipLaunchKernelGGL(scan, dim3(cdiv(nq, 256)), dim3(256), 0, stream, q_xyz, q_cu, nq, nb, t.ginfo, t.start,
                      t.rec, t.hdr + kHdrErr, r2, inv_cell, rcap, limit, self, tmp_key, kept, qid, t.hdr + kHdrSlot0 + slot);
   if (use_reg) {
     hipLaunchKernelGGL(k_sort_rows_reg<kRegRows>, dim3(cdiv(nq, 256)), dim3(256), 0, stream, tmp_key, kept, qid,
@@ -1010,9 +1034,11 @@ extern "C" size_t spr_radius_neighbors_workspace_bytes(int nq, int ns, int nb) {
 
 extern "C" int spr_radius_neighbors(const float* q_xyz, const int* q_cu, int nq,
                                     const float* s_xyz, const int* s_cu, int ns, int nb,
-                                    float radius, int limit, int algo, int* out_idx,
+                                    float radius, int limit, int algo, int select, int* out_idx,
                                     int* max_count, void* ws, size_t ws_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
+  SPR_REQUIRE(select == SPR_SELECT_NEAREST || select == SPR_SELECT_INDEX,
+              "radius_neighbors: select must be SPR_SELECT_NEAREST (0) or SPR_SELECT_INDEX (1), got %d", select);
   SPR_REQUIRE(nq > 0 && ns > 0 && nb >= 1, "radius_neighbors: empty input (nq=%d ns=%d)", nq, ns);
   SPR_REQUIRE(nb < 65536, "radius_neighbors: at most 65535 clouds per call");
   SPR_REQUIRE(radius > 0.f, "radius_neighbors: radius must be > 0");
@@ -1041,7 +1067,7 @@ extern "C" int spr_radius_neighbors(const float* q_xyz, const int* q_cu, int nq,
     SPR_REQUIRE(w.ok() && query_ws != nullptr, "radius_neighbors: workspace carve failed (table)");
     if (int rc = table_build(s_xyz, s_cu, ns, nb, radius, blob, build_ws, bws, stream)) return rc;
     return table_query(q_xyz, q_cu, nq, (q_xyz == s_xyz && q_cu == s_cu && nq == ns) ? 1 : 0, ns, nb, radius, limit, 0,
-                       blob, out_idx, max_count, query_ws, qws, stream);
+                       blob, out_idx, max_count, query_ws, qws, stream, -1, select);
   }
   const float r2 = radius * radius;  // neighbors.cpp:226 (float32)
   const float inv_cell = 1.0f / (radius * (1.0f + 1.0f / 256.0f));
@@ -1056,18 +1082,19 @@ extern "C" int spr_radius_neighbors(const float* q_xyz, const int* q_cu, int nq,
                                           (unsigned int)ns, 0, 64, stream));
   hipLaunchKernelGGL(k_gather_sorted, dim3(cdiv(ns, TB)), dim3(TB), 0, stream, s_xyz, vals2, ns,
                      rec);
+  const bool idx = select == SPR_SELECT_INDEX;
   if (limit <= 64) {
     constexpr int BLOCK = 128;
     const size_t lds = (size_t)limit * BLOCK * 8;
-    hipLaunchKernelGGL(k_query<BLOCK>, dim3(cdiv(nq, BLOCK)), dim3(BLOCK), lds, stream, q_xyz,
-                       q_cu, nq, s_cu, ns, nb, info, keys2, rec, r2, inv_cell, limit, out_idx,
-                       max_count);
+    const auto query = idx ? k_query<BLOCK, 1> : k_query<BLOCK, 0>;
+    hipLaunchKernelGGL(query, dim3(cdiv(nq, BLOCK)), dim3(BLOCK), lds, stream,
+                       q_xyz, q_cu, nq, s_cu, ns, nb, info, keys2, rec, r2, inv_cell, limit, out_idx, max_count);
   } else {
     constexpr int BLOCK = 64;
     const size_t lds = (size_t)limit * BLOCK * 8;
-    hipLaunchKernelGGL(k_query<BLOCK>, dim3(cdiv(nq, BLOCK)), dim3(BLOCK), lds, stream, q_xyz,
-                       q_cu, nq, s_cu, ns, nb, info, keys2, rec, r2, inv_cell, limit, out_idx,
-                       max_count);
+    const auto query = idx ? k_query<BLOCK, 1> : k_query<BLOCK, 0>;
+    hipLaunchKernelGGL(query, dim3(cdiv(nq, BLOCK)), dim3(BLOCK), lds, stream,
+                       q_xyz, q_cu, nq, s_cu, ns, nb, info, keys2, rec, r2, inv_cell, limit, out_idx, max_count);
   }
   hipLaunchKernelGGL(k_nbr_err, dim3(1), dim3(1), 0, stream, err, max_count);
   SPR_LAUNCH_CHECK();
@@ -1096,9 +1123,13 @@ extern "C" int spr_radius_table_build(const float* s_xyz, const int* s_cu, int n
 // algo, the selection algorithm: 0 = one thread per query (scan of its 27 cells into a scratch row + rank sort in
 // registers: the cheaper one for sparse rows), 1 = one wave per query (one pass, the row in registers, no scratch: the
 // faster one when rows are dense -- more supports in range than `limit`), -1 = the library's choice.
+// select: which `limit` of the supports in range a row keeps (see the head of this file); every algo honours it.
 extern "C" int spr_radius_table_query(const float* q_xyz, const int* q_cu, int nq, int self, int ns, int nb,
                                       float radius, int limit, int slot, const void* table, int* out_idx,
-                                      int* max_count, int algo, void* ws, size_t ws_bytes, void* stream_) {
+                                      int* max_count, int algo, int select, void* ws, size_t ws_bytes,
+                                      void* stream_) {
+  SPR_REQUIRE(select == SPR_SELECT_NEAREST || select == SPR_SELECT_INDEX,
+              "radius_table_query: select must be SPR_SELECT_NEAREST (0) or SPR_SELECT_INDEX (1), got %d", select);
   SPR_REQUIRE(q_xyz && q_cu && table && out_idx && max_count && nq > 0 && ns > 0 && nb >= 1, "radius_table_query: bad arguments");
   SPR_REQUIRE(limit >= 1 && limit <= 128, "radius_table_query: limit must be in [1,128], got %d", limit);
   SPR_REQUIRE(slot >= 0 && slot < kTableSlots, "radius_table_query: slot out of range");
@@ -1107,5 +1138,5 @@ extern "C" int spr_radius_table_query(const float* q_xyz, const int* q_cu, int n
               "radius_table_query: algo must be 0 (thread per query), 1 (wave per query) or -1 (the library's choice)");
   SPR_REQUIRE(ws != nullptr && ws_bytes >= table_query_ws_bytes(nq), "radius_table_query: workspace too small");
   return table_query(q_xyz, q_cu, nq, self ? 1 : 0, ns, nb, radius, limit, slot, table, out_idx, max_count, ws, ws_bytes,
-                     (hipStream_t)stream_, algo);
+                     (hipStream_t)stream_, algo, select);
 }

@@ -100,7 +100,7 @@ class cpp_neighbors:
         q_cu, s_cu = _cu(q_batches, dev), _cu(s_batches, dev)   # both alive until the results are read back
         for algo in (0, 1):                  # 0 = cell table, 1 = sorted keys (no geometry limit)
             rc = L.spr_radius_neighbors(_p(q), _p(q_cu), nq, _p(s), _p(s_cu), ns, nb,
-                                        ctypes.c_float(radius), int(limit), algo, _p(out), _p(mc), _p(ws),
+                                        ctypes.c_float(radius), int(limit), algo, 0, _p(out), _p(mc), _p(ws),
                                         ctypes.c_size_t(ws.numel()), _stream(dev))
             if rc:
                 _raise(L)

@@ -9,7 +9,16 @@ The pinned contract is the reference's CPU ``Preprocessor`` (its C++
 extensions): identical point order at every level, bit-exact barycentres and
 neighbour indices.  The reference's ``PreprocessorGPU`` depends on
 MinkowskiEngine + PyTorch3D (not vendored, no runnable oracle); here both
-names resolve to the same HIP implementation.
+names resolve to the same HIP implementation, with the CPU semantics by default.
+
+``neighbor_select='index'`` (argument of Preprocessor / PreprocessorGPU, key of
+the config, ``select=ops.SELECT_INDEX`` of batch_neighbors_kpconv) gives the
+neighbour rows of the reference's GPU path instead (batch_neighbors_kpconv_gpu,
+kpconv.py:265-292 -> pytorch3d.ops.ball_query): per query the K =
+neighborhood_limits[level] LOWEST support indices with d2 < r2, ascending,
+always K columns, padded with the shadow index.  The two rules keep different
+points wherever more than K supports lie in range.  Subsampling keeps the C++
+semantics under either rule (MinkowskiEngine's output order is undefined).
 
 Structure differs from the reference: the architecture string list is parsed
 ONCE into a pyramid plan (`plan_pyramid`) that both the encoder and the
@@ -23,6 +32,8 @@ import torch.nn as nn
 
 from . import ops
 from .kpconv_blocks import block_decider
+
+NEIGHBOR_SELECT = {'nearest': ops.SELECT_NEAREST, 'index': ops.SELECT_INDEX}
 
 _DOWN = ('pool', 'strided')
 _STOP = ('global', 'upsample')
@@ -140,14 +151,17 @@ def batch_grid_subsampling_kpconv(points, batches_len, features=None, labels=Non
                               max_p=max_p, order=order)
 
 
-def batch_neighbors_kpconv(queries, supports, q_batches, s_batches, radius, max_neighbors):
+def batch_neighbors_kpconv(queries, supports, q_batches, s_batches, radius, max_neighbors,
+                           select=ops.SELECT_NEAREST):
     """Replaces cpp_neighbors.batch_query + the column slice (kpconv.py:247-262).
-    Returns int32 [Nq, min(max_count, max_neighbors)], shadow index = Ns."""
+    Returns int32 [Nq, min(max_count, max_neighbors)], shadow index = Ns.
+    select=ops.SELECT_INDEX: the rows of batch_neighbors_kpconv_gpu (kpconv.py:265-292) instead -- the
+    max_neighbors lowest support indices in range, ascending, always max_neighbors columns."""
     limit = int(max_neighbors) if max_neighbors > 0 else 128
     idx, _ = ops.radius_neighbors(queries, supports,
                                   ops.lengths_to_cu(q_batches, queries.device),
                                   ops.lengths_to_cu(s_batches, queries.device),
-                                  radius, limit, exact_width=True)
+                                  radius, limit, exact_width=True, select=select)
     return idx
 
 
@@ -197,12 +211,24 @@ class Preprocessor(nn.Module):
     order=ops.ORDER_CANONICAL emits subsampled points in ascending voxel-key
     order instead of the reference's hash-map order (better gather locality;
     poses agree to rounding, indices are a relabelling).
+    neighbor_select: 'nearest' (default: the reference's CPU Preprocessor -- the
+    limit nearest supports, by distance, sliced to the widest row) or 'index'
+    (the reference's PreprocessorGPU, which RegTR.__init__ of the reference
+    hard-wires, qk_regtr_full.py:40: the limit lowest support indices in range,
+    ascending, always limit columns); None reads cfg.neighbor_select.  It
+    applies to the conv, pool and up-sampling searches; points and lengths do
+    not depend on it.
     """
 
     def __init__(self, cfg, compute_upsamples=True, order=ops.ORDER_REFERENCE,
-                 index_dtype=torch.int64):
+                 index_dtype=torch.int64, neighbor_select=None):
         super().__init__()
         self.cfg = cfg
+        if neighbor_select is None:
+            neighbor_select = cfg.get('neighbor_select', 'nearest')
+        if neighbor_select not in NEIGHBOR_SELECT:
+            raise ValueError(f"neighbor_select must be 'nearest' or 'index', got {neighbor_select!r}")
+        self.neighbor_select = neighbor_select
         self.compute_upsamples = compute_upsamples
         self.order = order
         self.index_dtype = index_dtype
@@ -262,10 +288,12 @@ class Preprocessor(nn.Module):
             if table[0] is None or not table[0].matches(supports, s_cu, radius):
                 table[0] = ops.RadiusTable(supports, s_cu, radius)
             prev = self._row_counts.get(key)
-            idx, m = table[0].query(queries, q_cu, limit, dense=None if prev is None else prev > 1.5 * limit)
+            idx, m = table[0].query(queries, q_cu, limit, dense=None if prev is None else prev > 1.5 * limit,
+                                    select=select)
             self._row_counts[key] = m
             return idx
 
+        select = NEIGHBOR_SELECT[self.neighbor_select]
         cu = ops.lengths_to_cu(lens_host, device)
         open_level(0, points, lens_host, cu)
         for l, lv in enumerate(levels):
@@ -296,4 +324,6 @@ class Preprocessor(nn.Module):
             yield meta, 'down', l
 
 
-PreprocessorGPU = Preprocessor  # kpconv.py:421
+# kpconv.py:421.  The name keeps the CPU semantics by default, like every caller of it has had so far; the neighbour
+# rows the reference's class of this name computes are PreprocessorGPU(cfg, neighbor_select='index').
+PreprocessorGPU = Preprocessor

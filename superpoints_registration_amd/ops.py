@@ -16,6 +16,9 @@ from . import _lib
 
 ACT_NONE, ACT_RELU, ACT_SIGMOID = 0, 1, 2
 ORDER_REFERENCE, ORDER_CANONICAL = 0, 1
+# which `limit` supports in range a neighbour row keeps (SPR_SELECT_*): the nearest (the reference's CPU Preprocessor)
+# or the lowest indices (its PreprocessorGPU: pytorch3d.ops.ball_query)
+SELECT_NEAREST, SELECT_INDEX = 0, 1
 
 
 def _stream(t: torch.Tensor):
@@ -283,10 +286,14 @@ def voxel_downsample(points: torch.Tensor, voxel_size: float) -> torch.Tensor:
 
 def radius_neighbors(queries: torch.Tensor, supports: torch.Tensor, q_cu: torch.Tensor,
                      s_cu: torch.Tensor, radius: float, limit: int,
-                     exact_width: bool = True, algo: int = 0) -> Tuple[torch.Tensor, int]:
+                     exact_width: bool = True, algo: int = 0,
+                     select: int = SELECT_NEAREST) -> Tuple[torch.Tensor, int]:
     """a2.  int32 [Nq, W] neighbour indices (shadow = Ns) and the untruncated
     max count.  exact_width=True slices to W = min(max_count, limit) like the
-    reference (one device->host read); False keeps W = limit (no sync)."""
+    reference (one device->host read); False keeps W = limit (no sync).
+    select=SELECT_INDEX keeps the `limit` lowest support indices in range, ascending, instead of the `limit`
+    nearest (the reference's batch_neighbors_kpconv_gpu, kpconv.py:265-292): W = limit always, and a search
+    without a single neighbour is not an error there."""
     queries = _dev(queries, "queries", torch.float32)
     supports = _dev(supports, "supports", torch.float32)
     q_cu = _dev(q_cu, "q_cu", torch.int32)
@@ -297,15 +304,17 @@ def radius_neighbors(queries: torch.Tensor, supports: torch.Tensor, q_cu: torch.
     out = torch.empty((nq, limit), dtype=torch.int32, device=queries.device)
     mc = torch.empty((1,), dtype=torch.int32, device=queries.device)
     _lib.check(L.spr_radius_neighbors(_ptr(queries), _ptr(q_cu), nq, _ptr(supports), _ptr(s_cu), ns,
-                                      nb, float(radius), int(limit), int(algo), _ptr(out), _ptr(mc),
-                                      _ptr(ws), ws.numel(), _stream(queries)), "spr_radius_neighbors")
+                                      nb, float(radius), int(limit), int(algo), int(select), _ptr(out),
+                                      _ptr(mc), _ptr(ws), ws.numel(), _stream(queries)), "spr_radius_neighbors")
     if not exact_width:
         return out, -1
     m = int(mc.item())
     if m == -2 and algo == 0:   # cell table too small for this geometry: exact same result, slower path
-        return radius_neighbors(queries, supports, q_cu, s_cu, radius, limit, exact_width, algo=1)
+        return radius_neighbors(queries, supports, q_cu, s_cu, radius, limit, exact_width, algo=1, select=select)
     if m < 0:
         raise RuntimeError("spr_radius_neighbors: cloud extent / radius exceeds 8191 cells per axis")
+    if select == SELECT_INDEX:  # kpconv.py:284-292: K columns whatever the counts, no emptiness check
+        return out, m
     if m < 1:  # cpp_neighbors/wrapper.cpp:201-205
         raise RuntimeError("Error")
     return out[:, :min(m, limit)], m
@@ -520,8 +529,9 @@ class RadiusTable:
                 and supports.shape[0] == self.ns and float(radius) == self.radius and self._slot < self._slots)
 
     def query(self, queries: torch.Tensor, q_cu: torch.Tensor, limit: int,
-              dense: Optional[bool] = None) -> Tuple[torch.Tensor, int]:
-        """int32 [Nq, min(max_count, limit)] and the untruncated max count, like radius_neighbors.
+              dense: Optional[bool] = None, select: int = SELECT_NEAREST) -> Tuple[torch.Tensor, int]:
+        """int32 [Nq, min(max_count, limit)] and the untruncated max count, like radius_neighbors
+        (select=SELECT_INDEX: [Nq, limit], the lowest indices in range; one table serves both rules).
         dense: True -> one wave per query (one pass, no scratch: faster when more supports lie in range than
         `limit`), False -> one thread per query (cheaper for sparse rows), None -> the library's default.  Same rows."""
         queries = _dev(queries, "queries", torch.float32)
@@ -536,13 +546,16 @@ class RadiusTable:
         slot, self._slot = self._slot, self._slot + 1
         _lib.check(L.spr_radius_table_query(_ptr(queries), _ptr(q_cu), nq, self_search, self.ns, self.nb, self.radius,
                                             int(limit), slot, _ptr(self.blob), _ptr(out), _ptr(mc),
-                                            -1 if dense is None else int(bool(dense)), _ptr(ws), ws.numel(),
-                                            _stream(queries)), "spr_radius_table_query")
+                                            -1 if dense is None else int(bool(dense)), int(select), _ptr(ws),
+                                            ws.numel(), _stream(queries)), "spr_radius_table_query")
         m = int(mc.item())
         if m == -2:     # cell table too small for this geometry: exact same result, slower path
-            return radius_neighbors(queries, self.supports, q_cu, self.s_cu, self.radius, limit, True, algo=1)
+            return radius_neighbors(queries, self.supports, q_cu, self.s_cu, self.radius, limit, True, algo=1,
+                                    select=select)
         if m < 0:
             raise RuntimeError("spr_radius_neighbors: cloud extent / radius exceeds 8191 cells per axis")
+        if select == SELECT_INDEX:
+            return out, m
         if m < 1:  # cpp_neighbors/wrapper.cpp:201-205
             raise RuntimeError("Error")
         return out[:, :min(m, limit)], m

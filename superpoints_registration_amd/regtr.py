@@ -29,7 +29,7 @@ import torch
 import torch.nn as nn
 
 from . import _concurrency, ops
-from .kpconv import KPFEncoder, Preprocessor
+from .kpconv import NEIGHBOR_SELECT, KPFEncoder, Preprocessor
 from .transformers import (PositionEmbeddingCoordsSine, PositionEmbeddingLearned, TransformerCrossEncoder,
                            TransformerCrossEncoderLayer, make_segments)
 
@@ -122,8 +122,12 @@ class RegTR(nn.Module):
                                           "ValueError in the reference itself, qk_regtr_full.py:505-511)")
         if cfg.get('pos_emb_type', 'sine') not in ('sine', 'learned'):
             raise NotImplementedError("pos_emb_type must be 'sine' or 'learned' (qk_regtr_full.py:52-58)")
+        if cfg.get('neighbor_select', 'nearest') not in NEIGHBOR_SELECT:
+            raise NotImplementedError("neighbor_select must be 'nearest' (the reference's CPU Preprocessor) or "
+                                      "'index' (its PreprocessorGPU, kpconv.py:265-292)")
 
-        self.preprocessor = Preprocessor(cfg, compute_upsamples=compute_upsamples, order=order)
+        self.preprocessor = Preprocessor(cfg, compute_upsamples=compute_upsamples, order=order,
+                                         neighbor_select=cfg.get('neighbor_select', 'nearest'))
         self.kpf_encoder = KPFEncoder(cfg, cfg.d_embed)
         self.feat_proj = nn.Linear(self.kpf_encoder.encoder_skip_dims[-1], cfg.d_embed, bias=True)
         if cfg.get('pos_emb_type', 'sine') == 'sine':
