@@ -52,6 +52,10 @@ const char* spr_last_error(void);
  *  grid_subsampling/grid_subsampling.cpp:109 batch_grid_subsampling), called
  * from models/backbone_kpconv/kpconv.py:174-185 (and the GPU variant :217).
  * Barycentres are bit-exact float32 (in-order sum * (float)(1.0/count)).
+ * Voxel keys are the reference's size_t keys, also for a point below the grid
+ * origin (the float32 origin can round to one ulp above the cloud's minimum):
+ * cell index -1, key arithmetic modulo 2^64.  SPR_ORDER_CANONICAL orders by
+ * that 64-bit key.  *out_total = -1: the grid needs keys beyond 2^40.
  *   xyz      [n,3] f32        cu [nb+1] i32
  *   out_xyz  [n,3] f32 (first *out_total rows valid)
  *   out_lens [nb] i32         out_total [1] i32 (both device)

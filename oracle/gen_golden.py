@@ -565,6 +565,36 @@ def gen_shim():
     print(os.path.basename(path), os.path.getsize(path) // 1024, 'KB')
 
 
+def gen_preprocess_edges():
+    """tests/golden/preprocess_edges.npz: what the reference's own C++ (oracle/_ref) makes of the edge inputs of
+    tests/preprocess_edge_cases.py.  Subsampling: per cloud its length, the SHA-256 of its output bytes and its rows
+    (whole up to 2 358 voxels, else the first and last 64).  Radius search: the reference's neighbour rows."""
+    sys.path.insert(0, os.path.join(REPO, 'tests'))
+    import preprocess_edge_cases as pe
+    fx = {}
+    cases = pe.sub_cases()
+    assert list(cases) == pe.SUB_NAMES
+    for name, c in cases.items():
+        sub, sub_lens = native.ref_grid_subsample(c.pts, c.lens, c.dl, c.max_p)
+        fx.update(pe.pack_sub(name, sub, sub_lens))
+    # the constructions hold what they promise
+    for m in pe.S2_COUNTS:
+        assert fx[f's2.m{m}.sub_lens'].tolist() == [m], m
+    assert fx['s2.batch.sub_lens'].tolist() == list(pe.S2_COUNTS)
+    assert fx['s2.batch.reversed.sub_lens'].tolist() == list(pe.S2_COUNTS[::-1])
+    for k in pe.S6_MAX_P:
+        assert fx[f's2.batch.max_p{k}.sub_lens'].tolist() == [min(m, k) for m in pe.S2_COUNTS]
+    print('max_p totals', [int(fx[f's2.batch.max_p{k}.sub_lens'].sum()) for k in pe.S6_MAX_P])
+    for c in pe.s7_cases():
+        print(c.name, 'reference voxels:', native.ref_grid_subsample(c.pts, c.lens, c.dl)[1].tolist())
+    for name in pe.RAD_GOLDEN:
+        for key, q, ql, s, sl in pe.golden_searches(name):
+            fx[f'{key}.nb'] = _idx16(native.ref_radius_neighbors(q, s, ql, sl, pe.radius_case(name).radius))
+    path = os.path.join(OUT, 'preprocess_edges.npz')
+    np.savez_compressed(path, **fx)
+    print(os.path.basename(path), len(fx), 'arrays', os.path.getsize(path) // 1024, 'KB')
+
+
 def main():
     assert ref_harness.available(), "needs /root/reference (dev container only)"
     os.makedirs(OUT, exist_ok=True)
@@ -594,6 +624,8 @@ def main():
             gen_formats()
         if 'shim' in what:
             gen_shim()
+        if 'preprocess_edges' in what:
+            gen_preprocess_edges()
         for case in ('c2', 'c3', 'c3w', 'c4'):
             if f'sized_{case}' in what or 'sized' in what:
                 gen_sized(case)

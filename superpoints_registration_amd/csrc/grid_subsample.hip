@@ -33,11 +33,14 @@ namespace {
 
 constexpr int kKeyBits = 40;
 constexpr unsigned long long kKeyMask = (1ull << kKeyBits) - 1;
+// Bit 63 of a point / voxel key: the reference's 64-bit key is wrapped (see k_keys).  Above the cloud bits
+// (nb < 2^23) and outside the bit range the radix sort looks at.
+constexpr unsigned long long kKeyWrapped = 1ull << 63;
 constexpr int kMaxSched = 40;
 
 struct CloudInfo {
   float org[3];
-  unsigned int nx, ny;
+  unsigned int nx, ny, nz;
 };
 
 // The bucket schedule travels as a kernel ARGUMENT (160 bytes): no per-device constant
@@ -116,6 +119,7 @@ __global__ __launch_bounds__(256) void k_bbox(const float* __restrict__ xyz,
       ci.org[d] = __fmul_rn(floorf(__fmul_rn(smn[d][0], inv)), dl);
     ci.nx = (unsigned int)floorf(__fdiv_rn(__fsub_rn(smx[0][0], ci.org[0]), dl)) + 1u;
     ci.ny = (unsigned int)floorf(__fdiv_rn(__fsub_rn(smx[1][0], ci.org[1]), dl)) + 1u;
+    ci.nz = (unsigned int)floorf(__fdiv_rn(__fsub_rn(smx[2][0], ci.org[2]), dl)) + 1u;  // only bounds the keys
     info[c] = ci;
   }
 }
@@ -127,17 +131,29 @@ __global__ void k_keys(const float* __restrict__ xyz, const int* __restrict__ cu
   if (i >= n) return;
   const int c = find_segment(cu, nb, i);
   const CloudInfo ci = info[c];
-  // grid_subsampling.cpp:53-56
-  const unsigned long long ix =
-      (unsigned long long)floorf(__fdiv_rn(__fsub_rn(xyz[3 * (size_t)i + 0], ci.org[0]), dl));
-  const unsigned long long iy =
-      (unsigned long long)floorf(__fdiv_rn(__fsub_rn(xyz[3 * (size_t)i + 1], ci.org[1]), dl));
-  const unsigned long long iz =
-      (unsigned long long)floorf(__fdiv_rn(__fsub_rn(xyz[3 * (size_t)i + 2], ci.org[2]), dl));
-  const unsigned long long key =
-      ix + (unsigned long long)ci.nx * iy + (unsigned long long)ci.nx * ci.ny * iz;
-  if (key > kKeyMask) atomicOr(err, 1);
-  keys[i] = ((unsigned long long)c << kKeyBits) | (key & kKeyMask);
+  // grid_subsampling.cpp:53-56.  The origin floor(min * (1/dl)) * dl can round to just ABOVE the cloud's minimum;
+  // the cell index of a point below it is floor(tiny negative) = -1, and the reference's (size_t) cast of it is the
+  // x86-64 one: 2^64 - 1, the key arithmetic wrapping modulo 2^64.  So the indices are signed here (the GPU's
+  // float -> unsigned long long conversion of -1.0f gives 2^32 - 1) and the key is their sum modulo 2^64: a point with
+  // ix = -1, iy >= 1 shares voxel (nx - 1, iy - 1); with iy = iz = 0 it has the key 2^64 - 1 and a voxel of its own.
+  const long long ix = (long long)floorf(__fdiv_rn(__fsub_rn(xyz[3 * (size_t)i + 0], ci.org[0]), dl));
+  const long long iy = (long long)floorf(__fdiv_rn(__fsub_rn(xyz[3 * (size_t)i + 1], ci.org[1]), dl));
+  const long long iz = (long long)floorf(__fdiv_rn(__fsub_rn(xyz[3 * (size_t)i + 2], ci.org[2]), dl));
+  const unsigned long long key = (unsigned long long)ix + (unsigned long long)ci.nx * (unsigned long long)iy +
+                                 (unsigned long long)ci.nx * ci.ny * (unsigned long long)iz;
+  // Sort field = the key's low 40 bits.  Unwrapped keys are < 2^40 or an error, as before.  A wrapped key w (as a
+  // signed number in [-(1 + nx + nx ny), -1]) sorts as 2^40 + w: behind every unwrapped key of its cloud, which is
+  // where the 64-bit order puts it, and distinct from all of them as long as the grid's nx ny nz cells end below it.
+  unsigned long long flag = 0;
+  if ((long long)key < 0) {
+    flag = kKeyWrapped;
+    const double cells = (double)ci.nx * (double)ci.ny * (double)ci.nz;
+    if ((long long)key < -(1ll << (kKeyBits - 1)) || cells > (double)((1ll << kKeyBits) + (long long)key))
+      atomicOr(err, 1);
+  } else if (key > kKeyMask) {
+    atomicOr(err, 1);
+  }
+  keys[i] = flag | ((unsigned long long)c << kKeyBits) | (key & kKeyMask);
   vals[i] = i;
 }
 
@@ -193,7 +209,7 @@ __global__ void k_cloud_lb(const unsigned long long* __restrict__ vkey,
   int lo = 0, hi = nvox;
   while (lo < hi) {
     const int mid = (lo + hi) >> 1;
-    if ((int)(vkey[mid] >> kKeyBits) < c)
+    if ((int)((vkey[mid] & ~kKeyWrapped) >> kKeyBits) < c)
       lo = mid + 1;
     else
       hi = mid;
@@ -225,7 +241,7 @@ __global__ void k_emit_canonical(const float* __restrict__ bary,
                                  const int* __restrict__ out_lens, float* out) {
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= *nvox_p) return;
-  const int c = (int)(vkey[v] >> kKeyBits);
+  const int c = (int)((vkey[v] & ~kKeyWrapped) >> kKeyBits);
   const int r = v - vcu[c];
   if (r >= out_lens[c]) return;
   const size_t o = (size_t)(out_cu[c] + r);
@@ -347,7 +363,10 @@ __global__ __launch_bounds__(1024) void k_umap_order(
       __syncthreads();
       for (int p = t; p < len; p += T) {
         const int el = cur[p];
-        const int b = fast_mod(vkey[ins[base + el]] & kKeyMask, (unsigned int)nbk, inv);
+        const unsigned long long vk = vkey[ins[base + el]];
+        // a wrapped key hashes with all its 64 bits (identity hash of the reference's size_t key): plain modulo, rare
+        const int b = (vk & kKeyWrapped) ? (int)((vk | ~kKeyMask) % (unsigned long long)nbk)
+                                         : fast_mod(vk & kKeyMask, (unsigned int)nbk, inv);
         bk[p] = b;
         atomicMin(&tf[b], p);
         atomicAdd(&tc[b], 1);
