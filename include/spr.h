@@ -9,7 +9,10 @@
  *     [src_0..src_{B-1}, tgt_0..tgt_{B-1}] as in qk_regtr_full.py:152;
  *   - `stream` is a hipStream_t passed as void*; all work is stream ordered,
  *     nothing synchronises, nothing allocates: scratch comes from the caller
- *     (`ws`, size from the matching *_workspace_bytes query);
+ *     (`ws`, size from the matching *_workspace_bytes query: the query measures the very layout the
+ *     entry point carves, so a buffer of that size is always accepted and a smaller one is refused,
+ *     status 2, before anything is enqueued -- except where a note below names a smaller layout an entry
+ *     point falls back to or needs: spr_attn_varlen_bwd, spr_bce_logits_mean, spr_transform_l1_pair);
  *   - return value 0 = success, anything else = failure; spr_last_error()
  *     returns a thread-local message.  The Python binding raises RuntimeError,
  *     which is what the reference's CPython modules raise

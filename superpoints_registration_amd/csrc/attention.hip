@@ -840,39 +840,51 @@ __global__ __launch_bounds__(256) void k_plane_scales(const float* __restrict__ 
 using namespace spr;
 
 static size_t attn_tp_(int t, int nseg) { return align_up((size_t)t + 16 * (size_t)nseg + KT2, PT); }
-// small scratch behind the planes: 3 absmax partial arrays, 3*256 row norms, 4 scales
-static constexpr size_t kAttnSmall = 3 * 2048 + 4096 + 256;
-
-extern "C" size_t spr_attn_workspace_bytes(int t, int nseg, int nhead, int head_dim) {
-  if (t < 0 || nseg < 0 || nhead < 0 || head_dim < 0) return 0;
-  const size_t d = (size_t)nhead * head_dim;
-  return 4 * align_up((size_t)(t > 0 ? t : 1) * d * 2, 256) + 2 * align_up(d * attn_tp_(t, nseg) * 2, 256) +
-         kAttnSmall;
-}
 
 namespace {
+// small scratch behind the planes: 3 absmax partial arrays, the row norms of the in-projection's weights, 4 scales
 struct AttnSmall {
   float *p0, *p1, *p2, *rowl1, *scales;
 };
-// carves the operand planes and the small scratch out of ws
-int carve(void* ws, size_t ws_bytes, int t, int nseg, int d, size_t tp, AttnPlanes& pl, AttnSmall& sm) {
-  Workspace w(ws, ws_bytes);
-  pl.qh = w.take<_Float16>((size_t)t * d);
-  pl.ql = w.take<_Float16>((size_t)t * d);
-  pl.kh = w.take<_Float16>((size_t)t * d);
-  pl.kl = w.take<_Float16>((size_t)t * d);
-  pl.vth = w.take<_Float16>((size_t)d * tp);
-  pl.vtl = w.take<_Float16>((size_t)d * tp);
+// The operand planes and the small scratch; t = 0 is measured as one token (the size queries' clamp).
+void attn_layout(Workspace& w, int t, int nseg, size_t d, AttnPlanes& pl, AttnSmall& sm) {
+  const size_t T = (size_t)(t > 0 ? t : 1), tp = attn_tp_(t, nseg);
+  pl.qh = w.take<_Float16>(T * d);
+  pl.ql = w.take<_Float16>(T * d);
+  pl.kh = w.take<_Float16>(T * d);
+  pl.kl = w.take<_Float16>(T * d);
+  pl.vth = w.take<_Float16>(d * tp);
+  pl.vtl = w.take<_Float16>(d * tp);
   sm.p0 = w.take<float>(kAmaxParts);
   sm.p1 = w.take<float>(kAmaxParts);
   sm.p2 = w.take<float>(kAmaxParts);
   sm.rowl1 = w.take<float>(1024);
-  sm.scales = w.take<float>(4);
-  SPR_REQUIRE(w.ok() && sm.scales != nullptr, "attention: workspace carve failed");
-  pl.scales = sm.scales;
-  return 0;
+  pl.scales = sm.scales = w.take<float>(4);
+}
+// spr_attn_inproj_varlen_fwd: the same, then (exact mode and tiny inputs only) the fp32 [t, 3 d] projection
+struct InprojWs {
+  size_t planes_bytes;   // what attn_layout took: the unfused core carves the same bytes again
+  float* qkv;
+};
+InprojWs attn_inproj_layout(Workspace& w, int t, int nseg, size_t d, AttnPlanes& pl, AttnSmall& sm) {
+  attn_layout(w, t, nseg, d, pl, sm);
+  InprojWs l;
+  l.planes_bytes = w.off;
+  l.qkv = w.take<float>((size_t)(t > 0 ? t : 1) * 3 * d);
+  return l;
+}
+}  // namespace
+
+extern "C" size_t spr_attn_workspace_bytes(int t, int nseg, int nhead, int head_dim) {
+  if (t < 0 || nseg < 0 || nhead < 0 || head_dim < 0) return 0;
+  Workspace w;
+  AttnPlanes pl{};
+  AttnSmall sm{};
+  attn_layout(w, t, nseg, (size_t)nhead * head_dim, pl, sm);
+  return w.used();
 }
 
+namespace {
 // does the core launched for `mode` write the per-query log-sum-exp (lse_out)?  k_attn_s does, k_attn does not.
 bool attn_core_writes_lse(int mode) { return mode != 0; }
 
@@ -931,11 +943,11 @@ extern "C" int spr_attn_varlen_fwd(const float* q, int q_stride, const float* k,
   const int d_model = nhead * head_dim;
   const size_t tp = attn_tp_(t, nseg);
   SPR_REQUIRE(tp < (1ul << 31), "attention: too many tokens");
-  SPR_REQUIRE(ws != nullptr && ws_bytes >= spr_attn_workspace_bytes(t, nseg, nhead, head_dim),
-              "attention: workspace too small (%zu bytes given)", ws_bytes);
+  Workspace w(ws, ws_bytes);
   AttnPlanes pl{};
   AttnSmall sm{};
-  if (int rc = carve(ws, ws_bytes, t, nseg, d_model, tp, pl, sm)) return rc;
+  attn_layout(w, t, nseg, d_model, pl, sm);
+  SPR_REQUIRE(ws != nullptr && w.ok(), "attention: workspace too small (%zu bytes given)", ws_bytes);
   if (int rc = launch_absmax2(q, t, d_model, q_stride, sm.p0, k, t, d_model, k_stride, sm.p1, stream)) return rc;
   if (int rc = launch_absmax(v, t, d_model, v_stride, sm.p2, stream)) return rc;
   hipLaunchKernelGGL(k_plane_scales, dim3(1), dim3(256), 0, stream, sm.p0, sm.p1, sm.p2, (const float*)nullptr,
@@ -950,9 +962,11 @@ extern "C" int spr_attn_varlen_fwd(const float* q, int q_stride, const float* k,
 
 extern "C" size_t spr_attn_inproj_workspace_bytes(int t, int nseg, int nhead, int head_dim) {
   if (t < 0 || nseg < 0 || nhead < 0 || head_dim < 0) return 0;
-  // operand planes + (exact mode only) the fp32 [t, 3 d] projection
-  return spr_attn_workspace_bytes(t, nseg, nhead, head_dim) +
-         align_up((size_t)(t > 0 ? t : 1) * 3 * nhead * head_dim * sizeof(float), 256);
+  Workspace w;
+  AttnPlanes pl{};
+  AttnSmall sm{};
+  attn_inproj_layout(w, t, nseg, (size_t)nhead * head_dim, pl, sm);
+  return w.used();
 }
 
 // Weight-side inputs of the fused in-projection, measured once per weight version:
@@ -977,16 +991,15 @@ extern "C" int spr_attn_inproj_varlen_fwd(const float* x_qk, const float* x_v, i
   SPR_REQUIRE(nhead * head_dim == 256, "attention in-projection: d_model must be 256 (got %d)", nhead * head_dim);
   SPR_REQUIRE(t >= 1 && nseg >= 1 && max_len_host >= 1, "attention: bad sizes");
   SPR_REQUIRE(x_qk && x_v && w_in && b_in, "attention in-projection: null operand");
-  SPR_REQUIRE(ws != nullptr && ws_bytes >= spr_attn_inproj_workspace_bytes(t, nseg, nhead, head_dim),
-              "attention in-projection: workspace too small (%zu bytes given)", ws_bytes);
   const int d = nhead * head_dim;
-  const size_t planes_bytes = spr_attn_workspace_bytes(t, nseg, nhead, head_dim);
   const int mode = spr::g_attn_mode.load(std::memory_order_relaxed);
   const size_t tp = attn_tp_(t, nseg);
   SPR_REQUIRE(tp < (1ul << 31), "attention: too many tokens");
+  Workspace w(ws, ws_bytes);
   AttnPlanes pl{};
   AttnSmall sm{};
-  if (int rc = carve(ws, planes_bytes, t, nseg, d, tp, pl, sm)) return rc;
+  const auto [planes_bytes, qkv] = attn_inproj_layout(w, t, nseg, d, pl, sm);
+  SPR_REQUIRE(ws != nullptr && w.ok(), "attention in-projection: workspace too small (%zu bytes given)", ws_bytes);
   const bool gemm_split = gemm_mode() == 1;
   if (mode == 0 || t < 256 || !gemm_split) {
     if (out_range != nullptr) {   // this route publishes no range: an infinite bound would be wrong, so measure later
@@ -995,7 +1008,6 @@ extern "C" int spr_attn_inproj_varlen_fwd(const float* x_qk, const float* x_v, i
     }
     // exact-f32 mode (and tiny inputs): plain projection into the workspace, then the
     // unfused core -- same results as spr_linear + spr_attn_varlen_fwd
-    float* qkv = (float*)((char*)ws + planes_bytes);
     const float *xp = nullptr, *xvp = nullptr, *wp = nullptr;
     if (gemm_split) {   // operand ranges for the split-fp16 GEMM (sm.* is rewritten by the core afterwards)
       if (int rc = launch_absmax(x_qk, t, d, d, sm.p0, stream)) return rc;
@@ -1080,9 +1092,9 @@ extern "C" int spr_attn_inproj_varlen_fwd(const float* x_qk, const float* x_v, i
 // ---- entry points for the fused cross-encoder chains (xenc.hip) --------------------------------
 size_t spr::attn_tp(int t, int nseg) { return ::attn_tp_(t, nseg); }
 int spr::attn_mode() { return spr::g_attn_mode.load(std::memory_order_relaxed); }
-int spr::attn_carve_planes(void* ws, size_t ws_bytes, int t, int nseg, int d, AttnPlanes& pl) {
+void spr::attn_layout_planes(Workspace& w, int t, int nseg, int d, AttnPlanes& pl) {
   AttnSmall sm{};
-  return carve(ws, ws_bytes, t, nseg, d, ::attn_tp_(t, nseg), pl, sm);
+  attn_layout(w, t, nseg, d, pl, sm);
 }
 int spr::attn_zero_gaps(const AttnPlanes& pl, int d, hipStream_t stream) {
   hipLaunchKernelGGL(k_attn_zero_gaps, dim3(d), dim3(256), 0, stream, pl.cu, pl.nseg, pl.tp, pl.vth, pl.vtl);

@@ -972,25 +972,43 @@ __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void k_attn_bwd_dkv_h(const A
 
 using namespace spr;
 
-// the least the backward runs with: its kernels then convert the fp32 tiles they stage themselves
-extern "C" size_t spr_attn_bwd_min_workspace_bytes(int t, int nhead) {
-  // lse, dsum [t, nhead]; four max-|x| partial arrays and the four operand scales of the split-fp16 form
-  return 2 * align_up((size_t)(t > 0 ? t : 1) * (size_t)(nhead > 0 ? nhead : 1) * sizeof(float), 256) +
-         align_up((size_t)4 * kAmaxParts * sizeof(float), 256) + 256;
-}
 // columns of the transposed operand planes: every segment padded to whole BT-column tiles.  size_t from the first
 // factor: the size query must not wrap where t + BT * nseg leaves int (the entry point refuses such sizes)
 static size_t attn_bwd_tc(int t, int nseg) {
   return ((size_t)(t > 0 ? t : 1) + BT - 1) / BT * BT + (size_t)BT * (size_t)(nseg > 0 ? nseg : 1);
 }
-static size_t attn_bwd_plane_bytes(int t, int nseg, int nhead) {
-  const size_t d = (size_t)(nhead > 0 ? nhead : 1) * BHD;
-  return 8 * align_up((size_t)(t > 0 ? t : 1) * d * 2, 256) + 6 * align_up(d * attn_bwd_tc(t, nseg) * 2, 256) +
-         align_up(((size_t)(nseg > 0 ? nseg : 1) + 2) * sizeof(int), 256);
+struct AttnBwdWs {
+  float *lse, *dsum;       // [t, nhead]
+  float *parts, *scales;   // split-fp16 form: four max-|x| partial arrays, the four operand scales
+  BwdPlanes pl;            // with_planes only: the operand planes of the split-fp16 form (k_attn_bwd_pack)
+};
+// Sizes below 1 are measured as 1 (the size queries' clamp).
+static AttnBwdWs attn_bwd_layout(Workspace& w, int t, int nseg, int nhead, bool with_planes) {
+  const size_t T = (size_t)(t > 0 ? t : 1), H = (size_t)(nhead > 0 ? nhead : 1), d = H * BHD;
+  AttnBwdWs l{};
+  l.lse = w.take<float>(T * H);
+  l.dsum = w.take<float>(T * H);
+  l.parts = w.take<float>((size_t)4 * kAmaxParts);
+  l.scales = w.take<float>(4);
+  if (!with_planes) return l;
+  const size_t tc = attn_bwd_tc(t, nseg);
+  for (_Float16** rp : {l.pl.rq, l.pl.rk, l.pl.rv, l.pl.ro})
+    for (int i = 0; i < 2; ++i) rp[i] = w.take<_Float16>(T * d);
+  for (_Float16** cp : {l.pl.cq, l.pl.ck, l.pl.co})
+    for (int i = 0; i < 2; ++i) cp[i] = w.take<_Float16>(d * tc);
+  l.pl.cst = w.take<int>((size_t)(nseg > 0 ? nseg : 1) + 2);   // nseg + 1 starts (the size has always counted one more)
+  l.pl.t = t;
+  l.pl.tc = (int)tc;
+  return l;
 }
-// with room for the operand planes of the split-fp16 form (k_attn_bwd_pack)
+
+// the least the backward runs with: its kernels then convert the fp32 tiles they stage themselves
+extern "C" size_t spr_attn_bwd_min_workspace_bytes(int t, int nhead) {
+  return measure(attn_bwd_layout, t, 1, nhead, false);
+}
+// with room for the operand planes
 extern "C" size_t spr_attn_bwd_workspace_bytes(int t, int nseg, int nhead) {
-  return spr_attn_bwd_min_workspace_bytes(t, nhead) + attn_bwd_plane_bytes(t, nseg, nhead);
+  return measure(attn_bwd_layout, t, nseg, nhead, true);
 }
 
 // q, k, v, out (the forward's output), dout: [t, nhead * 32] with unit inner stride and the given row strides;
@@ -1011,33 +1029,21 @@ extern "C" int spr_attn_varlen_bwd(const float* q, int q_stride, const float* k,
                   q_stride % 4 == 0 && k_stride % 4 == 0 && v_stride % 4 == 0 && o_stride % 4 == 0 && do_stride % 4 == 0,
               "attn_bwd: row strides must be multiples of 4 floats and >= nhead * 32");
   SPR_REQUIRE(attn_bwd_tc(t, nseg) < (1ul << 31), "attn_bwd: too many tokens or segments (t=%d nseg=%d)", t, nseg);
-  SPR_REQUIRE(ws != nullptr && ws_bytes >= spr_attn_bwd_min_workspace_bytes(t, nhead), "attn_bwd: workspace too small");
-  // the whole carve, checked once, in front of the first launch
+  // the operand planes exactly when the full layout fits, the minimal layout otherwise
   const bool split = attn_mode() != 0;
-  const bool planes = split && ws_bytes >= spr_attn_bwd_workspace_bytes(t, nseg, nhead);
   Workspace w(ws, ws_bytes);
+  AttnBwdWs l = attn_bwd_layout(w, t, nseg, nhead, split);
+  const bool planes = split && w.ok();
+  if (!planes) {
+    w = Workspace(ws, ws_bytes);
+    l = attn_bwd_layout(w, t, nseg, nhead, false);
+  }
+  SPR_REQUIRE(ws != nullptr && w.ok(), "attn_bwd: workspace too small");
   AttnBwdArgs a;
-  a.lse = w.take<float>((size_t)t * nhead);
-  a.dsum = w.take<float>((size_t)t * nhead);
-  float *parts = nullptr, *scales = nullptr;
-  BwdPlanes pl{};
-  if (split) {
-    parts = w.take<float>((size_t)4 * kAmaxParts);
-    scales = w.take<float>(4);
-  }
-  if (planes) {
-    const int tc = (int)attn_bwd_tc(t, nseg);
-    _Float16** r[4] = {pl.rq, pl.rk, pl.rv, pl.ro};
-    for (auto& rp : r)
-      for (int i = 0; i < 2; ++i) rp[i] = w.take<_Float16>((size_t)t * d);
-    _Float16** cpl[3] = {pl.cq, pl.ck, pl.co};
-    for (auto& cp : cpl)
-      for (int i = 0; i < 2; ++i) cp[i] = w.take<_Float16>((size_t)d * tc);
-    pl.cst = w.take<int>(nseg + 1);
-    pl.t = t;
-    pl.tc = tc;
-  }
-  SPR_REQUIRE(w.ok(), "attn_bwd: workspace carve failed");
+  a.lse = l.lse;
+  a.dsum = l.dsum;
+  float *parts = l.parts, *scales = l.scales;
+  const BwdPlanes& pl = l.pl;
   // the forward's log-sum-exp (split-fp16 forms only: the exact-f32 kernels keep their own sweep)
   const bool have_lse = lse_in != nullptr && attn_mode() != 0;
   if (have_lse) a.lse = const_cast<float*>(lse_in);

@@ -293,9 +293,9 @@ struct ProbsWs {
   _Float16 *qh, *ql, *kh, *kl;
   float *m, *rl, *qparts, *kparts, *scales;
 };
-int carve_probs(void* ws, size_t ws_bytes, int t, int nhead, ProbsWs& w) {
-  Workspace a(ws, ws_bytes);
+ProbsWs probs_layout(Workspace& a, int t, int nhead) {
   const size_t n = (size_t)t * nhead * HD;
+  ProbsWs w;
   w.qh = a.take<_Float16>(n);
   w.ql = a.take<_Float16>(n);
   w.kh = a.take<_Float16>(n);
@@ -305,16 +305,13 @@ int carve_probs(void* ws, size_t ws_bytes, int t, int nhead, ProbsWs& w) {
   w.qparts = a.take<float>(kAmaxParts);
   w.kparts = a.take<float>(kAmaxParts);
   w.scales = a.take<float>(4);
-  SPR_REQUIRE(a.ok() && w.scales != nullptr, "attention probs: workspace carve failed");
-  return 0;
+  return w;
 }
 }  // namespace
 
 extern "C" size_t spr_attn_probs_workspace_bytes(int t, int nhead, int head_dim) {
   if (t < 1 || nhead < 1 || head_dim != HD) return 0;
-  const size_t n = (size_t)t * nhead * HD;
-  return 4 * align_up(n * 2, 256) + 2 * align_up((size_t)t * nhead * 4, 256) + 2 * align_up(kAmaxParts * 4, 256) +
-         256;
+  return measure(probs_layout, t, nhead);
 }
 
 extern "C" int spr_attn_probs(const float* q, int q_stride, const float* k, int k_stride, const int* cu,
@@ -331,12 +328,11 @@ extern "C" int spr_attn_probs(const float* q, int q_stride, const float* k, int 
   SPR_REQUIRE(q_stride % 4 == 0 && k_stride % 4 == 0 && q_stride >= nhead * HD && k_stride >= nhead * HD &&
                   ((uintptr_t)q & 15) == 0 && ((uintptr_t)k & 15) == 0,
               "attention probs: q / k rows must be 16-byte aligned with strides >= nhead * 32 (multiples of 4 floats)");
-  SPR_REQUIRE(ws_bytes >= spr_attn_probs_workspace_bytes(t, nhead, head_dim),
-              "attention probs: workspace too small (%zu bytes given)", ws_bytes);
+  Workspace a(ws, ws_bytes);
+  const ProbsWs w = probs_layout(a, t, nhead);
+  SPR_REQUIRE(a.ok(), "attention probs: workspace too small (%zu bytes given)", ws_bytes);
   const long nqt1 = cdiv(max_len_host, QB), nqt2 = cdiv(max_rows_host, QB), nkr = cdiv(max_cols_host, KR);
   SPR_REQUIRE(nqt1 * nhead * nseg < (1l << 31) && nqt2 * nkr * nseg < (1l << 31), "attention probs: grid too large");
-  ProbsWs w{};
-  if (int rc = carve_probs(ws, ws_bytes, t, nhead, w)) return rc;
   const int d = nhead * HD;
   if (int rc = launch_absmax2(q, t, d, q_stride, w.qparts, k, t, d, k_stride, w.kparts, stream)) return rc;
   hipLaunchKernelGGL(k_probs_scales, dim3(1), dim3(256), 0, stream, w.qparts, w.kparts, scale * 1.4426950408889634f,

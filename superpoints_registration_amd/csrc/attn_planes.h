@@ -33,11 +33,12 @@ struct AttnPlanes {
 };
 
 // Shared by attention.hip and xenc.hip (the fused cross-encoder chains write the planes themselves):
-// padded column count of the transposed V planes, carving of the planes out of a workspace of
-// spr_attn_workspace_bytes(t, nseg, nhead, 32) bytes, zeroing of the gap / tail columns, and the
+// padded column count of the transposed V planes, the layout of the planes (and the scratch behind them: what
+// spr_attn_workspace_bytes(t, nseg, nhead, 32) measures) as takes on the caller's Workspace, zeroing of the gap /
+// tail columns, and the
 // attention core over planes that are already in place.  `mode`: 1 .. 4 (spr_set_attn_mode).
 size_t attn_tp(int t, int nseg);
-int attn_carve_planes(void* ws, size_t ws_bytes, int t, int nseg, int d, AttnPlanes& pl);
+void attn_layout_planes(Workspace& w, int t, int nseg, int d, AttnPlanes& pl);
 int attn_zero_gaps(const AttnPlanes& pl, int d, hipStream_t stream);
 // o_tiles != nullptr: `out` is a TILED token tensor of the fused chains (xenc.hip; o_tiles[s] = chain tiles in front
 // of segment s; 8 heads).

@@ -378,6 +378,34 @@ size_t aug_temp_bytes(size_t np, size_t stride, int nb) {
   return align_up(a > b ? a : b, 256) + 256;
 }
 
+// No points are measured as one point, no pairs as one pair (the size query's clamp).
+struct AugWs {
+  unsigned long long *skey, *skey2;   // sort keys in / out
+  unsigned int *sval, *sval2;         // sort values in / out
+  int* inv;                           // inverse permutation
+  float* T;                           // P' per pair
+  int *flag, *pos, *ra, *rb;          // survivor flags, their prefix, remapped ends
+  size_t temp_bytes;
+  void* temp;
+};
+AugWs aug_layout(Workspace& w, int ns, int nt, int nb, int stride) {
+  const size_t np = (size_t)ns + (size_t)nt, P = np > 0 ? np : 1, S = (size_t)stride;
+  AugWs l;
+  l.skey = w.take<unsigned long long>(P);
+  l.skey2 = w.take<unsigned long long>(P);
+  l.sval = w.take<unsigned int>(P);
+  l.sval2 = w.take<unsigned int>(P);
+  l.inv = w.take<int>(P);
+  l.T = w.take<float>(12 * (size_t)(nb > 0 ? nb : 1));
+  l.flag = w.take<int>(S + 1);
+  l.pos = w.take<int>(S + 1);
+  l.ra = w.take<int>(S + 1);
+  l.rb = w.take<int>(S + 1);
+  l.temp_bytes = aug_temp_bytes(P, S, nb);
+  l.temp = w.take<char>(l.temp_bytes);
+  return l;
+}
+
 // ---- pair decisions: float64 on the host -------------------------------------------------------------------------
 double aug_u64(uint32_t w) { return ((double)(w >> 9) + 0.5) * 1.1920928955078125e-7; }
 constexpr double kAugPi = 3.14159265358979323846;
@@ -476,17 +504,7 @@ extern "C" int spr_augment_draw(uint64_t seed, const uint64_t* pair_key_host, in
 
 extern "C" size_t spr_augment_workspace_bytes(int ns, int nt, int nb, int corr_stride) {
   if (ns < 0 || nt < 0 || nb < 0 || corr_stride < 0) return 0;
-  const size_t P = (size_t)ns + (size_t)nt > 0 ? (size_t)ns + (size_t)nt : 1, B = (size_t)(nb > 0 ? nb : 1),
-               S = (size_t)corr_stride;
-  size_t b = 0;
-  b += 2 * align_up(8 * P, 256);        // sort keys in / out
-  b += 2 * align_up(4 * P, 256);        // sort values in / out
-  b += align_up(4 * P, 256);            // inverse permutation
-  b += align_up(4 * 12 * B, 256);       // P' per pair
-  b += 2 * align_up(4 * (S + 1), 256);  // survivor flags, their prefix
-  b += 2 * align_up(4 * (S + 1), 256);  // remapped ends
-  b += aug_temp_bytes(P, S, nb);
-  return b;
+  return measure(aug_layout, ns, nt, nb, corr_stride);
 }
 
 extern "C" int spr_augment_pairs(const float* src_xyz, const int* src_cu, int ns, const float* tgt_xyz,
@@ -523,23 +541,9 @@ extern "C" int spr_augment_pairs(const float* src_xyz, const int* src_cu, int ns
   SPR_REQUIRE(!corr || (corr_off && corr_count && out_corr_count && (corr_stride == 0 || out_corr)),
               "augment_pairs: corr needs corr_off, corr_count, out_corr and out_corr_count");
   const int stride = corr ? corr_stride : 0;
-  SPR_REQUIRE(ws != nullptr && ws_bytes >= spr_augment_workspace_bytes(ns, nt, nb, stride), "augment_pairs: workspace too small");
-
   Workspace w(ws, ws_bytes);
-  const size_t P = np > 0 ? (size_t)np : 1;
-  unsigned long long* skey = w.take<unsigned long long>(P);
-  unsigned long long* skey2 = w.take<unsigned long long>(P);
-  unsigned int* sval = w.take<unsigned int>(P);
-  unsigned int* sval2 = w.take<unsigned int>(P);
-  int* inv = w.take<int>(P);
-  float* T = w.take<float>(12 * (size_t)nb);
-  int* flag = w.take<int>((size_t)stride + 1);
-  int* pos = w.take<int>((size_t)stride + 1);
-  int* ra = w.take<int>((size_t)stride + 1);
-  int* rb = w.take<int>((size_t)stride + 1);
-  const size_t temp_bytes = aug_temp_bytes(P, (size_t)stride, nb);
-  void* temp = w.take<char>(temp_bytes);
-  SPR_REQUIRE(w.ok() && temp != nullptr, "augment_pairs: workspace carve failed");
+  const auto [skey, skey2, sval, sval2, inv, T, flag, pos, ra, rb, temp_bytes, temp] = aug_layout(w, ns, nt, nb, stride);
+  SPR_REQUIRE(ws != nullptr && w.ok(), "augment_pairs: workspace too small");
 
   const int TB = 256;
   hipLaunchKernelGGL(k_aug_layout, dim3(1), dim3(64), 0, stream, nb, max_pts, src_cu, tgt_cu, flags, out_src_cu,

@@ -569,13 +569,19 @@ extern "C" int spr_act_bwd(const float* y, const float* dy, int act, long n, flo
   return 0;
 }
 
-extern "C" size_t spr_colsum_workspace_bytes(int n) { return (size_t)kColChunks * (n > 0 ? n : 1) * sizeof(float); }
+// kColChunks partial sums per column
+static float* colsum_layout(Workspace& w, int n) { return w.take<float>((size_t)kColChunks * (n > 0 ? n : 1)); }
+
+extern "C" size_t spr_colsum_workspace_bytes(int n) {
+  return measure(colsum_layout, n);
+}
 
 extern "C" int spr_colsum(const float* x, long m, int n, float* out, void* ws, size_t ws_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   SPR_REQUIRE(x && out && m >= 1 && n >= 1, "colsum: bad arguments");
-  SPR_REQUIRE(ws && ws_bytes >= spr_colsum_workspace_bytes(n), "colsum: workspace too small");
-  float* parts = (float*)ws;
+  Workspace w(ws, ws_bytes);
+  float* parts = colsum_layout(w, n);
+  SPR_REQUIRE(ws != nullptr && w.ok(), "colsum: workspace too small");
   if (n >= 4 && 1024 % n == 0 && ((uintptr_t)x & 15) == 0)
     hipLaunchKernelGGL(k_colsum_flat, dim3(kColChunks), dim3(256), 0, stream, x, (long)m, n, parts);
   else
@@ -584,8 +590,20 @@ extern "C" int spr_colsum(const float* x, long m, int n, float* out, void* ws, s
   return spr_reduce_parts(parts, kColChunks, n, 1.0f, out, 0, stream_);
 }
 
+namespace {
+struct LnBwdWs {
+  float *dg, *db;   // per-block partial sums of dgamma, dbeta
+};
+LnBwdWs layernorm_bwd_layout(Workspace& w, int c) {
+  LnBwdWs l;
+  l.dg = w.take<float>((size_t)kLnBlocks * (c > 0 ? c : 1));
+  l.db = w.take<float>((size_t)kLnBlocks * (c > 0 ? c : 1));
+  return l;
+}
+}  // namespace
+
 extern "C" size_t spr_layernorm_bwd_workspace_bytes(int c) {
-  return 2 * (size_t)kLnBlocks * (c > 0 ? c : 1) * sizeof(float);
+  return measure(layernorm_bwd_layout, c);
 }
 
 extern "C" int spr_layernorm_bwd(const float* x, int m, int c, const float* gamma, float eps, const float* dy_norm,
@@ -594,9 +612,9 @@ extern "C" int spr_layernorm_bwd(const float* x, int m, int c, const float* gamm
   hipStream_t stream = (hipStream_t)stream_;
   SPR_REQUIRE(m > 0 && c % 64 == 0 && c <= 1024, "layernorm_bwd: c must be a multiple of 64 and <= 1024 (c=%d)", c);
   SPR_REQUIRE(x && gamma && dx && dgamma && dbeta && (dy_norm || dy_pos), "layernorm_bwd: null operand");
-  SPR_REQUIRE(ws && ws_bytes >= spr_layernorm_bwd_workspace_bytes(c), "layernorm_bwd: workspace too small");
-  float* dg = (float*)ws;
-  float* db = dg + (size_t)kLnBlocks * c;
+  Workspace w(ws, ws_bytes);
+  const auto [dg, db] = layernorm_bwd_layout(w, c);
+  SPR_REQUIRE(ws != nullptr && w.ok(), "layernorm_bwd: workspace too small");
   const bool al16 = (((uintptr_t)x | (uintptr_t)dx | (uintptr_t)gamma | (uintptr_t)dy_norm | (uintptr_t)dy_pos) & 15) == 0;
   if (c == 256 && al16)
     hipLaunchKernelGGL(k_layernorm_bwd256, dim3(kLnBlocks), dim3(256), 0, stream, x, m, gamma, eps, dy_norm, dy_pos, dx,
@@ -614,25 +632,29 @@ extern "C" int spr_layernorm_bwd(const float* x, int m, int c, const float* gamm
 
 // scratch of the order-independent scatter-adds: the fixed-point accumulators + the range partials of the
 // incoming gradient
-extern "C" size_t spr_scatter_workspace_bytes(long rows, int c) {
-  return align_up((size_t)(rows > 0 ? rows : 1) * (size_t)(c > 0 ? c : 1) * sizeof(unsigned long long), 256) +
-         align_up(kAmaxParts * sizeof(float), 256);
-}
 namespace {
 struct FxScratch {
   unsigned long long* acc;
   float* parts;
 };
+FxScratch fx_layout(Workspace& w, long rows, int c) {
+  FxScratch f;
+  f.acc = w.take<unsigned long long>((size_t)(rows > 0 ? rows : 1) * (size_t)(c > 0 ? c : 1));
+  f.parts = w.take<float>(kAmaxParts);
+  return f;
+}
 int fx_scratch(void* ws, size_t ws_bytes, long rows, int c, hipStream_t stream, FxScratch* out) {
-  SPR_REQUIRE(ws != nullptr && ws_bytes >= spr_scatter_workspace_bytes(rows, c), "scatter: workspace too small");
   Workspace w(ws, ws_bytes);
-  out->acc = w.take<unsigned long long>((size_t)rows * c);
-  out->parts = w.take<float>(kAmaxParts);
-  SPR_REQUIRE(w.ok() && out->parts != nullptr, "scatter: workspace carve failed");
+  *out = fx_layout(w, rows, c);
+  SPR_REQUIRE(ws != nullptr && w.ok(), "scatter: workspace too small");
   SPR_HIP_CHECK(hipMemsetAsync(out->acc, 0, (size_t)rows * c * sizeof(unsigned long long), stream));
   return 0;
 }
 }  // namespace
+
+extern "C" size_t spr_scatter_workspace_bytes(long rows, int c) {
+  return measure(fx_layout, rows, c);
+}
 
 // dx [ns, c] is fully written (ws: spr_scatter_workspace_bytes(ns, c))
 extern "C" int spr_maxpool_bwd(const float* x, int ns, int c, const int* idx, int nq, int idx_stride, int k,
@@ -676,9 +698,24 @@ void launch_rowflag(const float* x, const float* s_xyz, int ns, int cin, unsigne
 }
 
 // the forward's per-support flags (launch_rowflag): flag[ns], its support records [ns + 1], one counter
-extern "C" size_t spr_kpconv_weighted_features_workspace_bytes(int ns) {
+namespace {
+struct RowFlagWs {
+  unsigned char* flag;
+  float4* sxf;
+  int* tile_ctr;
+};
+RowFlagWs rowflag_layout(Workspace& w, int ns) {
   const size_t n = ns > 0 ? (size_t)ns : 1;
-  return align_up(n, 256) + align_up((n + 1) * 16, 256) + 256;
+  RowFlagWs l;
+  l.flag = w.take<unsigned char>(n);
+  l.sxf = w.take<float4>(n + 1);
+  l.tile_ctr = w.take<int>(64);
+  return l;
+}
+}  // namespace
+
+extern "C" size_t spr_kpconv_weighted_features_workspace_bytes(int ns) {
+  return measure(rowflag_layout, ns);
 }
 
 // wf and cnt as the forward sums and counts them: same kernel, neighbours counted from the forward's per-support flags
@@ -689,11 +726,9 @@ extern "C" int spr_kpconv_weighted_features(const float* q_xyz, int nq, const fl
   hipStream_t stream = (hipStream_t)stream_;
   SPR_REQUIRE(nq > 0 && ns > 0 && cin >= 1 && n_kp >= 1 && n_kp <= kKPmax && kp_extent > 0.f && kmax >= 1 &&
                   kmax <= nbr_stride, "kpconv_weighted_features: bad arguments");
-  SPR_REQUIRE(ws && ws_bytes >= spr_kpconv_weighted_features_workspace_bytes(ns),
-              "kpconv_weighted_features: workspace too small");
-  unsigned char* flag = (unsigned char*)ws;
-  float4* sxf = (float4*)((char*)ws + align_up((size_t)ns, 256));
-  int* tile_ctr = (int*)((char*)sxf + align_up(((size_t)ns + 1) * 16, 256));
+  Workspace w(ws, ws_bytes);
+  const auto [flag, sxf, tile_ctr] = rowflag_layout(w, ns);
+  SPR_REQUIRE(ws != nullptr && w.ok(), "kpconv_weighted_features: workspace too small");
   launch_rowflag(x, s_xyz, ns, cin, flag, sxf, tile_ctr, stream);
   if (cin == 32)
     hipLaunchKernelGGL((k_kpconv_aux2<false, true>), dim3(cdiv(nq, 4)), dim3(256), 0, stream, q_xyz, nq, s_xyz, ns, nbr,

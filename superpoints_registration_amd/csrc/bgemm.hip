@@ -447,7 +447,21 @@ __global__ __launch_bounds__(256) void k_gemm_tn_h3(const float* __restrict__ Lm
 }  // namespace
 }  // namespace spr
 
-extern "C" size_t spr_tn_product_split_workspace_bytes(void) { return 2 * align_up(kAmaxParts * sizeof(float), 256); }
+namespace {
+struct TnSplitWs {
+  float *lp, *rp;   // max |L|, max |R| partials
+};
+TnSplitWs tn_split_layout(spr::Workspace& w) {
+  TnSplitWs l;
+  l.lp = w.take<float>(spr::kAmaxParts);
+  l.rp = w.take<float>(spr::kAmaxParts);
+  return l;
+}
+}  // namespace
+
+extern "C" size_t spr_tn_product_split_workspace_bytes(void) {
+  return measure(tn_split_layout);
+}
 
 // parts [nbatch][nl][nr], nbatch = ceil(rows / chunk): the caller sums them (spr_reduce_parts).  l_range / r_range:
 // range partials of L / R (NULL: measured here).  nl, nr multiples of 4; chunk a multiple of 16.
@@ -457,11 +471,9 @@ extern "C" int spr_tn_product_split(const float* Lm, const float* Rm, long rows,
   hipStream_t stream = (hipStream_t)stream_;
   SPR_REQUIRE(Lm && Rm && parts && rows >= 1 && nl >= 4 && nr >= 4 && nl % 4 == 0 && nr % 4 == 0 && chunk >= 16 &&
                   chunk % 16 == 0, "tn_product_split: bad arguments (rows=%ld nl=%d nr=%d chunk=%d)", rows, nl, nr, chunk);
-  SPR_REQUIRE(ws != nullptr && ws_bytes >= spr_tn_product_split_workspace_bytes(), "tn_product_split: workspace too small");
   Workspace w(ws, ws_bytes);
-  float* lp = w.take<float>(kAmaxParts);
-  float* rp = w.take<float>(kAmaxParts);
-  SPR_REQUIRE(w.ok(), "tn_product_split: workspace carve failed");
+  const auto [lp, rp] = tn_split_layout(w);
+  SPR_REQUIRE(ws != nullptr && w.ok(), "tn_product_split: workspace too small");
   const float* lparts = l_range;
   const float* rparts = r_range;
   int nlp = l_range_n, nrp = r_range_n;

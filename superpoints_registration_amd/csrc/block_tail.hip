@@ -490,13 +490,26 @@ extern "C" int spr_block_tail_tiles(const int* cu, int n, int nb, int tile_rows,
   return 0;
 }
 
+namespace {
+struct TailWs {
+  double* part;   // per tile and branch: sum and sum of squares of every output channel
+  float* stats;   // per cloud and branch: mean, rstd
+  float* mp[4];   // max |x| partials of xa, wa, xb, wb
+};
+// Sizes below 1 are measured as 1 (tile_rows: as 64; n_out: as 0), the size query's clamp.
+TailWs tail_layout(Workspace& w, int n, int nb, int kb, int n_out, int tile_rows) {
+  const size_t nbr = kb > 0 ? 2 : 1, B = (size_t)(nb > 0 ? nb : 1), no = (size_t)(n_out > 0 ? n_out : 0);
+  const size_t tiles = (size_t)cdiv(n > 0 ? n : 1, tile_rows > 0 ? tile_rows : 64) + B;
+  TailWs l;
+  l.part = w.take<double>(tiles * nbr * 2 * no);
+  l.stats = w.take<float>(B * nbr * 2 * no);
+  for (float*& p : l.mp) p = w.take<float>(kAmaxParts);
+  return l;
+}
+}  // namespace
+
 extern "C" size_t spr_block_tail_workspace_bytes(int n, int nb, int kb, int n_out, int tile_rows) {
-  const size_t nbr = kb > 0 ? 2 : 1;
-  const size_t tiles = (size_t)cdiv(n > 0 ? n : 1, tile_rows > 0 ? tile_rows : 64) + (size_t)(nb > 0 ? nb : 1);
-  const size_t no = (size_t)(n_out > 0 ? n_out : 0);
-  return align_up(tiles * nbr * 2 * no * sizeof(double), 256) +
-         align_up((size_t)(nb > 0 ? nb : 1) * nbr * 2 * no * sizeof(float), 256) +
-         4 * align_up(kAmaxParts * sizeof(float), 256);
+  return measure(tail_layout, n, nb, kb, n_out, tile_rows);
 }
 
 // xa_mean / xa_rstd (both or neither): xa is the RAW input of a per-cloud InstanceNorm + LeakyReLU(xa_slope) whose
@@ -517,16 +530,13 @@ extern "C" int spr_block_tail(const float* xa, int ka, const float* wa, const fl
   SPR_REQUIRE(!(kb > 0 && add != nullptr), "block_tail: either a projected shortcut (xb, wb) or a plain one (add)");
   SPR_REQUIRE(out_range == nullptr || (out_range_n >= 1 && (out_range_n & (out_range_n - 1)) == 0),
               "block_tail: out_range_n must be a power of two");
-  SPR_REQUIRE(ws != nullptr && ws_bytes >= spr_block_tail_workspace_bytes(n, nb, kb, n_out, sh.tr),
-              "block_tail: workspace too small");
-  const int nbr = kb > 0 ? 2 : 1;
   Workspace w(ws, ws_bytes);
+  const TailWs l = tail_layout(w, n, nb, kb, n_out, sh.tr);
+  SPR_REQUIRE(ws != nullptr && w.ok(), "block_tail: workspace too small");
   TailArgs a;
-  a.part = w.take<double>(((size_t)cdiv(n, sh.tr) + nb) * nbr * 2 * n_out);
-  a.stats = w.take<float>((size_t)nb * nbr * 2 * n_out);
-  float* mp[4];
-  for (int i = 0; i < 4; ++i) mp[i] = w.take<float>(kAmaxParts);
-  SPR_REQUIRE(w.ok() && mp[3] != nullptr, "block_tail: workspace carve failed");
+  a.part = l.part;
+  a.stats = l.stats;
+  float* const* mp = l.mp;
   a.xa = xa; a.xb = xb; a.wa = wa; a.wb = wb; a.add = add; a.cu = cu; a.tile_cu = tiles;
   a.tile_desc = reinterpret_cast<const int4*>(tiles + tiles_desc_offset(nb));
   a.nb = nb; a.n = n; a.n_total = n_out; a.slope = slope; a.out = out; a.out_range = out_range; a.nslots = out_range_n;

@@ -388,10 +388,10 @@ struct CircleWs {
   float *rcoef, *ccoef, *rgpart, *cgpart;
 };
 
-bool carve(void* ws, size_t ws_bytes, int nbatch, int max_n, int max_m, CircleWs& c) {
+CircleWs circle_layout(Workspace& w, int nbatch, int max_n, int max_m) {
   const size_t R = (size_t)nbatch * max_n, C = (size_t)nbatch * max_m;
   const size_t tn = cdiv(max_n, CT), tm = cdiv(max_m, CT);
-  Workspace w(ws, ws_bytes);
+  CircleWs c;
   c.axyz = w.take<float>(R * 3);
   c.rpart = w.take<float2>(R * tm * 2);
   c.cpart = w.take<float2>(C * tn * 2);
@@ -405,7 +405,7 @@ bool carve(void* ws, size_t ws_bytes, int nbatch, int max_n, int max_m, CircleWs
   c.ccoef = w.take<float>(C);
   c.rgpart = w.take<float>(R * tm);
   c.cgpart = w.take<float>(C * tn);
-  return w.ok() && c.cgpart != nullptr;
+  return c;
 }
 
 // the launches shared by the forward and the backward: transform, tile partials, merged statistics
@@ -427,11 +427,7 @@ using namespace spr;
 
 extern "C" size_t spr_circle_loss_workspace_bytes(int nbatch, int max_n, int max_m) {
   if (nbatch < 1 || max_n < 1 || max_m < 1) return 0;
-  const size_t R = (size_t)nbatch * max_n, C = (size_t)nbatch * max_m;
-  const size_t tn = cdiv(max_n, CT), tm = cdiv(max_m, CT);
-  return align_up(R * 12, 256) + align_up(R * tm * 16, 256) + align_up(C * tn * 16, 256) + align_up(R * tm, 256) +
-         align_up(C * tn, 256) + align_up(R * 16, 256) + align_up(C * 16, 256) + 2 * align_up(R * 4, 256) +
-         2 * align_up(C * 4, 256) + align_up(R * tm * 4, 256) + align_up(C * tn * 4, 256);
+  return measure(circle_layout, nbatch, max_n, max_m);
 }
 
 #define CIRCLE_ARGS_OK                                                                                           \
@@ -445,10 +441,9 @@ extern "C" int spr_circle_loss(const float* a, const float* bf, int d, const flo
   SPR_REQUIRE(CIRCLE_ARGS_OK && out, "circle_loss: bad arguments (nbatch=%d max_n=%d max_m=%d d=%d)", nbatch, max_n,
               max_m, d);
   SPR_REQUIRE((long)cdiv(max_n, CT) * cdiv(max_m, CT) < (1l << 31), "circle_loss: grid too large");
-  CircleWs c;
-  SPR_REQUIRE(ws && ws_bytes >= spr_circle_loss_workspace_bytes(nbatch, max_n, max_m) &&
-                  carve(ws, ws_bytes, nbatch, max_n, max_m, c),
-              "circle_loss: workspace too small");
+  Workspace w(ws, ws_bytes);
+  const CircleWs c = circle_layout(w, nbatch, max_n, max_m);
+  SPR_REQUIRE(ws != nullptr && w.ok(), "circle_loss: workspace too small");
   circle_stats(a, bf, d, xa, pose, xb, cu_a, cu_b, nbatch, max_n, max_m, r_p, r_n, c, stream);
   hipLaunchKernelGGL(k_circle_pair, dim3(nbatch), dim3(CB), 0, stream, cu_a, cu_b, c.rlse, c.rsel, c.clse, c.csel, out,
                      (const float*)nullptr, (float*)nullptr, (float*)nullptr);
@@ -464,10 +459,9 @@ extern "C" int spr_circle_loss_bwd(const float* a, const float* bf, int d, const
   SPR_REQUIRE(CIRCLE_ARGS_OK && gout && G && da && db,
               "circle_loss_bwd: bad arguments (nbatch=%d max_n=%d max_m=%d d=%d)", nbatch, max_n, max_m, d);
   SPR_REQUIRE((long)cdiv(max_n, CT) * cdiv(max_m, CT) < (1l << 31), "circle_loss_bwd: grid too large");
-  CircleWs c;
-  SPR_REQUIRE(ws && ws_bytes >= spr_circle_loss_workspace_bytes(nbatch, max_n, max_m) &&
-                  carve(ws, ws_bytes, nbatch, max_n, max_m, c),
-              "circle_loss_bwd: workspace too small");
+  Workspace w(ws, ws_bytes);
+  const CircleWs c = circle_layout(w, nbatch, max_n, max_m);
+  SPR_REQUIRE(ws != nullptr && w.ok(), "circle_loss_bwd: workspace too small");
   const int tn = cdiv(max_n, CT), tm = cdiv(max_m, CT);
   circle_stats(a, bf, d, xa, pose, xb, cu_a, cu_b, nbatch, max_n, max_m, r_p, r_n, c, stream);
   hipLaunchKernelGGL(k_circle_pair, dim3(nbatch), dim3(CB), 0, stream, cu_a, cu_b, c.rlse, c.rsel, c.clse, c.csel,

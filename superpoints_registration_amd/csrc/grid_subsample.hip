@@ -422,24 +422,53 @@ size_t sort_temp_bytes(int n) {
   return align_up(bytes > sb ? bytes : sb, 256) + 256;
 }
 
+// Sizes (n, nb) below 1 are measured as 1 (the size query's clamp).
+struct SubsampleWs {
+  CloudInfo* info;
+  unsigned long long *keys, *keys2, *vkey;
+  int *vals, *vals2, *flags, *vid, *vstart, *vfirst, *sval, *sval2, *listA, *listB, *nxt, *scan;
+  float* bary;
+  int *tfirst, *tcnt, *thead;   // bucket tables
+  int *cloud_cnt, *vcu, *out_cu;
+  int* scalars;                 // [0]=nvox [1]=err
+  size_t temp_bytes;
+  void* temp;
+};
+SubsampleWs subsample_layout(Workspace& w, int n, int nb) {
+  const size_t N = (size_t)(n > 0 ? n : 1), B = (size_t)(nb > 0 ? nb : 1);
+  SubsampleWs l;
+  l.info = w.take<CloudInfo>(B);
+  l.keys = w.take<unsigned long long>(N);
+  l.keys2 = w.take<unsigned long long>(N);
+  l.vkey = w.take<unsigned long long>(N);
+  for (int** p : {&l.vals, &l.vals2, &l.flags, &l.vid, &l.vstart, &l.vfirst, &l.sval, &l.sval2, &l.listA, &l.listB, &l.nxt,
+                  &l.scan})
+    *p = w.take<int>(N);
+  l.bary = w.take<float>(3 * N);
+  const size_t tsz = 3 * N + 16 * B + 64;
+  l.tfirst = w.take<int>(tsz);
+  l.tcnt = w.take<int>(tsz);
+  l.thead = w.take<int>(tsz);
+  l.cloud_cnt = w.take<int>(B + 1);
+  l.vcu = w.take<int>(B + 1);
+  l.out_cu = w.take<int>(B + 1);
+  l.scalars = w.take<int>(64);
+  l.temp_bytes = sort_temp_bytes(n);
+  l.temp = w.take<char>(l.temp_bytes);
+  // unused (a fourth per-cloud array and 768 scalar bytes that the size query has always counted): no kernel is handed
+  // a pointer into them; kept so that the size callers see does not change
+  (void)w.take<int>(B + 1);
+  (void)w.take<char>(768);
+  return l;
+}
+
 }  // namespace
 }  // namespace spr
 
 using namespace spr;
 
 extern "C" size_t spr_grid_subsample_workspace_bytes(int n, int nb) {
-  const size_t N = (size_t)(n > 0 ? n : 1), B = (size_t)(nb > 0 ? nb : 1);
-  size_t b = 0;
-  b += align_up(sizeof(CloudInfo) * B, 256);
-  b += 3 * align_up(8 * N, 256);           // keys in/out, vkey
-  b += 10 * align_up(4 * N, 256);          // vals in/out, flags, vid, vstart, vfirst, sval x2, listA, listB
-  b += 2 * align_up(4 * N, 256);           // nxt, scan
-  b += align_up(12 * N, 256);              // bary
-  b += 3 * align_up(4 * (3 * N + 16 * B + 64), 256);  // bucket tables
-  b += 4 * align_up(4 * (B + 1), 256);     // cloud_cnt, vcu, out_cu, misc
-  b += 1024;                               // scalars
-  b += sort_temp_bytes(n);
-  return b;
+  return measure(subsample_layout, n, nb);
 }
 
 extern "C" int spr_grid_subsample(const float* xyz, const int* cu, int n, int nb,
@@ -452,38 +481,11 @@ extern "C" int spr_grid_subsample(const float* xyz, const int* cu, int n, int nb
   SPR_REQUIRE(nb < (1 << 23), "grid_subsample: too many clouds");
   // reference: subsampling an empty batch is an error (wrapper.cpp:266-270)
   SPR_REQUIRE(n > 0, "grid_subsample: empty input");
-  SPR_REQUIRE(ws != nullptr && ws_bytes >= spr_grid_subsample_workspace_bytes(n, nb),
-              "grid_subsample: workspace too small");
   Workspace w(ws, ws_bytes);
+  const auto [info, keys, keys2, vkey, vals, vals2, flags, vid, vstart, vfirst, sval, sval2, listA, listB, nxt, scan, bary,
+              tfirst, tcnt, thead, cloud_cnt, vcu, out_cu, scalars, temp_bytes, temp] = subsample_layout(w, n, nb);
+  SPR_REQUIRE(ws != nullptr && w.ok(), "grid_subsample: workspace too small");
   const size_t N = (size_t)n;
-  CloudInfo* info = w.take<CloudInfo>(nb);
-  unsigned long long* keys = w.take<unsigned long long>(N);
-  unsigned long long* keys2 = w.take<unsigned long long>(N);
-  unsigned long long* vkey = w.take<unsigned long long>(N);
-  int* vals = w.take<int>(N);
-  int* vals2 = w.take<int>(N);
-  int* flags = w.take<int>(N);
-  int* vid = w.take<int>(N);
-  int* vstart = w.take<int>(N);
-  int* vfirst = w.take<int>(N);
-  int* sval = w.take<int>(N);
-  int* sval2 = w.take<int>(N);
-  int* listA = w.take<int>(N);
-  int* listB = w.take<int>(N);
-  int* nxt = w.take<int>(N);
-  int* scan = w.take<int>(N);
-  float* bary = w.take<float>(3 * N);
-  const size_t tsz = 3 * N + 16 * (size_t)nb + 64;
-  int* tfirst = w.take<int>(tsz);
-  int* tcnt = w.take<int>(tsz);
-  int* thead = w.take<int>(tsz);
-  int* cloud_cnt = w.take<int>(nb + 1);
-  int* vcu = w.take<int>(nb + 1);
-  int* out_cu = w.take<int>(nb + 1);
-  int* scalars = w.take<int>(64);  // [0]=nvox [1]=err
-  size_t temp_bytes = sort_temp_bytes(n);
-  void* temp = w.take<char>(temp_bytes);
-  SPR_REQUIRE(w.ok() && temp != nullptr, "grid_subsample: workspace carve failed");
   int* nvox = scalars;
   int* err = scalars + 1;
 
@@ -580,23 +582,39 @@ __global__ void k_order_keys(const float* __restrict__ xyz, const int* __restric
 }  // namespace
 }  // namespace spr
 
-extern "C" size_t spr_cell_order_workspace_bytes(int n) {
+namespace spr {
+namespace {
+struct CellOrderWs {
+  unsigned long long *keys, *keys2;
+  int* vals;
+  size_t temp_bytes;
+  void* temp;
+};
+CellOrderWs cell_order_layout(Workspace& w, int n) {
   const size_t N = (size_t)(n > 0 ? n : 1);
-  return 2 * align_up(8 * N, 256) + align_up(4 * N, 256) + sort_temp_bytes(n) + 256;
+  CellOrderWs l;
+  l.keys = w.take<unsigned long long>(N);
+  l.keys2 = w.take<unsigned long long>(N);
+  l.vals = w.take<int>(N);
+  l.temp_bytes = sort_temp_bytes(n);
+  l.temp = w.take<char>(l.temp_bytes);
+  (void)w.take<char>(256);   // unused: the size query has always counted it, and callers see the same size as before
+  return l;
+}
+}  // namespace
+}  // namespace spr
+
+extern "C" size_t spr_cell_order_workspace_bytes(int n) {
+  return measure(cell_order_layout, n);
 }
 
 extern "C" int spr_cell_order(const float* xyz, const int* cu, int n, int nb, float cell, int* order, void* ws,
                               size_t ws_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   SPR_REQUIRE(n >= 1 && nb >= 1 && nb < (1 << 30) && cell > 0.f, "cell_order: bad arguments");
-  SPR_REQUIRE(ws != nullptr && ws_bytes >= spr_cell_order_workspace_bytes(n), "cell_order: workspace too small");
   Workspace w(ws, ws_bytes);
-  unsigned long long* keys = w.take<unsigned long long>(n);
-  unsigned long long* keys2 = w.take<unsigned long long>(n);
-  int* vals = w.take<int>(n);
-  size_t tb = sort_temp_bytes(n);
-  void* temp = w.take<char>(tb);
-  SPR_REQUIRE(w.ok() && temp != nullptr, "cell_order: workspace carve failed");
+  auto [keys, keys2, vals, tb, temp] = cell_order_layout(w, n);
+  SPR_REQUIRE(ws != nullptr && w.ok(), "cell_order: workspace too small");
   hipLaunchKernelGGL(k_order_keys, dim3(cdiv(n, 256)), dim3(256), 0, stream, xyz, cu, n, nb, 1.0f / cell, keys, vals);
   SPR_LAUNCH_CHECK();
   int bits = 31;
@@ -651,12 +669,33 @@ size_t vox_temp_bytes(int n) {
                            32);
   return align_up(a > b ? a : b, 256);
 }
+struct VoxelWs {
+  unsigned long long *keys, *keys2;
+  int *vals, *vals2;
+  unsigned int *sel, *sel2;
+  int* err;
+  size_t temp_bytes;
+  void* temp;
+};
+VoxelWs voxel_layout(Workspace& w, int n) {
+  const size_t N = (size_t)(n > 0 ? n : 1);
+  VoxelWs l;
+  l.keys = w.take<unsigned long long>(N);
+  l.keys2 = w.take<unsigned long long>(N);
+  l.vals = w.take<int>(N);
+  l.vals2 = w.take<int>(N);
+  l.sel = w.take<unsigned int>(N);
+  l.sel2 = w.take<unsigned int>(N);
+  l.err = w.take<int>(1);
+  l.temp_bytes = vox_temp_bytes(n);
+  l.temp = w.take<char>(l.temp_bytes);
+  return l;
+}
 }  // namespace
 }  // namespace spr
 
 extern "C" size_t spr_voxel_downsample_workspace_bytes(int n) {
-  const size_t N = (size_t)(n > 0 ? n : 1);
-  return 2 * align_up(8 * N, 256) + 4 * align_up(4 * N, 256) + 256 + spr::vox_temp_bytes(n);
+  return measure(spr::voxel_layout, n);
 }
 
 // out_idx [n] i32: the first out_count[0] entries are the kept original indices (ascending);
@@ -665,18 +704,9 @@ extern "C" int spr_voxel_downsample(const float* xyz, int n, double voxel_size, 
                                     size_t ws_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   SPR_REQUIRE(n >= 1 && voxel_size > 0.0 && xyz && out_idx && out_count, "voxel_downsample: bad arguments");
-  SPR_REQUIRE(ws && ws_bytes >= spr_voxel_downsample_workspace_bytes(n), "voxel_downsample: workspace too small");
   Workspace w(ws, ws_bytes);
-  unsigned long long* keys = w.take<unsigned long long>(n);
-  unsigned long long* keys2 = w.take<unsigned long long>(n);
-  int* vals = w.take<int>(n);
-  int* vals2 = w.take<int>(n);
-  unsigned int* sel = w.take<unsigned int>(n);
-  unsigned int* sel2 = w.take<unsigned int>(n);
-  int* err = w.take<int>(1);
-  const size_t temp_bytes = vox_temp_bytes(n);
-  void* temp = w.take<char>(temp_bytes);
-  SPR_REQUIRE(w.ok() && temp != nullptr, "voxel_downsample: workspace carve failed");
+  const auto [keys, keys2, vals, vals2, sel, sel2, err, temp_bytes, temp] = voxel_layout(w, n);
+  SPR_REQUIRE(ws != nullptr && w.ok(), "voxel_downsample: workspace too small");
   SPR_HIP_CHECK(hipMemsetAsync(err, 0, sizeof(int), stream));
   SPR_HIP_CHECK(hipMemsetAsync(out_count, 0, sizeof(int), stream));
   const int TBk = 256;

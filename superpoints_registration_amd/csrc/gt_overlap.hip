@@ -346,6 +346,33 @@ size_t ov_scan_temp_bytes(size_t n) {
   return align_up(b, 256) + 256;
 }
 
+struct OvWs {
+  OvGrid* info;
+  int *ccu, *err, *count, *start, *cell_of, *rank;
+  OvRec* rec;
+  int *flag, *pos;
+  void* temp;
+  size_t cells, temp_bytes;
+};
+OvWs ov_layout(Workspace& w, int ns, int nt, int nb) {
+  OvWs l;
+  const size_t np = (size_t)ns + (size_t)nt, B = nb > 0 ? nb : 1;   // the query measures nb = 0 as one pair
+  l.cells = ov_cells(ns, nt, nb);
+  l.info = w.take<OvGrid>(2 * B);
+  l.ccu = w.take<int>(2 * B + 1);
+  l.err = w.take<int>(64);
+  l.count = w.take<int>(l.cells + 1);
+  l.start = w.take<int>(l.cells + 1);
+  l.cell_of = w.take<int>(np > 0 ? np : 1);
+  l.rank = w.take<int>(np > 0 ? np : 1);
+  l.rec = w.take<OvRec>(np > 0 ? np : 1);
+  l.flag = w.take<int>((size_t)ns + 1);
+  l.pos = w.take<int>((size_t)ns + 1);
+  l.temp_bytes = ov_scan_temp_bytes(l.cells + 1 > (size_t)ns + 1 ? l.cells + 1 : (size_t)ns + 1);
+  l.temp = w.take<char>(l.temp_bytes);
+  return l;
+}
+
 }  // namespace
 }  // namespace spr
 
@@ -353,17 +380,7 @@ using namespace spr;
 
 extern "C" size_t spr_gt_overlap_workspace_bytes(int ns, int nt, int nb) {
   if (ns < 0 || nt < 0 || nb < 0) return 0;
-  const size_t P = (size_t)ns + (size_t)nt, B = (size_t)(nb > 0 ? nb : 1), cells = ov_cells(ns, nt, nb);
-  size_t b = 0;
-  b += align_up(sizeof(OvGrid) * 2 * B, 256);       // grids
-  b += align_up(4 * (2 * B + 1), 256);              // combined cu
-  b += 256;                                         // error flag
-  b += 2 * align_up(4 * (cells + 1), 256);          // cell counts, cell starts
-  b += 2 * align_up(4 * (P > 0 ? P : 1), 256);      // cell of a point, its rank
-  b += align_up(sizeof(OvRec) * (P > 0 ? P : 1), 256);
-  b += 2 * align_up(4 * ((size_t)ns + 1), 256);     // mutual flags, their prefix
-  b += ov_scan_temp_bytes(cells + 1 > (size_t)ns + 1 ? cells + 1 : (size_t)ns + 1);
-  return b;
+  return measure(ov_layout, ns, nt, nb);
 }
 
 extern "C" int spr_gt_overlap(const float* src_xyz, const int* src_cu, int ns, const float* tgt_xyz,
@@ -380,24 +397,10 @@ extern "C" int spr_gt_overlap(const float* src_xyz, const int* src_cu, int ns, c
   SPR_REQUIRE(src_cu && tgt_cu && pose && corr_count, "gt_overlap: src_cu, tgt_cu, pose and corr_count must not be null");
   SPR_REQUIRE(ns == 0 || (src_xyz && src_corr && src_mask && corr), "gt_overlap: null source pointer with ns=%d", ns);
   SPR_REQUIRE(nt == 0 || (tgt_xyz && tgt_corr && tgt_mask), "gt_overlap: null target pointer with nt=%d", nt);
-  SPR_REQUIRE(ws != nullptr && ws_bytes >= spr_gt_overlap_workspace_bytes(ns, nt, nb), "gt_overlap: workspace too small");
-
-  const int np = ns + nt;
-  const size_t cells = ov_cells(ns, nt, nb);
   Workspace w(ws, ws_bytes);
-  OvGrid* info = w.take<OvGrid>(2 * (size_t)nb);
-  int* ccu = w.take<int>(2 * (size_t)nb + 1);
-  int* err = w.take<int>(64);
-  int* count = w.take<int>(cells + 1);
-  int* start = w.take<int>(cells + 1);
-  int* cell_of = w.take<int>(np > 0 ? np : 1);
-  int* rank = w.take<int>(np > 0 ? np : 1);
-  OvRec* rec = w.take<OvRec>(np > 0 ? np : 1);
-  int* flag = w.take<int>((size_t)ns + 1);
-  int* pos = w.take<int>((size_t)ns + 1);
-  size_t temp_bytes = ov_scan_temp_bytes(cells + 1 > (size_t)ns + 1 ? cells + 1 : (size_t)ns + 1);
-  void* temp = w.take<char>(temp_bytes);
-  SPR_REQUIRE(w.ok() && temp != nullptr, "gt_overlap: workspace carve failed");
+  const auto [info, ccu, err, count, start, cell_of, rank, rec, flag, pos, temp, cells, temp_bytes] = ov_layout(w, ns, nt, nb);
+  SPR_REQUIRE(ws != nullptr && w.ok(), "gt_overlap: workspace too small");
+  const int np = ns + nt;
 
   const double h0 = radius * (1.0 + 1.0 / 256.0);
   const double r2 = radius * radius;

@@ -1328,30 +1328,78 @@ extern "C" int spr_debug_kp_trace(unsigned long long* out, int n) {   // n <= 8 
 }
 #endif
 
-static inline size_t plan_desc_bytes(int nq) { return align_up((size_t)cdiv(nq > 0 ? nq : 1, kRingTQ) * 8 * sizeof(int4), 256); }
+// The two persistent blobs and the workspace, each laid out once: the size queries measure these functions, the
+// producers and the consumer carve with them.
+struct KpPlan {
+  int4* desc;      // 8 descriptors per tile of kRingTQ queries
+  int* pad_word;
+};
+static KpPlan plan_view(Workspace& w, int nq) {
+  KpPlan p;
+  p.desc = w.take<int4>((size_t)cdiv(nq > 0 ? nq : 1, kRingTQ) * 8);
+  p.pad_word = w.take<int>(64);
+  return p;
+}
+struct KpWPlanes {
+  _Float16 *hi, *lo;   // pre-split fragment-order weights (room for 32 kernel points)
+};
+static KpWPlanes wplanes_view(Workspace& w, int cin, int cout) {
+  const size_t n = (size_t)32 * (size_t)(cin > 0 ? cin : 0) * (size_t)(cout > 0 ? cout : 0);
+  KpWPlanes p;
+  p.hi = w.take<_Float16>(n);
+  p.lo = w.take<_Float16>(n);
+  return p;
+}
+struct KpWs {
+  unsigned char* flag;
+  float4* sxf;         // {x,y,z,flag} support records
+  KpWPlanes wplanes;
+  float *x_parts, *w_parts;
+  KpPlan plan;
+  int* tile_ctr;
+};
+static KpWs kpconv_layout(Workspace& w, int nq, int ns, int cin, int cout) {
+  const size_t n = (size_t)(ns > 0 ? ns : 1);
+  KpWs l;
+  l.flag = w.take<unsigned char>(n);
+  l.sxf = w.take<float4>(n + 1);
+  l.wplanes = wplanes_view(w, cin, cout);
+  l.x_parts = w.take<float>(kAmaxParts);
+  l.w_parts = w.take<float>(kAmaxParts);
+  l.plan = plan_view(w, nq);
+  l.tile_ctr = w.take<int>(64);
+  return l;
+}
 static inline int w_chunk(int cin) { return cin % 64 == 0 ? 64 : 32; }
 static inline bool ring_shape(int cin, int cout) {
   return (cin == 32 || cin == 64) && cin * cout <= 4096 && cout % 32 == 0 && 8 % (cout / 16) == 0;
 }
 
-extern "C" size_t spr_kpconv_plan_bytes(int nq) { return plan_desc_bytes(nq) + 256; }
+extern "C" size_t spr_kpconv_plan_bytes(int nq) {
+  return measure(plan_view, nq);
+}
+
+static int launch_plan(const int* nbr, int nq, int ns, int nbr_stride, int kmax, int rows_sorted, const int* order,
+                       const KpPlan& p, hipStream_t stream) {
+  const int ntiles = cdiv(nq, kRingTQ);
+  hipLaunchKernelGGL(k_kp_tiles, dim3(cdiv((long)ntiles * 64, 256)), dim3(256), 0, stream, nbr, nq, ns, nbr_stride,
+                     kmax, rows_sorted, order, ntiles, p.desc, p.pad_word);
+  SPR_LAUNCH_CHECK();
+  return 0;
+}
 
 extern "C" int spr_kpconv_plan(const int* nbr, int nq, int ns, int nbr_stride, int kmax, int rows_sorted,
                                const int* order, void* plan, size_t plan_bytes, void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   SPR_REQUIRE(nq > 0 && ns > 0 && kmax >= 1 && kmax <= nbr_stride, "kpconv plan: bad sizes");
-  SPR_REQUIRE(plan != nullptr && plan_bytes >= spr_kpconv_plan_bytes(nq), "kpconv plan: buffer too small");
-  const int ntiles = cdiv(nq, kRingTQ);
-  int4* desc = (int4*)plan;
-  int* pad_word = (int*)((char*)plan + plan_desc_bytes(nq));
-  hipLaunchKernelGGL(k_kp_tiles, dim3(cdiv((long)ntiles * 64, 256)), dim3(256), 0, stream, nbr, nq, ns, nbr_stride,
-                     kmax, rows_sorted, order, ntiles, desc, pad_word);
-  SPR_LAUNCH_CHECK();
-  return 0;
+  Workspace w(plan, plan_bytes);
+  const KpPlan p = plan_view(w, nq);
+  SPR_REQUIRE(plan != nullptr && w.ok(), "kpconv plan: buffer too small");
+  return launch_plan(nbr, nq, ns, nbr_stride, kmax, rows_sorted, order, p, stream);
 }
 
 extern "C" size_t spr_kpconv_wplanes_bytes(int cin, int cout) {
-  return 2 * align_up((size_t)32 * (size_t)(cin > 0 ? cin : 0) * (size_t)(cout > 0 ? cout : 0) * 2, 256);
+  return measure(wplanes_view, cin, cout);
 }
 
 extern "C" int spr_kpconv_prep_weights(const float* weights, int n_kp, int cin, int cout, const float* w_range,
@@ -1360,9 +1408,9 @@ extern "C" int spr_kpconv_prep_weights(const float* weights, int n_kp, int cin, 
   SPR_REQUIRE(n_kp == kKP && cin % 32 == 0 && cout % 32 == 0 && cout <= 256,
               "kpconv weight planes exist for the MFMA shapes only (15 kernel points, channels in multiples of 32)");
   SPR_REQUIRE(w_range != nullptr && w_range_n >= 1, "kpconv weight planes: the weight range is required");
-  SPR_REQUIRE(wplanes != nullptr && bytes >= spr_kpconv_wplanes_bytes(cin, cout), "kpconv weight planes: buffer too small");
-  _Float16* wh = (_Float16*)wplanes;
-  _Float16* wl = (_Float16*)((char*)wplanes + align_up((size_t)32 * cin * cout * 2, 256));
+  Workspace w(wplanes, bytes);
+  const auto [wh, wl] = wplanes_view(w, cin, cout);
+  SPR_REQUIRE(wplanes != nullptr && w.ok(), "kpconv weight planes: buffer too small");
   hipLaunchKernelGGL(k_w_prep, dim3(cdiv((long)n_kp * cin * cout, 256)), dim3(256), 0, stream, weights, cin, cout,
                      w_chunk(cin), w_range, w_range_n, wh, wl);
   SPR_LAUNCH_CHECK();
@@ -1370,11 +1418,7 @@ extern "C" int spr_kpconv_prep_weights(const float* weights, int n_kp, int cin, 
 }
 
 extern "C" size_t spr_kpconv_workspace_bytes(int nq, int ns, int cin, int cout) {
-  // flag bytes + {x,y,z,flag} support records + pre-split fragment-order weights (hi, lo fp16; up to
-  // 32 kernel points)
-  const size_t n = (size_t)(ns > 0 ? ns : 1);
-  return align_up(n, 256) + align_up(16 * (n + 1), 256) + spr_kpconv_wplanes_bytes(cin, cout) +
-         2 * align_up(kAmaxParts * sizeof(float), 256) + spr_kpconv_plan_bytes(nq) + 256;
+  return measure(kpconv_layout, nq, ns, cin, cout);
 }
 
 // x_range / w_range: operand ranges handed in (see spr_linear); NULL = measured here.
@@ -1394,20 +1438,13 @@ extern "C" int spr_kpconv_fwd(const float* q_xyz, int nq, const float* s_xyz, in
   SPR_REQUIRE(kmax >= 1 && kmax <= nbr_stride, "kpconv: bad kmax=%d stride=%d", kmax, nbr_stride);
   SPR_REQUIRE(cin >= 1 && cout >= 1 && n_kp >= 1 && n_kp <= 32, "kpconv: bad dims");
   SPR_REQUIRE(kp_extent > 0.f, "kpconv: KP_extent must be > 0");
-  SPR_REQUIRE(ws != nullptr && ws_bytes >= spr_kpconv_workspace_bytes(nq, ns, cin, cout), "kpconv: workspace too small");
-  unsigned char* flag = (unsigned char*)ws;
-  float4* sxf = (float4*)((char*)ws + align_up((size_t)ns, 256));
-  _Float16* wh = (_Float16*)((char*)sxf + align_up(((size_t)ns + 1) * 16, 256));
-  _Float16* wl = (_Float16*)((char*)wh + align_up((size_t)32 * cin * cout * 2, 256));
-  float* x_parts = (float*)((char*)wl + align_up((size_t)32 * cin * cout * 2, 256));
-  float* w_parts = x_parts + align_up(kAmaxParts * sizeof(float), 256) / sizeof(float);
-  void* ws_plan = (char*)w_parts + align_up(kAmaxParts * sizeof(float), 256);
-  int* tile_ctr = (int*)((char*)ws_plan + spr_kpconv_plan_bytes(nq));
+  Workspace w(ws, ws_bytes);
+  const auto [flag, sxf, own_wplanes, x_parts, w_parts, own_plan, tile_ctr] = kpconv_layout(w, nq, ns, cin, cout);
+  SPR_REQUIRE(ws != nullptr && w.ok(), "kpconv: workspace too small");
   SPR_REQUIRE(wplanes == nullptr || w_range != nullptr, "kpconv: prepared weight planes come with the range they were scaled by");
-  if (wplanes != nullptr) {
-    wh = (_Float16*)wplanes;
-    wl = (_Float16*)((char*)wplanes + align_up((size_t)32 * cin * cout * 2, 256));
-  }
+  // buffers handed in were sized when they were filled (spr_kpconv_prep_weights, spr_kpconv_plan)
+  Workspace given_w(const_cast<void*>(wplanes), SIZE_MAX), given_p(const_cast<void*>(plan), SIZE_MAX);
+  const auto [wh, wl] = wplanes != nullptr ? wplanes_view(given_w, cin, cout) : own_wplanes;
   const float inv_extent = 1.0f / kp_extent;
 
   if (cin == 1 && (impl == 0 || impl == 2) && n_kp <= 16) {
@@ -1445,13 +1482,9 @@ extern "C" int spr_kpconv_fwd(const float* q_xyz, int nq, const float* s_xyz, in
     const bool ring_ok = impl == 0 && ring_shape(cin, cout) && kmax <= 128 && (size_t)ns * cin * 4 < (1ull << 32) &&
                          (size_t)nq * nbr_stride * 4 < (1ull << 32);
     if (ring_ok) {
-      if (plan == nullptr) {
-        if (int rc = spr_kpconv_plan(nbr, nq, ns, nbr_stride, kmax, rows_sorted, nullptr, ws_plan,
-                                     spr_kpconv_plan_bytes(nq), stream_)) return rc;
-        plan = ws_plan;
-      }
-      const int4* desc = (const int4*)plan;
-      const int* pad_word = (const int*)((const char*)plan + plan_desc_bytes(nq));
+      if (plan == nullptr)
+        if (int rc = launch_plan(nbr, nq, ns, nbr_stride, kmax, rows_sorted, nullptr, own_plan, stream)) return rc;
+      const auto [desc, pad_word] = plan != nullptr ? plan_view(given_p, nq) : own_plan;
 #define SPR_RING_ARGS                                                                                       \
   q_xyz, nq, ns, nbr, nbr_stride, kmax, x, wh, wl, kernel_points, inv_extent, sxf, desc, pad_word, xp, wp, \
       n_xp, n_wp, tile_ctr, out, stream

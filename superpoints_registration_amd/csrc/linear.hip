@@ -993,7 +993,21 @@ int spr::launch_gemm_grouped(const float* a, int k, const float* b, float* c, co
   return 1;
 }
 
-extern "C" size_t spr_linear_workspace_bytes(void) { return 2 * align_up(kAmaxParts * sizeof(float), 256); }
+namespace {
+struct LinearWs {
+  float *ap, *wp;   // max |x|, max |w| partials
+};
+LinearWs linear_layout(Workspace& w) {
+  LinearWs l;
+  l.ap = w.take<float>(kAmaxParts);
+  l.wp = w.take<float>(kAmaxParts);
+  return l;
+}
+}  // namespace
+
+extern "C" size_t spr_linear_workspace_bytes(void) {
+  return measure(linear_layout);
+}
 
 extern "C" int spr_linear(const float* x, int m, int k, const float* w, int n, const float* bias,
                           const float* residual, int act, float* out, const float* x_range, int x_range_n,
@@ -1016,12 +1030,10 @@ extern "C" int spr_linear(const float* x, int m, int k, const float* w, int n, c
   const float *a_parts = nullptr, *w_parts = nullptr;
   int n_ap = kAmaxParts, n_wp = kAmaxParts;
   if (spr::gemm_mode() == 1) {
-    SPR_REQUIRE(ws != nullptr && ws_bytes >= spr_linear_workspace_bytes(),
-                "linear: workspace too small (%zu bytes given, spr_linear_workspace_bytes() needed)", ws_bytes);
     Workspace wk(ws, ws_bytes);
-    float* ap = wk.take<float>(kAmaxParts);
-    float* wp = wk.take<float>(kAmaxParts);
-    SPR_REQUIRE(wk.ok(), "linear: workspace carve failed");
+    const auto [ap, wp] = linear_layout(wk);
+    SPR_REQUIRE(ws != nullptr && wk.ok(),
+                "linear: workspace too small (%zu bytes given, spr_linear_workspace_bytes() needed)", ws_bytes);
     // ranges handed in (x: published by its producer; w: measured once per weight version by
     // the caller, spr_absmax) are not measured again -- with both there is no pre-pass at all
     a_parts = x_range != nullptr ? x_range : ap;

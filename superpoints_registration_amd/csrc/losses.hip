@@ -308,12 +308,39 @@ extern "C" int spr_overlap_pool(const float* ov_prev, int ns_prev, const int* po
 // cannot wrap size_t inside it
 static constexpr int kLossMaxD = 46336;
 
+namespace {
+// InfoNCE of one pair, forward and backward (the backward writes t and wsym into its outputs and leaves the row terms
+// unused, at the same offsets).  spr_loss_workspace_bytes measures this layout: the other two users of that query,
+// BCE and the transform L1, need one array of block partials (loss_partials), which pa alone exceeds.
+struct InfonceWs {
+  float *logits, *t, *wsym, *axyz, *rl, *rm;
+  double *pa, *pb;
+  size_t lws;        // two spr_linear workspaces
+  char *lw1, *lw2;
+};
+InfonceWs infonce_layout(Workspace& w, int n_max, int m_max, int d) {
+  const size_t n = (size_t)(n_max > 0 ? n_max : 1), m = (size_t)(m_max > 0 ? m_max : 1);
+  InfonceWs l;
+  l.logits = w.take<float>(n * m);
+  l.t = w.take<float>(n * d);
+  l.wsym = w.take<float>((size_t)d * d);
+  l.axyz = w.take<float>(n * 3);
+  l.rl = w.take<float>(n);
+  l.rm = w.take<float>(n);
+  l.pa = w.take<double>(cdiv(n, RB));
+  l.pb = w.take<double>(cdiv(n, RB));
+  l.lws = spr_linear_workspace_bytes();
+  l.lw1 = w.take<char>(l.lws);
+  l.lw2 = w.take<char>(l.lws);
+  (void)w.take<char>(1024);   // unused: the size query has always counted it, and callers see the same size as before
+  return l;
+}
+double* loss_partials(Workspace& w, int n) { return w.take<double>(cdiv(n, RB)); }
+}  // namespace
+
 extern "C" size_t spr_loss_workspace_bytes(int n_max, int m_max, int d) {
   if (n_max < 0 || m_max < 0 || d < 0) return 0;
-  const size_t n = (size_t)(n_max > 0 ? n_max : 1), m = (size_t)(m_max > 0 ? m_max : 1);
-  return align_up(n * m * 4, 256) + align_up(n * d * 4, 256) + align_up((size_t)d * d * 4, 256) +
-         align_up(n * 12, 256) + 2 * align_up(n * 4, 256) + 2 * align_up((size_t)cdiv(n, RB) * 8, 256) +
-         2 * spr_linear_workspace_bytes() + 1024;
+  return measure(infonce_layout, n_max, m_max, d);
 }
 
 extern "C" int spr_bce_logits_mean(const float* x, const float* y, int n, float* out, void* ws,
@@ -321,8 +348,9 @@ extern "C" int spr_bce_logits_mean(const float* x, const float* y, int n, float*
   hipStream_t stream = (hipStream_t)stream_;
   SPR_REQUIRE(n >= 1, "bce: n must be >= 1");
   const int nb = cdiv(n, RB);
-  SPR_REQUIRE(ws != nullptr && ws_bytes >= (size_t)nb * 8, "bce: workspace too small");
-  double* partial = (double*)ws;
+  Workspace w(ws, ws_bytes);
+  double* partial = loss_partials(w, n);
+  SPR_REQUIRE(ws != nullptr && w.ok(), "bce: workspace too small");
   hipLaunchKernelGGL(k_bce_partial, dim3(nb), dim3(RB), 0, stream, x, y, n, partial);
   hipLaunchKernelGGL(k_finish, dim3(1), dim3(RB), 0, stream, partial, (const double*)nullptr, nb, 1.0 / n, out);
   SPR_LAUNCH_CHECK();
@@ -336,21 +364,10 @@ extern "C" int spr_infonce_pair(const float* anchor_feat, int n, const float* po
   hipStream_t stream = (hipStream_t)stream_;
   SPR_REQUIRE(n >= 1 && m >= 1 && d >= 32 && d % 32 == 0, "infonce: bad sizes n=%d m=%d d=%d", n, m, d);
   SPR_REQUIRE(d <= kLossMaxD, "infonce: d=%d, at most %d (d * d is an int in the launches)", d, kLossMaxD);
-  SPR_REQUIRE(ws != nullptr && ws_bytes >= spr_loss_workspace_bytes(n, m, d), "infonce: workspace too small");
   Workspace w(ws, ws_bytes);
-  float* logits = w.take<float>((size_t)n * m);
-  float* t = w.take<float>((size_t)n * d);
-  float* wsym = w.take<float>((size_t)d * d);
-  float* axyz = w.take<float>((size_t)n * 3);
-  float* rl = w.take<float>(n);
-  float* rm = w.take<float>(n);
+  const auto [logits, t, wsym, axyz, rl, rm, pa, pb, lws, lw1, lw2] = infonce_layout(w, n, m, d);
+  SPR_REQUIRE(ws != nullptr && w.ok(), "infonce: workspace too small");
   const int nb = cdiv(n, RB);
-  double* pa = w.take<double>(nb);
-  double* pb = w.take<double>(nb);
-  const size_t lws = spr_linear_workspace_bytes();
-  char* lw1 = w.take<char>(lws);
-  char* lw2 = w.take<char>(lws);
-  SPR_REQUIRE(w.ok() && pb != nullptr && lw2 != nullptr, "infonce: workspace carve failed");
   hipLaunchKernelGGL(k_wsym, dim3(cdiv(d * d, 256)), dim3(256), 0, stream, W, d, wsym);
   hipLaunchKernelGGL(k_transform, dim3(cdiv(n, 256)), dim3(256), 0, stream, pose_gt, anchor_xyz, n, axyz);
   // logits = (A W_sym) B^T : W_sym is symmetric, so the NT GEMM applies it as is
@@ -373,8 +390,9 @@ extern "C" int spr_transform_l1_pair(const float* pose_gt, const float* pose_pre
   hipStream_t stream = (hipStream_t)stream_;
   SPR_REQUIRE(n >= 1, "transform_l1: n must be >= 1");
   const int nb = cdiv(n, RB);
-  SPR_REQUIRE(ws != nullptr && ws_bytes >= (size_t)nb * 8, "transform_l1: workspace too small");
-  double* partial = (double*)ws;
+  Workspace w(ws, ws_bytes);
+  double* partial = loss_partials(w, n);
+  SPR_REQUIRE(ws != nullptr && w.ok(), "transform_l1: workspace too small");
   hipLaunchKernelGGL(k_tloss_partial, dim3(nb), dim3(RB), 0, stream, pose_gt, pose_pred, xyz, n, partial);
   hipLaunchKernelGGL(k_finish, dim3(1), dim3(RB), 0, stream, partial, (const double*)nullptr, nb, 1.0 / (3.0 * n),
                      out);
@@ -410,21 +428,12 @@ extern "C" int spr_infonce_pair_dlogits(const float* anchor_feat, int n, const f
   hipStream_t stream = (hipStream_t)stream_;
   SPR_REQUIRE(n >= 1 && m >= 1 && d >= 32 && d % 32 == 0, "infonce_bwd: bad sizes n=%d m=%d d=%d", n, m, d);
   SPR_REQUIRE(d <= kLossMaxD, "infonce_bwd: d=%d, at most %d (d * d is an int in the launches)", d, kLossMaxD);
-  SPR_REQUIRE(ws != nullptr && ws_bytes >= spr_loss_workspace_bytes(n, m, d), "infonce_bwd: workspace too small");
   Workspace w(ws, ws_bytes);
-  float* logits = w.take<float>((size_t)n * m);
-  (void)w.take<float>((size_t)n * d);
-  (void)w.take<float>((size_t)d * d);
-  float* axyz = w.take<float>((size_t)n * 3);
-  (void)w.take<float>(n);
-  (void)w.take<float>(n);
-  const int nb = cdiv(n, RB);
-  (void)w.take<double>(nb);
-  (void)w.take<double>(nb);
-  const size_t lws = spr_linear_workspace_bytes();
-  char* lw1 = w.take<char>(lws);
-  char* lw2 = w.take<char>(lws);
-  SPR_REQUIRE(w.ok() && lw2 != nullptr, "infonce_bwd: workspace carve failed");
+  const InfonceWs l = infonce_layout(w, n, m, d);
+  SPR_REQUIRE(ws != nullptr && w.ok(), "infonce_bwd: workspace too small");
+  float *logits = l.logits, *axyz = l.axyz;
+  char *lw1 = l.lw1, *lw2 = l.lw2;
+  const size_t lws = l.lws;
   hipLaunchKernelGGL(k_wsym, dim3(cdiv(d * d, 256)), dim3(256), 0, stream, W, d, wsym_out);
   hipLaunchKernelGGL(k_transform, dim3(cdiv(n, 256)), dim3(256), 0, stream, pose_gt, anchor_xyz, n, axyz);
   if (int rc = spr_linear(anchor_feat, n, d, wsym_out, d, nullptr, nullptr, SPR_ACT_NONE, t_out, nullptr, 0, nullptr, 0,

@@ -893,19 +893,83 @@ long long build_pairs(const int* cu_host, int npairs, PairDesc* h) {
   return off;
 }
 
-// bytes of the scratch, and of everything corr_setup carves around it
-size_t pair_mat_bytes(const int* cu_host, int npairs) {
+// The correlation scratch and everything corr_setup needs around it.  split: gemm_mode() == 1, the grouped split-fp16
+// product with its tile records and the two operand ranges (the size queries measure with them).
+struct CorrWs {
+  size_t total;   // floats of mat
+  float* mat;
+  PairDesc* pd;
+  GemmGroup* gg;
+  float *sparts, *tparts;
+};
+CorrWs corr_layout(Workspace& w, const int* cu_host, int npairs, bool split) {
   long long off = 0;
   for (int b = 0; b < npairs; ++b)
     off = next_pair_off(off, cu_host[b + 1] - cu_host[b], cu_host[npairs + b + 1] - cu_host[npairs + b]);
-  return align_up((size_t)off * 4, 256);
+  CorrWs l{};
+  l.total = (size_t)off;
+  l.mat = w.take<float>(l.total);
+  l.pd = w.take<PairDesc>(npairs);
+  if (split) {
+    l.gg = w.take<GemmGroup>(npairs);
+    l.sparts = w.take<float>(kAmaxParts);
+    l.tparts = w.take<float>(kAmaxParts);
+  }
+  return l;
 }
-size_t corr_ws_bytes(const int* cu_host, int npairs) {
-  return pair_mat_bytes(cu_host, npairs) + align_up(sizeof(PairDesc) * npairs, 256) +
-         align_up(sizeof(GemmGroup) * npairs, 256) + 2 * align_up(kAmaxParts * sizeof(float), 256);
+// The matching head (spr_match_workspace_bytes = spr_sinkhorn_workspace_bytes measure it with both heads wanted).
+struct HeadWs {
+  float* epi;   // {scale, softplus alpha, 1 / (e^beta + 0.02)}: the epilogue reads [0], the view all
+  CorrWs corr;
+  float *row_lse, *col_lse, *u, *v;
+};
+HeadWs head_layout(Workspace& w, const int* cu_host, int npairs, bool split, bool want_match, bool want_sinkhorn) {
+  const size_t T = (size_t)cu_host[2 * npairs];
+  HeadWs l{};
+  l.epi = w.take<float>(4);
+  l.corr = corr_layout(w, cu_host, npairs, split);
+  if (want_match) {
+    l.row_lse = w.take<float>(T);
+    l.col_lse = w.take<float>(T);
+  }
+  if (want_sinkhorn) {
+    l.u = w.take<float>(T);
+    l.v = w.take<float>(T);
+  }
+  (void)w.take<char>(1792);   // unused: the size query has always counted it, and callers see the same size as before
+  return l;
 }
-size_t match_ws_bytes(const int* cu_host, int npairs) {
-  return corr_ws_bytes(cu_host, npairs) + 4 * align_up((size_t)cu_host[2 * npairs] * 4, 256) + 2048;
+// spr_sinkhorn_bwd
+struct SinkhornBwdWs {
+  CorrWs corr;
+  float *corr_copy, *dmat;
+  GemmRec *rs, *rt;
+  double *U, *V;   // [max(n_iters, 1)][T] potentials in double (see k_row_lse)
+  float *du, *dva, *dvb;
+  double *zero, *parts;
+  float* epi;
+};
+SinkhornBwdWs sinkhorn_bwd_layout(Workspace& w, const int* cu_host, int npairs, int n_iters, bool split) {
+  const size_t T = (size_t)cu_host[2 * npairs], it = (size_t)(n_iters > 0 ? n_iters : 1);
+  SinkhornBwdWs l;
+  l.corr = corr_layout(w, cu_host, npairs, split);
+  l.corr_copy = w.take<float>(l.corr.total);
+  l.dmat = w.take<float>(l.corr.total);
+  l.rs = w.take<GemmRec>(npairs);
+  l.rt = w.take<GemmRec>(npairs);
+  l.U = w.take<double>(it * T);
+  l.V = w.take<double>(it * T);
+  l.du = w.take<float>(T);
+  l.dva = w.take<float>(T);
+  l.dvb = w.take<float>(T);
+  l.zero = w.take<double>(T);
+  l.parts = w.take<double>(2 * 1024);
+  l.epi = w.take<float>(4);
+  // unused: the size query has always counted U, V and zero as 4 it + 2 float arrays of T, each rounded up on its own,
+  // and 2816 bytes more; callers see the same size as before
+  const size_t a4 = align_up(T * 4, 256);
+  (void)w.take<char>((4 * it + 2) * a4 - 2 * align_up(it * T * 8, 256) - align_up(T * 8, 256) + 2816);
+  return l;
 }
 
 }  // namespace
@@ -914,10 +978,10 @@ size_t match_ws_bytes(const int* cu_host, int npairs) {
 using namespace spr;
 
 extern "C" size_t spr_match_workspace_bytes(const int* cu_host, int npairs) {
-  return match_ws_bytes(cu_host, npairs);
+  return measure(head_layout, cu_host, npairs, true, true, true);
 }
 extern "C" size_t spr_sinkhorn_workspace_bytes(const int* cu_host, int npairs) {
-  return match_ws_bytes(cu_host, npairs);
+  return spr_match_workspace_bytes(cu_host, npairs);
 }
 
 namespace {
@@ -984,16 +1048,15 @@ struct Corr {
     return l + 1 < npairs ? h[l + 1].off : total;
   }
 };
-int corr_setup(Corr& c, const float* feat, int d, const int* cu_dev, const int* cu_host, int npairs, Workspace& w,
-               hipStream_t stream, bool one_group) {
+int corr_setup(Corr& c, const float* feat, int d, const int* cu_dev, const int* cu_host, int npairs, const CorrWs& cw,
+               bool split, hipStream_t stream, bool one_group) {
   c.feat = feat;
   c.d = d;
   c.npairs = npairs;
   c.h.resize(npairs);
   c.total = build_pairs(cu_host, npairs, c.h.data());
-  c.mat = w.take<float>((size_t)c.total);
-  c.pd = w.take<PairDesc>(npairs);
-  SPR_REQUIRE(w.ok() && c.mat && c.pd, "match: workspace carve failed");
+  c.mat = cw.mat;
+  c.pd = cw.pd;
   c.max_n = 0;
   c.max_m = 0;
   c.min_m = 1 << 30;
@@ -1008,22 +1071,16 @@ int corr_setup(Corr& c, const float* feat, int d, const int* cu_dev, const int* 
   long long g = pair_bytes > 0 ? budget / pair_bytes : npairs;
   c.per_group = one_group ? npairs : (int)(g < 1 ? 1 : (g > npairs ? npairs : g));
   c.ngroups = cdiv(npairs, c.per_group);
-  c.grouped = gemm_mode() == 1 && d % 32 == 0;
-  c.gg = nullptr;
+  c.grouped = split && d % 32 == 0;
+  c.gg = c.grouped ? cw.gg : nullptr;
   int bm = 1, bn = 1;
-  if (c.grouped) {
-    c.gg = w.take<GemmGroup>(npairs);
-    SPR_REQUIRE(w.ok() && c.gg != nullptr, "match: workspace carve failed");
-    gemm_group_tile(c.max_m, &bm, &bn);
-  }
+  if (c.grouped) gemm_group_tile(c.max_m, &bm, &bn);
   // descriptors are rebuilt on the device from cu (no pageable host copy)
   hipLaunchKernelGGL(k_build_pairs, dim3(1), dim3(64), 0, stream, cu_dev, npairs, c.pd, c.gg, d, bm, bn, c.per_group);
   // two range measurements serve every pair: all src tokens (A operands), all tgt tokens (B)
   c.sparts = c.tparts = nullptr;
-  if (gemm_mode() == 1) {
-    float* ps = w.take<float>(kAmaxParts);
-    float* pt = w.take<float>(kAmaxParts);
-    SPR_REQUIRE(w.ok() && pt != nullptr, "match: workspace carve failed");
+  if (split) {
+    float *ps = cw.sparts, *pt = cw.tparts;
     const int nsrc = cu_host[npairs], ntot = cu_host[2 * npairs];
     if (int rc = launch_absmax2(feat, nsrc, d, d, ps, feat + (size_t)nsrc * d, ntot - nsrc, d, d, pt, stream))
       return rc;
@@ -1095,27 +1152,18 @@ int match_head(const HeadArgs& a, bool want_match, bool want_sinkhorn) {
   hipStream_t stream = a.stream;
   SPR_REQUIRE(a.npairs >= 1 && a.d % 32 == 0 && a.n_iters >= 0, "%s: need npairs >= 1, d %% 32 == 0, n_iters >= 0",
               a.name);
-  SPR_REQUIRE(a.ws_bytes >= match_ws_bytes(a.cu_host, a.npairs), "%s: workspace too small", a.name);
+  const bool split = gemm_mode() == 1;
   Workspace w(a.ws, a.ws_bytes);
+  const auto [epi, corr_ws, row_lse, col_lse, u, v] = head_layout(w, a.cu_host, a.npairs, split, want_match, want_sinkhorn);
+  SPR_REQUIRE(a.ws != nullptr && w.ok(), "%s: workspace too small", a.name);
   const float scale = 1.0f / sqrtf((float)a.d);
-  float* epi = w.take<float>(4);       // {scale, softplus alpha, 1 / (e^beta + 0.02)}: the epilogue reads [0], the view all
-  SPR_REQUIRE(w.ok() && epi != nullptr, "%s: workspace carve failed", a.name);
   hipLaunchKernelGGL(k_epi_params, dim3(1), dim3(64), 0, stream, scale, want_sinkhorn ? a.alpha : nullptr,
                      want_sinkhorn ? a.beta : nullptr, epi);
   const float* aff = want_sinkhorn ? epi : nullptr;
   Corr c;
-  if (corr_setup(c, a.feat, a.d, a.cu, a.cu_host, a.npairs, w, stream, false)) return 1;
+  if (corr_setup(c, a.feat, a.d, a.cu, a.cu_host, a.npairs, corr_ws, split, stream, false)) return 1;
   const int T = a.cu_host[2 * a.npairs];
-  float *row_lse = nullptr, *col_lse = nullptr, *u = nullptr, *v = nullptr;
-  if (want_match) {
-    row_lse = w.take<float>(T);
-    col_lse = w.take<float>(T);
-    SPR_REQUIRE(w.ok() && col_lse != nullptr, "%s: workspace carve failed", a.name);
-  }
   if (want_sinkhorn) {
-    u = w.take<float>(T);
-    v = w.take<float>(T);
-    SPR_REQUIRE(w.ok() && v != nullptr, "%s: workspace carve failed", a.name);
     SPR_HIP_CHECK(hipMemsetAsync(u, 0, sizeof(float) * T, stream));
     SPR_HIP_CHECK(hipMemsetAsync(v, 0, sizeof(float) * T, stream));
   }
@@ -1249,11 +1297,7 @@ extern "C" int spr_weighted_procrustes_bwd(const float* a, const float* b, const
 }
 
 extern "C" size_t spr_sinkhorn_bwd_workspace_bytes(const int* cu_host, int npairs, int n_iters) {
-  const int tmax = cu_host[2 * npairs];
-  const int it = n_iters > 0 ? n_iters : 1;
-  return corr_ws_bytes(cu_host, npairs) + 2 * pair_mat_bytes(cu_host, npairs) +
-         2 * align_up(sizeof(GemmRec) * npairs, 256) + (size_t)(4 * it + 5) * align_up((size_t)tmax * 4, 256) + 1024 +
-         align_up(2 * 1024 * sizeof(double), 256) + 2048;
+  return measure(sinkhorn_bwd_layout, cu_host, npairs, n_iters, true);
 }
 
 // Gradient of (w, t_hat) = spr_sinkhorn_correspondences(feat, ...) w.r.t. feat, alpha, beta.
@@ -1266,26 +1310,15 @@ extern "C" int spr_sinkhorn_bwd(const float* feat, int d, const float* xyz, cons
   SPR_REQUIRE(npairs >= 1 && d % 32 == 0 && n_iters >= 0, "sinkhorn_bwd: bad arguments");
   SPR_REQUIRE(feat && xyz && cu && cu_host && alpha && beta && dw && dthat && dfeat && dalpha && dbeta,
               "sinkhorn_bwd: null operand");
-  SPR_REQUIRE(ws_bytes >= spr_sinkhorn_bwd_workspace_bytes(cu_host, npairs, n_iters), "sinkhorn_bwd: workspace too small");
+  const bool split = gemm_mode() == 1;
   Workspace w(ws, ws_bytes);
+  const auto [corr_ws, corr, dmat, rs, rt, U, V, du, dva, dvb, zero, parts, epi] =
+      sinkhorn_bwd_layout(w, cu_host, npairs, n_iters, split);
+  SPR_REQUIRE(ws != nullptr && w.ok(), "sinkhorn_bwd: workspace too small");
   Corr c;
-  if (corr_setup(c, feat, d, cu, cu_host, npairs, w, stream, true)) return 1;     // the backward keeps every matrix
+  if (corr_setup(c, feat, d, cu, cu_host, npairs, corr_ws, split, stream, true)) return 1;     // the backward keeps every matrix
   if (corr_gemm(c, 0, 0, nullptr, stream, nullptr)) return 1;
   const int T = cu_host[2 * npairs];
-  float* corr = w.take<float>((size_t)c.total);
-  float* dmat = w.take<float>((size_t)c.total);
-  GemmRec* rs = w.take<GemmRec>(npairs);
-  GemmRec* rt = w.take<GemmRec>(npairs);
-  const int it_n = n_iters > 0 ? n_iters : 1;
-  double* U = w.take<double>((size_t)it_n * T);      // potentials in double (see k_row_lse)
-  double* V = w.take<double>((size_t)it_n * T);
-  float* du = w.take<float>(T);
-  float* dva = w.take<float>(T);
-  float* dvb = w.take<float>(T);
-  double* zero = w.take<double>(T);
-  double* parts = w.take<double>(2 * 1024);
-  float* epi = w.take<float>(4);
-  SPR_REQUIRE(w.ok() && epi != nullptr, "sinkhorn_bwd: workspace carve failed");
   const float scale = 1.0f / sqrtf((float)d);
   SPR_HIP_CHECK(hipMemsetAsync(dmat, 0, sizeof(float) * (size_t)c.total, stream));
   SPR_HIP_CHECK(hipMemcpyAsync(corr, c.mat, sizeof(float) * (size_t)c.total, hipMemcpyDeviceToDevice, stream));

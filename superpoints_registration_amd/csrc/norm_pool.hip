@@ -384,10 +384,29 @@ __global__ void k_gather_rows(const float* __restrict__ x, int n_src, int c,
 
 using namespace spr;
 
-extern "C" size_t spr_instnorm_workspace_bytes(int max_len, int nb, int c) {
+namespace {
+struct InstnormWs {
+  double* part;         // per cloud and split: sums
+  float *mean, *rstd;   // [nb][c]
+  double *m1, *m2;      // backward only
+};
+// Sizes below 1 are measured as 1 (the size queries' clamp).  spr_instnorm_stats runs the forward's layout as well.
+InstnormWs instnorm_layout(Workspace& w, int max_len, int nb, int c, bool backward) {
   const size_t B = (size_t)(nb > 0 ? nb : 1), C = (size_t)(c > 0 ? c : 1);
-  const int ns = in_nsplit(max_len);
-  return align_up(B * ns * 2 * C * sizeof(double), 256) + 2 * align_up(B * C * sizeof(float), 256);
+  InstnormWs l{};
+  l.part = w.take<double>(B * in_nsplit(max_len) * 2 * C);
+  l.mean = w.take<float>(B * C);
+  l.rstd = w.take<float>(B * C);
+  if (backward) {
+    l.m1 = w.take<double>(B * C);
+    l.m2 = w.take<double>(B * C);
+  }
+  return l;
+}
+}  // namespace
+
+extern "C" size_t spr_instnorm_workspace_bytes(int max_len, int nb, int c) {
+  return measure(instnorm_layout, max_len, nb, c, false);
 }
 
 // out_range: NULL, or out_range_n (a power of two) zero-initialised floats that receive partial
@@ -404,14 +423,13 @@ extern "C" int spr_instnorm(const float* x, const int* cu, int n, int nb, int ma
   float* rstd = nullptr;
   if (norm) {
     SPR_REQUIRE(max_len_host >= 1 && max_len_host <= n, "instnorm: bad max_len_host=%d", max_len_host);
-    SPR_REQUIRE(ws != nullptr && ws_bytes >= spr_instnorm_workspace_bytes(max_len_host, nb, c),
-                "instnorm: workspace too small");
     Workspace w(ws, ws_bytes);
+    const InstnormWs l = instnorm_layout(w, max_len_host, nb, c, false);
+    SPR_REQUIRE(ws != nullptr && w.ok(), "instnorm: workspace too small");
     const int nsplit = in_nsplit(max_len_host);
-    double* part = w.take<double>((size_t)nb * nsplit * 2 * c);
-    mean = w.take<float>((size_t)nb * c);
-    rstd = w.take<float>((size_t)nb * c);
-    SPR_REQUIRE(w.ok() && rstd != nullptr, "instnorm: workspace carve failed");
+    double* part = l.part;
+    mean = l.mean;
+    rstd = l.rstd;
     hipLaunchKernelGGL(k_in_stats, dim3(nb, nsplit, cdiv(c, 64)), dim3(256), 0, stream, x, cu, c, nsplit, part);
     hipLaunchKernelGGL(k_in_final, dim3(cdiv((long)nb * c, 256)), dim3(256), 0, stream, part, cu,
                        nb, c, nsplit, eps, mean, rstd);
@@ -431,12 +449,10 @@ extern "C" int spr_instnorm_stats(const float* x, const int* cu, int n, int nb, 
   hipStream_t stream = (hipStream_t)stream_;
   SPR_REQUIRE(x && cu && mean && rstd && n > 0 && nb >= 1 && c >= 4 && c % 4 == 0, "instnorm_stats: bad arguments (c=%d)", c);
   SPR_REQUIRE(max_len_host >= 1 && max_len_host <= n, "instnorm_stats: bad max_len_host=%d", max_len_host);
-  SPR_REQUIRE(ws != nullptr && ws_bytes >= spr_instnorm_workspace_bytes(max_len_host, nb, c),
-              "instnorm_stats: workspace too small");
   Workspace w(ws, ws_bytes);
+  double* part = instnorm_layout(w, max_len_host, nb, c, false).part;
+  SPR_REQUIRE(ws != nullptr && w.ok(), "instnorm_stats: workspace too small");
   const int nsplit = in_nsplit(max_len_host);
-  double* part = w.take<double>((size_t)nb * nsplit * 2 * c);
-  SPR_REQUIRE(w.ok() && part != nullptr, "instnorm_stats: workspace carve failed");
   hipLaunchKernelGGL(k_in_stats, dim3(nb, nsplit, cdiv(c, 64)), dim3(256), 0, stream, x, cu, c, nsplit, part);
   hipLaunchKernelGGL(k_in_final, dim3(cdiv((long)nb * c, 256)), dim3(256), 0, stream, part, cu, nb, c, nsplit, eps, mean,
                      rstd);
@@ -445,8 +461,7 @@ extern "C" int spr_instnorm_stats(const float* x, const int* cu, int n, int nb, 
 }
 
 extern "C" size_t spr_instnorm_bwd_workspace_bytes(int max_len, int nb, int c) {
-  const size_t B = (size_t)(nb > 0 ? nb : 1), C = (size_t)(c > 0 ? c : 1);
-  return spr_instnorm_workspace_bytes(max_len, nb, c) + 2 * align_up(B * C * sizeof(double), 256);
+  return measure(instnorm_layout, max_len, nb, c, true);
 }
 
 // x: the forward input, out: the forward output (sign pattern of the LeakyReLU), dout: its gradient.
@@ -461,16 +476,12 @@ extern "C" int spr_instnorm_bwd(const float* x, const float* out, const float* d
   double *m1 = nullptr, *m2 = nullptr;
   if (norm) {
     SPR_REQUIRE(max_len_host >= 1 && max_len_host <= n, "instnorm_bwd: bad max_len_host=%d", max_len_host);
-    SPR_REQUIRE(ws != nullptr && ws_bytes >= spr_instnorm_bwd_workspace_bytes(max_len_host, nb, c),
-                "instnorm_bwd: workspace too small");
     Workspace w(ws, ws_bytes);
+    const InstnormWs l = instnorm_layout(w, max_len_host, nb, c, true);
+    SPR_REQUIRE(ws != nullptr && w.ok(), "instnorm_bwd: workspace too small");
     const int nsplit = in_nsplit(max_len_host);
-    double* part = w.take<double>((size_t)nb * nsplit * 2 * c);
-    mean = w.take<float>((size_t)nb * c);
-    rstd = w.take<float>((size_t)nb * c);
-    m1 = w.take<double>((size_t)nb * c);
-    m2 = w.take<double>((size_t)nb * c);
-    SPR_REQUIRE(w.ok() && m2 != nullptr, "instnorm_bwd: workspace carve failed");
+    double* part = l.part;
+    mean = l.mean; rstd = l.rstd; m1 = l.m1; m2 = l.m2;
     hipLaunchKernelGGL(k_in_stats, dim3(nb, nsplit, cdiv(c, 64)), dim3(256), 0, stream, x, cu, c, nsplit, part);
     hipLaunchKernelGGL(k_in_final, dim3(cdiv((long)nb * c, 256)), dim3(256), 0, stream, part, cu, nb, c, nsplit,
                        eps, mean, rstd);

@@ -308,23 +308,20 @@ struct BwdWorkspace {
 
 int group_rows(int t) { return t < kGroup ? (t + 31) / 32 * 32 : kGroup; }
 
-// false if ws is too small (ws = NULL with a huge size: measures)
-bool carve(void* ws, size_t ws_bytes, int t, BwdWorkspace& w, size_t* used) {
-  Workspace a(ws, ws_bytes);
+BwdWorkspace bwd_layout(Workspace& a, int t) {
+  BwdWorkspace w;
   const size_t g = (size_t)group_rows(t);
   const int nslab = (int)((g + kSlab - 1) / kSlab);
-  bool ok = true;
   for (int l = 1; l <= 4; ++l) {
-    ok &= (w.h[l] = a.take<float>(g * width(l))) != nullptr;
-    ok &= (w.d[l] = a.take<float>(g * width(l))) != nullptr;
+    w.h[l] = a.take<float>(g * width(l));
+    w.d[l] = a.take<float>(g * width(l));
   }
-  for (int l = 0; l < 5; ++l) ok &= (w.parts[l] = a.take<float>((size_t)nslab * width(l) * width(l + 1))) != nullptr;
-  ok &= (w.btmp = a.take<float>(256)) != nullptr;
-  ok &= (w.desc = a.take<PmDesc>(5 * kMaxSlab)) != nullptr;
+  for (int l = 0; l < 5; ++l) w.parts[l] = a.take<float>((size_t)nslab * width(l) * width(l + 1));
+  w.btmp = a.take<float>(256);
+  w.desc = a.take<PmDesc>(5 * kMaxSlab);
   w.colws_bytes = spr_colsum_workspace_bytes(256);
-  ok &= (w.colws = a.take<char>(w.colws_bytes)) != nullptr;
-  if (used) *used = a.off;
-  return ok;
+  w.colws = a.take<char>(w.colws_bytes);
+  return w;
 }
 
 int check_common(const char* what, const float* xyz, const float* const* params_host, int t, int d_model) {
@@ -368,10 +365,7 @@ extern "C" int spr_posemb_mlp(const float* xyz, const float* const* params_host,
 
 extern "C" size_t spr_posemb_mlp_bwd_workspace_bytes(int t) {
   if (t <= 0) return 256;
-  BwdWorkspace w;
-  size_t used = 0;
-  carve(nullptr, ~(size_t)0 >> 1, t, w, &used);
-  return used;
+  return measure(bwd_layout, t);
 }
 
 extern "C" int spr_posemb_mlp_bwd(const float* xyz, const float* const* params_host, const float* dpe, int t,
@@ -389,8 +383,9 @@ extern "C" int spr_posemb_mlp_bwd(const float* xyz, const float* const* params_h
   }
   SPR_REQUIRE(dpe != nullptr && ((uintptr_t)dpe & 15) == 0, "posemb_mlp_bwd: dpe is null or not 16-byte aligned");
   SPR_REQUIRE(t <= (1 << 30), "posemb_mlp_bwd: too many tokens (%d)", t);
-  BwdWorkspace w;
-  SPR_REQUIRE(ws != nullptr && ((uintptr_t)ws & 255) == 0 && carve(ws, ws_bytes, t, w, nullptr),
+  Workspace a(ws, ws_bytes);
+  const BwdWorkspace w = bwd_layout(a, t);
+  SPR_REQUIRE(ws != nullptr && ((uintptr_t)ws & 255) == 0 && a.ok(),
               "posemb_mlp_bwd: workspace too small or misaligned (%zu bytes, need %zu)", ws_bytes,
               spr_posemb_mlp_bwd_workspace_bytes(t));
   if (int rc = ensure_dyn_lds((const void*)k_posemb_mlp_chain, (int)kBwdLds)) return rc;

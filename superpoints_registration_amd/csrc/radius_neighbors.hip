@@ -904,12 +904,8 @@ struct TableView {
   int* start;
   float4* rec;
 };
-size_t table_bytes(int ns, int nb) {
-  return align_up(64 * sizeof(int), 256) + align_up(sizeof(GridCloud) * (size_t)(nb > 0 ? nb : 1), 256) +
-         align_up(4 * table_cells_alloc(ns), 256) + align_up(16 * (size_t)(ns > 0 ? ns : 1), 256);
-}
-TableView table_view(void* blob, int ns, int nb) {
-  Workspace w(blob, table_bytes(ns, nb));
+// The three layouts of the table path.  Sizes (ns, nb, nq) below 1 are measured as 1 (the size queries' clamp).
+TableView table_layout(Workspace& w, int ns, int nb) {
   TableView t;
   t.hdr = w.take<int>(64);
   t.ginfo = w.take<GridCloud>(nb > 0 ? nb : 1);
@@ -917,23 +913,39 @@ TableView table_view(void* blob, int ns, int nb) {
   t.rec = w.take<float4>(ns > 0 ? ns : 1);
   return t;
 }
-size_t table_build_ws_bytes(int ns) {
-  return 2 * align_up(4 * (size_t)(ns > 0 ? ns : 1), 256) + align_up(4 * (table_cells_alloc(ns) / kScanBlock), 256);
+struct TableBuildWs {
+  int *cell_of, *rank, *bsum;
+};
+TableBuildWs table_build_layout(Workspace& w, int ns) {
+  TableBuildWs b;
+  b.cell_of = w.take<int>(ns > 0 ? ns : 1);
+  b.rank = w.take<int>(ns > 0 ? ns : 1);
+  b.bsum = w.take<int>(table_cells_alloc(ns) / kScanBlock);
+  return b;
 }
-size_t table_query_ws_bytes(int nq) {
+// limits up to kRegRows: the scratch rows are capped there and sorted in registers (k_sort_rows_reg); a query with
+// more candidates in range than the cap takes the scan's second (histogram-cut) pass, as before beyond 2 * limit
+constexpr int kRegRows = 64, kMaxRowCap = 128;
+int table_row_cap(int limit) { return limit <= kRegRows ? min(nbr_row_cap(limit), kRegRows) : nbr_row_cap(limit); }
+struct TableQueryWs {
+  unsigned long long* tmp_key;   // unsorted (d2, id) key rows
+  int *kept, *qid;               // kept counts, query ids
+};
+TableQueryWs table_query_layout(Workspace& w, int nq, int rcap) {
   const size_t Q = (size_t)(nq > 0 ? nq : 1);
-  return align_up(8 * Q * 128, 256) + 2 * align_up(4 * Q, 256);   // unsorted (d2, id) key rows (cap <= 128), kept counts, query ids
+  TableQueryWs q;
+  q.tmp_key = w.take<unsigned long long>(Q * rcap);
+  q.kept = w.take<int>(Q);
+  q.qid = w.take<int>(Q);
+  // unused: what rows of kMaxRowCap keys would add, so that one size serves every limit
+  (void)w.take<char>(align_up(8 * Q * kMaxRowCap, 256) - align_up(8 * Q * rcap, 256));
+  return q;
 }
 
-int table_build(const float* s_xyz, const int* s_cu, int ns, int nb, float radius, void* blob, void* ws,
-                size_t ws_bytes, hipStream_t stream) {
-  const TableView t = table_view(blob, ns, nb);
-  Workspace w(ws, ws_bytes);
-  int* cell_of = w.take<int>((size_t)ns);
-  int* rank = w.take<int>((size_t)ns);
+int table_build(const float* s_xyz, const int* s_cu, int ns, int nb, float radius, const TableView& t,
+                const TableBuildWs& b, hipStream_t stream) {
+  int *cell_of = b.cell_of, *rank = b.rank, *bsum = b.bsum;
   const int nblk = (int)(table_cells_alloc(ns) / kScanBlock);
-  int* bsum = w.take<int>((size_t)nblk);
-  SPR_REQUIRE(w.ok() && bsum != nullptr, "radius table: workspace carve failed");
   const float inv_cell = 1.0f / (radius * (1.0f + 1.0f / 256.0f));
   const int TB = 256;
   SPR_HIP_CHECK(hipMemsetAsync(t.hdr, 0, 8 * sizeof(int), stream));
@@ -953,19 +965,12 @@ int table_build(const float* s_xyz, const int* s_cu, int ns, int nb, float radiu
 // algo: 1 = wave per query (k_knn_wave), anything else = thread per query (k_scan_table + rank sort).  Rows are
 // identical either way.
 int table_query(const float* q_xyz, const int* q_cu, int nq, int self, int ns, int nb, float radius, int limit,
-                int slot, const void* blob, int* out_idx, int* max_count, void* ws, size_t ws_bytes,
+                int slot, const TableView& t, const TableQueryWs& q, int* out_idx, int* max_count,
                 hipStream_t stream, int algo = -1, int select = SPR_SELECT_NEAREST) {
-  const TableView t = table_view(const_cast<void*>(blob), ns, nb);
-  Workspace w(ws, ws_bytes);
-  // limits up to kRegRows: the scratch rows are capped there and sorted in registers (k_sort_rows_reg); a query with
-  // more candidates in range than the cap takes the scan's second (histogram-cut) pass, as before beyond 2 * limit
-  constexpr int kRegRows = 64;
   const bool use_reg = limit <= kRegRows;
-  const int rcap = use_reg ? min(nbr_row_cap(limit), kRegRows) : nbr_row_cap(limit);
-  unsigned long long* tmp_key = w.take<unsigned long long>((size_t)nq * rcap);
-  int* kept = w.take<int>((size_t)nq);
-  int* qid = w.take<int>((size_t)nq);
-  SPR_REQUIRE(w.ok() && qid != nullptr, "radius query: workspace carve failed");
+  const int rcap = table_row_cap(limit);
+  unsigned long long* tmp_key = q.tmp_key;
+  int *kept = q.kept, *qid = q.qid;
   const float r2 = radius * radius;  // neighbors.cpp:226 (float32)
   const float inv_cell = 1.0f / (radius * (1.0f + 1.0f / 256.0f));
   if (algo == 1) {   // the one-pass wave-per-query selection instead of scan + rank sort
@@ -1013,23 +1018,45 @@ size_t nbr_sort_temp_bytes(int n) {
   return align_up(bytes, 256) + 256;
 }
 
+// spr_radius_neighbors: the sort path's buffers, then the cell-table path's (the table itself, its build scratch, the
+// query scratch).  Every call is laid out for both: algo picks a path only after the size is known to serve either.
+struct NbrWs {
+  NbrCloud* info;
+  unsigned long long *keys, *keys2;
+  int *vals, *vals2;
+  float4* rec;
+  int* err;
+  size_t temp_bytes;
+  void* temp;
+  TableView table;
+  TableBuildWs build;
+  TableQueryWs query;
+};
+NbrWs nbr_layout(Workspace& w, int nq, int ns, int nb, int rcap) {
+  const size_t N = (size_t)(ns > 0 ? ns : 1);
+  NbrWs l;
+  l.info = w.take<NbrCloud>(nb > 0 ? nb : 1);
+  l.keys = w.take<unsigned long long>(N);
+  l.keys2 = w.take<unsigned long long>(N);
+  l.vals = w.take<int>(N);
+  l.vals2 = w.take<int>(N);
+  l.rec = w.take<float4>(N);
+  l.err = w.take<int>(16);
+  l.temp_bytes = nbr_sort_temp_bytes(ns);
+  l.temp = w.take<char>(l.temp_bytes);
+  l.table = table_layout(w, ns, nb);
+  l.build = table_build_layout(w, ns);
+  l.query = table_query_layout(w, nq, rcap);
+  return l;
+}
+
 }  // namespace
 }  // namespace spr
 
 using namespace spr;
 
 extern "C" size_t spr_radius_neighbors_workspace_bytes(int nq, int ns, int nb) {
-  const size_t N = (size_t)(ns > 0 ? ns : 1), B = (size_t)(nb > 0 ? nb : 1);
-  size_t b = 0;
-  b += align_up(sizeof(NbrCloud) * B, 256);
-  b += 2 * align_up(8 * N, 256);
-  b += 2 * align_up(4 * N, 256);
-  b += align_up(16 * N, 256);
-  b += 256;
-  b += nbr_sort_temp_bytes(ns);
-  // cell-table path: the table itself, its build scratch, the query scratch
-  b += table_bytes(ns, nb) + table_build_ws_bytes(ns) + table_query_ws_bytes(nq);
-  return b;
+  return measure(nbr_layout, nq, ns, nb, kMaxRowCap);
 }
 
 extern "C" int spr_radius_neighbors(const float* q_xyz, const int* q_cu, int nq,
@@ -1043,31 +1070,16 @@ extern "C" int spr_radius_neighbors(const float* q_xyz, const int* q_cu, int nq,
   SPR_REQUIRE(nb < 65536, "radius_neighbors: at most 65535 clouds per call");
   SPR_REQUIRE(radius > 0.f, "radius_neighbors: radius must be > 0");
   SPR_REQUIRE(limit >= 1 && limit <= 128, "radius_neighbors: limit must be in [1,128], got %d", limit);
-  SPR_REQUIRE(ws != nullptr && ws_bytes >= spr_radius_neighbors_workspace_bytes(nq, ns, nb),
-              "radius_neighbors: workspace too small");
   Workspace w(ws, ws_bytes);
-  const size_t N = (size_t)ns;
-  NbrCloud* info = w.take<NbrCloud>(nb);
-  unsigned long long* keys = w.take<unsigned long long>(N);
-  unsigned long long* keys2 = w.take<unsigned long long>(N);
-  int* vals = w.take<int>(N);
-  int* vals2 = w.take<int>(N);
-  float4* rec = w.take<float4>(N);
-  int* err = w.take<int>(16);
-  size_t temp_bytes = nbr_sort_temp_bytes(ns);
-  void* temp = w.take<char>(temp_bytes);
-  SPR_REQUIRE(w.ok() && temp != nullptr, "radius_neighbors: workspace carve failed");
+  const auto [info, keys, keys2, vals, vals2, rec, err, temp_bytes, temp, table, build_ws, query_ws] =
+      nbr_layout(w, nq, ns, nb, table_row_cap(limit));
+  SPR_REQUIRE(ws != nullptr && w.ok(), "radius_neighbors: workspace too small");
 
   const int TB = 256;
   if (algo == 0) {
-    void* blob = w.take<char>(table_bytes(ns, nb));
-    const size_t bws = table_build_ws_bytes(ns), qws = table_query_ws_bytes(nq);
-    void* build_ws = w.take<char>(bws);
-    void* query_ws = w.take<char>(qws);
-    SPR_REQUIRE(w.ok() && query_ws != nullptr, "radius_neighbors: workspace carve failed (table)");
-    if (int rc = table_build(s_xyz, s_cu, ns, nb, radius, blob, build_ws, bws, stream)) return rc;
+    if (int rc = table_build(s_xyz, s_cu, ns, nb, radius, table, build_ws, stream)) return rc;
     return table_query(q_xyz, q_cu, nq, (q_xyz == s_xyz && q_cu == s_cu && nq == ns) ? 1 : 0, ns, nb, radius, limit, 0,
-                       blob, out_idx, max_count, query_ws, qws, stream, -1, select);
+                       table, query_ws, out_idx, max_count, stream, -1, select);
   }
   const float r2 = radius * radius;  // neighbors.cpp:226 (float32)
   const float inv_cell = 1.0f / (radius * (1.0f + 1.0f / 256.0f));
@@ -1103,18 +1115,28 @@ extern "C" int spr_radius_neighbors(const float* q_xyz, const int* q_cu, int nq,
 
 // ---- cell table built once, queried several times (Preprocessor: conv / pool / up-sampling searches that share
 // supports and radius).  Results are those of spr_radius_neighbors (algo 0), row for row. ----------------------
-extern "C" size_t spr_radius_table_bytes(int ns, int nb) { return table_bytes(ns, nb); }
-extern "C" size_t spr_radius_table_build_workspace_bytes(int ns, int nb) { (void)nb; return table_build_ws_bytes(ns); }
-extern "C" size_t spr_radius_table_query_workspace_bytes(int nq) { return table_query_ws_bytes(nq); }
+extern "C" size_t spr_radius_table_bytes(int ns, int nb) {
+  return measure(table_layout, ns, nb);
+}
+extern "C" size_t spr_radius_table_build_workspace_bytes(int ns, int nb) {
+  (void)nb;
+  return measure(table_build_layout, ns);
+}
+extern "C" size_t spr_radius_table_query_workspace_bytes(int nq) {
+  return measure(table_query_layout, nq, kMaxRowCap);
+}
 extern "C" int spr_radius_table_slots(void) { return kTableSlots; }
 
 extern "C" int spr_radius_table_build(const float* s_xyz, const int* s_cu, int ns, int nb, float radius, void* table,
                                       size_t table_bytes_, void* ws, size_t ws_bytes, void* stream_) {
   SPR_REQUIRE(s_xyz && s_cu && table && ns > 0 && nb >= 1 && nb < 65536, "radius_table_build: bad arguments");
   SPR_REQUIRE(radius > 0.f, "radius_table_build: radius must be > 0");
-  SPR_REQUIRE(table_bytes_ >= table_bytes(ns, nb) && ((uintptr_t)table & 255) == 0, "radius_table_build: table too small or misaligned");
-  SPR_REQUIRE(ws != nullptr && ws_bytes >= table_build_ws_bytes(ns), "radius_table_build: workspace too small");
-  return table_build(s_xyz, s_cu, ns, nb, radius, table, ws, ws_bytes, (hipStream_t)stream_);
+  Workspace tw(table, table_bytes_), w(ws, ws_bytes);
+  const TableView t = table_layout(tw, ns, nb);
+  const TableBuildWs b = table_build_layout(w, ns);
+  SPR_REQUIRE(tw.ok() && ((uintptr_t)table & 255) == 0, "radius_table_build: table too small or misaligned");
+  SPR_REQUIRE(ws != nullptr && w.ok(), "radius_table_build: workspace too small");
+  return table_build(s_xyz, s_cu, ns, nb, radius, t, b, (hipStream_t)stream_);
 }
 
 // self != 0: the queries ARE the table's supports (same array, same cu) -> cell-order walk.  slot in
@@ -1136,7 +1158,10 @@ extern "C" int spr_radius_table_query(const float* q_xyz, const int* q_cu, int n
   SPR_REQUIRE(!self || nq == ns, "radius_table_query: a self search has nq == ns");
   SPR_REQUIRE(algo >= -1 && algo <= 1,
               "radius_table_query: algo must be 0 (thread per query), 1 (wave per query) or -1 (the library's choice)");
-  SPR_REQUIRE(ws != nullptr && ws_bytes >= table_query_ws_bytes(nq), "radius_table_query: workspace too small");
-  return table_query(q_xyz, q_cu, nq, self ? 1 : 0, ns, nb, radius, limit, slot, table, out_idx, max_count, ws, ws_bytes,
+  Workspace tw(const_cast<void*>(table), SIZE_MAX), w(ws, ws_bytes);   // the table's size was checked when it was built
+  const TableView t = table_layout(tw, ns, nb);
+  const TableQueryWs q = table_query_layout(w, nq, table_row_cap(limit));
+  SPR_REQUIRE(ws != nullptr && w.ok(), "radius_table_query: workspace too small");
+  return table_query(q_xyz, q_cu, nq, self ? 1 : 0, ns, nb, radius, limit, slot, t, q, out_idx, max_count,
                      (hipStream_t)stream_, algo, select);
 }

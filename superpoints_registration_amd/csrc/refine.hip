@@ -213,9 +213,13 @@ __global__ __launch_bounds__(kThreads) void k_refine_pairs(
 
 using namespace spr;
 
+// pairs too long for LDS: one working set per pair, which the kernel carves by pair_bytes as it carves LDS
+static bool refine_needs_ws(int npairs, int max_n) { return npairs >= 1 && max_n > kLdsN && max_n <= SPR_REFINE_MAX_N; }
+static char* refine_layout(Workspace& w, int npairs, int max_n) { return w.take<char>((size_t)npairs * pair_bytes(max_n)); }
+
 extern "C" size_t spr_refine_pairs_workspace_bytes(int npairs, int max_n) {
-  if (npairs < 1 || max_n <= kLdsN || max_n > SPR_REFINE_MAX_N) return 0;
-  return (size_t)npairs * pair_bytes(max_n);
+  if (!refine_needs_ws(npairs, max_n)) return 0;
+  return measure(refine_layout, npairs, max_n);
 }
 
 extern "C" int spr_refine_pairs(const float* val, const float* val2, const int* ind, const float* overlap,
@@ -237,12 +241,14 @@ extern "C" int spr_refine_pairs(const float* val, const float* val2, const int* 
   SPR_REQUIRE(!(flags & SPR_REFINE_SINKHORN) || pose_in, "refine_pairs: the Sinkhorn mode needs pose_in");
   SPR_REQUIRE(max_n <= SPR_REFINE_MAX_N, "refine_pairs: %d entries in one pair, the cap is %d", max_n,
               SPR_REFINE_MAX_N);
-  const size_t need = spr_refine_pairs_workspace_bytes(npairs, max_n);
-  SPR_REQUIRE(need == 0 || (ws && ws_bytes >= need), "refine_pairs: workspace of %zu bytes, %zu needed", ws_bytes, need);
+  const bool need = refine_needs_ws(npairs, max_n);
+  Workspace w(ws, ws_bytes);
+  char* sets = need ? refine_layout(w, npairs, max_n) : nullptr;
+  SPR_REQUIRE(!need || (ws != nullptr && w.ok()), "refine_pairs: workspace of %zu bytes is too small", ws_bytes);
   if (int rc = ensure_dyn_lds((const void*)k_refine_pairs, (int)kLdsBytes)) return rc;
   hipLaunchKernelGGL(k_refine_pairs, dim3(npairs), dim3(kThreads), kLdsBytes, stream, val, val2, ind, overlap, xyz, cu,
                      npairs, t_total, k_b, out_cu, flags, lowe_thres, acceptance_radius, n_steps, pose_in, max_n, pose,
-                     val_out, ind_out, src_pts, tgt_pts, status, (char*)ws, need ? pair_bytes(max_n) : (size_t)0);
+                     val_out, ind_out, src_pts, tgt_pts, status, sets, need ? pair_bytes(max_n) : (size_t)0);
   SPR_LAUNCH_CHECK();
   return 0;
 }

@@ -46,28 +46,47 @@ void set_error(const char* fmt, ...);
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
-// Bump allocator over a caller supplied workspace.  A take that does not fit returns nullptr and leaves the
-// allocator marked: every entry point checks ok() behind its last take and before its first launch, so a carve
-// that asks for more than the size query promised comes back as an error code, never as a null pointer in a kernel.
+// Bump allocator over a caller supplied workspace.  A take that does not fit (or whose size does not fit size_t)
+// returns nullptr and leaves the allocator marked: every entry point checks ok() behind its last take and before its
+// first launch, so a carve that asks for more than it was given comes back as an error code, never as a null pointer
+// in a kernel.
+//
+// Every operator writes its layout ONCE, as a function that performs the takes on a Workspace&.  The size query runs
+// that function on a measuring Workspace (no memory: every take returns nullptr, used() is the layout's byte count);
+// the entry point runs it on Workspace(ws, ws_bytes).  So a buffer of the query's size always fits the carve, and one
+// that is a byte shorter fails its last take.  Layout functions never look at the pointers they hand out.
 struct Workspace {
   char* base;
   size_t size;
   size_t off;
   bool failed;
+  Workspace() : base(nullptr), size(SIZE_MAX), off(0), failed(false) {}   // measuring
   Workspace(void* p, size_t n) : base((char*)p), size(n), off(0), failed(false) {}
   bool ok() const { return !failed; }
+  size_t used() const { return failed ? SIZE_MAX : off; }   // a layout beyond size_t is never under-reported
   template <typename T>
   T* take(size_t count) {
-    size_t bytes = align_up(count * sizeof(T), 256);
-    if (off + bytes > size) {
+    if (count > (SIZE_MAX - 255) / sizeof(T)) {
       failed = true;
       return nullptr;
     }
-    T* r = (T*)(base + off);
+    size_t bytes = align_up(count * sizeof(T), 256);
+    if (bytes > size - off) {   // off <= size always
+      failed = true;
+      return nullptr;
+    }
+    T* r = base ? (T*)(base + off) : nullptr;
     off += bytes;
     return r;
   }
 };
+// The byte count of a layout: what its function takes from a measuring Workspace (the body of a size query).
+template <typename Layout, typename... Args>
+size_t measure(Layout layout, Args... args) {
+  Workspace w;
+  layout(w, args...);
+  return w.used();
+}
 
 // ---- optional per-launch HIP-event timing (bench.py roofline legs) ----------
 // code: fused KPConv = cin * 100000 + cout; attention core (k_attn_s) = -1.

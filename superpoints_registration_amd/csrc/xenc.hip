@@ -1167,14 +1167,32 @@ extern "C" int spr_xenc_debug_stamps(unsigned long long* out_host, int clear) {
 }
 #endif
 
-// bytes of one tiled token tensor: an upper bound of the tile count (tiles do not straddle clouds) x 128 KiB; a
-// row-major [t, 256] tensor (the attention output when the core cannot write tiles) fits as well
-static size_t xenc_tiled_bytes(int t, int nseg) { return (size_t)(cdiv(t, XTOK) + nseg) * XTOK * XD * sizeof(float); }
+struct XencWs {
+  AttnPlanes pl;
+  float *obuf, *xa, *xb, *pos_t;   // tiled: attention output, residual stream ping / pong, positional embedding
+  int* ctr;                        // one tile counter per chain launch
+  int* tfirst;
+};
+constexpr int kXencCounters = 256;
+// A tiled token tensor: an upper bound of the tile count (tiles do not straddle clouds) x 128 KiB; a row-major
+// [t, 256] tensor (the attention output when the core cannot write tiles) fits as well
+static size_t xenc_tiled_floats(int t, int nseg) { return ((size_t)cdiv(t, XTOK) + (size_t)nseg) * XTOK * XD; }
+static XencWs xenc_layout(Workspace& w, int t, int nseg) {
+  XencWs l{};
+  attn_layout_planes(w, t, nseg, XD, l.pl);
+  const size_t act = xenc_tiled_floats(t, nseg);
+  l.obuf = w.take<float>(act);
+  l.xa = w.take<float>(act);
+  l.xb = w.take<float>(act);
+  l.pos_t = w.take<float>(act);
+  l.ctr = w.take<int>(kXencCounters);
+  l.tfirst = w.take<int>((size_t)nseg + 1);
+  return l;
+}
 
 extern "C" size_t spr_xenc_workspace_bytes(int t, int nseg) {
   if (t < 1 || nseg < 1) return 0;
-  return spr_attn_workspace_bytes(t, nseg, 8, 32) + 4 * xenc_tiled_bytes(t, nseg) + 1024 +
-         align_up((size_t)(nseg + 1) * sizeof(int), 256);
+  return measure(xenc_layout, t, nseg);
 }
 
 // x [t, 256] tokens of all clouds (packed), pos [t, 256] positional embedding, cu [nseg + 1],
@@ -1188,26 +1206,18 @@ extern "C" int spr_xenc_forward(const void* plan_host, const float* x, const flo
   SPR_REQUIRE(x && pos && cu && kv_self && kv_cross && out, "xenc_forward: null argument");
   SPR_REQUIRE(t >= 1 && nseg >= 1 && max_len_host >= 1, "xenc_forward: bad sizes");
   SPR_REQUIRE((size_t)t * XD * 4 < (1ull << 32), "xenc_forward: too many tokens");
-  SPR_REQUIRE(ws != nullptr && ws_bytes >= spr_xenc_workspace_bytes(t, nseg), "xenc_forward: workspace too small");
+  Workspace w(ws, ws_bytes);
+  auto [pl, obuf, xa, xb, pos_t, ctr, tfirst] = xenc_layout(w, t, nseg);
+  SPR_REQUIRE(ws != nullptr && w.ok(), "xenc_forward: workspace too small");
   const int mode = attn_mode();
   SPR_REQUIRE(gemm_mode() == 1 && (mode >= 1 && mode <= 4),
               "xenc_forward: needs the split-fp16 arithmetic (gemm mode 1, attention mode 1 .. 4)");
-  const size_t planes_bytes = spr_attn_workspace_bytes(t, nseg, 8, 32);
-  AttnPlanes pl{};
-  if (int rc = attn_carve_planes(ws, planes_bytes, t, nseg, XD, pl)) return rc;
   pl.cu = cu;
   pl.nseg = nseg;
   pl.t_total = t;
   pl.tp = (int)attn_tp(t, nseg);
-  const size_t act = xenc_tiled_bytes(t, nseg);
-  SPR_REQUIRE(act < (1ull << 32), "xenc_forward: too many tokens");
-  float* obuf = (float*)((char*)ws + planes_bytes);            // attention output, tiled
-  float* xa = (float*)((char*)ws + planes_bytes + act);        // residual stream, tiled, ping
-  float* xb = (float*)((char*)ws + planes_bytes + 2 * act);    //                          pong
-  float* pos_t = (float*)((char*)ws + planes_bytes + 3 * act); // positional embedding, tiled
-  int* ctr = (int*)((char*)ws + planes_bytes + 4 * act);       // one tile counter per chain launch
-  SPR_HIP_CHECK(hipMemsetAsync(ctr, 0, 1024, stream));
-  int* tfirst = (int*)((char*)ws + planes_bytes + 4 * act + 1024);
+  SPR_REQUIRE(xenc_tiled_floats(t, nseg) * sizeof(float) < (1ull << 32), "xenc_forward: too many tokens");
+  SPR_HIP_CHECK(hipMemsetAsync(ctr, 0, kXencCounters * sizeof(int), stream));
   hipLaunchKernelGGL(k_xenc_tiles, dim3(1), dim3(64), 0, stream, cu, nseg, tfirst);
   if (int rc = attn_zero_gaps(pl, XD, stream)) return rc;
   const int L = plan->n_layers;

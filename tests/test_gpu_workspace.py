@@ -691,6 +691,152 @@ def test_whole_inference_forward(device, monkeypatch):
     run_three(monkeypatch, f, "inference forward", guard=1 << 16, verify_every=256)
 
 
+# ---- one byte short is refused -------------------------------------------------------------------------------------------
+class _OneByteShort(Arena):
+    """Hands out [GUARD, GUARD + nbytes - 1): the guards still stand around the nbytes the caller asked for."""
+
+    def __call__(self, nbytes, device):
+        view = super().__call__(nbytes, device)
+        return view[:-1] if nbytes > 0 else view
+
+
+# Operators that by contract do not refuse a workspace below their full size query (a fixed list).
+# spr_attn_varlen_bwd: below spr_attn_bwd_workspace_bytes it runs without the operand planes, down to
+# spr_attn_bwd_min_workspace_bytes: the result must be production's, bit for bit.
+FALLS_BACK = ("attention backward",)
+
+
+def _one_byte_short(monkeypatch, what, prepare, run):
+    """prepare() builds fresh inputs with production's workspace (a forward whose backward is the case, say); run(state)
+    is the one operator call under test.  Refused: RuntimeError naming the workspace, nothing written to the buffer
+    (the refusal comes before the first launch or memset), guards intact, and production unchanged afterwards."""
+    production = _flat(run(prepare()))
+    state = prepare()
+    arena = _OneByteShort(0xFF)
+    with monkeypatch.context() as m:
+        m.setattr(ops, "_workspace", arena)
+        if what in FALLS_BACK:
+            got = _flat(run(state))
+        else:
+            with pytest.raises(RuntimeError, match="workspace"):
+                run(state)
+            got = None
+    assert arena.calls >= 1 and all(n > 0 for _, n, _ in arena.records), f"{what}: no workspace was asked for"
+    torch.cuda.synchronize()
+    if got is None:
+        for _, n, buf in arena.records:
+            assert bool((buf[arena.guard:arena.guard + n] == 0xFF).all()), f"{what}: the refused call wrote to its workspace"
+    arena.verify()
+    for label, other in (("with a workspace one byte short", got), ("after the refusal", _flat(run(prepare())))):
+        if other is not None:
+            assert len(other) == len(production) > 0, what
+            for i, (p, r) in enumerate(zip(production, other)):
+                assert torch.equal(_bits(p), _bits(r)), f"{what}: output {i} {label} differs from production"
+
+
+def test_one_byte_short_is_refused(device, monkeypatch):
+    """One smallest-shape case per layout style, each handed its size query minus one byte."""
+    cases = []
+
+    def case(what, run, prepare=lambda: None):
+        cases.append((what, prepare, run))
+
+    # token operators, SEGS["one"]
+    lens, cu, s_self, s_cross, kv_cross, mx, qkv = _tokens("one", device, 9)
+    d = qkv.to(device)
+    q, k, v = d[:, :256].contiguous(), d[:, 256:512].contiguous(), d[:, 512:].contiguous()
+    w_in, b_in = synthetic.rand((768, 256), 33, -0.1, 0.1).to(device), synthetic.rand((768,), 34, -0.2, 0.2).to(device)
+    dgo = synthetic.rand((sum(lens), 256), 44).to(device)
+    case("attention", lambda _: ops.attention_raw(q, k, v, cu, s_cross, mx, 8, want_lse=True))
+    case("attention with in-projection", lambda _: ops.attention_inproj(q, q, w_in, b_in, cu, s_cross, mx, 8))
+    case("attention_probs", lambda _: ops.attention_probs(q, k, cu, s_cross, mx, 8))
+    case("attention backward", lambda fwd: ops.attention_bwd(q, k, v, fwd[0], dgo, cu, kv_cross, mx, 8, lse=fwd[1]),
+         lambda: ops.attention_raw(q, k, v, cu, s_cross, mx, 8, want_lse=True))
+    enc = _encoder(device, 1, 1024, True)
+    pos = synthetic.rand((sum(lens), 256), 45).to(device)
+    with torch.no_grad():
+        enc.forward_packed(q, cu, s_self, s_cross, mx, pos=pos, pos_bound=1.0)
+    plan = enc._spr_xenc
+    case("xenc_forward", lambda _: ops.xenc_forward(plan, q, pos, cu, s_self, s_cross, mx))
+
+    # products
+    x, w = synthetic.rand((1, 256), 1, -3.0, 3.0).to(device), synthetic.rand((256, 256), 2, -0.2, 0.2).to(device)
+    case("linear", lambda _: ops.linear_raw(x, w))
+
+    # point operators, POINT_COUNTS[0]
+    counts = POINT_COUNTS[0]
+    _, pts, pcu = _clouds(counts, device, 2)
+    case("grid_subsample", lambda _: ops.grid_subsample(pts, pcu, 0.1))
+    for algo in (0, 1):            # 1: the path ops.radius_neighbors falls back to when the cell table overflows
+        case(f"radius_neighbors algo {algo}", lambda _, algo=algo: ops.radius_neighbors(pts, pts, pcu, pcu, 0.2, 40, algo=algo))
+    src, scu, tgt, tcu, pose = _overlap_inputs(counts, device)
+    keys, off = [11, 12, 13], scu[:-1].cpu().tolist()
+
+    def overlap(_):
+        out = ops.gt_overlap(src, scu, tgt, tcu, pose, 0.05)
+        return out[:4], _owned(out[4], off, out[5]), torch.tensor(out[5])
+    case("gt_overlap", overlap)
+    _, _, s_mask, t_mask, corr, cnt = ops.gt_overlap(src, scu, tgt, tcu, pose, 0.05)
+    psrc, swap, perturb = ops.augment_draw(7, keys, 'small')
+
+    def augment(_):
+        aug = ops.augment_pairs(src, scu, tgt, tcu, pose, psrc, swap, perturb, 'small', 0.005, seed=7, pair_keys=keys,
+                                src_mask=s_mask, tgt_mask=t_mask, corr=corr, corr_off=off, corr_count=cnt)
+        return aug['src_cu'], aug['tgt_cu'], aug['pose'], aug['status'], aug['corr_count']
+    case("augment_pairs", augment)
+    n = sum(counts)
+    xin = synthetic.rand((n, 64), 201, -5.0, 7.0).to(device)
+    case("instnorm", lambda _: ops.instnorm_raw(xin, pcu, max_len=max(counts)))
+    ka, kb, n_out = TAIL_SHAPES[0]
+    xa, wa, xb, wb, ad, tcu_ = tail_inputs(ka, kb, n_out, TAIL_LENS, device)
+    case("block_tail", lambda _: ops.block_tail(xa, wa, tcu_, xb=xb, wb=wb, add=ad))
+    kpts, nb_, kx, kw, kp, ext, _ = _kp_inputs("c32", device)
+    case("kpconv", lambda _: ops.kpconv_raw(kpts, kpts, nb_.clone(), kx, kw.clone(), kp, ext, rows_sorted=True, impl=0))
+
+    # matching head, Sinkhorn backward, refinement
+    feat, xyz_h, mcu, cu_host = _match_inputs(device)
+    B, tsrc = len(MATCH_PAIRS), cu_host[len(MATCH_PAIRS)]
+    dfeat, xyz = feat.to(device), xyz_h.to(device)
+    case("match_and_sinkhorn", lambda _: ops.match_and_sinkhorn(dfeat, xyz, mcu, cu_host, B, 0.9, 1.1, 3, top2=True))
+    gw, gt = synthetic.rand((tsrc,), 13).to(device), synthetic.rand((tsrc, 3), 14).to(device)
+
+    def sinkhorn_forward():
+        lf = feat.clone().to(device).requires_grad_(True)
+        al = torch.tensor(0.9, device=device, requires_grad=True)
+        be = torch.tensor(1.1, device=device, requires_grad=True)
+        w_, that = ops.sinkhorn_correspondences(lf, xyz, mcu, cu_host, B, al, be, 3)
+        return (w_ * gw).sum() + (that * gt).sum(), (lf, al, be)
+
+    def backward(state):
+        loss, leaves = state
+        loss.backward()
+        return [t.grad for t in leaves]
+    case("sinkhorn backward", backward, sinkhorn_forward)
+    rng = np.random.default_rng(17)
+    P = refine_pack([synth_pair(rng, 4097, 4108)], device)
+    case("refine_pairs", lambda _: ops.refine_pairs(P['val'], P['val2'], P['ind'], P['ov'], P['xyz'], P['cu'], P['cu_host'], 1,
+                                                    None, ratio=True, median=True, overlap_prune=True, lgr_steps=2,
+                                                    lowe_thres=0.9, acceptance_radius=0.3))
+
+    # losses
+    inp = ops_inputs()
+    fs, ft, xs, xt = inp["sk.fs"], inp["sk.ft"], (inp["sk.xs"] * 0.3).to(device), (inp["sk.xt"] * 0.3).to(device)
+    W = synthetic.rand((256, 256), 16, -0.05, 0.05)
+    lpose = torch.tensor([[1.0, 0, 0, 0.02], [0, 1, 0, -0.01], [0, 0, 1, 0.0]]).to(device)
+
+    def infonce_forward():
+        leaves = tuple(t.clone().to(device).requires_grad_(True) for t in (fs, ft, W))
+        return ops.infonce_pair(leaves[0], leaves[1], xs, lpose, xt, leaves[2], 0.2, 0.4), leaves
+    case("infonce_pair", lambda _: infonce_forward()[0].detach())
+    case("infonce_pair backward", backward, infonce_forward)
+    cfs, cft, cxs, cxt = circle_case(seed=sorted(CIRCLE_REGIMES).index("ragged") + 1, **CIRCLE_REGIMES["ragged"])
+    case("circle_loss", lambda _: circle_run(device, cfs, cft, cxs, cxt)[0])
+
+    assert set(FALLS_BACK) <= {c[0] for c in cases}
+    for what, prepare, run in cases:
+        _one_byte_short(monkeypatch, what, prepare, run)
+
+
 # ---- coverage: keep this test last ---------------------------------------------------------------------------------------
 # call sites that no case can reach at small size, with the reason (none so far)
 EXCLUDED = {}
