@@ -134,6 +134,24 @@ int spr_radius_table_query(const float* q_xyz, const int* q_cu, int nq, int self
                            float radius, int limit, int slot, const void* table, int* out_idx,
                            int* max_count, int algo, int select, void* ws, size_t ws_bytes, void* stream);
 
+/* Count-only query against a built cell table: what calibrate_neighbors (kpconv.py:714-747 of the reference) needs
+ * of a neighbour matrix with unbounded rows, without the matrix.  Per query, the number of supports of the same
+ * cloud with d2 < r*r: exactly the candidates of spr_radius_table_query (same float32 d2, same strict <, same
+ * 27 cells, same cell-order walk when self != 0), uncut -- no ceiling of 128 and none of hist_n.
+ *   counts [nq] i32 or NULL: counts[i] = the count of query i;
+ *   hist [nb, hist_n] i32 or NULL, 1 <= hist_n <= 4096: hist[c * hist_n + k] += the number of queries of cloud c
+ *     whose count is exactly k, for k < hist_n; a query with hist_n or more supports in range is not binned (what
+ *     np.bincount(c, minlength=hist_n)[:hist_n] makes of a row clipped at hist_n columns).  Added to, not
+ *     overwritten: the caller zeroes it.  The row of a cloud without queries is not touched;
+ *   status [1] i32 device: 0 fine, -1 / -2 the table's error codes as spr_radius_table_query reports them in
+ *     *max_count (extent / radius beyond 8191 cells per axis; geometry too large for the table) -- counts and hist
+ *     are then left as they were.
+ * No workspace and no result slot of the table.  Arguments are checked on the host before the launch.
+ */
+int spr_radius_table_count(const float* q_xyz, const int* q_cu, int nq, int self, int ns, int nb,
+                           float radius, const void* table, int* counts, int* hist, int hist_n,
+                           int* status, void* stream);
+
 /* ---- 8f-5: ground-truth overlap masks and mutual correspondences ---------------
  * Replaces compute_overlap(src, tgt, search_voxel_size) (utils/pointcloud.py:8-65: one Open3D kd-tree radius query
  * per point), called per pair by the loaders (data_loaders/threedmatch.py:78-84) and by

@@ -609,6 +609,106 @@ __global__ __launch_bounds__(256) void k_scan_table(
   if ((threadIdx.x & 63) == 0 && m > 0) atomicMax(max_count, m);
 }
 
+// Count kernel (spr_radius_table_count: calibration of neighborhood_limits): k_scan_table's first pass with
+// everything but `total++` taken out -- the same cells, the same nine record runs, the same d2 and strict <, the same
+// cell-order walk of a self search -- so counts[i] is the number of candidates the row-producing kernels select
+// from, without the 128-column ceiling of a row.  No scratch row, no LDS per thread; what remains of the memory
+// traffic is the record stream itself.
+// Histogram: the workgroup's 256 queries are consecutive, so all but a few of them belong to the cloud of its first
+// query.  That cloud's bins are counted in LDS (hist_n ints) and flushed once, one vector atomic per bin in use;
+// a query of a later cloud (a workgroup that spans a cloud boundary) goes to global memory with an atomic of its own.
+// Integer adds commute: the histogram is exact in any order.
+constexpr int kCountHistMax = 4096;   // 16 KB of LDS
+
+__global__ __launch_bounds__(256) void k_count_table(
+    const float* __restrict__ q_xyz, const int* __restrict__ q_cu, int nq, int nb,
+    const GridCloud* __restrict__ info, const int* __restrict__ start, const float4* __restrict__ rec,
+    const int* __restrict__ hdr, float r2, float inv_cell, int self, int* __restrict__ counts,
+    int* __restrict__ hist, int hist_n, int* __restrict__ status) {
+  extern __shared__ int l_count_hist[];   // [hist_n] when hist != nullptr
+  const int err = hdr[kHdrErr];
+  if (blockIdx.x == 0 && threadIdx.x == 0) *status = (err & 1) ? -1 : (err & 2) ? -2 : 0;
+  if (err) return;                        // the table holds nothing to walk: outputs stay as they are
+  const int t0 = blockIdx.x * 256, t = t0 + threadIdx.x;
+  int c0 = 0;
+  if (hist) {
+    c0 = find_segment(q_cu, nb, t0);      // t0 < nq: the grid is cdiv(nq, 256)
+    for (int k = threadIdx.x; k < hist_n; k += 256) l_count_hist[k] = 0;
+    __syncthreads();
+  }
+  if (t < nq) {
+    const int c = find_segment(q_cu, nb, t);
+    const GridCloud g = info[c];
+    int i = t;
+    float qx, qy, qz;
+    if (self) {                           // the query IS record t (cell order); it reports at its own index
+      const float4 me = rec[t];
+      i = __float_as_int(me.w);
+      qx = me.x, qy = me.y, qz = me.z;
+    } else {
+      qx = q_xyz[3 * (size_t)t + 0], qy = q_xyz[3 * (size_t)t + 1], qz = q_xyz[3 * (size_t)t + 2];
+    }
+    const int cx = cell_coord(qx, g.mn[0], inv_cell);
+    const int cy = cell_coord(qy, g.mn[1], inv_cell);
+    const int cz = cell_coord(qz, g.mn[2], inv_cell);
+    const int xlo = max(cx - 1, 0), xhi = min(cx + 1, g.dim[0] - 1);
+    auto run_of = [&](int k) -> int2 {
+      const int z = cz + k / 3 - 1, y = cy + k % 3 - 1;
+      const bool in = xlo <= xhi && z >= 0 && z < g.dim[2] && y >= 0 && y < g.dim[1];
+      const long long L0 = in ? grid_cell(g, xlo, y, z) : 0;
+      const long long L1 = in ? grid_cell(g, xhi, y, z) + 1 : 0;
+      const int b = start[L0];
+      return make_int2(b, in ? start[L1] : b);
+    };
+    Runs9 runs;
+    runs.r0 = run_of(0); runs.r1 = run_of(1); runs.r2 = run_of(2);
+    runs.r3 = run_of(3); runs.r4 = run_of(4); runs.r5 = run_of(5);
+    runs.r6 = run_of(6); runs.r7 = run_of(7); runs.r8 = run_of(8);
+    int total = 0;
+    // the 9 record runs as ONE candidate sequence, 8 records in flight (as in k_scan_table)
+    int k = 0, j = runs.r0.x, e = runs.r0.y;
+    while (k < 9) {
+      float4 s8[8];
+      bool v8[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        while (k < 9 && j >= e) {
+          ++k;
+          const int2 r = pick9(k, runs);
+          j = r.x;
+          e = r.y;
+        }
+        v8[u] = k < 9;
+        s8[u] = rec[v8[u] ? j : 0];
+        j += v8[u] ? 1 : 0;
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        // nanoflann.hpp:432-440: diff = query - support; result += diff*diff
+        const float dx = __fsub_rn(qx, s8[u].x), dy = __fsub_rn(qy, s8[u].y), dz = __fsub_rn(qz, s8[u].z);
+        float d2 = __fmul_rn(dx, dx);
+        d2 = __fadd_rn(d2, __fmul_rn(dy, dy));
+        d2 = __fadd_rn(d2, __fmul_rn(dz, dz));
+        total += (v8[u] && d2 < r2) ? 1 : 0;   // strict, nanoflann.hpp:249
+      }
+    }
+    if (counts) counts[i] = total;
+    if (hist && total < hist_n) {         // hist_n or more in range: not binned (bincount(...)[:hist_n] of a clipped row)
+      if (c == c0)
+        atomicAdd(&l_count_hist[total], 1);
+      else
+        atomicAdd(hist + (size_t)c * hist_n + total, 1);
+    }
+  }
+  if (hist) {
+    __syncthreads();
+    for (int k = threadIdx.x; k < hist_n; k += 256) {
+      const int v = l_count_hist[k];
+      if (v) atomicAdd(hist + (size_t)c0 * hist_n + k, v);
+    }
+  }
+}
+
 // Sort kernel: one thread per query row; keys staged slot-major in LDS
 // (conflict-free) and ordered by ranking, four ranks per pass over the row so
 // each LDS read feeds four compares.  LDS holds the first `lslots` entries of a row (the launcher passes the
@@ -1164,4 +1264,26 @@ extern "C" int spr_radius_table_query(const float* q_xyz, const int* q_cu, int n
   SPR_REQUIRE(ws != nullptr && w.ok(), "radius_table_query: workspace too small");
   return table_query(q_xyz, q_cu, nq, self ? 1 : 0, ns, nb, radius, limit, slot, t, q, out_idx, max_count,
                      (hipStream_t)stream_, algo, select);
+}
+
+// Count-only query against a built table: per query the number of supports with d2 < r2 (the candidates of
+// spr_radius_table_query, uncut), and / or their per-cloud histogram.  Needs no workspace: the table is prebuilt and
+// the outputs are the caller's.  Uses no result slot of the table.
+extern "C" int spr_radius_table_count(const float* q_xyz, const int* q_cu, int nq, int self, int ns, int nb,
+                                      float radius, const void* table, int* counts, int* hist, int hist_n,
+                                      int* status, void* stream_) {
+  SPR_REQUIRE(q_xyz && q_cu && table && status && nq > 0 && ns > 0 && nb >= 1, "radius_table_count: bad arguments");
+  SPR_REQUIRE(radius > 0.f, "radius_table_count: radius must be > 0");
+  SPR_REQUIRE(!self || nq == ns, "radius_table_count: a self search has nq == ns");
+  SPR_REQUIRE(!hist || (hist_n >= 1 && hist_n <= kCountHistMax),
+              "radius_table_count: hist_n must be in [1,%d], got %d", kCountHistMax, hist_n);
+  Workspace tw(const_cast<void*>(table), SIZE_MAX);   // the table's size was checked when it was built
+  const TableView t = table_layout(tw, ns, nb);
+  const float r2 = radius * radius;  // neighbors.cpp:226 (float32)
+  const float inv_cell = 1.0f / (radius * (1.0f + 1.0f / 256.0f));
+  hipLaunchKernelGGL(k_count_table, dim3(cdiv(nq, 256)), dim3(256), hist ? sizeof(int) * (size_t)hist_n : 0,
+                     (hipStream_t)stream_, q_xyz, q_cu, nq, nb, t.ginfo, t.start, t.rec, t.hdr, r2, inv_cell,
+                     self ? 1 : 0, counts, hist, hist_n, status);
+  SPR_LAUNCH_CHECK();
+  return 0;
 }

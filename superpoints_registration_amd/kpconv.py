@@ -3,7 +3,8 @@
 Public names follow the reference's ``src/models/backbone_kpconv/kpconv.py`` so
 that RegTR-style callers keep working: KPFEncoder (:22-92), Preprocessor
 (:295-418) / PreprocessorGPU (:421-549), batch_grid_subsampling_kpconv (:174),
-batch_neighbors_kpconv (:247) and their *_gpu aliases (:217, :265).
+batch_neighbors_kpconv (:247) and their *_gpu aliases (:217, :265),
+calibrate_neighbors (:714, defined in calibration.py).
 
 The pinned contract is the reference's CPU ``Preprocessor`` (its C++
 extensions): identical point order at every level, bit-exact barycentres and
@@ -25,7 +26,7 @@ ONCE into a pyramid plan (`plan_pyramid`) that both the encoder and the
 preprocessor consume, instead of two hand-rolled loops with running state.
 """
 from dataclasses import dataclass
-from typing import List
+from typing import List, Optional
 
 import torch
 import torch.nn as nn
@@ -54,7 +55,7 @@ class LevelPlan:
     radius: float    # r_normal of the level (kpconv.py:319, doubles per level :406)
     has_conv: bool   # at least one non-strided block -> conv neighbours needed
     down: bool       # the level ends with a strided block -> subsample + pools
-    limit: int       # neighborhood_limits[level]
+    limit: Optional[int]   # neighborhood_limits[level]; None when the config carries none (calibrate_neighbors)
 
 
 def plan_pyramid(cfg):
@@ -63,7 +64,10 @@ def plan_pyramid(cfg):
     Channel / radius bookkeeping follows KPFEncoder.__init__ (kpconv.py:27-79):
     'simple' halves the advertised width, every strided block doubles radius
     and width and opens a new level.  Level bookkeeping follows
-    Preprocessor.forward (kpconv.py:334-408)."""
+    Preprocessor.forward (kpconv.py:334-408).  A config without neighborhood_limits
+    (missing or None: the limits are what calibrate_neighbors is about to find) plans
+    the same blocks and levels, with limit=None."""
+    limits = getattr(cfg, 'neighborhood_limits', None)
     r = cfg.first_subsampling_dl * cfg.conv_radius
     in_dim, out_dim, level = cfg.in_feats_dim, cfg.first_feats_dim, 0
     blocks: List[BlockPlan] = []
@@ -88,7 +92,7 @@ def plan_pyramid(cfg):
         levels.append(LevelPlan(radius=mem[0].radius,
                                 has_conv=any(not b.down for b in mem),
                                 down=mem[-1].down,
-                                limit=int(cfg.neighborhood_limits[l])))
+                                limit=None if limits is None else int(limits[l])))
     return blocks, levels, in_dim
 
 
@@ -327,3 +331,5 @@ class Preprocessor(nn.Module):
 # kpconv.py:421.  The name keeps the CPU semantics by default, like every caller of it has had so far; the neighbour
 # rows the reference's class of this name computes are PreprocessorGPU(cfg, neighbor_select='index').
 PreprocessorGPU = Preprocessor
+
+from .calibration import calibrate_neighbors, coverage  # noqa: E402,F401  (kpconv.py:714; needs plan_pyramid above)

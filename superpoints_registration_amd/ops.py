@@ -560,6 +560,41 @@ class RadiusTable:
             raise RuntimeError("Error")
         return out[:, :min(m, limit)], m
 
+    def count(self, queries: torch.Tensor, q_cu: torch.Tensor, hist_n: Optional[int] = None, *,
+              counts: bool = True, hist: Optional[torch.Tensor] = None):
+        """(int32 [Nq] untruncated counts of supports in range, int32 [nb, hist_n] per-cloud histogram of them or
+        None) without building a row (spr_radius_table_count): the candidates are those of query(), uncut -- no 128
+        columns, no hist_n.  A query with hist_n or more supports in range is not binned.  Takes no result slot and
+        no workspace; one device->host read of the status.
+        counts=False skips the per-query output (returns None for it); hist= an int32 [nb, hist_n] tensor to ADD the
+        histogram to instead of a fresh zeroed one (hist_n is then its width)."""
+        queries = _dev(queries, "queries", torch.float32)
+        q_cu = _dev(q_cu, "q_cu", torch.int32)
+        nq = queries.shape[0]
+        self_search = int(queries.data_ptr() == self.supports.data_ptr() and nq == self.ns
+                          and q_cu.data_ptr() == self.s_cu.data_ptr())
+        if hist is not None:
+            if (not hist.is_cuda or hist.dtype != torch.int32 or not hist.is_contiguous()
+                    or hist.dim() != 2 or hist.shape[0] != self.nb or hist_n not in (None, hist.shape[1])):
+                raise ValueError("RadiusTable.count: hist must be a contiguous int32 [nb, hist_n] device tensor")
+            hist_n = hist.shape[1]
+        elif hist_n is not None:    # at least one element, so that a refused width reaches the library as a width
+            hist = torch.zeros((self.nb * max(int(hist_n), 1),), dtype=torch.int32,
+                               device=queries.device).view(self.nb, -1)
+        out = torch.empty((nq,), dtype=torch.int32, device=queries.device) if counts else None
+        st = torch.empty((1,), dtype=torch.int32, device=queries.device)
+        _lib.check(_lib.lib().spr_radius_table_count(_ptr(queries), _ptr(q_cu), nq, self_search, self.ns, self.nb,
+                                                     self.radius, _ptr(self.blob), _ptr(out), _ptr(hist),
+                                                     0 if hist_n is None else int(hist_n), _ptr(st),
+                                                     _stream(queries)), "spr_radius_table_count")
+        s = int(st.item())
+        if s == -2:     # no count through the sorted-key search (algo 1): rows of hist_n indices are what this avoids
+            raise RuntimeError("spr_radius_table_count: the clouds' bounding boxes need more cells at this radius than "
+                               "the table holds (64 per support point + 2^20); voxelise or split the cloud")
+        if s < 0:
+            raise RuntimeError("spr_radius_table_count: cloud extent / radius exceeds 8191 cells per axis")
+        return out, hist
+
 
 def _wants_grad(*tensors) -> bool:
     """True when the call must go through autograd.py (gradients enabled and asked for)."""
