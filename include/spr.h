@@ -695,6 +695,54 @@ int spr_refine_pairs(const float* val, const float* val2, const int* ind, const 
                      float* pose, float* val_out, long long* ind_out, float* src_pts, float* tgt_pts, int* status,
                      void* ws, size_t ws_bytes, void* stream);
 
+/* ---- RANSAC for all pairs in one call (cfg.use_ransac) ------------------------
+ * Replaces the per-pair loop of RegTR.ransac (qk_regtr_full.py:400-421): per pair n_hyp random `sample`-point subsets
+ * WITH replacement, compute_rigid_transform on each, the hypothesis with the lowest mean residual over all of the
+ * pair's correspondences wins.  Two launches for the whole batch; no workspace (score and hyp_pose are outputs).
+ * a, b [T,3] f32 and w [T] f32 packed by set_cu [npairs+1] i32 (device) -- exactly what spr_refine_pairs returns as
+ * src_pts, tgt_pts, val_out and out_cu; pair p has n_p = set_cu[p+1] - set_cu[p] entries.
+ *
+ * 1. Draws (idx == NULL).  Philox4x32-10 with the key and counter layout of the augmentation draw contract above,
+ *    stream tag 3, side 0.  With SB = (sample + 3) / 4, sample s of hypothesis h of a pair with key k (< 2^63) and n
+ *    entries is word s & 3 of the block with
+ *      counter = (h * SB + (s >> 2), q & 0xffffffff, 3, q >> 32),  q = 2 k,   key = (seed & 0xffffffff, seed >> 32)
+ *      idx = (uint64(word) * n) >> 32
+ *    Multiply-shift without rejection: an index is over-represented by at most n / 2^32 (relative 3e-6 at n = 16 384).
+ *    A pair's draws depend on (seed, pair_key, n, n_hyp, sample) only.  Calls with n_hyp * SB >= 2^32 are refused with
+ *    a status return.  spr_ransac_draw is the same function on the host (the known-answer entry; n_host [npairs]).
+ *    With idx [npairs, n_hyp, sample] i32 (device) the samples are read instead and seed / pair_key are unused.
+ * 2. Hypothesis h = compute_rigid_transform (utils/se3_torch.py:109-163) on the `sample` gathered triples
+ *    (a[i], b[i], w[i]); duplicates count as often as they are drawn.  Float64 throughout, the arithmetic of
+ *    spr_weighted_procrustes: w~ = w / max(sum w, 1e-6), centroids, covariance sum (a - abar)(b - bbar)^T w~, one-sided
+ *    Jacobi SVD, the det <= 0 flip, t = bbar - R abar; the result is rounded to float32 into hyp_pose.  Summation
+ *    order, for the seven first-pass sums and the nine covariance entries alike: lane l of the hypothesis's wave adds
+ *    its samples l, l + 64, l + 128, ... in ascending order; the 64 lane sums are then combined by the butterfly
+ *    x += x(lane ^ 32), ^ 16, ^ 8, ^ 4, ^ 2, ^ 1.  The order does not depend on what else is in the batch.
+ * 3. score[h] = mean_i || b_i - (R a_i + t) || over all n entries from the ROUNDED float32 pose, in spr_pose_scores'
+ *    float32 arithmetic and order: v_r = b_r - (((x R_r0 + y R_r1) + z R_r2) + t_r), d2 = (v_0^2 + v_1^2) + v_2^2,
+ *    lane l adds sqrtf(d2) of entries l, l + 64, ... ascending, the same butterfly, then / (float)n.  So score[p] is
+ *    bit-equal to spr_pose_scores(hyp_pose[p], a_p, b_p) (a NaN is a NaN in both; its sign and payload are not
+ *    specified).
+ * 4. best = 0; for h = 1 .. n_hyp-1: if (score[h] < score[best]) best = h.  The first minimum; a NaN never wins; if
+ *    score[0] is NaN, best stays 0.  pose[p] is a bit copy of hyp_pose[p][best].
+ * 5. A pair's outputs depend on that pair's inputs and key only: no atomics, the same bits alone or at any place in
+ *    any batch.  status [npairs] i32 stays on the device (nothing here reads it back): 0 or
+ *      SPR_RANSAC_EMPTY       n_p == 0: pose = [I | 0], best = -1, score / hyp_pose of the pair not written
+ *      SPR_RANSAC_BAD_INDEX   an explicit idx outside [0, n_p): that sample is taken as 0, never a wild read
+ *      SPR_RANSAC_BAD_LAYOUT  set_cu does not ascend from 0 (anywhere: every pair then reports it): pose zeros, nothing
+ *                             else written.  set_cu[npairs] <= T is the caller's to guarantee.
+ * pose [npairs,3,4] f32, best [npairs] i32, score [npairs,n_hyp] f32, hyp_pose [npairs,n_hyp,3,4] f32.
+ * At most 65 535 pairs per call.
+ */
+#define SPR_RANSAC_EMPTY 1
+#define SPR_RANSAC_BAD_INDEX 2
+#define SPR_RANSAC_BAD_LAYOUT 4
+int spr_ransac_draw(uint64_t seed, const uint64_t* pair_key_host, const int* n_host, int npairs, int n_hyp,
+                    int sample, int* idx_host);
+int spr_ransac_pairs(const float* a, const float* b, const float* w, const int* set_cu, int npairs, int n_hyp,
+                     int sample, uint64_t seed, const uint64_t* pair_key, const int* idx, float* pose, int* best,
+                     float* score, float* hyp_pose, int* status, void* stream);
+
 /* ---- a13: Sinkhorn (slack) soft correspondences -----------------------------
  * Replaces the Sinkhorn branch of softmax_correlation
  * (qk_regtr_full.py:525-536 / :635-647) + sinkhorn() and the weighted target

@@ -104,6 +104,8 @@ SIGNATURES = {
     "spr_refine_pairs_workspace_bytes": (_sz, [_i, _i]),
     "spr_refine_pairs": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _i, _f, _f, _i, _vp, _i, _vp, _vp, _vp, _vp,
                               _vp, _vp, _vp, _sz, _vp]),
+    "spr_ransac_draw": (_i, [_u64, _vp, _vp, _i, _i, _i, _vp]),
+    "spr_ransac_pairs": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "spr_sinkhorn_workspace_bytes": (_sz, [_vp, _i]),
     "spr_match_sinkhorn": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "spr_sinkhorn_correspondences": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp,

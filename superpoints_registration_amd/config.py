@@ -32,6 +32,8 @@ _COMMON = dict(
     deform_radius=5.0, KP_extent=2.0, KP_influence='linear', use_batch_norm=True,
     batch_norm_momentum=0.02, modulated=False, num_kernel_points=15,
     use_lgr=False, use_ransac=False, remove_points_from_val=False, threshold_corr=False,
+    # not YAML keys: the literals of the reference's ransac() (qk_regtr_full.py:402-403) and the seed of its keyed draws
+    ransac_itr=500, ransac_sample_size=100, ransac_seed=0,
     remove_outliers_overlap=False, use_overlap_as_weights=False, use_ratio_test=False,
     lowe_thres=0.9, use_attn_affinity=False, use_corr_affinity=False,
     attention_type='dot_prod', nhead=8, d_embed=256, d_feedforward=1024, dropout=0.0,

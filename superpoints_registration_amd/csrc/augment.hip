@@ -21,49 +21,18 @@
 
 #include <cmath>
 
+#include "philox.h"
 #include "spr_common.h"
 
 namespace spr {
 namespace {
 
-constexpr uint32_t kPhM0 = 0xD2511F53u, kPhM1 = 0xCD9E8D57u, kPhW0 = 0x9E3779B9u, kPhW1 = 0xBB67AE85u;
-
-struct Philox4 {
-  uint32_t w[4];
-};
-
-__host__ __device__ inline Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                                 uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)kPhM0 * c0, p1 = (uint64_t)kPhM1 * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-    c1 = (uint32_t)p1;
-    c3 = (uint32_t)p0;
-    c0 = n0;
-    c2 = n2;
-    k0 += kPhW0;
-    k1 += kPhW1;
-  }
-  Philox4 o;
-  o.w[0] = c0, o.w[1] = c1, o.w[2] = c2, o.w[3] = c3;
-  return o;
-}
-
-// block (element, q = 2 pair_key + side, tag) of a seed
-__host__ __device__ inline Philox4 aug_block(uint64_t seed, uint64_t pair_key, int side, uint32_t element,
-                                             uint32_t tag) {
-  const uint64_t q = 2 * pair_key + (uint64_t)side;
-  return philox4x32_10(element, (uint32_t)q, tag, (uint32_t)(q >> 32), (uint32_t)seed, (uint32_t)(seed >> 32));
-}
-
-constexpr uint32_t kTagPair = 0, kTagNoise = 1, kTagKey = 2;
-
+// Philox4x32-10, the block layout and the stream tags: philox.h
 __device__ __forceinline__ float aug_u32(uint32_t w) { return __fmul_rn((float)(w >> 9) + 0.5f, 1.1920928955078125e-7f); }
 
 // (r(w0) cos(w1), r(w0) sin(w1), r(w2) cos(w3)): the accurate logf / sincosf / sqrtf, one rounding per operation
 __device__ __forceinline__ void aug_noise(uint64_t seed, uint64_t pair_key, int side, int i, float* n) {
-  const Philox4 b = aug_block(seed, pair_key, side, (uint32_t)i, kTagNoise);
+  const Philox4 b = philox_block(seed, pair_key, side, (uint32_t)i, kTagNoise);
   const float r0 = sqrtf(__fmul_rn(-2.f, logf(aug_u32(b.w[0]))));
   const float r1 = sqrtf(__fmul_rn(-2.f, logf(aug_u32(b.w[2]))));
   float s0, c0, s1, c1;
@@ -75,7 +44,7 @@ __device__ __forceinline__ void aug_noise(uint64_t seed, uint64_t pair_key, int 
 }
 
 __device__ __forceinline__ uint32_t aug_key(uint64_t seed, uint64_t pair_key, int side, int i) {
-  return aug_block(seed, pair_key, side, (uint32_t)i, kTagKey).w[0];
+  return philox_block(seed, pair_key, side, (uint32_t)i, kTagKey).w[0];
 }
 
 // cloud c of the stacked sequence: (pair, side, first global point, length)
@@ -418,13 +387,13 @@ void aug_normal2(uint32_t a, uint32_t b, double* c, double* s) {
 
 void aug_decide(uint64_t seed, uint64_t pair_key, int mode, unsigned char* perturb_src, unsigned char* swap,
                 float* P) {
-  const Philox4 b0 = aug_block(seed, pair_key, 0, 0, kTagPair);
+  const Philox4 b0 = philox_block(seed, pair_key, 0, 0, kTagPair);
   if (perturb_src) *perturb_src = aug_u64(b0.w[0]) > 0.5 ? 1 : 0;
   if (swap) *swap = aug_u64(b0.w[1]) > 0.5 ? 1 : 0;
   if (!P) return;
   double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0};
   if (mode != SPR_AUG_NONE) {
-    const Philox4 b1 = aug_block(seed, pair_key, 0, 1, kTagPair), b2 = aug_block(seed, pair_key, 0, 2, kTagPair);
+    const Philox4 b1 = philox_block(seed, pair_key, 0, 1, kTagPair), b2 = philox_block(seed, pair_key, 0, 2, kTagPair);
     if (mode == SPR_AUG_SMALL) {
       const double std_ = 0.1;
       const double z = 2.0 * aug_u64(b1.w[0]) - 1.0, s = std::sqrt(1.0 - z * z), phi = 2.0 * kAugPi * aug_u64(b1.w[1]);

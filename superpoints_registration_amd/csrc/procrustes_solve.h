@@ -107,6 +107,35 @@ static __device__ void svd3_jacobi(const double A[3][3], double U[3][3], double 
   }
 }
 
+// The serial end of the solve, shared with ransac.hip: the pose [R | t] (12 floats, row-major [3,4], rounded to float32)
+// from the reduced covariance cov [3x3, row-major] and the weighted centroids ca, cb.
+static __device__ void procrustes_pose(const double* cov, const double* ca, const double* cb, float* out) {
+  double A[3][3], U[3][3], S[3], V[3][3];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) A[r][c] = cov[3 * r + c];
+  svd3_jacobi(A, U, S, V);
+  // R = V U^T, flip V[:,2] when det <= 0  (se3_torch.py:150-157)
+  double R[3][3];
+  for (int pass = 0; pass < 2; ++pass) {
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c)
+        R[r][c] = V[r][0] * U[c][0] + V[r][1] * U[c][1] + V[r][2] * U[c][2];
+    const double det = R[0][0] * (R[1][1] * R[2][2] - R[1][2] * R[2][1]) -
+                       R[0][1] * (R[1][0] * R[2][2] - R[1][2] * R[2][0]) +
+                       R[0][2] * (R[1][0] * R[2][1] - R[1][1] * R[2][0]);
+    if (det > 0.0) break;
+    for (int r = 0; r < 3; ++r) V[r][2] = -V[r][2];
+  }
+  for (int r = 0; r < 3; ++r) {
+    double t = cb[r];
+    for (int c = 0; c < 3; ++c) {
+      out[4 * r + c] = (float)R[r][c];
+      t -= R[r][c] * ca[c];
+    }
+    out[4 * r + 3] = (float)t;
+  }
+}
+
 // The pose [R | t] (12 floats, row-major [3,4]) of the weighted point set (a_i, b_i, w_i), i in [0, n): thread 0 writes
 // it to `out` (global or LDS; no barrier behind the store).  a(i, d) / b(i, d): coordinate d of point i as float;
 // w(i): its weight as float, read only when `weighted`.  Every thread of the 256-thread workgroup must call this;
@@ -142,32 +171,7 @@ __device__ __forceinline__ void procrustes_block(int n, bool weighted, FA a, FB 
       for (int c = 0; c < 3; ++c) cov[3 * r + c] += da[r] * db[c];
   }
   block_reduce_d(cov, 9, sh);
-  if (threadIdx.x == 0) {
-    double A[3][3], U[3][3], S[3], V[3][3];
-    for (int r = 0; r < 3; ++r)
-      for (int c = 0; c < 3; ++c) A[r][c] = cov[3 * r + c];
-    svd3_jacobi(A, U, S, V);
-    // R = V U^T, flip V[:,2] when det <= 0  (se3_torch.py:150-157)
-    double R[3][3];
-    for (int pass = 0; pass < 2; ++pass) {
-      for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c)
-          R[r][c] = V[r][0] * U[c][0] + V[r][1] * U[c][1] + V[r][2] * U[c][2];
-      const double det = R[0][0] * (R[1][1] * R[2][2] - R[1][2] * R[2][1]) -
-                         R[0][1] * (R[1][0] * R[2][2] - R[1][2] * R[2][0]) +
-                         R[0][2] * (R[1][0] * R[2][1] - R[1][1] * R[2][0]);
-      if (det > 0.0) break;
-      for (int r = 0; r < 3; ++r) V[r][2] = -V[r][2];
-    }
-    for (int r = 0; r < 3; ++r) {
-      double t = cb[r];
-      for (int c = 0; c < 3; ++c) {
-        out[4 * r + c] = (float)R[r][c];
-        t -= R[r][c] * ca[c];
-      }
-      out[4 * r + 3] = (float)t;
-    }
-  }
+  if (threadIdx.x == 0) procrustes_pose(cov, ca, cb, out);
 }
 
 #endif

@@ -1438,7 +1438,100 @@ def refine_pairs(val, val2, ind, overlap, xyz, cu, cu_host: Sequence[int], npair
                                   _ptr(o_src), _ptr(o_tgt), _ptr(status), _ptr(ws), ws.numel() if ws is not None else 0,
                                   _stream(val)), "spr_refine_pairs")
     return {'pose': pose, 'val': o_val[:S], 'ind': o_ind[:S], 'src_pts': o_src[:S], 'tgt_pts': o_tgt[:S],
-            'out_cu': out_cu, 'status': status}
+            'out_cu': out_cu, 'out_cu_dev': meta[B:], 'status': status}
+
+
+RANSAC_EMPTY, RANSAC_BAD_INDEX, RANSAC_BAD_LAYOUT = 1, 2, 4
+
+
+def _ransac_sizes(what: str, n_hyp, sample):
+    n_hyp, sample = int(n_hyp), int(sample)
+    if n_hyp < 1 or sample < 1:
+        raise ValueError(f"{what}: n_hyp {n_hyp} and sample {sample} must be at least 1")
+    if n_hyp * ((sample + 3) // 4) >= 2 ** 32:
+        raise ValueError(f"{what}: n_hyp * ceil(sample / 4) = {n_hyp * ((sample + 3) // 4)} does not fit the 32-bit "
+                         "block counter")
+    return n_hyp, sample
+
+
+def _pair_keys(what: str, pair_keys, B: int) -> np.ndarray:
+    if isinstance(pair_keys, torch.Tensor):
+        pair_keys = pair_keys.tolist()
+    keys = list(range(B)) if pair_keys is None else [int(k) for k in np.asarray(pair_keys, dtype=object).reshape(-1)]
+    if len(keys) != B:
+        raise ValueError(f"{what}: {len(keys)} pair keys for {B} pairs")
+    if any(not 0 <= k < 2 ** 63 for k in keys):
+        raise ValueError(f"{what}: pair keys must lie in [0, 2^63)")
+    return np.asarray(keys, dtype=np.uint64)
+
+
+def ransac_draw(seed: int, pair_keys, n, n_hyp: int, sample: int) -> np.ndarray:
+    """The sample indices ransac_pairs draws for pairs `pair_keys` of `n` entries each under `seed`, through the
+    library's host path (spr_ransac_draw; the draw contract is in include/spr.h): int32 [B, n_hyp, sample].  Needs no
+    device."""
+    n_hyp, sample = _ransac_sizes("ransac_draw", n_hyp, sample)
+    n_h = [int(x) for x in np.asarray(n).reshape(-1)]
+    pk = _pair_keys("ransac_draw", pair_keys, len(n_h))
+    if any(not 0 <= x < 2 ** 31 for x in n_h):
+        raise ValueError(f"ransac_draw: n {n_h} must lie in [0, 2^31)")
+    if not 0 <= int(seed) < 2 ** 64:
+        raise ValueError("ransac_draw: seed must lie in [0, 2^64)")
+    n_arr = np.asarray(n_h, dtype=np.int32)
+    out = np.zeros((len(n_h), n_hyp, sample), dtype=np.int32)
+    _lib.check(_lib.lib().spr_ransac_draw(int(seed), pk.ctypes.data, n_arr.ctypes.data, len(n_h), n_hyp, sample,
+                                          out.ctypes.data), "spr_ransac_draw")
+    return out
+
+
+def ransac_pairs(a, b, w, set_cu, set_cu_host: Sequence[int], *, n_hyp: int = 500, sample: int = 100, seed: int = 0,
+                 pair_keys=None, idx=None) -> dict:
+    """RANSAC (RegTR.ransac, qk_regtr_full.py:400-421) for all pairs of a batch in one call (spr_ransac_pairs; the
+    contract -- draws, summation order, arg-min rule -- is in include/spr.h).  a, b [T,3] and w [T] packed by set_cu
+    int32 [B+1] with its host copy set_cu_host: what refine_pairs returns as src_pts, tgt_pts, val, out_cu_dev and
+    out_cu.  Per pair n_hyp hypotheses of `sample` entries drawn with replacement from Philox blocks keyed on
+    (seed, pair key); pair_keys None = the position in the batch.  idx int32 [B, n_hyp, sample] replaces the draws.
+    Returns a dict of device tensors: pose [B,3,4], best [B] int32 (-1 for an empty pair), score [B, n_hyp],
+    hyp_pose [B, n_hyp, 3, 4], status [B] int32 (0, RANSAC_EMPTY, RANSAC_BAD_INDEX, RANSAC_BAD_LAYOUT) -- nothing here
+    reads it back."""
+    n_hyp, sample = _ransac_sizes("ransac_pairs", n_hyp, sample)
+    cu_h = [int(c) for c in set_cu_host]
+    B = len(cu_h) - 1
+    if B < 1 or cu_h[0] != 0 or any(y < x for x, y in zip(cu_h, cu_h[1:])):
+        raise ValueError(f"ransac_pairs: set_cu_host {cu_h[:8]}{'...' if len(cu_h) > 8 else ''} is not an ascending "
+                         "prefix from 0 over at least one pair")
+    if B > 65535:
+        raise ValueError(f"ransac_pairs: {B} pairs, at most 65535 per call")
+    T = cu_h[-1]
+    shapes = tuple(tuple(t.shape) if isinstance(t, torch.Tensor) else None for t in (a, b, w, set_cu))
+    if shapes[0] != (T, 3) or shapes[1] != (T, 3) or shapes[2] not in ((T,), (T, 1)) or shapes[3] != (B + 1,):
+        raise ValueError(f"ransac_pairs: a / b / w / set_cu of shapes {shapes}; set_cu_host describes {T} entries in "
+                         f"{B} pairs")
+    pk = _pair_keys("ransac_pairs", pair_keys, B)
+    if not 0 <= int(seed) < 2 ** 64:
+        raise ValueError("ransac_pairs: seed must lie in [0, 2^64)")
+    if idx is not None and (not isinstance(idx, torch.Tensor) or tuple(idx.shape) != (B, n_hyp, sample)):
+        raise ValueError(f"ransac_pairs: idx {tuple(idx.shape) if isinstance(idx, torch.Tensor) else type(idx)}, "
+                         f"expected {(B, n_hyp, sample)}")
+    a, b = _dev(a, "a", torch.float32), _dev(b, "b", torch.float32)
+    w = _dev(w, "w", torch.float32).reshape(-1)
+    set_cu = _dev(set_cu, "set_cu", torch.int32)
+    dev = a.device
+    if T == 0:                    # every pair empty: the library wants real pointers
+        a, b, w = a.new_zeros((1, 3)), b.new_zeros((1, 3)), w.new_zeros((1,))
+    pk_dev = None
+    if idx is None:
+        pk_dev = torch.from_numpy(pk.view(np.int64)).to(dev)
+    else:
+        idx = _dev(idx, "idx", torch.int32)
+    pose = torch.empty((B, 3, 4), dtype=torch.float32, device=dev)
+    best = torch.empty((B,), dtype=torch.int32, device=dev)
+    score = torch.empty((B, n_hyp), dtype=torch.float32, device=dev)
+    hyp_pose = torch.empty((B, n_hyp, 3, 4), dtype=torch.float32, device=dev)
+    status = torch.empty((B,), dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().spr_ransac_pairs(_ptr(a), _ptr(b), _ptr(w), _ptr(set_cu), B, n_hyp, sample, int(seed),
+                                           _ptr(pk_dev), _ptr(idx), _ptr(pose), _ptr(best), _ptr(score),
+                                           _ptr(hyp_pose), _ptr(status), _stream(a)), "spr_ransac_pairs")
+    return {'pose': pose, 'best': best, 'score': score, 'hyp_pose': hyp_pose, 'status': status}
 
 
 def _match_head(feat, xyz, cu, cu_host: Sequence[int], npairs: int, alpha, beta, n_iters: int, *, match: bool,

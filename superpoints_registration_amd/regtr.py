@@ -171,7 +171,7 @@ class RegTR(nn.Module):
         B = len(batch['src_xyz'])
         tokens, xyz_c, lens_c, meta = self._encode(list(batch['src_xyz']) + list(batch['tgt_xyz']))
         batch['kpconv_meta'] = meta                      # qk_regtr_full.py:153
-        return self._register(tokens, xyz_c, lens_c[:B], lens_c[B:])
+        return self._register(tokens, xyz_c, lens_c[:B], lens_c[B:], pair_keys=batch.get('pair_key'))
 
     def _encode(self, clouds):
         """The per-cloud half of the forward: pyramid, KPConv encoder, feat_proj.  Nothing here looks across clouds.
@@ -212,9 +212,10 @@ class RegTR(nn.Module):
         tokens = ops.linear(feats_un, self.feat_proj.weight, self.feat_proj.bias)
         return tokens, meta['points'][-1], meta['_lens_host'][-1], meta
 
-    def _register(self, tokens, xyz_c, src_lens, tgt_lens, segments=None):
+    def _register(self, tokens, xyz_c, src_lens, tgt_lens, segments=None, pair_keys=None):
         """The per-pair half: position embedding, cross-encoder, overlap head, matching + pose on tokens / points
-        packed [src_0..src_{B-1}, tgt_0..tgt_{B-1}].  segments: make_segments(src_lens, tgt_lens) if the caller has it."""
+        packed [src_0..src_{B-1}, tgt_0..tgt_{B-1}].  segments: make_segments(src_lens, tgt_lens) if the caller has it.
+        pair_keys: what keys the RANSAC draws of use_ransac ([B] ints; None = the position in the batch)."""
         cfg = self.cfg
         B = len(src_lens)
         device = tokens.device
@@ -253,7 +254,7 @@ class RegTR(nn.Module):
         src_xyz_all, tgt_xyz_all = xyz_c[:n_src], xyz_c[n_src:]
         refined = None
         if refine:
-            refined = self._refined_pose(xyz_c, overlap, val, val2, ind, cu, cu_host, B, cond)
+            refined = self._refined_pose(xyz_c, overlap, val, val2, ind, cu, cu_host, B, cond, pair_keys)
             pose = refined['pose']
         elif cfg.use_sinkhorn:
             if w is None:
@@ -334,10 +335,11 @@ class RegTR(nn.Module):
             tokens, xyz_c, lens_c, meta = self._encode(clouds)
         return EncodedClouds(tokens, xyz_c, lens_c, cu=meta['_cu'][len(meta['points']) - 1], kpconv_meta=meta)
 
-    def register(self, enc: EncodedClouds, pairs) -> dict:
+    def register(self, enc: EncodedClouds, pairs, pair_keys=None) -> dict:
         """forward()'s output dict for the pairs (src_index, tgt_index) into `enc`: one ops.pair_gather per tensor
         lays tokens and points out as [src_0..src_{P-1}, tgt_0..tgt_{P-1}], then the unchanged second half of
-        forward() runs (position embedding of the gathered points, cross-encoder, overlap head, matching + pose)."""
+        forward() runs (position embedding of the gathered points, cross-encoder, overlap head, matching + pose).
+        pair_keys: as batch['pair_key'] of forward() (the RANSAC draws of use_ransac; None = the position in `pairs`)."""
         self._inference_only("register")
         pairs = [tuple(p) for p in pairs]
         if not pairs:
@@ -356,7 +358,7 @@ class RegTR(nn.Module):
             rows = sum(src_lens) + sum(tgt_lens)
             tok = ops.pair_gather(tokens, enc.cu, idx[:P], idx[P:], segments[0], rows=rows)
             xyz = ops.pair_gather(points, enc.cu, idx[:P], idx[P:], segments[0], rows=rows)
-            return self._register(tok, xyz, src_lens, tgt_lens, segments)
+            return self._register(tok, xyz, src_lens, tgt_lens, segments, pair_keys)
 
     # ------------------------------------------------------------------ #
     def compute_loss(self, pred, batch):
@@ -414,13 +416,14 @@ class RegTR(nn.Module):
         losses['total'] = losses['T'] + 0.1 * losses['feature'] + losses['overlap']
         return losses
 
-    def _refined_pose(self, xyz_c, overlap, val, val2, ind, cu, cu_host, B, cond):
+    def _refined_pose(self, xyz_c, overlap, val, val2, ind, cu, cu_host, B, cond, pair_keys=None):
         """The config-off refinements of RegTR.softmax_correlation (qk_regtr_full.py:445-668) for all pairs in ONE
         library call (ops.refine_pairs): Lowe ratio test (:370-384), median threshold (:471-473), overlap weighting
         (:484-494), top-k pruning (:499-502), then the pose, then LGR (:386-398).  With use_sinkhorn the Sinkhorn solve
-        goes first and its pose stands (:525-536); RANSAC (:400-421) follows per pair, only when use_ransac -- its 500
-        hypotheses as ONE batched Procrustes launch + one scoring launch.  The per-pair tensors returned are views
-        of the packed outputs."""
+        goes first and its pose stands (:525-536); RANSAC (:400-421) follows only when use_ransac, for all pairs in one
+        ops.ransac_pairs call: cfg.ransac_itr (500) hypotheses of cfg.ransac_sample_size (100) entries per pair, drawn
+        from (cfg.ransac_seed, pair key) -- pair_keys [B] ints, None = the position in the batch -- so a pair's pose
+        is the same on every call.  The per-pair tensors returned are views of the packed outputs."""
         cfg = self.cfg
         on = lambda f: bool(cfg.get(f, False))
         sink, topk, lgr = bool(cfg.use_sinkhorn), on('remove_points_from_val'), on('use_lgr')
@@ -430,6 +433,9 @@ class RegTR(nn.Module):
             raise ValueError("use_overlap_as_weights needs remove_outliers_overlap (as in the reference)")
         if sink and lgr and not topk and any(n != m for n, m in zip(n_src, n_tgt)):
             raise ValueError("use_lgr over the Sinkhorn point sets needs src and tgt clouds of equal length "
+                             "(or remove_points_from_val), as in the reference")
+        if sink and on('use_ransac') and not topk and any(n != m for n, m in zip(n_src, n_tgt)):
+            raise ValueError("use_ransac over the Sinkhorn point sets needs src and tgt clouds of equal length "
                              "(or remove_points_from_val), as in the reference")
         sk_pose = None
         if sink:   # the Sinkhorn pose ignores the pruned correspondences (:525-536)
@@ -451,9 +457,13 @@ class RegTR(nn.Module):
             out['src_pts'] = [xyz_c[cu_host[b]:cu_host[b + 1]] for b in range(B)]
             out['tgt_pts'] = [xyz_c[cu_host[B + b]:cu_host[B + b + 1]] for b in range(B)]
         out['pose'] = r['pose']
-        if on('use_ransac'):
-            out['pose'] = torch.stack([self._ransac(out['src_pts'][b].contiguous(), out['tgt_pts'][b].contiguous(),
-                                                    out['val'][b].contiguous()) for b in range(B)])
+        if on('use_ransac'):   # all pairs in one call, over the packed sets refine_pairs left on the device
+            a, bb = r['src_pts'], r['tgt_pts']
+            if sink and not topk:  # the clouds themselves: with equal lengths they are packed by out_cu already
+                a, bb = xyz_c[:cu_host[B]], xyz_c[cu_host[B]:]
+            out['pose'] = ops.ransac_pairs(a, bb, r['val'], r['out_cu_dev'], oc, n_hyp=int(cfg.get('ransac_itr', 500)),
+                                           sample=int(cfg.get('ransac_sample_size', 100)),
+                                           seed=int(cfg.get('ransac_seed', 0)), pair_keys=pair_keys)['pose']
         return out
 
     @staticmethod
