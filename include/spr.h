@@ -152,6 +152,45 @@ int spr_radius_table_count(const float* q_xyz, const int* q_cu, int nq, int self
                            float radius, const void* table, int* counts, int* hist, int hist_n,
                            int* status, void* stream);
 
+/* ---- a2: neighbour ties in the reference's order ---------------------------------
+ * The rows above order an equal-d2 run by index.  batch_nanoflann_neighbors (neighbors.cpp:211-332) orders it by the
+ * kd-tree's visit order passed through an unstable std::sort (nanoflann.hpp:1279-1289): a deterministic function of
+ * the cloud's supports, in cloud order, and of the query.  These entry points restate that function (nanoflann's tree
+ * build with leaf size 10, its radius search with eps 0, libstdc++'s introsort on the distance alone; csrc/tie_order.h)
+ * and rewrite, in place, the rows of a SPR_SELECT_NEAREST matrix in which an equal-d2 run touches the kept columns --
+ * two kept entries with the same d2, or the last kept entry of a row cut at `width` and an entry behind the cut.
+ * Afterwards the matrix equals the reference's, cut to its first `width` columns (kpconv.py:259-260), index for index.
+ * Every other row keeps its bits.
+ *   tree: spr_kdtree_replay_size(ns, nb) bytes, 256-byte aligned, owned by the caller; built once per support set
+ *     (it does not depend on the radius) by spr_kdtree_replay_build, one wave per cloud.  Its first int32 is the depth
+ *     of the deepest cloud's tree (nodes on the longest root-to-leaf path) once the build has run: the caller reads
+ *     it and passes it as `depth`, which sizes the walk stacks;
+ *   nbr [nq, stride] i32: the matrix as spr_radius_neighbors / spr_radius_table_query wrote it; width <= stride: the
+ *     kept columns, min(max_count, limit); max_count: the search's untruncated widest row, which sizes a row's
+ *     scratch;
+ *   status [4] i32 device, written by every call: [0] rows_fixed, the rows rewritten; [1] set_mismatch, rows whose
+ *     replayed neighbours are not the row's (left as they were; never expected); [2] rows whose replay did not fit
+ *     max_count or depth (left as they were); [3] != 0: the tree is not one of these supports, failed to build, or is
+ *     deeper than `depth` -- decided before any row is touched, and no row is.
+ * A workspace smaller than the query's is refused before anything is enqueued.  The two size queries end in _size,
+ * not _bytes: the workspace's is not monotone in max_count or depth (the fix-up runs fewer lanes, each with its own
+ * stack and scratch, as a lane's share grows), which every *_bytes query of this header is.  spr_tie_order_host is the same
+ * function on host memory (tree included; status on the host), spr_std_sort_replay_host the sort alone: perm_host
+ * [n] = the order std::sort leaves n pairs (i, keys_host[i]) in when it compares keys only, *heap_ranges_host = the
+ * ranges that exhausted the depth limit and were heap-sorted.
+ */
+size_t spr_kdtree_replay_size(int ns, int nb);
+int spr_kdtree_replay_build(const float* s_xyz, const int* s_cu, int ns, int nb, void* tree, size_t tree_bytes,
+                            void* stream);
+size_t spr_tie_order_workspace_size(int nq, int max_count, int depth);
+int spr_tie_order(const float* q_xyz, const int* q_cu, int nq, const float* s_xyz, const int* s_cu, int ns, int nb,
+                  float radius, const void* tree, int depth, int* nbr, int stride, int width, int max_count,
+                  int* status, void* ws, size_t ws_bytes, void* stream);
+int spr_tie_order_host(const float* q_xyz_host, const int* q_cu_host, int nq, const float* s_xyz_host,
+                       const int* s_cu_host, int ns, int nb, float radius, int* nbr_host, int stride, int width,
+                       int max_count, int* status_host);
+int spr_std_sort_replay_host(const float* keys_host, int n, int* perm_host, int* heap_ranges_host);
+
 /* ---- 8f-5: ground-truth overlap masks and mutual correspondences ---------------
  * Replaces compute_overlap(src, tgt, search_voxel_size) (utils/pointcloud.py:8-65: one Open3D kd-tree radius query
  * per point), called per pair by the loaders (data_loaders/threedmatch.py:78-84) and by

@@ -36,6 +36,12 @@ SIGNATURES = {
     "spr_radius_table_build": (_i, [_vp, _vp, _i, _i, _f, _vp, _sz, _vp, _sz, _vp]),
     "spr_radius_table_query": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _sz, _vp]),
     "spr_radius_table_count": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i, _vp, _vp]),
+    "spr_kdtree_replay_size": (_sz, [_i, _i]),
+    "spr_kdtree_replay_build": (_i, [_vp, _vp, _i, _i, _vp, _sz, _vp]),
+    "spr_tie_order_workspace_size": (_sz, [_i, _i, _i]),
+    "spr_tie_order": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _f, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "spr_tie_order_host": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _f, _vp, _i, _i, _i, _vp]),
+    "spr_std_sort_replay_host": (_i, [_vp, _i, _vp, _vp]),
     "spr_gt_overlap_workspace_bytes": (_sz, [_i, _i, _i]),
     "spr_gt_overlap": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                             _sz, _vp]),

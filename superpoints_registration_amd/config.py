@@ -44,6 +44,9 @@ _COMMON = dict(
     # which supports a neighbour row keeps when more than the level's limit lie in range: 'nearest' (the reference's
     # CPU Preprocessor, cpp_neighbors) or 'index' (its PreprocessorGPU: pytorch3d ball_query, lowest indices first)
     neighbor_select='nearest',
+    # the order inside an equal-distance run of a 'nearest' row: 'index' (ascending support index) or 'reference' (the
+    # order cpp_neighbors' kd-tree search and std::sort leave it in: matrices equal to the reference's, index for index)
+    tie_order='index',
     # solver section of the YAML files (read by training.configure_optimizers / Trainer)
     optimizer='AdamW', base_lr=0.0001, weight_decay=0.0001, grad_clip=0.1, scheduler='step',
     scheduler_param=[127800, 0.5], reg_success_thresh_rot=10, reg_success_thresh_trans=0.1,

@@ -25,6 +25,8 @@ def _lib():
         L = ctypes.CDLL(_LIB)          # OSError if the library is missing: there is no CPU fallback
         L.spr_grid_subsample_workspace_bytes.restype = ctypes.c_size_t
         L.spr_radius_neighbors_workspace_bytes.restype = ctypes.c_size_t
+        L.spr_kdtree_replay_size.restype = ctypes.c_size_t
+        L.spr_tie_order_workspace_size.restype = ctypes.c_size_t
         L.spr_last_error.restype = ctypes.c_char_p
         _L = L
     return _L
@@ -82,10 +84,15 @@ class cpp_neighbors:
     """Replaces radius_neighbors.cpython-*.so (cpp_neighbors/wrapper.cpp)."""
 
     @staticmethod
-    def batch_query(queries, supports, q_batches, s_batches, radius=0.1, limit=128):
+    def batch_query(queries, supports, q_batches, s_batches, radius=0.1, limit=128, ties='index'):
         """-> int32 [Nq, max_count] neighbour indices into `supports`, shadow index = Ns, rows ordered
         by distance.  `limit` = the library's cap on the row width (128); the reference's callers
-        slice to neighborhood_limits (<= 74) anyway (kpconv.py:259-260)."""
+        slice to neighborhood_limits (<= 74) anyway (kpconv.py:259-260).
+        ties: the order inside a run of equal distances -- 'index' (ascending support index) or 'reference' (the
+        order the module this replaces leaves it in: the matrix then equals its matrix, cut to `limit` columns,
+        index for index)."""
+        if ties not in ('index', 'reference'):
+            raise ValueError(f"ties must be 'index' or 'reference', got {ties!r}")
         L = _lib()
         dev = torch.device("cuda")
         q = torch.as_tensor(np.ascontiguousarray(queries, dtype=np.float32)).to(dev)
@@ -109,4 +116,26 @@ class cpp_neighbors:
                 break
         if m < 1:
             raise RuntimeError("Error")                                   # wrapper.cpp:201-205
+        if ties == 'reference':
+            _reference_ties(L, dev, q, q_cu, nq, s, s_cu, ns, nb, radius, out, limit, m)
         return out[:, :min(m, limit)].cpu().numpy()
+
+
+def _reference_ties(L, dev, q, q_cu, nq, s, s_cu, ns, nb, radius, out, limit, m):
+    """spr_kdtree_replay_build + spr_tie_order on the [nq, limit] matrix `out` (include/spr.h), in place."""
+    tree = torch.empty(L.spr_kdtree_replay_size(ns, nb), dtype=torch.uint8, device=dev)
+    if L.spr_kdtree_replay_build(_p(s), _p(s_cu), ns, nb, _p(tree), ctypes.c_size_t(tree.numel()), _stream(dev)):
+        _raise(L)
+    depth, bad = tree[:8].view(torch.int32).tolist()
+    if bad:
+        raise RuntimeError("kd-tree replay failed to build (non-finite coordinates)")
+    ws = torch.empty(L.spr_tie_order_workspace_size(nq, m, depth), dtype=torch.uint8, device=dev)
+    st = torch.empty(4, dtype=torch.int32, device=dev)
+    if L.spr_tie_order(_p(q), _p(q_cu), nq, _p(s), _p(s_cu), ns, nb, ctypes.c_float(radius), _p(tree), depth, _p(out),
+                       int(limit), min(m, limit), m, _p(st), _p(ws), ctypes.c_size_t(ws.numel()), _stream(dev)):
+        _raise(L)
+    st = st.tolist()
+    if any(st[1:]):
+        raise RuntimeError(f"tie order replay disagrees with the search: set_mismatch {st[1]}, overflow {st[2]}, "
+                           f"tree error {st[3]}")
+    cpp_neighbors.last_ties = {"rows_fixed": st[0], "set_mismatch": st[1], "rows": nq}

@@ -32,6 +32,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from . import tie_order as _tie
 from .kpconv_blocks import block_decider
 
 NEIGHBOR_SELECT = {'nearest': ops.SELECT_NEAREST, 'index': ops.SELECT_INDEX}
@@ -222,10 +223,16 @@ class Preprocessor(nn.Module):
     ascending, always limit columns); None reads cfg.neighbor_select.  It
     applies to the conv, pool and up-sampling searches; points and lengths do
     not depend on it.
+    tie_order: 'index' (default: an equal-distance run of a 'nearest' row is in
+    ascending index order) or 'reference' (the order the reference's kd-tree
+    search and std::sort leave it in: every matrix equals the reference's CPU
+    Preprocessor's, index for index; tie_order.py); None reads cfg.tie_order.
+    One kd-tree replay per level serves its conv, pool and up-sampling fix-ups;
+    `tie_status` then maps (level, kind) to the latest (rows_fixed, ...) status.
     """
 
     def __init__(self, cfg, compute_upsamples=True, order=ops.ORDER_REFERENCE,
-                 index_dtype=torch.int64, neighbor_select=None):
+                 index_dtype=torch.int64, neighbor_select=None, tie_order=None):
         super().__init__()
         self.cfg = cfg
         if neighbor_select is None:
@@ -233,6 +240,10 @@ class Preprocessor(nn.Module):
         if neighbor_select not in NEIGHBOR_SELECT:
             raise ValueError(f"neighbor_select must be 'nearest' or 'index', got {neighbor_select!r}")
         self.neighbor_select = neighbor_select
+        if tie_order is None:
+            tie_order = cfg.get('tie_order', 'index')
+        self.tie_order = _tie.check(tie_order, neighbor_select)
+        self.tie_status = {}
         self.compute_upsamples = compute_upsamples
         self.order = order
         self.index_dtype = index_dtype
@@ -287,6 +298,7 @@ class Preprocessor(nn.Module):
         # One cell table per (supports, radius): a level's conv and pool searches and the previous level's
         # up-sampling search (radius 2 r = the next level's r) all look into the same one.
         table = [None]
+        tree = [None]                             # tie_order='reference': one kd-tree replay per support set
 
         def search(key, queries, q_cu, supports, s_cu, radius, limit):
             if table[0] is None or not table[0].matches(supports, s_cu, radius):
@@ -295,6 +307,10 @@ class Preprocessor(nn.Module):
             idx, m = table[0].query(queries, q_cu, limit, dense=None if prev is None else prev > 1.5 * limit,
                                     select=select)
             self._row_counts[key] = m
+            if self.tie_order == 'reference':
+                if tree[0] is None or not tree[0].matches(supports, s_cu):
+                    tree[0] = _tie.ReplayTree(supports, s_cu)
+                self.tie_status[key] = tree[0].apply(idx, queries, q_cu, radius, m)
             return idx
 
         select = NEIGHBOR_SELECT[self.neighbor_select]

@@ -287,13 +287,20 @@ def voxel_downsample(points: torch.Tensor, voxel_size: float) -> torch.Tensor:
 def radius_neighbors(queries: torch.Tensor, supports: torch.Tensor, q_cu: torch.Tensor,
                      s_cu: torch.Tensor, radius: float, limit: int,
                      exact_width: bool = True, algo: int = 0,
-                     select: int = SELECT_NEAREST) -> Tuple[torch.Tensor, int]:
+                     select: int = SELECT_NEAREST, tie_order: str = 'index') -> Tuple[torch.Tensor, int]:
     """a2.  int32 [Nq, W] neighbour indices (shadow = Ns) and the untruncated
     max count.  exact_width=True slices to W = min(max_count, limit) like the
     reference (one device->host read); False keeps W = limit (no sync).
     select=SELECT_INDEX keeps the `limit` lowest support indices in range, ascending, instead of the `limit`
     nearest (the reference's batch_neighbors_kpconv_gpu, kpconv.py:265-292): W = limit always, and a search
-    without a single neighbour is not an error there."""
+    without a single neighbour is not an error there.
+    tie_order='reference' (nearest rule, exact_width only): equal-d2 runs in the order the reference's kd-tree search
+    and std::sort leave them in instead of by index (tie_order.py); the default rows, bits and launches are unchanged."""
+    if tie_order != 'index':
+        from . import tie_order as _tie
+        _tie.check(tie_order, select)
+        if not exact_width:
+            raise ValueError("tie_order='reference' needs exact_width=True (the fix-up is sized by the max count)")
     queries = _dev(queries, "queries", torch.float32)
     supports = _dev(supports, "supports", torch.float32)
     q_cu = _dev(q_cu, "q_cu", torch.int32)
@@ -310,13 +317,16 @@ def radius_neighbors(queries: torch.Tensor, supports: torch.Tensor, q_cu: torch.
         return out, -1
     m = int(mc.item())
     if m == -2 and algo == 0:   # cell table too small for this geometry: exact same result, slower path
-        return radius_neighbors(queries, supports, q_cu, s_cu, radius, limit, exact_width, algo=1, select=select)
+        return radius_neighbors(queries, supports, q_cu, s_cu, radius, limit, exact_width, algo=1, select=select,
+                                tie_order=tie_order)
     if m < 0:
         raise RuntimeError("spr_radius_neighbors: cloud extent / radius exceeds 8191 cells per axis")
     if select == SELECT_INDEX:  # kpconv.py:284-292: K columns whatever the counts, no emptiness check
         return out, m
     if m < 1:  # cpp_neighbors/wrapper.cpp:201-205
         raise RuntimeError("Error")
+    if tie_order != 'index':
+        _tie.apply(out[:, :min(m, limit)], queries, q_cu, supports, s_cu, radius, m)
     return out[:, :min(m, limit)], m
 
 

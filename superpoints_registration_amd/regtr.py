@@ -127,7 +127,8 @@ class RegTR(nn.Module):
                                       "'index' (its PreprocessorGPU, kpconv.py:265-292)")
 
         self.preprocessor = Preprocessor(cfg, compute_upsamples=compute_upsamples, order=order,
-                                         neighbor_select=cfg.get('neighbor_select', 'nearest'))
+                                         neighbor_select=cfg.get('neighbor_select', 'nearest'),
+                                         tie_order=cfg.get('tie_order', 'index'))
         self.kpf_encoder = KPFEncoder(cfg, cfg.d_embed)
         self.feat_proj = nn.Linear(self.kpf_encoder.encoder_skip_dims[-1], cfg.d_embed, bias=True)
         if cfg.get('pos_emb_type', 'sine') == 'sine':
