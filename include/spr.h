@@ -78,6 +78,33 @@ size_t spr_voxel_downsample_workspace_bytes(int n);
 int spr_voxel_downsample(const float* xyz, int n, double voxel_size, int* out_idx,
                          int* out_count, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- raw KITTI scans of a whole batch -> the forward's clouds, one call ----------
+ * Replaces the point path of KittiDataset.__getitem__ (data_loaders/kitti_pred.py:203-230) for every scan
+ * of a batch: voxel_down_sample(xyz, voxel_size), the crop to crop_radius, the ground cut.  Per cloud b
+ *   kept  = the first point (lowest index) of every voxel, voxel = trunc((double)p / voxel_size) per axis
+ *           (spr_voxel_downsample's arithmetic);
+ *   kept &= crop_radius <= 0 or sqrt(x*x + y*y) <= crop_radius   (float64, every operation rounded once);
+ *   kept &= !remove_ground  or z > -1.0                           (strict)
+ * in the loader's order: the masks act on the filter's output, so a voxel whose first point is masked yields
+ * nothing (not its second point).  No sort: a per-cloud open-addressing table of point indices, five launches
+ * and one memset for the whole batch, nothing read back.
+ *   pts     [n, stride] f32, stride 3 or 4 (4: np.fromfile(...).reshape(-1, 4) as it is; the 4th column is
+ *           never read)            cu [nb+1] i32 (device), every cloud at least one point
+ *   out_xyz [n,3] f32, out_idx [n] i32: the first m rows are valid, m = out_cu[nb].  out_idx = the kept point's
+ *           index inside its own cloud; ascending inside a cloud, clouds in input order
+ *   out_cu  [nb+1] i32: cloud boundaries of the output (a cloud may come out empty)
+ *   status  [1] i32: 0, or one of SPR_PREPARE_* (the outputs are then meaningless)
+ *   scratch int32 [scratch_len], scratch_len >= spr_prepare_scans_scratch_len(n, nb) (a count of ints, not
+ *           bytes); a shorter one is refused, status 2, before anything is enqueued.  n <= 2^31 - 1025.
+ */
+#define SPR_PREPARE_RANGE (-1)      /* a coordinate is not finite or not inside +-2^20 voxels (|p / voxel| < 2^20) */
+#define SPR_PREPARE_PROBE (-2)      /* a point found no slot in its cloud's table region (cannot happen: load <= 1/2) */
+#define SPR_PREPARE_BAD_LAYOUT (-3) /* cu is not an ascending prefix from 0 to n */
+size_t spr_prepare_scans_scratch_len(int n, int nb);
+int spr_prepare_scans(const float* pts, int stride, const int* cu, int n, int nb, double voxel_size,
+                      double crop_radius, int remove_ground, int* scratch, size_t scratch_len,
+                      float* out_xyz, int* out_idx, int* out_cu, int* status, void* stream);
+
 /* ---- a2: batched fixed-radius neighbours ---------------------------------
  * Replaces radius_neighbors.batch_query(queries, supports, q_batches,
  * s_batches, radius=) (cpp_wrappers/cpp_neighbors/wrapper.cpp:58-75 ->

@@ -27,6 +27,9 @@ SIGNATURES = {
     "spr_grid_subsample": (_i, [_vp, _vp, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "spr_voxel_downsample_workspace_bytes": (_sz, [_i]),
     "spr_voxel_downsample": (_i, [_vp, _i, ctypes.c_double, _vp, _vp, _vp, _sz, _vp]),
+    "spr_prepare_scans_scratch_len": (_sz, [_i, _i]),
+    "spr_prepare_scans": (_i, [_vp, _i, _vp, _i, _i, ctypes.c_double, ctypes.c_double, _i, _vp, _sz, _vp, _vp, _vp, _vp,
+                               _vp]),
     "spr_radius_neighbors_workspace_bytes": (_sz, [_i, _i, _i]),
     "spr_radius_neighbors": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _f, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "spr_radius_table_bytes": (_sz, [_i, _i]),

@@ -72,6 +72,7 @@ CONFIGS = {
         num_refinement_steps=10, acceptance_radius=0.6, overlap_radius=0.3,
         scheduler_param=[135800, 0.5], reg_success_thresh_rot=5, reg_success_thresh_trans=2,
         augment_noise=0.01, perturb_pose='large',
+        crop_radius=0.0, remove_ground=False,      # read by kitti.prepare_pairs (kitti_pred.py:221-230)
     ),
     # conf/qk_regtr_full_modelnet.yaml
     'modelnet': dict(

@@ -1,0 +1,49 @@
+"""The KITTI loader's point path on the device: raw Velodyne scans of a whole batch -> the batch dict of the forward.
+
+KittiDataset.__getitem__ (data_loaders/kitti_pred.py:203-230) runs, per scan and on the CPU, kiss-icp's first-point
+voxel filter at config.first_subsampling_dl, the crop to config.crop_radius and the ground cut of config.remove_ground.
+prepare_pairs does the same for every scan of a batch with one library call (ops.prepare_scans) and one device->host
+copy.  (The loader's ICP refinement of the ground-truth pose, :161-183, is a cached offline step and stays outside.)
+"""
+from typing import List, Optional, Sequence
+
+import torch
+
+from . import ops
+
+
+def prepare_pairs(src_scans: Sequence[torch.Tensor], tgt_scans: Sequence[torch.Tensor], cfg,
+                  pose: Optional[torch.Tensor] = None) -> dict:
+    """src_scans / tgt_scans: B raw scans each, [n_i, 3] or [n_i, 4] float32 device tensors (4 columns:
+    np.fromfile(...).reshape(-1, 4) as it is, x y z reflectance; all scans of a call have the same width).  cfg: the
+    experiment's config (first_subsampling_dl; crop_radius and remove_ground default to 0.0 and False).  pose: [B,3,4]
+    or [B,4,4] ground truth (src -> tgt), passed through.
+    Returns the collate_pair dict RegTR.forward and Trainer.train_step read: 'src_xyz' / 'tgt_xyz' (lists of [m_i, 3],
+    views of one packed tensor), 'pose', and 'src_index' / 'tgt_index' (lists of int64 [m_i]: each kept point's row in
+    its raw scan, to take reflectance or labels along).  A scan of which nothing survives raises ValueError."""
+    src, tgt = list(src_scans), list(tgt_scans)
+    B = len(src)
+    if B < 1 or len(tgt) != B:
+        raise ValueError(f"prepare_pairs: {B} source scans, {len(tgt)} target scans")
+    scans = src + tgt
+    widths = {tuple(s.shape[1:]) if isinstance(s, torch.Tensor) else None for s in scans}
+    if len(widths) != 1 or next(iter(widths)) not in ((3,), (4,)):
+        raise ValueError("prepare_pairs: scans must all be [n, 3] or all be [n, 4], got trailing shapes "
+                         f"{sorted(map(str, widths))}")
+    lens = [int(s.shape[0]) for s in scans]
+    if min(lens) < 1:
+        b = lens.index(min(lens))
+        raise ValueError(f"prepare_pairs: the {'source' if b < B else 'target'} scan of pair {b % B} is empty")
+    dev = scans[0].device
+    xyz, out_cu, idx = ops.prepare_scans(torch.cat([s.to(torch.float32) for s in scans]), ops.lengths_to_cu(lens, dev),
+                                         float(cfg.first_subsampling_dl), float(cfg.get('crop_radius', 0.0)),
+                                         bool(cfg.get('remove_ground', False)))
+    out_lens = [b - a for a, b in zip(out_cu, out_cu[1:])]
+    for b, m in enumerate(out_lens):
+        if m == 0:
+            raise ValueError(f"prepare_pairs: nothing of the {'source' if b < B else 'target'} scan of pair {b % B} "
+                             f"survives the crop (crop_radius {cfg.get('crop_radius', 0.0)}, remove_ground "
+                             f"{cfg.get('remove_ground', False)})")
+    clouds: List[torch.Tensor] = list(torch.split(xyz, out_lens))
+    index: List[torch.Tensor] = list(torch.split(idx.long(), out_lens))
+    return {'src_xyz': clouds[:B], 'tgt_xyz': clouds[B:], 'pose': pose, 'src_index': index[:B], 'tgt_index': index[B:]}

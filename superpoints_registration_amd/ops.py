@@ -284,6 +284,46 @@ def voxel_downsample(points: torch.Tensor, voxel_size: float) -> torch.Tensor:
     return points[idx[:m].long()]
 
 
+def prepare_scans(points: torch.Tensor, cu: torch.Tensor, voxel_size: float, crop_radius: float = 0.0,
+                  remove_ground: bool = False) -> Tuple[torch.Tensor, list, torch.Tensor]:
+    """The KITTI loader's point path (kitti_pred.py:203-230) for all raw scans of a batch in one call
+    (spr_prepare_scans; the contract is in include/spr.h): first point of every voxel, then the crop to crop_radius
+    (<= 0: none) and, with remove_ground, the cut z > -1, both on the filter's output.  points [n, 3 | 4] float32
+    packed by cu int32 [nb+1] on the device (4 columns: raw Velodyne records, the 4th is never read).
+    Returns (xyz [m,3], out_cu, idx [m] int32): the kept points in ascending original index per cloud, the output's
+    cloud boundaries as a host list of nb+1 ints (a cloud may come out empty) and each kept point's index inside its
+    own input cloud.  One device->host copy for the whole batch (status and out_cu together)."""
+    if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] not in (3, 4):
+        raise ValueError(f"prepare_scans: points must be [n, 3] or [n, 4], got "
+                         f"{tuple(points.shape) if isinstance(points, torch.Tensor) else type(points)}")
+    points = _dev(points, "points", torch.float32)
+    cu = _dev(cu, "cu", torch.int32).reshape(-1)
+    n, stride, nb = points.shape[0], points.shape[1], cu.numel() - 1
+    if n < 1 or nb < 1 or nb > n:
+        raise ValueError(f"prepare_scans: {n} points in {nb} clouds; every cloud holds at least one point")
+    L = _lib.lib()
+    dev = points.device
+    # scratch by torch.empty, not the shared workspace: the table alone is 8 bytes per point of the whole batch
+    scratch = torch.empty((L.spr_prepare_scans_scratch_len(n, nb),), dtype=torch.int32, device=dev)
+    xyz = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    idx = torch.empty((n,), dtype=torch.int32, device=dev)
+    tail = torch.empty((nb + 2,), dtype=torch.int32, device=dev)      # out_cu [nb+1], then the status word
+    _lib.check(L.spr_prepare_scans(_ptr(points), stride, _ptr(cu), n, nb, float(voxel_size), float(crop_radius),
+                                   int(bool(remove_ground)), _ptr(scratch), scratch.numel(), _ptr(xyz), _ptr(idx),
+                                   _ptr(tail), ctypes.c_void_p(tail.data_ptr() + 4 * (nb + 1)), _stream(points)),
+               "spr_prepare_scans")
+    host = tail.tolist()
+    out_cu, status = host[:nb + 1], host[nb + 1]
+    if status == -1:
+        raise RuntimeError("spr_prepare_scans: coordinates exceed 2^20 voxels (or are not finite)")
+    if status != 0:
+        raise RuntimeError("spr_prepare_scans: " + ("a point found no slot in its cloud's table" if status == -2 else
+                                                    "cu is not an ascending prefix from 0 to the number of points")
+                           + f" (status {status})")
+    m = out_cu[nb]
+    return xyz[:m], out_cu, idx[:m]
+
+
 def radius_neighbors(queries: torch.Tensor, supports: torch.Tensor, q_cu: torch.Tensor,
                      s_cu: torch.Tensor, radius: float, limit: int,
                      exact_width: bool = True, algo: int = 0,
