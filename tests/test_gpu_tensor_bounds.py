@@ -1,0 +1,719 @@
+"""GPU: every operator that fetches rows or tiles, with its INPUTS flush against a guard band (tests/tensor_arena.py).
+
+tests/test_gpu_workspace.py puts every output and every piece of host-side scratch between bands; here the operands
+go there as well, through the arena's put(): the last row of every input tensor -- features, coordinates, weights,
+index, length and cu tensors -- ends where a band begins.  A clamped tail fetch, a transposed LDS read or a dwordx4
+row load that goes past the last row and reaches a result then reads NaN (flavour 1) or bytes that differ from run to
+run (flavour 2) instead of a neighbour's finite floats.  Every case builds its inputs anew per run and goes through
+run_three of the workspace module (production, flavour 1, flavour 2; bands intact, finite wherever production is
+finite, the same BITS as production), so the comparison code is that module's.
+
+Shapes: the smallest at which the last tile of each operand is partial, all of them shapes the suite already holds
+against float64 (or against the reference, for the index operators); each case names the test that does.
+
+Operands outside this check, because the host layer copies them before the library sees them: the per-pair feature
+and keypoint LISTS of ops.circle_loss (concatenated by ops.circle_loss), the pair_keys / draw tables of augment_draw,
+augment_pairs and ransac_pairs (built on the host and uploaded), bool masks handed to ops.augment_pairs (cast to uint8,
+a copy: the augmentation case therefore also hands them over as uint8, which is taken as it is), the BgemmDesc records
+of autograd.bgemm, int64 or non-contiguous tensors that ops._dev converts, and the parameters of a module (the
+cross-encoder's weights: its plan packs them).
+
+The last test checks that the cases called every spr_* entry point that ops.py, autograd.py, tie_order.py, augment.py
+and overlap.py reference, under the arena: a new operator fails it until it has a case here.  Run the module as a
+whole."""
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import augment_replica as ar
+import forward_cases as fc
+import tensor_arena
+import test_gpu_workspace as W
+import tie_order_cases as tc
+from conftest import load_golden
+from oracle.gen_golden import ops_inputs
+from superpoints_registration_amd import _lib, autograd, ops, synthetic
+from superpoints_registration_amd.transformers import make_segments
+from test_gpu_attn_core_loop import KV_SEGS, LENS
+from test_gpu_block_tail import LENS as TAIL_LENS, SHAPES as TAIL_SHAPES, _inputs as tail_inputs
+from test_gpu_circle_loss import POSE as CIRCLE_POSE, REGIMES as CIRCLE_REGIMES, R_N, R_P, make_case as circle_case
+from test_gpu_match_range import F64, U, _features, _pack, _pcase, _res_bound, _rot
+from test_gpu_posemb_learned import BWD_SEEDS, bwd_case as posemb_case
+from test_gpu_prepare_scans import CASES as SCAN_CASES
+from test_gpu_ransac import make_set, pack as ransac_pack, tails_case
+from test_gpu_refine import pack as refine_pack, synth_pair
+from test_gpu_xenc import _encoder
+
+pytestmark = pytest.mark.gpu
+T = torch.from_numpy
+CALLED = set()           # spr_* entry points called while a tensor arena was installed
+
+
+# entry points with a host-only form beside the one that takes device operands: only the latter counts
+DEVICE_FORM = {"spr_augment_draw": lambda args: args[7] is not None and args[13] is not None}    # pair keys / keys out
+
+
+class _Recorder:
+    """The library, noting every entry point CALLED while the tensor arena is installed -- at the call, not when the
+    attribute is fetched, and for an entry point of DEVICE_FORM only when the call is of the form with device
+    operands: a case that uses the host form alone does not cover it."""
+
+    def __init__(self, lib):
+        self._lib = lib
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if not name.startswith("spr_"):
+            return fn
+
+        def call(*args):
+            if torch.empty is not tensor_arena._REAL["empty"] and DEVICE_FORM.get(name, lambda a: True)(args):
+                CALLED.add(name)
+            return fn(*args)
+        return call
+
+
+@pytest.fixture(autouse=True)
+def _recording(monkeypatch):
+    real = _lib.lib()
+    monkeypatch.setattr(_lib, "lib", lambda: _Recorder(real))
+
+
+def bounded(monkeypatch, f, what):
+    """f(put) builds its inputs, passes every device operand through put and runs the operator."""
+    return W.run_three(monkeypatch, f, what, placed=True)
+
+
+def _leaves(device, *host):
+    return [t.clone().to(device).requires_grad_(True) for t in host]
+
+
+# ---- the arena on the device -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("flavour", [1, 2])
+def test_the_arena_guards_device_allocations(device, monkeypatch, flavour):
+    """What tests/test_tensor_arena_host.py shows on CPU tensors, once on the device: layout, poison, put(), and a
+    store one element past the end -- into the allocated band, so nothing faults -- named by verify()."""
+    arena = tensor_arena.TensorArena(flavour)
+    with monkeypatch.context() as m:
+        arena.install(m)
+        t = torch.empty((100, 3), dtype=torch.float32, device=device)
+        z = torch.zeros(7, dtype=torch.int32, device="cuda")
+        host = torch.empty(4)
+        p = arena.put(torch.arange(5, dtype=torch.float32, device=device))
+    assert arena.calls == 3 and not host.is_cuda
+    buf = arena.records[0][3]
+    assert t.is_cuda and t.data_ptr() % tensor_arena.ALIGN == 0 and buf.numel() == 2 * tensor_arena.BAND + 1200
+    assert t.data_ptr() + 1200 == buf[tensor_arena.BAND + 1200:].data_ptr()
+    assert bool(t.isnan().all()) if flavour == 1 else not bool(t.any())
+    assert not bool(z.any()) and p.tolist() == [0.0, 1.0, 2.0, 3.0, 4.0]
+    assert arena.damage() == []
+    p.as_strided((1,), (1,), p.storage_offset() + 5).fill_(0.0)
+    with pytest.raises(AssertionError, match=r"20 bytes allocated at test_gpu_tensor_bounds.py:.* after .*offset 0"):
+        arena.verify()
+
+
+# ---- attention -----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode", [4, 1, 0])
+def test_attention_core(device, monkeypatch, mode):
+    """The inputs of test_gpu_attn_core_loop.py::test_core_vs_fp64 (LENS: 65 / 129 / 193 / 257 reach the clamped fetch),
+    self and cross, which holds them against float64 in every mode."""
+    qkv = synthetic.rand((sum(LENS), 768), 9, -2, 2).to(device)
+
+    def f(put):
+        q, k, v = (put(qkv[:, i:i + 256].contiguous()) for i in (0, 256, 512))
+        cu = put(ops.lengths_to_cu(LENS, device))
+        return [ops.attention_raw(q, k, v, cu, put(torch.tensor(seg, dtype=torch.int32, device=device)), max(LENS), 8,
+                                  want_lse=True) for seg in KV_SEGS]
+    ops.set_attn_mode(mode)
+    try:
+        bounded(monkeypatch, f, f"attention mode {mode}")
+    finally:
+        ops.set_attn_mode(ops.DEFAULT_ATTN_MODE)
+
+
+def _placed_tokens(put, segs, device):
+    s_l, t_l = W.SEGS[segs]
+    cu, s_self, s_cross, mx = make_segments(s_l, t_l, device)
+    return put(cu), put(s_self), put(s_cross), mx
+
+
+@pytest.mark.parametrize("shared", [True, False])
+@pytest.mark.parametrize("segs", list(W.SEGS))
+def test_attention_with_in_projection(device, monkeypatch, segs, shared):
+    """The inputs of test_gpu_workspace.py::test_attention_with_in_projection, which holds them against float64."""
+    tot = sum(sum(x) for x in W.SEGS[segs])
+    x_qk, x_v = synthetic.rand((tot, 256), 31, -1.5, 1.5).to(device), synthetic.rand((tot, 256), 32, -1.5, 1.5).to(device)
+    w, b = synthetic.rand((768, 256), 33, -0.1, 0.1).to(device), synthetic.rand((768,), 34, -0.2, 0.2).to(device)
+
+    def f(put):
+        cu, _, s_cross, mx = _placed_tokens(put, segs, device)
+        d_qk = put(x_qk.clone())
+        d_v = d_qk if shared else put(x_v.clone())
+        dw, db = put(w.clone()), put(b.clone())
+        return ops.attention_inproj(d_qk, d_v, dw, db, cu, s_cross, mx, 8, w_prep=ops.inproj_prepare(dw))
+    bounded(monkeypatch, f, f"in-projection {segs} shared={shared}")
+
+
+@pytest.mark.parametrize("average", [True, False])
+@pytest.mark.parametrize("segs", list(W.SEGS))
+def test_attention_probs(device, monkeypatch, segs, average):
+    """The inputs of test_gpu_workspace.py::test_attention_probs, which holds them against float64."""
+    qkv = W._tokens(segs, device, 12)[-1].to(device)
+
+    def f(put):
+        cu, _, s_cross, mx = _placed_tokens(put, segs, device)
+        return ops.attention_probs(put(qkv[:, :256].contiguous()), put(qkv[:, 256:512].contiguous()), cu, s_cross, mx, 8,
+                                   average=average)
+    bounded(monkeypatch, f, f"attention_probs {segs}")
+
+
+@pytest.mark.parametrize("route", ["planes", "min"])
+@pytest.mark.parametrize("segs", list(W.SEGS))
+def test_attention_backward(device, monkeypatch, segs, route):
+    """The inputs of test_gpu_workspace.py::test_attention_backward, which holds them against float64 on both routes."""
+    lens, _, _, _, kv_cross, _, qkv = W._tokens(segs, device, 41)
+    d, go = qkv.to(device), synthetic.rand((sum(lens), 256), 44).to(device)
+    if route == "min":
+        recorder = _lib.lib()
+        monkeypatch.setattr(_lib, "lib", lambda: W._MinBwdLib(recorder))
+
+    def f(put):
+        cu, _, s_cross, mx = _placed_tokens(put, segs, device)
+        q, k, v = (put(d[:, i:i + 256].contiguous()) for i in (0, 256, 512))
+        out, lse = ops.attention_raw(q, k, v, cu, s_cross, mx, 8, want_lse=True)
+        return ops.attention_bwd(q, k, v, out, put(go.clone()), cu, kv_cross, mx, 8, lse=lse)
+    bounded(monkeypatch, f, f"attention backward {segs} {route}")
+
+
+@pytest.mark.parametrize("n_layers,final", [(1, True), (2, False)])
+@pytest.mark.parametrize("segs", list(W.SEGS))
+def test_cross_encoder_stack(device, monkeypatch, segs, n_layers, final):
+    """x and pos placed; the inputs of test_gpu_workspace.py::test_cross_encoder_stack, which holds them against
+    float64.  The encoder is built per run, so its plan and prepared weights are built inside the arena."""
+    tot = sum(sum(x) for x in W.SEGS[segs])
+    g = torch.Generator().manual_seed(5)
+    x = (torch.randn(tot, 256, generator=g) * 1.7).to(device)
+    pos = torch.rand(tot, 256, generator=g).mul(2).sub(1).to(device)
+
+    def f(put):
+        enc = _encoder(device, n_layers, 1024, final)
+        cu, s_self, s_cross, mx = _placed_tokens(put, segs, device)
+        with torch.no_grad():
+            out = enc.forward_packed(put(x.clone()), cu, s_self, s_cross, mx, pos=put(pos.clone()), pos_bound=1.0)
+        assert getattr(enc, '_spr_xenc', None) is not None, "the fused route was not taken"
+        return out
+    bounded(monkeypatch, f, f"xenc {segs} {n_layers} layers")
+
+
+# ---- products and reductions -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("act", [ops.ACT_RELU, ops.ACT_SIGMOID])
+@pytest.mark.parametrize("m,k,n", [(1, 256, 256), (257, 64, 32)])
+def test_linear_forward_and_backward(device, monkeypatch, m, k, n, act):
+    """The inputs of test_gpu_workspace.py::test_linear_forward_and_backward (float64 there); the sigmoid's backward
+    (spr_act_bwd reads y) is that of test_gpu_backward.py::test_linear_backward."""
+    x, w = synthetic.rand((m, k), 1, -3.0, 3.0), synthetic.rand((n, k), 2, -0.2, 0.2)
+    b, r, go = synthetic.rand((n,), 3), synthetic.rand((m, n), 4), synthetic.rand((m, n), 5).to(device)
+
+    def f(put):
+        leaves = _leaves(device, x, w, b, r)
+        y = ops.linear(*(put(t) for t in leaves), act)
+        y.backward(put(go.clone()))
+        return [y] + [t.grad for t in leaves]
+    bounded(monkeypatch, f, f"linear {m}x{k}x{n} act {act}")
+
+
+@pytest.mark.parametrize("f64", [True, False])
+@pytest.mark.parametrize("rows", [1, 257])
+def test_tn_products(device, monkeypatch, rows, f64):
+    """f64: the inputs of test_gpu_workspace.py::test_tn_product_f64.  Split: the dW product of
+    test_linear_forward_and_backward's (257, 64, 32) shape, 64 x 32, held against float64 there."""
+    nl = 15 if f64 else 64
+    L, R = synthetic.rand((rows, nl), 6).to(device), synthetic.rand((rows, 64), 7).to(device)
+
+    def f(put):
+        return autograd._tn_product(put(L.clone()), put(R.clone()), rows, nl, 64, f64=f64)
+    out = bounded(monkeypatch, f, f"tn_product rows={rows} f64={f64}")
+    assert W._rel(out, L.cpu().double().t() @ R.cpu().double()) <= 2e-5
+
+
+def test_bgemm_and_softmax_rows_in_the_dual_softmax_backward(device, monkeypatch):
+    """The `quads` batch of test_gpu_match_range.py::test_dual_softmax_backward_shapes (m % 4 = 0 .. 3), which holds
+    the gradient against float64: score products through autograd.bgemm, spr_softmax_rows on both of them."""
+    fs, ft = _features("quads", "unit", seed=2)
+    feat, cu_host = _pack(fs, ft)
+    gv = synthetic.rand((feat.shape[0],), 210).to(device)
+
+    def f(put):
+        leaf, = _leaves(device, feat)
+        val, ind = ops.match_dualsoftmax(put(leaf), put(torch.tensor(cu_host, dtype=torch.int32, device=device)), cu_host,
+                                         len(fs))
+        (val * gv).sum().backward()
+        return val, ind, leaf.grad
+    bounded(monkeypatch, f, "dual softmax backward")
+
+
+@pytest.mark.parametrize("m", [1, 257])
+def test_layernorm_forward_and_backward(device, monkeypatch, m):
+    """The inputs of test_gpu_workspace.py::test_layernorm_backward (float64 there); the forward at these row counts:
+    test_gpu_forward_range.py::test_layernorm_rows_widths_regimes."""
+    x, g, b, p = synthetic.rand((m, 256), 5, -3, 5), synthetic.rand((256,), 6, 0.5, 1.5), synthetic.rand((256,), 7), \
+        synthetic.rand((m, 256), 8).to(device)
+    g1, g2 = synthetic.rand((m, 256), 9).to(device), synthetic.rand((m, 256), 10).to(device)
+
+    def f(put):
+        leaves = _leaves(device, x, g, b)
+        n, npos = ops.layernorm(*(put(t) for t in leaves), 1e-5, pos=put(p.clone()))
+        (n * g1).sum().add((npos * g2).sum()).backward()
+        return [n, npos] + [t.grad for t in leaves]
+    bounded(monkeypatch, f, f"layernorm {m}")
+
+
+@pytest.mark.parametrize("counts", W.POINT_COUNTS)
+def test_instance_norm(device, monkeypatch, counts):
+    """The inputs of test_gpu_workspace.py::test_instance_norm, which holds forward, statistics and backward against
+    float64."""
+    n = sum(counts)
+    x, add, go = synthetic.rand((n, 64), 201, -5.0, 7.0), synthetic.rand((n, 64), 77), synthetic.rand((n, 64), 78).to(device)
+
+    def f(put):
+        cu = put(ops.lengths_to_cu(list(counts), device))
+        lx, la = _leaves(device, x, add)
+        px = put(lx)
+        y = ops.instnorm(px, cu, add=put(la), slope=0.1, max_len=max(counts))
+        y.backward(put(go.clone()))
+        mean, rstd = ops.instnorm_stats(px.detach(), cu, max_len=max(counts))
+        return y, lx.grad, la.grad, mean, rstd, ops.instnorm_raw(px.detach(), cu)
+    bounded(monkeypatch, f, f"instnorm {counts}")
+
+
+@pytest.mark.parametrize("form", ["shortcut", "none"])
+def test_block_tail(device, monkeypatch, form):
+    """The inputs of test_gpu_block_tail.py::test_block_tail_vs_float64_and_separate_operators[SHAPES[0]] and
+    ::test_block_tail_without_shortcut_tensor, which hold them against float64."""
+    ka, kb, n_out = TAIL_SHAPES[0]
+    if form == "shortcut":
+        args = tail_inputs(ka, kb, n_out, TAIL_LENS, device)
+    else:
+        args = tail_inputs(32, 0, 128, TAIL_LENS, device, add=False)
+
+    def f(put):
+        xa, wa, xb, wb, ad, cu = (None if t is None else put(t.clone()) for t in args)
+        return ops.block_tail(xa, wa, cu, xb=xb, wb=wb, add=ad)
+    bounded(monkeypatch, f, f"block_tail {form}")
+
+
+# ---- KPConv ------------------------------------------------------------------------------------------------------------
+def _kp_call(put, device, q, s, nb, x, w, kp, ext, impl):
+    dev = [put(T(np.ascontiguousarray(a)).to(device)) for a in (q, s, nb.astype(np.int32), x, w, kp)]
+    return ops.kpconv_raw(*dev, ext, rows_sorted=True, impl=impl)
+
+
+@pytest.mark.parametrize("kmax", [1, 9, 65, 129])
+@pytest.mark.parametrize("route", list(fc.KP_ROUTES))
+def test_kpconv_row_widths(device, monkeypatch, route, kmax):
+    """The inputs of test_gpu_forward_range.py::test_kpconv_row_widths, which holds them against float64."""
+    impl, cin, cout = fc.KP_ROUTES[route]
+    q, s, nb = fc.kp_cloud_case(150, 200, kmax, 1e2, 0.25, 45, rows_sorted=True, fill=0.9)
+    x, w, kp = fc.kp_features(200, cin, 46), fc.kp_weights(cin, cout, 47), fc.random_kernel_points(0.25, 48)
+    bounded(monkeypatch, lambda put: _kp_call(put, device, q, s, nb, x, w, kp, 0.25, impl), f"kpconv {route} kmax {kmax}")
+
+
+@pytest.mark.parametrize("nq", [1, 17])
+@pytest.mark.parametrize("route", list(fc.KP_ROUTES))
+def test_kpconv_query_counts(device, monkeypatch, route, nq):
+    """The sorted-row inputs of test_gpu_forward_range.py::test_kpconv_query_counts (float64 there)."""
+    impl, cin, cout = fc.KP_ROUTES[route]
+    q, s, nb = fc.kp_cloud_case(nq, 120, 12, 1e2, 0.125, 49, rows_sorted=True)
+    x, w, kp = fc.kp_features(120, cin, 50), fc.kp_weights(cin, cout, 51), fc.random_kernel_points(0.125, 52)
+    bounded(monkeypatch, lambda put: _kp_call(put, device, q, s, nb, x, w, kp, 0.125, impl), f"kpconv {route} nq {nq}")
+
+
+@pytest.mark.parametrize("tag", ["c1", "c32", "c64", "c128"])
+def test_kpconv_backward(device, monkeypatch, tag):
+    """Weighted features, the dx scatter, dW; the golden inputs of test_gpu_workspace.py::test_kpconv_backward, which
+    holds them against float64."""
+    pts, nb, x, w, kp, ext, _ = W._kp_inputs(tag, device)
+    go = synthetic.rand((600, w.shape[2]), 90).to(device)
+
+    def f(put):
+        lx, lw = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
+        p = put(pts.clone())
+        out = ops.kpconv(p, p, put(nb.clone()), put(lx), put(lw), put(kp.clone()), ext, rows_sorted=True)
+        out.backward(put(go.clone()))
+        return out, lx.grad, lw.grad
+    bounded(monkeypatch, f, f"kpconv backward {tag}")
+
+
+def test_maxpool_and_gather(device, monkeypatch):
+    """Forward and backward; the inputs of test_gpu_backward.py::test_maxpool_and_gather_backward, which holds them
+    against float64 (the forward selection: test_gpu_forward_range.py::test_maxpool_selection)."""
+    gold, inp = load_golden("ops.npz"), ops_inputs()
+    idx = T(gold["mp.idx"].astype(np.int32)).to(device)
+    x, go = inp["in.x"], synthetic.rand((idx.shape[0], 64), 80).to(device)
+    sel = torch.tensor([5, 0, 5, 599, 17], dtype=torch.int32, device=device)
+
+    def f(put):
+        a, b = _leaves(device, x, x)
+        pooled, rows = ops.maxpool(put(a), put(idx.clone())), ops.gather_rows(put(b), put(sel.clone()))
+        pooled.backward(put(go.clone()))
+        rows.backward(put(go[:5].clone()))
+        return pooled, rows, a.grad, b.grad
+    bounded(monkeypatch, f, "maxpool / gather_rows")
+
+
+@pytest.mark.parametrize("c", [256, 3])
+def test_pair_gather(device, monkeypatch, c):
+    """Copies: held to torch indexing, bit for bit (the criterion of
+    test_gpu_encode_once.py::test_pair_gather_is_torch_indexing)."""
+    lens, si, ti = [70, 129, 33, 1], [0, 2, 3], [1, 1, 0]
+    x = synthetic.rand((sum(lens), c), 61).to(device)
+    off = np.concatenate([[0], np.cumsum(lens)])
+    out_lens = [lens[i] for i in si] + [lens[i] for i in ti]
+
+    def f(put):
+        return ops.pair_gather(put(x.clone()), put(ops.lengths_to_cu(lens, device)),
+                               put(torch.tensor(si, dtype=torch.int32, device=device)),
+                               put(torch.tensor(ti, dtype=torch.int32, device=device)),
+                               put(ops.lengths_to_cu(out_lens, device)), rows=sum(out_lens))
+    got = bounded(monkeypatch, f, f"pair_gather c={c}")
+    assert torch.equal(got, torch.cat([x[off[i]:off[i + 1]] for i in si + ti]))
+
+
+# ---- position embeddings -------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("d_model", fc.PE_DMODEL)
+@pytest.mark.parametrize("n", [1, 257])
+def test_posemb_sine(device, monkeypatch, n, d_model):
+    """The |x| ~ 1 inputs of test_gpu_forward_range.py::test_posemb_magnitudes, which holds them against float64."""
+    xyz = fc.pe_xyz(n, 1.0, 31).to(device)
+    bounded(monkeypatch, lambda put: ops.posemb_sine(put(xyz.clone()), d_model, 1.0), f"posemb_sine n={n} d={d_model}")
+
+
+@pytest.mark.parametrize("tokens", [1, 65])
+def test_posemb_mlp(device, monkeypatch, tokens):
+    """Forward and backward; the inputs of test_gpu_posemb_learned.py::test_backward_against_float64_autograd, which
+    holds these shapes against float64 (its forward: ::test_forward_against_float64 of the same module)."""
+    xyz, params, dpe, _ = posemb_case(load_golden("posemb_learned_ops.npz"), tokens, BWD_SEEDS[tokens])
+
+    def f(put):
+        leaves = [p.detach().clone().to(device).requires_grad_(True) for p in params]
+        pe = ops.posemb_mlp(put(xyz.to(device)), [put(p) for p in leaves])
+        pe.backward(put(dpe.to(device)))
+        return [pe] + [p.grad for p in leaves]
+    bounded(monkeypatch, f, f"posemb_mlp T={tokens}")
+
+
+# ---- matching head, pose solve, refinement ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("n_iters", [0, 3])
+def test_matching_head(device, monkeypatch, n_iters):
+    """The inputs of test_gpu_workspace.py::test_matching_head (MATCH_PAIRS), which holds them against float64."""
+    feat, xyz_h, cu0, cu_host = W._match_inputs(device)
+    B = len(W.MATCH_PAIRS)
+    dfeat, dxyz = feat.to(device), xyz_h.to(device)
+
+    def f(put):
+        ft, xyz, cu = put(dfeat.clone()), put(dxyz.clone()), put(cu0.clone())
+        return (ops.match_dualsoftmax_raw(ft, cu, cu_host, B), ops.match_dualsoftmax_top2(ft, cu, cu_host, B),
+                ops.sinkhorn_correspondences_raw(ft, xyz, cu, cu_host, B, 0.9, 1.1, n_iters),
+                ops.match_and_sinkhorn(ft, xyz, cu, cu_host, B, 0.9, 1.1, n_iters, top2=True))
+    bounded(monkeypatch, f, f"matching head n_iters={n_iters}")
+
+
+@pytest.mark.parametrize("n_iters", [0, 3])
+def test_sinkhorn_backward(device, monkeypatch, n_iters):
+    """The inputs of test_gpu_workspace.py::test_sinkhorn_backward, which holds them against float64."""
+    feat, xyz_h, cu0, cu_host = W._match_inputs(device)
+    dxyz = xyz_h.to(device)
+    B, tsrc = len(W.MATCH_PAIRS), cu_host[len(W.MATCH_PAIRS)]
+    gw, gt = synthetic.rand((tsrc,), 13).to(device), synthetic.rand((tsrc, 3), 14).to(device)
+
+    def f(put):
+        lf, = _leaves(device, feat)
+        al = torch.tensor(0.9, device=device, requires_grad=True)
+        be = torch.tensor(1.1, device=device, requires_grad=True)
+        w, that = ops.sinkhorn_correspondences(put(lf), put(dxyz.clone()), put(cu0.clone()), cu_host, B, al, be, n_iters)
+        ((w * gw).sum() + (that * gt).sum()).backward()
+        return w, that, lf.grad, al.grad, be.grad
+    bounded(monkeypatch, f, f"sinkhorn backward n_iters={n_iters}")
+
+
+def test_weighted_procrustes_forward_and_backward(device, monkeypatch):
+    """The `off1e3` inputs of test_gpu_match_range.py::test_procrustes_backward_geometries (500 points: a partial last
+    tile), which holds the gradients against float64; the pose: ::test_procrustes_geometries_one_batch."""
+    a, b, w, _ = _pcase("off1e3", torch.Generator().manual_seed(300))
+    w = torch.ones(a.shape[0]) if w is None else w
+    go = synthetic.rand((1, 3, 4), 301).to(device)
+
+    def f(put):
+        leaves = _leaves(device, a.float(), b.float(), w.float())
+        pose = ops.weighted_procrustes(*(put(t) for t in leaves),
+                                       put(torch.tensor([0, a.shape[0]], dtype=torch.int32, device=device)))
+        pose.backward(put(go.clone()))
+        return [pose] + [t.grad for t in leaves]
+    bounded(monkeypatch, f, "weighted_procrustes")
+
+
+def test_pose_residuals_and_scores(device, monkeypatch):
+    """The n = 65 inputs of test_gpu_match_range.py::test_pose_residuals_and_scores, which holds them against float64
+    (the scores; the residuals without its empty sets, asserted below)."""
+    n, g = 65, torch.Generator().manual_seed(95 + 65)
+    poses = torch.stack([torch.cat([_rot(g), torch.randn(3, 1, generator=g, dtype=F64) * 1e3], 1).float() for _ in range(7)])
+    a = (torch.randn((n, 3), generator=g) * 30 + 1e3)
+    b = (a.to(F64) @ poses[0, :, :3].to(F64).t() + poses[0, :, 3].to(F64)).float() + torch.randn((n, 3), generator=g)
+    da, db, dp = a.to(device), b.to(device), poses.to(device)
+
+    def f(put):
+        pa, pb = put(da.clone()), put(db.clone())
+        pc = put(torch.tensor([0, n // 3, n], dtype=torch.int32, device=device))
+        return [ops.pose_scores(put(dp[:nh].clone()), pa, pb) for nh in (1, 3, 5, 7)] + \
+            [ops.pose_residuals(put(dp[:2].clone()), pa, pb, pc)]
+    res = bounded(monkeypatch, f, "pose residuals / scores")[-1].cpu().to(F64)
+    for s, sl in enumerate((slice(0, n // 3), slice(n // 3, n))):          # other sets than that test's: its bound
+        ref, bnd = _res_bound(poses[s], a[sl], b[sl])
+        assert bool(((res[sl] - ref).abs() <= bnd).all()), f"pose_residuals set {s}"
+
+
+def test_refine_pairs(device, monkeypatch):
+    """The 4 097-entry pair of test_gpu_workspace.py::test_refine_pairs."""
+    P = refine_pack([synth_pair(np.random.default_rng(17), 4097, 4108)], device)
+
+    def f(put):
+        val, val2, ind, ov, xyz, cu = (put(P[k].clone()) for k in ('val', 'val2', 'ind', 'ov', 'xyz', 'cu'))
+        return ops.refine_pairs(val, val2, ind, ov, xyz, cu, P['cu_host'], 1, None, ratio=True, median=True,
+                                overlap_prune=True, lgr_steps=2, lowe_thres=0.9, acceptance_radius=0.3)
+    out = bounded(monkeypatch, f, "refine_pairs")
+    assert not bool(out['status'].any()) and bool(torch.isfinite(out['pose']).all())
+
+
+def test_ransac_pairs(device, monkeypatch):
+    """Sets of 65 and 130 entries, 5 hypotheses of 100 samples: test_gpu_ransac.py's tails_case holds production
+    against the replica and the parent first (::test_sample_tails without its empty pair)."""
+    ns, seed = (65, 130), 165
+    tails_case(device, ns, 5, 100, seed=seed)
+    rng = np.random.default_rng(seed)
+    P = ransac_pack([make_set(rng, n) for n in ns], device)
+
+    def f(put):
+        return ops.ransac_pairs(put(P['a'].clone()), put(P['b'].clone()), put(P['w'].clone()), put(P['cu'].clone()),
+                                P['cu_host'], n_hyp=5, sample=100, seed=seed, pair_keys=[7, 10])
+    bounded(monkeypatch, f, "ransac_pairs")
+
+
+# ---- losses ------------------------------------------------------------------------------------------------------------
+def test_loss_kernels(device, monkeypatch):
+    """The inputs of test_gpu_workspace.py::test_loss_kernels (values) and
+    test_gpu_backward.py::test_loss_kernels_backward (gradients), which hold them against float64."""
+    inp = ops_inputs()
+    fs, ft, xs, xt = inp["sk.fs"], inp["sk.ft"], (inp["sk.xs"] * 0.3).to(device), (inp["sk.xt"] * 0.3).to(device)
+    Wm = synthetic.rand((256, 256), 16, -0.05, 0.05)
+    pose = torch.tensor([[1.0, 0, 0, 0.02], [0, 1, 0, -0.01], [0, 0, 1, 0.0]]).to(device)
+    x, y = synthetic.rand((500,), 17, 0.01, 0.99), (synthetic.rand((500,), 18) > 0).float().to(device)
+    pp = (pose.cpu() + 0.05 * synthetic.rand((3, 4), 19))
+
+    def f(put):
+        la, lp, lw, lx, lpp = _leaves(device, fs, ft, Wm, x, pp)
+        pxs, pxt, ppose = put(xs.clone()), put(xt.clone()), put(pose.clone())
+        nce = ops.infonce_pair(put(la), put(lp), pxs, ppose, pxt, put(lw), 0.2, 0.4)
+        nce.backward()
+        bce = ops.bce_logits_mean(put(lx), put(y.clone()))
+        bce.backward()
+        l1 = ops.transform_l1_pair(ppose, put(lpp), pxs)
+        l1.backward()
+        return nce, la.grad, lp.grad, lw.grad, bce, lx.grad, l1, lpp.grad, ops.sum_scaled(put(y.clone()), 0.5)
+    bounded(monkeypatch, f, "loss kernels")
+
+
+def test_circle_loss(device, monkeypatch):
+    """The `ragged` case of test_gpu_circle_loss.py (same seed), held against float64 there.  The lists are
+    concatenated by ops.circle_loss: the pose and the concatenation's operands are what is placed."""
+    fs, ft, xs, xt = circle_case(seed=sorted(CIRCLE_REGIMES).index("ragged") + 1, **CIRCLE_REGIMES["ragged"])
+    B = len(fs)
+
+    def f(put):
+        a, b = _leaves(device, *fs), _leaves(device, *ft)
+        out = ops.circle_loss([put(t) for t in a], [put(t) for t in b], [put(t.to(device)) for t in xs],
+                              put(CIRCLE_POSE.expand(B, 3, 4).contiguous().to(device)), [put(t.to(device)) for t in xt],
+                              R_P, R_N)
+        out[torch.isfinite(out.detach())].sum().div(B).backward()
+        return out, [t.grad for t in a], [t.grad for t in b]
+    bounded(monkeypatch, f, "circle loss")
+
+
+# ---- point operators ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("counts", W.POINT_COUNTS)
+def test_subsampling_and_ordering(device, monkeypatch, counts):
+    """The inputs of test_gpu_workspace.py::test_subsampling_and_ordering; index operators, exact by construction
+    (test_gpu_preprocess_edges.py holds these operators against the reference)."""
+    _, pts, cu0 = W._clouds(counts, device, 1)
+
+    def f(put):
+        p, cu = put(pts.clone()), put(cu0.clone())
+        sub, lens = ops.grid_subsample(p, cu, 0.1)
+        return sub, lens, ops.voxel_downsample(p, 0.1), ops.cell_order(p, cu, 0.1)
+    sub, lens, vox, order = bounded(monkeypatch, f, f"subsampling {counts}")
+    assert int(lens.sum()) == sub.shape[0] and 1 <= vox.shape[0] <= pts.shape[0]
+
+
+@pytest.mark.parametrize("name", ["lens_255_1_256_2", "stride4_nan_reflectance"])
+@pytest.mark.parametrize("crop_radius,remove_ground", [(0.0, False), (1.5, True)], ids=["plain", "crop_ground"])
+def test_prepare_scans(device, monkeypatch, name, crop_radius, remove_ground):
+    """The inputs of test_gpu_prepare_scans.py::test_equals_the_loader_and_the_per_cloud_route, which holds them against
+    the loader's route; 4-column records: the NaN 4th column must never reach a result, nor must the band behind it."""
+    clouds, voxel = SCAN_CASES[name]
+    pts = T(np.concatenate(clouds)).to(device)
+
+    def f(put):
+        xyz, out_cu, idx = ops.prepare_scans(put(pts.clone()), put(ops.lengths_to_cu([len(c) for c in clouds], device)),
+                                             voxel, crop_radius, remove_ground)
+        return xyz, torch.tensor(out_cu), idx
+    xyz, out_cu, _ = bounded(monkeypatch, f, f"prepare_scans {name}")
+    assert int(out_cu[-1]) == xyz.shape[0] > 0
+
+
+@pytest.mark.parametrize("counts", W.POINT_COUNTS)
+def test_radius_searches(device, monkeypatch, counts):
+    """Both algorithms, the table's build, its three query forms and its count; the inputs of
+    test_gpu_workspace.py::test_radius_searches, which holds the rows against brute force in float64.  Counts: what
+    test_gpu_calibrate.py::test_counts_agree_with_the_row_producing_kernels asks, the row's own length."""
+    host, pts, cu0 = W._clouds(counts, device, 2)
+    n = pts.shape[0]
+
+    def f(put):
+        p, cu = put(pts.clone()), put(cu0.clone())
+        a0, m0 = ops.radius_neighbors(p, p, cu, cu, 0.2, 40, algo=0)
+        a1, m1 = ops.radius_neighbors(p, p, cu, cu, 0.2, 40, algo=1)
+        out = [a0, a1, torch.tensor([m0, m1])]
+        for dense in (None, True, False):
+            table = ops.RadiusTable(p, cu, 0.2)
+            q, m = table.query(p, cu, 40, dense=dense)
+            out += [q, torch.tensor([m])]
+        cnt, hist = ops.RadiusTable(p, cu, 0.2).count(p, cu, 64)
+        q2 = put(pts.clone())                  # not the table's own tensors: the cross-search form
+        cnt2, _ = ops.RadiusTable(p, cu, 0.2).count(q2, put(cu0.clone()), 64)
+        return out + [cnt, hist, cnt2]
+    out = bounded(monkeypatch, f, f"radius {counts}")
+    for q in (out[1], out[3], out[5], out[7]):
+        assert torch.equal(out[0], q)
+    assert int(out[2][0]) <= 40
+    assert torch.equal(out[9], (out[0] != n).sum(1).to(torch.int32)) and torch.equal(out[9], out[11])
+
+
+@pytest.mark.parametrize("name,limit", [("batch3", 17), ("n1", 5), ("lat.r57", 40)])
+def test_radius_neighbors_in_the_reference_tie_order(device, monkeypatch, name, limit):
+    """The kd-tree replay build and the fix-up; cases of
+    test_gpu_tie_order.py::test_radius_neighbors_gives_the_reference_rows, which holds them against the reference's rows
+    (asserted here as well)."""
+    c, gold = tc.cases()[name], tc.load_golden()
+    sup, qry = T(np.array(c.sup)).to(device), T(np.array(c.qry)).to(device)
+
+    def f(put):
+        s, scu = put(sup.clone()), put(ops.lengths_to_cu(list(c.s_lens), device))
+        q, qcu = (s, scu) if c.qry is c.sup else (put(qry.clone()), put(ops.lengths_to_cu(list(c.q_lens), device)))
+        rows, mc = ops.radius_neighbors(q, s, qcu, scu, c.radius, limit, tie_order='reference')
+        return rows, torch.tensor([mc])
+    rows, _ = bounded(monkeypatch, f, f"tie order {name}")
+    assert np.array_equal(rows.cpu().numpy(), tc.reference_rows(gold, name, limit))
+
+
+def test_overlap_pool(device, monkeypatch):
+    """The width-7 shape of test_gpu_match_range.py::test_overlap_pool_edges with a valid first column in every row (a
+    mean of nothing is NaN by contract); float64 under that test's bound."""
+    ns, g = 50, torch.Generator().manual_seed(700)
+    ov = torch.rand(ns, generator=g).to(device)
+    idx = torch.randint(0, ns + 1, (40, 7), generator=g)
+    idx[:, 0] = torch.arange(40) % ns
+    idx = idx.to(torch.int32).to(device)
+    got = bounded(monkeypatch, lambda put: ops.overlap_pool(put(ov.clone()), put(idx.clone()), ns), "overlap_pool")
+    ext, valid = torch.cat([ov.cpu().double(), torch.zeros(1, dtype=F64)]), (idx.cpu() < ns).double()
+    ref = (ext[idx.cpu().long()] * valid).sum(1) / valid.sum(1)
+    assert bool(((got.cpu().to(F64) - ref.clamp(0, 1)).abs() <= (7 + 2) * U * ref.abs() + 1e-30).all())
+
+
+@pytest.mark.parametrize("counts", W.POINT_COUNTS)
+def test_gt_overlap_and_augment(device, monkeypatch, counts):
+    """The inputs of test_gpu_workspace.py::test_gt_overlap_and_augment (test_gpu_gt_overlap.py and
+    test_gpu_augment.py hold the operators against their replicas).  The draws come from the device form of
+    ops.augment_draw (cu tensors placed; noise and keys are ragged device stores) and are held against the numpy
+    Philox replica under the bound of test_gpu_augment.py::test_draw_buffers_against_the_numpy_philox; augment_pairs
+    runs on them and with inline draws, and the two must agree in every bit
+    (::test_inline_draws_equal_explicit_buffers)."""
+    src0, scu0, tgt0, tcu0, pose0 = W._overlap_inputs(counts, device)
+    seed, keys = 7, [11, 12, 13]
+    off = scu0[:-1].cpu().tolist()
+    ns, nt = src0.shape[0], tgt0.shape[0]
+
+    def owned(aug):
+        # the rows the call owns, as in the workspace module: the rest is never written (include/spr.h)
+        n_s, n_t = int(aug['src_cu'][-1]), int(aug['tgt_cu'][-1])
+        for k in ('src_xyz', 'src_perm', 'src_mask'):
+            aug[k] = aug[k][:n_s]
+        for k in ('tgt_xyz', 'tgt_perm', 'tgt_mask'):
+            aug[k] = aug[k][:n_t]
+        aug['corr'] = W._owned(aug['corr'], off, aug['corr_count'].tolist())
+        return aug
+
+    def f(put):
+        src, scu, tgt, tcu, pose = (put(t.clone()) for t in (src0, scu0, tgt0, tcu0, pose0))
+        s_corr, t_corr, s_mask, t_mask, corr, cnt = ops.gt_overlap(src, scu, tgt, tcu, pose, 0.05)
+        psrc, swap, perturb, noise, dkeys = ops.augment_draw(seed, keys, 'small', scu, tcu, ns, nt)
+        inline = ops.augment_pairs(src, scu, tgt, tcu, pose, psrc, swap, perturb, 'small', 0.005, seed=seed,
+                                   pair_keys=keys, src_mask=s_mask, tgt_mask=t_mask, corr=corr, corr_off=off, corr_count=cnt)
+        # uint8 masks are taken as they are (bool ones are cast, a copy): placed, they end at a band as well
+        explicit = ops.augment_pairs(src, scu, tgt, tcu, pose, psrc, swap, perturb, 'small', 0.005,
+                                     src_mask=put(s_mask.view(torch.uint8).clone()),
+                                     tgt_mask=put(t_mask.view(torch.uint8).clone()), corr=put(corr.clone()), corr_off=off,
+                                     corr_count=cnt, noise=noise, keys=dkeys)
+        return s_corr, t_corr, s_mask, t_mask, W._owned(corr, off, cnt), torch.tensor(cnt), owned(inline), \
+            owned(explicit), noise, dkeys
+    out = bounded(monkeypatch, f, f"gt_overlap + augment {counts}")
+    assert int(out[5].sum()) > 0 and not bool(out[6]['status'].any()) and int(out[6]['corr_count'].sum()) > 0
+    for k in out[6]:
+        assert torch.equal(out[6][k], out[7][k]), f"inline and explicit draws differ in {k}"
+    want_k, want_n, want_r = [], [], []
+    for side in (0, 1):
+        for pk, n in zip(keys, counts):
+            want_k.append(ar.keys(seed, pk, side, n))
+            nz, r = ar.noise64(seed, pk, side, n)
+            want_n.append(nz)
+            want_r.append(r)
+    assert np.array_equal(out[9].cpu().numpy().view(np.uint32), np.concatenate(want_k))
+    err = np.abs(out[8].cpu().numpy().astype(np.float64) - np.concatenate(want_n))
+    assert np.all(err <= 2e-6 * np.concatenate(want_r)), float((err / np.concatenate(want_r)).max())
+
+
+def test_weight_ranges_in_one_launch(device, monkeypatch):
+    """ops.prime_weight_ranges (spr_absmax_multi) and the single measurement (spr_absmax); the maxima are exact
+    (test_gpu_range.py::test_prime_weight_ranges_measures_all_stale_weights_in_one_launch)."""
+    g = torch.Generator().manual_seed(2)
+    host = [torch.randn(shape, generator=g).mul(scale) for shape, scale in (((257, 64), 1.0), ((15, 32, 32), 40.0), ((3, 5), 7.0))]
+
+    def f(put):
+        ws = [put(t.to(device)) for t in host]
+        assert ops.prime_weight_ranges(ws) == len(ws)
+        one = put(host[0].to(device))
+        return [ops._get_range(w)[0].max() for w in ws] + [ops._static_range(one)[0].max()]
+    got = bounded(monkeypatch, f, "weight ranges")
+    for m, t in zip(got, host + host[:1]):
+        assert float(m) == float(t.abs().max())
+
+
+# ---- coverage: keep this test last ---------------------------------------------------------------------------------------
+# entry points that are host-only or take no device operand
+EXEMPT = (r"_bytes$", r"_len$", r"_size$", r"_slots$", r"_tile_rows$", r"^spr_range_parts$", r"^spr_layernorm_range_count$",
+          r"_host$", r"^spr_version$", r"^spr_selftest$", r"^spr_set_[a-z]+_mode$", r"^spr_prof_",
+          r"^spr_ransac_draw$")     # its draw table is written to a host array; it has no device operand
+# entry points that no case can reach at small size, with the reason (none so far)
+UNREACHED = {}
+
+
+def test_every_entry_point_was_called_under_the_arena(device):
+    pkg = os.path.dirname(ops.__file__)
+    text = "".join(open(os.path.join(pkg, n)).read() for n in ("ops.py", "autograd.py", "tie_order.py", "augment.py",
+                                                               "overlap.py"))
+    referenced = {n for n in _lib.SIGNATURES if re.search(rf"\b{n}\b", text)}
+    wanted = {n for n in referenced if not any(re.search(p, n) for p in EXEMPT)}
+    assert len(wanted) >= 70, len(wanted)
+    missing = sorted(n for n in wanted if n not in CALLED and n not in UNREACHED)
+    assert not missing, f"no case of this module called {missing} with guarded tensors"

@@ -10,6 +10,13 @@ reproducible results.  A case whose shape no existing test holds against float64
 float64 evaluation on the CPU under that operator's existing criterion (imported from its test module, or restated
 with the test named where it is written inline there); a case that reuses an existing test's inputs names that test.
 
+The two poisoned runs also sit in the tensor arena (tests/tensor_arena.py): every tensor the host layer allocates with
+torch.empty and its kin -- the outputs, the scratch handed over by pointer, plans and planes -- lies between guard
+bands and starts out as poison, 0xFF with the 0xFF workspace and zeros with the zero one.  The same three runs then
+also show a store outside a tensor, a returned element that was never written (the caching allocator would hand
+production last call's correct value there) and scratch read before it is written.  Regions of a returned tensor
+that include/spr.h declares not written are cut away inside the case (_owned).
+
 The last test of the module checks that the cases above reached every `_workspace(` / `_loss_ws(` call site of ops.py
 and autograd.py: a new operator fails it until it has a case here.  Run the module as a whole."""
 import math
@@ -37,6 +44,7 @@ from test_gpu_ops import _close
 from test_gpu_posemb_learned import BWD_SEEDS, _ours as posemb_grads, bwd_case as posemb_case
 from test_gpu_refine import pack as refine_pack, synth_pair
 from test_gpu_xenc import _encoder, _oracle64
+from tensor_arena import TensorArena
 from workspace_arena import GUARD, Arena
 
 pytestmark = pytest.mark.gpu
@@ -62,21 +70,34 @@ def _bits(t):
     return t.contiguous().view(-1).view(torch.uint8) if t.numel() else t.reshape(-1)
 
 
-def run_three(monkeypatch, f, what, guard=GUARD, verify_every=0):
+def run_three(monkeypatch, f, what, guard=GUARD, verify_every=0, placed=False):
     """production / poison 0xFF / poison 0x00; asserts in the order: guards, finiteness, bit equality.  Returns the
-    production result."""
-    production = f()
-    runs, arenas = [_flat(production)], []
-    for poison in (0xFF, 0x00):
+    production result.  The two poisoned runs also sit in the tensor arena (tests/tensor_arena.py), flavour 1 with 0xFF
+    and flavour 2 with 0x00: every tensor the case allocates through Python -- outputs, host-side scratch, plans and
+    planes -- lies between bands that are checked after the workspace guards, and its unwritten elements hold the
+    poison, so the finiteness and bit-equality checks below speak for them as well.
+    placed: f takes one argument, put, and passes its inputs through it: the identity in production, the arena's put()
+    in the poisoned runs, where every input then ends flush against a band (tests/test_gpu_tensor_bounds.py, whose
+    cases include operators without a workspace: only there may a case ask for none)."""
+    production = f(lambda t: t) if placed else f()
+    runs, arenas, tensor_arenas = [_flat(production)], [], []
+    for flavour, poison in ((1, 0xFF), (2, 0x00)):
         arena = Arena(poison, guard, verify_every)
+        tensors = TensorArena(flavour, guard, verify_every)
         with monkeypatch.context() as m:
             m.setattr(ops, "_workspace", arena)
-            runs.append(_flat(f()))
+            tensors.install(m)
+            runs.append(_flat(f(tensors.put) if placed else f()))
         arenas.append(arena)
+        tensor_arenas.append(tensors)
         SEEN.update(arena.callers)
     for arena in arenas:
         arena.verify()
-        assert arena.calls > 0, f"{what}: the case never asked for a workspace"
+        if not placed:
+            assert arena.calls > 0, f"{what}: the case never asked for a workspace"
+    for tensors in tensor_arenas:
+        tensors.verify()
+        assert tensors.calls > 0, f"{what}: the case never allocated a tensor"
     prod = runs[0]
     assert len(prod) > 0 and all(len(r) == len(prod) for r in runs), what
     for name, run in (("0xFF", runs[1]), ("0x00", runs[2])):
