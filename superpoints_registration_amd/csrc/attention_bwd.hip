@@ -8,9 +8,9 @@
 //   dQ       = scale . dS K,    dS = P o (dP - D),  P = exp2(c S - L), dP = dO V^T    (sweep 2 of) k_attn_bwd_dq
 //   dV = P^T dO,  dK = scale . dS^T Q                                                 k_attn_bwd_dkv
 //
-// Arithmetic: attention mode 0 (spr_set_attn_mode): exact f32 MFMA (v_mfma_f32_32x32x2_f32) like spr_bgemm; mode 1 / 2
-// (default): the split-fp16 form further down.  fp32 softmax with v_exp_f32 in both; fixed summation order ->
-// bitwise reproducible gradients.
+// Arithmetic: attention mode 0 (spr_set_attn_mode): exact f32 MFMA (v_mfma_f32_32x32x2_f32) like spr_bgemm; every other
+// mode (1 .. 4; 4 is the default): the split-fp16 form further down -- the backward depends on the mode only through
+// mode != 0.  fp32 softmax with v_exp_f32 in both; fixed summation order -> bitwise reproducible gradients.
 //
 // Layout trick (no LDS round trip for the probabilities): the 32x32 C tile holds column n = lane % 32 and the
 // rows 8 (r / 4) + 4 (lane / 32) + r % 4 in registers r = 0..15.  A C tile whose ROWS are the contraction
@@ -380,7 +380,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_dkv(const AttnBwdArgs a) {
 
 
 // ======================================================================================================
-// Split-fp16 form (attention mode 1, the default): the same two kernels with every product on
+// Split-fp16 form (every attention mode but 0; the default is 4): the same two kernels with every product on
 // v_mfma_f32_32x32x16_f16 over range-scaled hi/lo operand planes (3 matrix instructions per product and k-step, fp32
 // accumulation -- the forward's arithmetic, spr_common.h split_pk_s), 5.3x less matrix time than the f32 form.
 //   operand scales (powers of two, measured per call): sq, sk, sv, sdo bring max|q|, |k|, |v|, |dO| into

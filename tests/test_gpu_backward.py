@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+from attn_bwd_cases import attention_grads_f64 as _attention_f64
 from conftest import load_golden
 from oracle import torch_oracle as O
 from oracle.gen_golden import grad_sample_indices, loss_inputs, ops_inputs, pairs_for
@@ -151,21 +152,6 @@ def test_attention_backward(device, attn_mode):
         outs.append((a @ v).transpose(0, 1).reshape(-1, 256))
     torch.cat(outs).backward(go.double())
     assert _rel(dq.grad, cq.grad) <= 2e-5, f"attention dqkv {_rel(dq.grad, cq.grad):.2e}"
-
-
-def _attention_f64(q0, k0, v0, go, lens, kv_seg):
-    cq, ck, cv = (t.double().requires_grad_(True) for t in (q0, k0, v0))
-    offs = np.concatenate([[0], np.cumsum(lens)])
-    outs = []
-    for s in range(len(lens)):
-        ks = kv_seg[s]
-        q = cq[offs[s]:offs[s + 1]].view(-1, 8, 32).transpose(0, 1)
-        k = ck[offs[ks]:offs[ks + 1]].view(-1, 8, 32).transpose(0, 1)
-        v = cv[offs[ks]:offs[ks + 1]].view(-1, 8, 32).transpose(0, 1)
-        a = torch.softmax(q @ k.transpose(1, 2) / math.sqrt(32), -1)
-        outs.append((a @ v).transpose(0, 1).reshape(-1, 256))
-    torch.cat(outs).backward(go.double())
-    return cq.grad, ck.grad, cv.grad
 
 
 @pytest.mark.parametrize("qs,ks,vs,gs", [(1.0, 1.0, 1.0, 1.0), (1e-4, 3e3, 1e5, 1e-7), (40.0, 1.0, 1e-6, 1e6),

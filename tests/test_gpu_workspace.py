@@ -28,6 +28,7 @@ import pytest
 import torch
 
 import forward_cases as fc
+from attn_bwd_cases import MinBwdLib as _MinBwdLib, attention_grads_f64 as _attention_f64
 from conftest import load_golden
 from oracle import torch_oracle as O
 from oracle.gen_golden import loss_inputs, ops_inputs, pairs_for
@@ -35,7 +36,7 @@ from superpoints_registration_amd import _lib, autograd, get_config, ops, synthe
 from superpoints_registration_amd.regtr import RegTR
 from superpoints_registration_amd.transformers import make_segments
 from test_gpu_attn_maps import _ref_maps
-from test_gpu_backward import _attention_f64, _rel
+from test_gpu_backward import _rel
 from test_gpu_block_tail import LENS as TAIL_LENS, SHAPES as TAIL_SHAPES, _inputs as tail_inputs
 from test_gpu_circle_loss import REGIMES as CIRCLE_REGIMES, make_case as circle_case, run as circle_run
 from test_gpu_forward_range import _bounded
@@ -192,18 +193,6 @@ def test_attention_probs(device, monkeypatch, segs, average):
         got = maps[s]
         assert (got[..., :lq, :lk] - ref).abs().max().item() <= 1e-5, (segs, s)
         assert not got[..., lq:, :].any() and not got[..., :, lk:].any()
-
-
-class _MinBwdLib:
-    """The library with spr_attn_bwd_workspace_bytes answering the minimum: the route without operand planes."""
-
-    def __init__(self, lib):
-        self._lib = lib
-
-    def __getattr__(self, name):
-        if name == "spr_attn_bwd_workspace_bytes":
-            return lambda t, nseg, nhead: self._lib.spr_attn_bwd_min_workspace_bytes(t, nhead)
-        return getattr(self._lib, name)
 
 
 @pytest.mark.parametrize("route", ["planes", "min"])
