@@ -324,6 +324,80 @@ int spr_augment_pairs(const float* src_xyz, const int* src_cu, int ns, const flo
                       int* out_src_perm, int* out_tgt_perm, int* out_corr, int* out_corr_count, int* status, void* ws,
                       size_t ws_bytes, void* stream);
 
+/* ---- 8f-7: ModelNet training pairs (crop, transform, resample, jitter, shuffle) ------
+ * Replaces the per-sample CPU chain SplitSourceRef -> RandomCrop(partial) -> RandomTransformSE3_euler(rot_mag,
+ * trans_mag) -> Resampler(num_points) -> RandomJitter() -> ShufflePoints() of the reference's ModelNet loader
+ * (data_loaders/modelnet.py:102-109, data_loaders/modelnet_transforms.py) for noise_type 'crop': one raw cloud in,
+ * a partially overlapping (source, reference) pair with its pose, overlap masks and correspondences out.  One call
+ * generates all nb pairs; every draw is a pure function of (seed, pair_key, side, element, stream tag).
+ *
+ * Draw contract.  Philox4x32-10, key, counter layout and u(w) of 8f-6, q = 2 * pair_key + side (side 0 = source,
+ * 1 = reference cloud; pair-level draws use side 0 unless a side is named).  Words of a block: w0..w3.
+ *   tag 16, host, float64 (libm acos / sin / cos):
+ *     element 0 of side s: that side's crop direction (uniform_2_sphere): phi = 2 pi u(w0), z = 2 u(w1) - 1,
+ *       theta = acos z, dir = (sin theta cos phi, sin theta sin phi, cos theta)
+ *     element 1: angles (a_x, a_y, a_z) = ((u(w0..w2) * pi) * rot_mag) / 180
+ *     element 2: translation t = -trans_mag + (2 * trans_mag) * u(w0..w2)
+ *     R = (Rx Ry) Rz with the matrices of modelnet_transforms.py:342-351, every entry ((a0 b0 + a1 b1) + a2 b2);
+ *     [R | t] is rounded to float32
+ *   tag 17: the resample key of a point = w0 of the block whose element is the point's RAW local index
+ *   tag 18: up-sampling extras: position n_kept + j takes the kept point floor(u(w0 of element j) * n_kept) (float64;
+ *     the product is exact), the kept points counted in ascending raw order (the cropped cloud's own order)
+ *   tag 19: jitter noise = the 8f-6 float32 normal triple of the block whose element is the RESAMPLED position
+ *   tag 20: the shuffle key = w0 of the block whose element is the resampled position
+ *
+ * spr_modelnet_draw: the decisions of nb pairs into HOST arrays (dirs_host [nb,2,3] f64, transform_host [nb,3,4] f32;
+ *   each may be NULL) and, when any of them is given, the device buffers of the per-point draws of a batch with the
+ *   given cu and DEVICE pair_key [nb] u64: rkeys [2,n_total] u32 (tag 17), extra [2,nb*k] u32 (tag 18, the words w0),
+ *   noise [2,nb*k,3] f32 (tag 19), skeys [2,nb*k] u32 (tag 20); first index = side, pair b owns entries from b*k.
+ *   These are the values spr_modelnet_pairs generates inline when it is handed NULL for them: bit for bit.
+ *
+ * spr_modelnet_pairs.  Contract (float64 on the exactly converted float32 inputs, one rounding per operation, sums of
+ * three products as ((a0 b0 + a1 b1) + a2 b2), no contraction; f32(.) = rounded to float32).  Cloud b = rows
+ * [cu[b], cu[b+1]) of xyz, n points, local ("raw") indices 0..n-1; both sides start from the same n points.
+ *   1 centre and project (per side): c = f32(S / n), S = the float64 sum of the cloud in this fixed order: partial
+ *     p_t = x_t + x_(t+1024) + ... (ascending, t < 1024, absent terms skipped); inside every run of 64 consecutive
+ *     partials six rounds p_t <- p_t + p_(t xor o), o = 32, 16, 8, 4, 2, 1; the 16 run sums added in ascending order
+ *     from 0.  v = f32(x - c); d = dot3(v, dir).
+ *   2 crop mask (RandomCrop.crop): p_keep = 1 keeps everything; p_keep = 0.5 keeps d > 0; otherwise numpy's 'linear'
+ *     percentile: h = (n-1) * (q / 100), lo = floor(h), t = h - lo, a / b = the lo-th / min(lo+1, n-1)-th smallest d,
+ *     thr = a + (b-a) t if t < 0.5 else b - (b-a) (1-t); keep d > thr.  q is the caller's float64 (1 - f32(p)) * 100
+ *     evaluated as the reference does (30.000001907348633 for 0.7).
+ *   3 a kept source point is "overlap" iff its raw index is kept on the reference side, and the other way round; the
+ *     correspondences are the raw indices kept on both sides, in ascending raw order.
+ *   4 transform, source only: x' = f32(dot3(R_i, x) + t_i);  pose = f32([R^T | -(R^T t)]) maps source -> reference.
+ *   5 resample to k per side: the kept points in the stable ascending order of their tag-17 keys, cut to k; with
+ *     n_kept < k all of them in that order, then the tag-18 extras.  A correspondence survives iff both its ends were
+ *     selected; where a point occupies several positions it maps to the LARGEST one (numpy's repeated-index
+ *     assignment).  Survivors keep their order.
+ *   6 jitter, both sides: e = clamp(f32(noise * scale), -clip, clip) per component, x'' = f32(x' + e).
+ *   7 shuffle, both sides: out[j] = resampled[perm[j]], perm = the stable ascending order of the tag-20 keys; overlap
+ *     flags and raw indices are gathered with the points, correspondences go through the inverse permutation.
+ * Outputs, k entries per pair and side, pair b from b*k: src_xyz / tgt_xyz [nb*k,3] f32, src_overlap / tgt_overlap
+ * [nb*k] u8, src_index / tgt_index [nb*k] i32 (the raw local index of every output point), pose [nb,3,4] f32,
+ * corr [2, nb*k] i32 (row 0 source, row 1 reference output indices; pair b owns columns [b*k, b*k + corr_count[b])),
+ * corr_count [nb] i32 -- the only data-dependent size.
+ * status [nb] i32: 0; 1 = a non-finite coordinate, transform or direction in that pair; 2 = a side keeps no point
+ * after the crop (n <= 1, or every d equal); 3 = the cloud is longer than max_len_host or outside xyz.  A pair with a
+ * non-zero status has zero points, flags and indices and no correspondences (its pose is still written for 2); other
+ * pairs are unaffected.
+ * max_len_host: an upper bound of the longest cloud, at most 8192; k in [1, 8192]; p_keep in (0, 1].  Violations are
+ * refused on the host before any launch.  Ragged lengths and empty clouds are legal.
+ *   xyz [n_total,3] f32, cu [nb+1] i32, transform [nb,3,4] f32, dirs [nb,2,3] f64, pair_key [nb] u64 (all device);
+ *   rkeys / extra / noise / skeys: the explicit draw buffers above, each NULL = generated inline (pair_key required).
+ */
+int spr_modelnet_draw(uint64_t seed, const uint64_t* pair_key_host, int nb, double rot_mag, double trans_mag,
+                      double* dirs_host, float* transform_host, const uint64_t* pair_key, const int* cu, int n_total,
+                      int k, unsigned int* rkeys, unsigned int* extra, float* noise, unsigned int* skeys, void* stream);
+size_t spr_modelnet_pairs_workspace_size(int n_total, int nb, int k);
+int spr_modelnet_pairs(const float* xyz, const int* cu, int n_total, int nb, int max_len_host, float p_src, float p_tgt,
+                       double q_src, double q_tgt, int k, float scale, float clip, const float* transform,
+                       const double* dirs, uint64_t seed, const uint64_t* pair_key, const unsigned int* rkeys,
+                       const unsigned int* extra, const float* noise, const unsigned int* skeys, float* src_xyz,
+                       float* tgt_xyz, float* pose, unsigned char* src_overlap, unsigned char* tgt_overlap,
+                       int* src_index, int* tgt_index, int* corr, int* corr_count, int* status, void* ws,
+                       size_t ws_bytes, void* stream);
+
 /* ---- a4: KPConv forward ---------------------------------------------------
  * Replaces KPConv.forward(q_pts, s_pts, neighb_inds, x)
  * (models/backbone_kpconv/kpconv_blocks.py:269-414; rigid kernel, linear

@@ -18,6 +18,7 @@ _f = ctypes.c_float
 _sz = ctypes.c_size_t
 _l = ctypes.c_long
 _u64 = ctypes.c_uint64
+_d = ctypes.c_double
 
 # name -> (restype, argtypes); mirrors include/spr.h exactly
 SIGNATURES = {
@@ -54,6 +55,10 @@ SIGNATURES = {
     "spr_augment_pairs": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _f, _i,
                                _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                _sz, _vp]),
+    "spr_modelnet_draw": (_i, [_u64, _vp, _i, _d, _d, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "spr_modelnet_pairs_workspace_size": (_sz, [_i, _i, _i]),
+    "spr_modelnet_pairs": (_i, [_vp, _vp, _i, _i, _i, _f, _f, _d, _d, _i, _f, _f, _vp, _vp, _u64, _vp, _vp, _vp, _vp,
+                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "spr_kpconv_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "spr_kpconv_fwd": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _f, _vp, _i, _vp, _i, _vp,
                             _i, _vp, _vp, _vp, _sz, _vp]),

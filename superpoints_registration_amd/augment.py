@@ -5,8 +5,8 @@ ShufflePoints() -> RandomSwap() per pair on the CPU, on the global numpy / rando
 (data_loaders/__init__.py:17-54, data_loaders/transforms.py:15-179).  Here all pairs of a step are augmented by one
 library call (ops.augment_pairs -> spr_augment_pairs, csrc/augment.hip) and every draw is a pure function of
 (seed, pair_key): a pair is augmented identically whatever batch, position or rank it lands in.  The draw contract and
-the float64 apply contract are in include/spr.h ("8f-6").  ModelNet's own pipeline (modelnet_transforms.py) is out of
-scope.
+the float64 apply contract are in include/spr.h ("8f-6").  ModelNet's own pipeline (modelnet_transforms.py) is
+modelnet.make_pairs (include/spr.h "8f-7").
 """
 from typing import List, Sequence, Tuple
 

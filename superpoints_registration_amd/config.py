@@ -82,6 +82,8 @@ CONFIGS = {
         use_sinkhorn=False, sinkhorn_itr=1, slack=False, r_p=0.12, r_n=0.24,
         num_refinement_steps=5, acceptance_radius=0.05, overlap_radius=0.04,
         augment_noise=0.005, perturb_pose='small',
+        # read by modelnet.make_pairs (conf/qk_regtr_full_modelnet.yaml:16-20)
+        partial=[0.7, 0.7], num_points=1024, noise_type='crop', rot_mag=45.0, trans_mag=0.5,
     ),
 }
 

@@ -27,20 +27,9 @@
 namespace spr {
 namespace {
 
-// Philox4x32-10, the block layout and the stream tags: philox.h
-__device__ __forceinline__ float aug_u32(uint32_t w) { return __fmul_rn((float)(w >> 9) + 0.5f, 1.1920928955078125e-7f); }
-
-// (r(w0) cos(w1), r(w0) sin(w1), r(w2) cos(w3)): the accurate logf / sincosf / sqrtf, one rounding per operation
+// Philox4x32-10, the block layout, the stream tags and the float32 normal triple: philox.h
 __device__ __forceinline__ void aug_noise(uint64_t seed, uint64_t pair_key, int side, int i, float* n) {
-  const Philox4 b = philox_block(seed, pair_key, side, (uint32_t)i, kTagNoise);
-  const float r0 = sqrtf(__fmul_rn(-2.f, logf(aug_u32(b.w[0]))));
-  const float r1 = sqrtf(__fmul_rn(-2.f, logf(aug_u32(b.w[2]))));
-  float s0, c0, s1, c1;
-  sincosf(__fmul_rn(6.2831855f, aug_u32(b.w[1])), &s0, &c0);
-  sincosf(__fmul_rn(6.2831855f, aug_u32(b.w[3])), &s1, &c1);
-  n[0] = __fmul_rn(r0, c0);
-  n[1] = __fmul_rn(r0, s0);
-  n[2] = __fmul_rn(r1, c1);
+  philox_normal3(philox_block(seed, pair_key, side, (uint32_t)i, kTagNoise), n);
 }
 
 __device__ __forceinline__ uint32_t aug_key(uint64_t seed, uint64_t pair_key, int side, int i) {

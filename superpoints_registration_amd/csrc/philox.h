@@ -1,5 +1,5 @@
 // Philox4x32-10 and the (seed, pair_key, side, element, tag) block layout of the draw contracts in include/spr.h:
-// one definition for augment.hip (tags 0, 1, 2) and ransac.hip (tag 3), host and device.
+// one definition for augment.hip (tags 0, 1, 2), ransac.hip (tag 3) and modelnet_pairs.hip (tags 16-20), host and device.
 #pragma once
 #include <cstdint>
 
@@ -39,5 +39,25 @@ __host__ __device__ inline Philox4 philox_block(uint64_t seed, uint64_t pair_key
 }
 
 constexpr uint32_t kTagPair = 0, kTagNoise = 1, kTagKey = 2, kTagRansac = 3;
+// 8f-7 (ModelNet pairs): pair decisions, resample keys, up-sampling extras, jitter noise, shuffle keys
+constexpr uint32_t kTagMnPair = 16, kTagMnResample = 17, kTagMnExtra = 18, kTagMnNoise = 19, kTagMnShuffle = 20;
+
+#ifdef __HIPCC__
+// u(w) in float32 (exact: 24 significant bits)
+__device__ __forceinline__ float philox_u32(uint32_t w) { return __fmul_rn((float)(w >> 9) + 0.5f, 1.1920928955078125e-7f); }
+
+// The float32 normal triple of a block (8f-6): (r(w0) cos(w1), r(w0) sin(w1), r(w2) cos(w3)) with the accurate
+// logf / sincosf / sqrtf, one rounding per operation
+__device__ __forceinline__ void philox_normal3(const Philox4& b, float* n) {
+  const float r0 = sqrtf(__fmul_rn(-2.f, logf(philox_u32(b.w[0]))));
+  const float r1 = sqrtf(__fmul_rn(-2.f, logf(philox_u32(b.w[2]))));
+  float s0, c0, s1, c1;
+  sincosf(__fmul_rn(6.2831855f, philox_u32(b.w[1])), &s0, &c0);
+  sincosf(__fmul_rn(6.2831855f, philox_u32(b.w[3])), &s1, &c1);
+  n[0] = __fmul_rn(r0, c0);
+  n[1] = __fmul_rn(r0, s0);
+  n[2] = __fmul_rn(r1, c1);
+}
+#endif
 
 }  // namespace spr
