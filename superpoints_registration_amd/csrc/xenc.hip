@@ -85,6 +85,32 @@ struct ChainConsts {
   int nf;                               // d_ff / 32
 };
 
+// Everything a chain launch is told, as ONE by-value kernel argument: the kernel reads it from the kernel-argument
+// segment where it needs it (k_xenc_chain, "arguments") instead of holding ~90 SGPRs of it from entry to exit.
+struct ChainArgs {
+  ChainConsts c;
+  const float *o_g, *x_g;
+  float* xo_g;
+  const float* pos_g;
+  float *pos_t, *ln_g;
+  AttnPlanes pl;
+  int* tile_ctr;
+  const int* tfirst_g;
+  int stamp_on;
+};
+typedef const __attribute__((address_space(4))) ChainArgs* ChainArgsP;   // constant address space: scalar loads
+
+// x, behind a statement the compiler cannot look through: what is computed from the result is computed where the
+// result is made (not once in front of the tile loop, to be carried -- and spilled -- across every stage)
+__device__ __forceinline__ int opaque_v(int x) {
+  asm volatile("" : "+v"(x));
+  return x;
+}
+__device__ __forceinline__ ChainArgsP opaque_s(ChainArgsP p) {
+  asm volatile("" : "+s"(p));
+  return p;
+}
+
 template <int N>
 __device__ __forceinline__ void wait_vm() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
@@ -99,20 +125,22 @@ __device__ __forceinline__ void wait_vm_any(int n) {   // n wave uniform, a mult
 #undef SPR_W
 }
 
-// LDS-DMA: 16 bytes per lane from base + off (per-lane byte offset) to LDS at dst_s + 16 * lane.
-__device__ __forceinline__ void dma16(const void* base, unsigned off, unsigned dst_s) {
+// LDS-DMA: 16 bytes per lane from base + off (per-lane byte offset) to LDS at M0 + offset + 16 * lane.
+// Four 1-KiB pieces behind ONE M0 / address setup: the instruction's immediate offset moves the global AND the LDS
+// address, so piece q of a 4-KiB group is the same instruction with offset q KiB.
+// dma_first() is piece 0 of a group: it loads M0, spends the wait state an LDS-DMA needs behind an M0 write and issues
+// the piece in ONE statement, so nothing can come between the M0 write and its first use.  dma_q<Q>() (Q = 1 .. 3) are
+// the bare instruction and name M0 as clobbered: they rely on nothing having written M0 since the group's dma_first()
+// (the chunk loops hold no instruction that uses M0: LDS instructions of this architecture do not, and the kernel is
+// built -- and checked at build time, csrc/Makefile -- without SGPR spills, whose lane writes could).
+// `base` is the weight stream's address as a wave-uniform 64-bit value (k_xenc_chain builds it from two
+// readfirstlane results, so it is an SGPR pair by construction and never a value the compiler reloads from a lane).
+__device__ __forceinline__ void dma_first(unsigned long long base, unsigned off, unsigned dst_s) {
   asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
                : : "v"(off), "s"(base), "s"(dst_s) : "memory", "m0");
 }
-// Four 1-KiB pieces behind ONE M0 / address setup: the instruction's immediate offset moves the global AND the LDS
-// address (LDS address = M0 + offset + 16 lane), so piece q of a 4-KiB group is the same instruction with offset q KiB.
-// dma_set() loads M0; dma_q<Q>() relies on nothing having written M0 since (the chunk loops hold no instruction that
-// uses M0: LDS instructions of this architecture do not).
-__device__ __forceinline__ void dma_set(unsigned dst_s) {
-  asm volatile("s_mov_b32 m0, %0" : : "s"(dst_s) : "memory", "m0");
-}
 template <int Q>
-__device__ __forceinline__ void dma_q(const void* base, unsigned off) {
+__device__ __forceinline__ void dma_q(unsigned long long base, unsigned off) {
   asm volatile("global_load_lds_dwordx4 %0, %1 offset:%2" : : "v"(off), "s"(base), "n"(Q * 1024) : "memory", "m0");
 }
 // (the trailing s_nop keeps the compiler's next instruction from overwriting the data registers of a
@@ -302,44 +330,76 @@ __device__ unsigned long long g_xenc_stamps[64 * 64];
 // Layouts: HEAD chains read x_g and o_g TILED; the prologue (!HEAD) reads x_g and pos_g
 // row-major and writes their tiled copies to xo_g and pos_t; xo_g is tiled unless TAIL == 0 (then it is the stack's
 // row-major output); pos_t is read by every HEAD chain with an in-projection tail; ln_g is row-major.
+//
+// Arguments.  The kernel lives at the edge of both register files (512 vector registers, ~100 scalar), and a value the
+// compiler spills comes back through scratch memory: a vector-memory load it waits for with s_waitcnt vmcnt(0) -- blind
+// to the LDS-DMAs of the weight ring queued behind it, that wait drains the ring (see load_c above).  So the kernel
+// keeps almost nothing across its stages:
+//   - the arguments stay in the kernel-argument segment; every stage reads the few it uses through args(), an opaque
+//     copy of the segment's address, by scalar loads (counted by lgkmcnt, never by vmcnt) and drops them at its end;
+//   - lane constants (lane, r, h, token, validity and what is derived from them: table, fragment and tensor addresses)
+//     are made again at the head of every stage from the thread index (relane()).
+// What stays for the whole kernel: the thread index, the weight stream's base (an SGPR pair), the ring's state.
 template <bool HEAD, bool FFN, int TAIL>
-__global__ __launch_bounds__(256, 1) void k_xenc_chain(ChainConsts c, const float* o_g, const float* x_g, float* xo_g,
-                                                       const float* pos_g, float* pos_t, float* ln_g, AttnPlanes pl, int T,
-                                                       int ntiles, int* tile_ctr, const int* __restrict__ tfirst_g,
-                                                       int stamp_on) {
+__global__ __launch_bounds__(256, 1) void k_xenc_chain(ChainArgs args_by_value) {
+  (void)args_by_value;                 // read through the kernel-argument segment: explicit arguments start at offset 0
+  const ChainArgsP ka = (ChainArgsP)__builtin_amdgcn_kernarg_segment_ptr();
+  auto args = [&]() __attribute__((always_inline)) { return opaque_s(ka); };
   constexpr bool XO_TILED = TAIL != 0;
   extern __shared__ __align__(16) unsigned char ring[];
   float* tab = reinterpret_cast<float*>(ring + XSLOTS * XCHUNK);
-  const int d_ff = 32 * c.nf;
-  int* cu_s = reinterpret_cast<int*>(tab + T_B1 + d_ff + T_PAD);     // cu_seqlens [nseg + 1]
-  int* tf_s = cu_s + pl.nseg + 1;                                      // tiles in front of every segment [nseg + 1]
-  const int tid = threadIdx.x, lane = tid & 63;
+  const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int r = lane & 31, h = lane >> 5;
+  int lane = tid & 63, r = lane & 31, h = lane >> 5;
+  auto relane = [&]() __attribute__((always_inline)) {
+    lane = opaque_v(tid) & 63;
+    r = lane & 31;
+    h = lane >> 5;
+  };
   const unsigned ring_s = (unsigned)(uintptr_t)ring;
-  const int nch = (HEAD ? 8 : 0) + (FFN ? 2 * c.nf : 0) + (TAIL == 2 ? 24 : 0);   // chunks per tile
+#ifdef SPR_XENC_STAMP
+  const int stamp_on = ka->stamp_on;
+#endif
   // Tiles are dealt by a device counter (tile_ctr, zeroed by the host before the launch): workgroups that run
   // slower (or start later) take fewer tiles.  (A staggered start -- four phase groups per XCD, so that the
   // chip does not load its tile operands in one burst -- was measured and changed nothing: the operand phases
   // are bound by what ONE CU's vector-memory path moves, 128 KB per tile tensor at ~25 GB/s, not by HBM.)
   __shared__ int s_tile[2];
-  // ---- parameter tables and cu_seqlens into LDS (the steady state reads its operands from LDS only) ----
-  for (int i = tid; i < 256; i += 256) {
-    tab[T_BO + i] = HEAD ? c.bo[i] : 0.f;
-    tab[T_B2 + i] = FFN ? c.b2[i] : 0.f;
-    tab[T_GM + i] = FFN ? c.g_mid[i] : 0.f;
-    tab[T_BM + i] = FFN ? c.b_mid[i] : 0.f;
-    tab[T_GT + i] = TAIL >= 1 ? c.g_tail[i] : 0.f;
-    tab[T_BT + i] = TAIL >= 1 ? c.b_tail[i] : 0.f;
-  }
-  for (int i = tid; i < 768; i += 256) tab[T_BIN + i] = TAIL == 2 ? c.bin[i] : 0.f;
-  for (int i = tid; i < d_ff + T_PAD; i += 256) tab[T_B1 + i] = (FFN && i < d_ff) ? c.b1[i] : 0.f;
-  for (int i = tid; i <= pl.nseg; i += 256) {
-    cu_s[i] = pl.cu[i];
-    tf_s[i] = tfirst_g[i];
+  int nch, nseg, ntiles;
+  int *cu_s, *tf_s;
+  unsigned long long w_s;              // the weight stream: chunks of XCHUNK bytes in consumption order
+  {
+    const ChainArgsP k = ka;
+    const int nf = k->c.nf, d_ff = 32 * nf;
+    nseg = k->pl.nseg;
+    cu_s = reinterpret_cast<int*>(tab + T_B1 + d_ff + T_PAD);     // cu_seqlens [nseg + 1]
+    tf_s = cu_s + nseg + 1;                                        // tiles in front of every segment [nseg + 1]
+    nch = (HEAD ? 8 : 0) + (FFN ? 2 * nf : 0) + (TAIL == 2 ? 24 : 0);   // chunks per tile
+    const unsigned long long w = (unsigned long long)(uintptr_t)k->c.w;
+    w_s = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(w >> 32)) << 32) |
+          (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)w);
+    // ---- parameter tables and cu_seqlens into LDS (the steady state reads its operands from LDS only) ----
+    const float *bo = k->c.bo, *b1 = k->c.b1, *b2 = k->c.b2, *bin = k->c.bin, *g_mid = k->c.g_mid, *b_mid = k->c.b_mid,
+                *g_tail = k->c.g_tail, *b_tail = k->c.b_tail;
+    for (int i = tid; i < 256; i += 256) {
+      tab[T_BO + i] = HEAD ? bo[i] : 0.f;
+      tab[T_B2 + i] = FFN ? b2[i] : 0.f;
+      tab[T_GM + i] = FFN ? g_mid[i] : 0.f;
+      tab[T_BM + i] = FFN ? b_mid[i] : 0.f;
+      tab[T_GT + i] = TAIL >= 1 ? g_tail[i] : 0.f;
+      tab[T_BT + i] = TAIL >= 1 ? b_tail[i] : 0.f;
+    }
+    for (int i = tid; i < 768; i += 256) tab[T_BIN + i] = TAIL == 2 ? bin[i] : 0.f;
+    for (int i = tid; i < d_ff + T_PAD; i += 256) tab[T_B1 + i] = (FFN && i < d_ff) ? b1[i] : 0.f;
+    const int* cu_g = k->pl.cu;
+    const int* tfirst_g = k->tfirst_g;
+    for (int i = tid; i <= nseg; i += 256) {
+      cu_s[i] = cu_g[i];
+      tf_s[i] = tfirst_g[i];
+    }
   }
   __syncthreads();
-  ntiles = tf_s[pl.nseg];                // (the host only knows an upper bound)
+  ntiles = __builtin_amdgcn_readfirstlane(tf_s[nseg]);    // (the host only knows an upper bound)
 
   // ---- weight ring -----------------------------------------------------------------------------------
   // Chunk g lives in slot g % 4.  acquire() -- at step 8 of chunk g - 1 -- makes chunk g readable (every wave
@@ -358,21 +418,21 @@ __global__ __launch_bounds__(256, 1) void k_xenc_chain(ChainConsts c, const floa
     if (++i_pos == nch) i_pos = 0;
     if (++i_slot == XSLOTS) i_slot = 0;
   };
-  // piece j of the armed chunk (j is a constant after unrolling): pieces 0 and 4 set M0 for their group of four (the
-  // wait state M0 needs in front of an LDS-DMA is the s_nop), the others are ONE instruction
+  // piece j of the armed chunk (j is a constant after unrolling): pieces 0 and 4 set M0 for their group of four
+  // (dma_first), the others are ONE instruction
   auto piece = [&](int j) __attribute__((always_inline)) {
 #ifdef SPR_XENC_STAMP
     if (stamp_on & 2) return;             // ablation: no weight DMA (garbage results)
 #endif
     switch (j) {
-      case 0: dma_set(dma_dst); asm volatile("s_nop 0"); dma_q<0>(c.w, dma_off); break;
-      case 1: dma_q<1>(c.w, dma_off); break;
-      case 2: dma_q<2>(c.w, dma_off); break;
-      case 3: dma_q<3>(c.w, dma_off); break;
-      case 4: dma_set(dma_dst + 4096); asm volatile("s_nop 0"); dma_q<0>(c.w, dma_off4); break;
-      case 5: dma_q<1>(c.w, dma_off4); break;
-      case 6: dma_q<2>(c.w, dma_off4); break;
-      default: dma_q<3>(c.w, dma_off4); break;
+      case 0: dma_first(w_s, dma_off, dma_dst); break;
+      case 1: dma_q<1>(w_s, dma_off); break;
+      case 2: dma_q<2>(w_s, dma_off); break;
+      case 3: dma_q<3>(w_s, dma_off); break;
+      case 4: dma_first(w_s, dma_off4, dma_dst + 4096); break;
+      case 5: dma_q<1>(w_s, dma_off4); break;
+      case 6: dma_q<2>(w_s, dma_off4); break;
+      default: dma_q<3>(w_s, dma_off4); break;
     }
   };
   auto acquire = [&]() __attribute__((always_inline)) -> const unsigned char* {
@@ -392,9 +452,9 @@ __global__ __launch_bounds__(256, 1) void k_xenc_chain(ChainConsts c, const floa
     return p;
   };
   // first tile; staggered start
-  if (tid == 0) s_tile[0] = atomicAdd(tile_ctr, 1);
+  if (tid == 0) s_tile[0] = atomicAdd(ka->tile_ctr, 1);
   __syncthreads();
-  int tile = s_tile[0];
+  int tile = __builtin_amdgcn_readfirstlane(s_tile[0]);
   if (tile >= ntiles) return;
   // prologue: chunks 0, 1, 2 in flight, chunk 0 acquired, its first fragments read
 #pragma unroll 1
@@ -470,6 +530,17 @@ __global__ __launch_bounds__(256, 1) void k_xenc_chain(ChainConsts c, const floa
     slot = nxt;
   };
   auto no_side = [](int) __attribute__((always_inline)) {};
+  // The first XPF fragments of the chunk in `slot`, read again.  The last steps of a stage's last chunk have read them
+  // already, but between two stages of a tile every register is wanted (the tile, the tensor added to it and the next
+  // operand planes: 3 x 128), and 24 registers of fragments carried across that are 24 registers spilled.  Read in front
+  // of a stage's first chunk instead, the reads of the last steps are dead and the compiler drops them; the slot is the
+  // one those steps read, acquired eight steps before the stage ended.
+  auto refill = [&]() __attribute__((always_inline)) {
+    XSB();
+#pragma unroll
+    for (int i = 0; i < XPF; ++i) frag_ld(slot, lane, i, cy.h[i], cy.l[i]);
+    XSB();
+  };
   // accumulator <- bias table block (scaled), one group of four per call (g = 0..3)
   auto bias_group = [&](f32x16& a, const float* tb, float sc, int g) __attribute__((always_inline)) {
     const f32x4 t = *reinterpret_cast<const f32x4*>(tb + 8 * g + 4 * h);
@@ -482,26 +553,33 @@ __global__ __launch_bounds__(256, 1) void k_xenc_chain(ChainConsts c, const floa
 #pragma unroll 1
   for (int it = 0; tile < ntiles; ++it) {
     stamp_it = it;
-    if (tid == 0) s_tile[(it + 1) & 1] = atomicAdd(tile_ctr, 1);       // the next tile (read at the end of this one)
+    if (tid == 0) s_tile[(it + 1) & 1] = atomicAdd(args()->tile_ctr, 1);   // the next tile (read at the end of this one)
     // Tiles never straddle a segment (cloud): tile = (segment, 128-token slice of it).  A wave's 32 tokens then sit in
     // 32 consecutive, 32-byte aligned columns of the transposed V planes (one segment, vstart is a multiple of 16).
     int sg;
     {
-      int lo = 0, hi = pl.nseg;                        // largest s with tf[s] <= tile (skips empty segments)
+      int lo = 0, hi = nseg;                           // largest s with tf[s] <= tile (skips empty segments)
       while (hi - lo > 1) {
         const int mid = (lo + hi) >> 1;
-        if (tf_s[mid] <= tile) lo = mid; else hi = mid;
+        if (__builtin_amdgcn_readfirstlane(tf_s[mid]) <= tile) lo = mid; else hi = mid;
       }
       sg = lo;
     }
-    const int seg_beg = cu_s[sg], seg_end = cu_s[sg + 1];
-    const int tok_w = seg_beg + (tile - tf_s[sg]) * XTOK + wave * 32;     // first token of the wave
-    const int tok = tok_w + r;
-    const bool valid = tok < seg_end;
+    // (wave-uniform values read from LDS: made scalars by hand, the compiler takes an LDS read for a lane value)
+    const int seg_beg = __builtin_amdgcn_readfirstlane(cu_s[sg]), seg_end = __builtin_amdgcn_readfirstlane(cu_s[sg + 1]);
+    const int tok_w = seg_beg + (tile - __builtin_amdgcn_readfirstlane(tf_s[sg])) * XTOK + wave * 32;   // first token of the wave
     const bool wave_valid = tok_w < seg_end;               // lane 0 of the wave is valid: its stores do issue
-    const int tokc = valid ? tok : seg_end - 1;
     const size_t wb4 = ((size_t)tile * 4 + wave) * XWAVE4;       // the wave's block of the tiled tensors
-    (void)T;
+    // the lane's token, made again with the lane constants at the head of every stage (stage())
+    int tok = 0, tokc = 0;
+    bool valid = false;
+    auto stage = [&]() __attribute__((always_inline)) {
+      relane();
+      tok = tok_w + r;
+      valid = tok < seg_end;
+      tokc = valid ? tok : seg_end - 1;
+      return args();
+    };
     f32x16 v[8];
     f16x8 ph[16], pw[16];
     XSTAMP(0);
@@ -509,13 +587,17 @@ __global__ __launch_bounds__(256, 1) void k_xenc_chain(ChainConsts c, const floa
 
     if constexpr (HEAD) {
       // ---- x' = o Wo^T + bo + x ------------------------------------------------------------------
-      load_t(o_g, wb4, lane, v);
+      const ChainArgsP k = stage();
+      const float* const x_g = k->x_g;         // (for the end of the stage, read with the rest: one scalar-load wait less)
+      float* const xo_g = k->xo_g;
+      const float un_o = k->c.un_o;
+      load_t(k->o_g, wb4, lane, v);
 #pragma unroll
-      for (int b = 0; b < 8; ++b) split_block(v[b], c.o_scale, ph[2 * b], pw[2 * b], ph[2 * b + 1], pw[2 * b + 1]);
+      for (int b = 0; b < 8; ++b) split_block(v[b], k->c.o_scale, ph[2 * b], pw[2 * b], ph[2 * b + 1], pw[2 * b + 1]);
 #pragma unroll
       for (int b = 0; b < 8; ++b)
 #pragma unroll
-        for (int g = 0; g < 4; ++g) bias_group(v[b], tab + T_BO + 32 * b, c.res_o, g);
+        for (int g = 0; g < 4; ++g) bias_group(v[b], tab + T_BO + 32 * b, k->c.res_o, g);
       XSTAMP(1);
 #pragma unroll
       for (int b = 0; b < 8; ++b) {
@@ -523,13 +605,14 @@ __global__ __launch_bounds__(256, 1) void k_xenc_chain(ChainConsts c, const floa
         if (b == 0) XSTAMP(2);
       }
       XSTAMP(3);
+      stage();
       {
         f32x16 t_x[8];
         load_t(x_g, wb4, lane, t_x);
 #pragma unroll
         for (int b = 0; b < 8; ++b)
 #pragma unroll
-          for (int e = 0; e < 16; ++e) v[b][e] = v[b][e] * c.un_o + t_x[b][e];
+          for (int e = 0; e < 16; ++e) v[b][e] = v[b][e] * un_o + t_x[b][e];
       }
       // the new residual stream (FFN: parked there, re-read behind the loop)
       if constexpr (XO_TILED) store_t(xo_g, wb4, lane, v);
@@ -539,34 +622,39 @@ __global__ __launch_bounds__(256, 1) void k_xenc_chain(ChainConsts c, const floa
       if constexpr (FFN) s_cnt += 32;
       XSTAMP(4);
     } else {
-      load_c(x_g, tokc, h, v);
-      store_t(xo_g, wb4, lane, v);          // prologue: the tiled copy of x the chains read
+      const ChainArgsP k = stage();
+      load_c(k->x_g, tokc, h, v);
+      store_t(k->xo_g, wb4, lane, v);          // prologue: the tiled copy of x the chains read
     }
 
     if constexpr (FFN) {
       // ---- x'' = x' + linear2(relu(linear1(norm3(x')))) -------------------------------------------
       // stream order F0, F1, G0, F2, G1, ..., F(nf-1), G(nf-2), G(nf-1): the ReLU + split of hidden chunk c
       // runs as side slices of F(c+1); two linear1 accumulators A / B alternate (nf is even)
+      const ChainArgsP k = stage();
+      const float bs1 = k->c.bs1, h_mul = k->c.h_mul, un_f = k->c.un_f;
+      const int nf = k->c.nf;
+      float* const xo_g = k->xo_g;             // (for the end of the stage)
       f32x16 y[8];
       {
         float mean, rstd;
-        ln_stats(v, c.eps_mid, mean, rstd);
+        ln_stats(v, k->c.eps_mid, mean, rstd);
 #pragma unroll
         for (int b = 0; b < 8; ++b) {
           const f32x16 t = ln_block(v[b], b, h, mean, rstd, tab + T_GM, tab + T_BM);
-          split_block(t, c.x2_scale, ph[2 * b], pw[2 * b], ph[2 * b + 1], pw[2 * b + 1]);
+          split_block(t, k->c.x2_scale, ph[2 * b], pw[2 * b], ph[2 * b + 1], pw[2 * b + 1]);
         }
       }
 #pragma unroll
       for (int b = 0; b < 8; ++b)
 #pragma unroll
-        for (int g = 0; g < 4; ++g) bias_group(y[b], tab + T_B2 + 32 * b, c.res_f, g);
+        for (int g = 0; g < 4; ++g) bias_group(y[b], tab + T_B2 + 32 * b, k->c.res_f, g);
       f32x16 A, B;
       unsigned int hu[8], lu[8];
       f16x8 hh[2], hl[2];
       const float* b1t = tab + T_B1;
 #pragma unroll
-      for (int g = 0; g < 4; ++g) bias_group(A, b1t, c.bs1, g);
+      for (int g = 0; g < 4; ++g) bias_group(A, b1t, bs1, g);
       XSTAMP(5);
       // side of F(c): slices 0..7 ReLU + split of the previous accumulator P (hidden chunk c - 1), slices
       // 8..11 re-initialise P with the bias of hidden chunk c + 1 (the table is padded past d_ff)
@@ -579,12 +667,12 @@ __global__ __launch_bounds__(256, 1) void k_xenc_chain(ChainConsts c, const floa
           if (!(s & 1)) {
             ra = fmaxf(P[2 * q], 0.f);
             rb = fmaxf(P[2 * q + 1], 0.f);
-            split_pk_s_hi(ra, rb, c.h_mul, hu[q]);
+            split_pk_s_hi(ra, rb, h_mul, hu[q]);
           } else {
-            split_pk_s_lo(ra, rb, c.h_mul, hu[q], lu[q]);
+            split_pk_s_lo(ra, rb, h_mul, hu[q], lu[q]);
           }
         } else if (s < 20) {
-          bias_group(P, b1t + 32 * cnext, c.bs1, s - 16);
+          bias_group(P, b1t + 32 * cnext, bs1, s - 16);
         }
       };
       auto pack_h = [&]() __attribute__((always_inline)) {
@@ -593,12 +681,13 @@ __global__ __launch_bounds__(256, 1) void k_xenc_chain(ChainConsts c, const floa
         hh[1] = __builtin_bit_cast(f16x8, (u32x4){hu[4], hu[5], hu[6], hu[7]});
         hl[1] = __builtin_bit_cast(f16x8, (u32x4){lu[4], lu[5], lu[6], lu[7]});
       };
+      if constexpr (HEAD) refill();
       // F0 (side: bias of hidden chunk 1 into B)
       chunk_f(std::false_type{}, A, ph, pw, [&](int s) __attribute__((always_inline)) {
-        if (s < 4) bias_group(B, b1t + 32, c.bs1, s);
+        if (s < 4) bias_group(B, b1t + 32, bs1, s);
       });
       XSTAMP(6);
-      const int npair = c.nf / 2 - 1;
+      const int npair = nf / 2 - 1;
 #pragma unroll 1
       for (int j = 0; j < npair; ++j) {
         const int c1 = 2 * j + 1;
@@ -611,7 +700,7 @@ __global__ __launch_bounds__(256, 1) void k_xenc_chain(ChainConsts c, const floa
         if (j == 0) XSTAMP(7);
       }
       {
-        const int c1 = c.nf - 1;                                                                        // last pair
+        const int c1 = nf - 1;                                                                        // last pair
 #ifdef SPR_XENC_STAMP
         step_stamp = 15;
 #endif
@@ -626,11 +715,12 @@ __global__ __launch_bounds__(256, 1) void k_xenc_chain(ChainConsts c, const floa
         step_stamp = -1;
 #endif
 #pragma unroll
-        for (int s = 0; s < 8; ++s) split_pk_s(fmaxf(B[2 * s], 0.f), fmaxf(B[2 * s + 1], 0.f), c.h_mul, hu[s], lu[s]);
+        for (int s = 0; s < 8; ++s) split_pk_s(fmaxf(B[2 * s], 0.f), fmaxf(B[2 * s + 1], 0.f), h_mul, hu[s], lu[s]);
         pack_h();
         chunk_g(y, hh, hl, no_side);                                                                    // G(nf - 1)
       }
       XSTAMP(8);
+      stage();
       {
         f32x16 t_x[8];
         if constexpr (XO_TILED) load_t(xo_g, wb4, lane, t_x);             // x' again (this lane stored it)
@@ -638,7 +728,7 @@ __global__ __launch_bounds__(256, 1) void k_xenc_chain(ChainConsts c, const floa
 #pragma unroll
         for (int b = 0; b < 8; ++b)
 #pragma unroll
-          for (int e = 0; e < 16; ++e) v[b][e] = y[b][e] * c.un_f + t_x[b][e];
+          for (int e = 0; e < 16; ++e) v[b][e] = y[b][e] * un_f + t_x[b][e];
       }
       if constexpr (TAIL == 2) store_t(xo_g, wb4, lane, v);
       if constexpr (TAIL == 0) store_c(xo_g, tok, h, valid, v);
@@ -646,30 +736,39 @@ __global__ __launch_bounds__(256, 1) void k_xenc_chain(ChainConsts c, const floa
     }
 
     if constexpr (TAIL == 1) {
+      const ChainArgsP k = stage();
       float mean, rstd;
-      ln_stats(v, c.eps_tail, mean, rstd);
+      ln_stats(v, k->c.eps_tail, mean, rstd);
 #pragma unroll
       for (int b = 0; b < 8; ++b) v[b] = ln_block(v[b], b, h, mean, rstd, tab + T_GT, tab + T_BT);
-      store_c(ln_g, tok, h, valid, v);
+      store_c(k->ln_g, tok, h, valid, v);
     }
     if constexpr (TAIL == 2) {
       // ---- Q / K / V planes of norm(x) + pos ------------------------------------------------------
+      // (read here, in front of the chunk loops: a read left to its use inside a conditional store slice stays there,
+      // scalar load and lgkmcnt(0) wait, in every slice)
+      const ChainArgsP k = stage();
+      const float bs_in = k->c.bs_in, un_in = k->c.un_in;
+      const float pmul[3] = {un_in * k->c.pmul[0], un_in * k->c.pmul[1], un_in * k->c.pmul[2]};
+      _Float16 *const p_qh = k->pl.qh, *const p_ql = k->pl.ql, *const p_kh = k->pl.kh, *const p_kl = k->pl.kl,
+                     *const p_vth = k->pl.vth, *const p_vtl = k->pl.vtl;
+      const int t_total = k->pl.t_total;
       {
         float mean, rstd;
-        ln_stats(v, c.eps_tail, mean, rstd);
+        ln_stats(v, k->c.eps_tail, mean, rstd);
         f32x16 t_p[8];
         if constexpr (HEAD) {
-          load_t(pos_t, wb4, lane, t_p);
+          load_t(k->pos_t, wb4, lane, t_p);
         } else {
-          load_c(pos_g, tokc, h, t_p);
-          store_t(pos_t, wb4, lane, t_p);   // prologue: the tiled copy of the positional embedding
+          load_c(k->pos_g, tokc, h, t_p);
+          store_t(k->pos_t, wb4, lane, t_p);   // prologue: the tiled copy of the positional embedding
         }
 #pragma unroll
         for (int b = 0; b < 8; ++b) {
           f32x16 t = ln_block(v[b], b, h, mean, rstd, tab + T_GT, tab + T_BT);
 #pragma unroll
           for (int e = 0; e < 16; ++e) t[e] += t_p[b][e];
-          split_block(t, c.xt_scale, ph[2 * b], pw[2 * b], ph[2 * b + 1], pw[2 * b + 1]);
+          split_block(t, k->c.xt_scale, ph[2 * b], pw[2 * b], ph[2 * b + 1], pw[2 * b + 1]);
         }
       }
       XSTAMP(10);
@@ -681,17 +780,17 @@ __global__ __launch_bounds__(256, 1) void k_xenc_chain(ChainConsts c, const floa
       f32x16 A, B;
       unsigned int hu[8], lu[8];
 #pragma unroll
-      for (int g = 0; g < 4; ++g) bias_group(A, bint, c.bs_in, g);
+      for (int g = 0; g < 4; ++g) bias_group(A, bint, bs_in, g);
       // bias of block fbn, a quarter per call: per register (Q / K) or per lane (V)
       auto bias_next = [&](f32x16& P, int fbn, int q) __attribute__((always_inline)) {
         if (fbn >= 16) {
-          const float t = bint[32 * fbn + r] * c.bs_in;
+          const float t = bint[32 * fbn + r] * bs_in;
           P[4 * q + 0] = t;
           P[4 * q + 1] = t;
           P[4 * q + 2] = t;
           P[4 * q + 3] = t;
         } else {
-          bias_group(P, bint + 32 * fbn, c.bs_in, q);
+          bias_group(P, bint + 32 * fbn, bs_in, q);
         }
       };
       // epilogue slices of accumulator P = feature block fbp (kind WHICH: 0 Q, 1 K, 2 V), then bias of block fbn
@@ -701,7 +800,7 @@ __global__ __launch_bounds__(256, 1) void k_xenc_chain(ChainConsts c, const floa
         if (s < 16) {
           // split of register pair q: hi plane in slice 2 q, lo plane in 2 q + 1 (a slice must fit the issue cycles an
           // MFMA leaves free).  un_in is a power of two: folded into the plane multiplier, same bits.
-          const float pm = c.un_in * c.pmul[WHICH];
+          const float pm = pmul[WHICH];
           const int q = s >> 1;
           if (!(s & 1)) split_pk_s_hi(P[2 * q], P[2 * q + 1], pm, hu[q]);
           else split_pk_s_lo(P[2 * q], P[2 * q + 1], pm, hu[q], lu[q]);
@@ -722,8 +821,8 @@ __global__ __launch_bounds__(256, 1) void k_xenc_chain(ChainConsts c, const floa
             // d' = 16 h + e.  The order of d inside a head is free as long as Q and K agree (both are
             // written here) -- the scores sum over it.
             if (valid) {
-              _Float16* pb = WHICH == 0 ? (s < 20 ? pl.qh : pl.ql) : (s < 20 ? pl.kh : pl.kl);
-              const size_t row = ((size_t)head * pl.t_total + tokc) * 32 + 16 * h + 8 * (s & 1);
+              _Float16* pb = WHICH == 0 ? (s < 20 ? p_qh : p_ql) : (s < 20 ? p_kh : p_kl);
+              const size_t row = ((size_t)head * t_total + tokc) * 32 + 16 * h + 8 * (s & 1);
               store16(pb + row, (u32x4){src[o4], src[o4 + 1], src[o4 + 2], src[o4 + 3]});
             }
           } else {
@@ -733,7 +832,7 @@ __global__ __launch_bounds__(256, 1) void k_xenc_chain(ChainConsts c, const floa
             // inside the gap in front of the next segment)
             const int t0 = tok_w + 16 * (s & 1) + 4 * h;
             if (t0 < seg_end) {
-              _Float16* pb = s < 20 ? pl.vth : pl.vtl;
+              _Float16* pb = s < 20 ? p_vth : p_vtl;
               // (blocked planes, attn_v_off: the wave's instruction writes the head's 1-KiB block of this 16-column group)
               const size_t o0 = attn_v_off(head * 32 + r, (size_t)(vcol_w + 16 * (s & 1) + 8 * h), XD);
               store16(pb + o0, (u32x4){src[o4], src[o4 + 1], src[o4 + 2], src[o4 + 3]});
@@ -748,9 +847,10 @@ __global__ __launch_bounds__(256, 1) void k_xenc_chain(ChainConsts c, const floa
       auto count = [&](bool vblock) __attribute__((always_inline)) {
         if (wave_valid) s_cnt += (vblock && tok_w + 16 >= seg_end) ? 2 : 4;
       };
+      if constexpr (HEAD || FFN) refill();
       // block 0 (side: bias of block 1 into B)
       chunk_f(std::false_type{}, A, ph, pw, [&](int s) __attribute__((always_inline)) {
-        if (s < 4) bias_group(B, bint + 32, c.bs_in, s);
+        if (s < 4) bias_group(B, bint + 32, bs_in, s);
       });
       XSTAMP(11);
       // blocks fb (odd, into B) and fb + 1 (into A); which_tag = kind of the blocks whose epilogues run beside them
@@ -782,7 +882,7 @@ __global__ __launch_bounds__(256, 1) void k_xenc_chain(ChainConsts c, const floa
       count(true);
       XSTAMP(14);
     }
-    tile = s_tile[(it + 1) & 1];   // written before this tile's first barrier: ordered by the barriers since
+    tile = __builtin_amdgcn_readfirstlane(s_tile[(it + 1) & 1]);   // written before this tile's first barrier: ordered by the barriers since
   }
   wait_vm<0>();   // the chunks issued past the end of the stream must have landed before the LDS is released
 }
@@ -914,8 +1014,8 @@ int launch_chain(const ChainConsts& c, const float* o, const float* x, float* xo
     if (ea != nullptr) stamp_on |= atoi(ea) & 14;
   }
 #endif
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, c, o, x, xo, pos, pos_t, ln, pl, T, ntiles, tile_ctr, tfirst,
-                     stamp_on);
+  const ChainArgs args{c, o, x, xo, pos, pos_t, ln, pl, tile_ctr, tfirst, stamp_on};
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, args);
   SPR_LAUNCH_CHECK();
   return 0;
 }
