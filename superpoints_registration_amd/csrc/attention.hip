@@ -20,6 +20,7 @@
 //   K / V tiles of 32 keys are staged in LDS (row stride 33 / 32 words ->
 //   conflict-free fragment reads) and shared by the four waves.
 #include "attn_planes.h"
+#include "lds_dma.h"
 #include "spr_common.h"
 #include <atomic>
 #include <type_traits>
@@ -104,7 +105,7 @@ __global__ __launch_bounds__(256) void k_attn(
     asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(vreg) : "v"(vp_));
   };
   auto stash = [&](int kt, int buf) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     __builtin_amdgcn_sched_barrier(0);
     const bool in = kt + sr < klen;                // rows past the segment read as zero
     float* kd = Ks[buf] + sr * KS + sc4;
@@ -468,18 +469,14 @@ __global__ __launch_bounds__(256, WPS) void k_attn_s(
   const unsigned vstep = (unsigned)(nhead * HD * KT2);                                          // halves per tile
   const unsigned koff = (unsigned)(skr * HD + skc) * 2u;                                        // bytes inside a tile
   const unsigned voff = (unsigned)attn_v_off(svr, (size_t)svc, nhead * HD) * 2u;
-  auto dma16 = [&](const _Float16* base, unsigned off, unsigned dst) __attribute__((always_inline)) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" : : "v"(off), "s"(base), "s"(dst)
-                 : "memory", "m0");
-  };
   auto fetch = [&](int kt, int nbuf, auto tail_tag) __attribute__((always_inline)) {   // nbuf: the buffer tile kt will be read from
     const size_t kel = kbase + (size_t)(unsigned)kt * HD, vel = vbase + (size_t)((unsigned)kt / KT2) * vstep;
     const _Float16 *kh_t = kh_g + kel, *kl_t = kl_g + kel, *vth_t = vth_g + vel, *vtl_t = vtl_g + vel;
     const unsigned ko = decltype(tail_tag)::value ? (unsigned)(min(skr, klen - 1 - kt) * HD + skc) * 2u : koff;
-    dma16(kh_t, ko, kdst_h + (unsigned)nbuf * 4096u);
-    if constexpr (H3) dma16(kl_t, ko, kdst_l + (unsigned)nbuf * 4096u);
-    dma16(vth_t, voff, vdst_h + (unsigned)nbuf * 4096u);
-    if constexpr (H3) dma16(vtl_t, voff, vdst_l + (unsigned)nbuf * 4096u);
+    lds_dma16_first(kh_t, ko, kdst_h + (unsigned)nbuf * 4096u);
+    if constexpr (H3) lds_dma16_first(kl_t, ko, kdst_l + (unsigned)nbuf * 4096u);
+    lds_dma16_first(vth_t, voff, vdst_h + (unsigned)nbuf * 4096u);
+    if constexpr (H3) lds_dma16_first(vtl_t, voff, vdst_l + (unsigned)nbuf * 4096u);
   };
   // the fetch of the tile at kt, if there is one: full tiles never clamp
   auto fetch_next = [&](int kt, int nbuf) __attribute__((always_inline)) {
@@ -487,7 +484,7 @@ __global__ __launch_bounds__(256, WPS) void k_attn_s(
     else if (kt < klen) fetch(kt, nbuf, std::true_type{});
   };
   auto stash = [&]() {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's pieces of the next tile have landed
+    wait_vm<0>();      // this wave's pieces of the next tile have landed
   };
 
   constexpr float kOff = 4.0f;        // a fresh reference puts the row maximum at 2^kOff

@@ -630,20 +630,17 @@ __global__ __launch_bounds__(256) void k_attn_bwd_pack(const AttnBwdArgs a, cons
   *reinterpret_cast<bu32x4*>(cp[1] + o) = *reinterpret_cast<const bu32x4*>(tl + d * CS + 8 * c8);
 }
 
-#ifndef SPR_ATTN_BWD_NB
-#define SPR_ATTN_BWD_NB 1
-#endif
-constexpr int NB = SPR_ATTN_BWD_NB;       // tile buffers.  1 (default): two barriers per iteration, half the LDS, THREE
-                                          // workgroups per CU (measured 127.7 vs 131.0 ms per training step against 2)
+// ONE tile buffer in the two kernels below: two barriers per iteration, half the LDS of a double buffer, THREE
+// workgroups per CU (measured 127.7 vs 131.0 ms per training step against two buffers and two workgroups)
 constexpr int DQ_BUF_HALVES = 4 * R_HALVES + 2 * C_HALVES;     // K: R + C planes, V: R planes
 constexpr int DKV_BUF_HALVES = 4 * R_HALVES + 4 * C_HALVES;    // Q and dO: R + C planes
 
 // grid (query tile, head, query segment)
 // HL: the per-query log-sum-exp comes from the forward (a.lse, spr_attn_varlen_fwd): no sweep 1
 template <bool PL, bool HL>
-__global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void k_attn_bwd_dq_h(const AttnBwdArgs a, const float* __restrict__ scales,
+__global__ __launch_bounds__(256, 3) void k_attn_bwd_dq_h(const AttnBwdArgs a, const float* __restrict__ scales,
                                                           const BwdPlanes pl) {
-  __shared__ __align__(16) _Float16 tiles[NB * DQ_BUF_HALVES];
+  __shared__ __align__(16) _Float16 tiles[DQ_BUF_HALVES];
   __shared__ float red_m[2][BT], red_l[2][BT];
   const int head = blockIdx.y, seg = blockIdx.z;
   const int qbeg = a.cu[seg], qlen = a.cu[seg + 1] - qbeg;
@@ -657,12 +654,13 @@ __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void k_attn_bwd_dq_h(const At
   const int hoff = head * BHD;
   const float sq = scales[0], sk = scales[1], sv = scales[2], sdo = scales[3];
   const float c = a.scale * kLog2e / (sq * sk);
-  auto KRh = [&](int b) { return tiles + b * DQ_BUF_HALVES; };
-  auto KRl = [&](int b) { return tiles + b * DQ_BUF_HALVES + R_HALVES; };
-  auto VRh = [&](int b) { return tiles + b * DQ_BUF_HALVES + 2 * R_HALVES; };
-  auto VRl = [&](int b) { return tiles + b * DQ_BUF_HALVES + 3 * R_HALVES; };
-  auto KCh = [&](int b) { return tiles + b * DQ_BUF_HALVES + 4 * R_HALVES; };
-  auto KCl = [&](int b) { return tiles + b * DQ_BUF_HALVES + 4 * R_HALVES + C_HALVES; };
+  // the planes inside the tile buffer
+  auto KRh = [&]() { return tiles; };
+  auto KRl = [&]() { return tiles + R_HALVES; };
+  auto VRh = [&]() { return tiles + 2 * R_HALVES; };
+  auto VRl = [&]() { return tiles + 3 * R_HALVES; };
+  auto KCh = [&]() { return tiles + 4 * R_HALVES; };
+  auto KCl = [&]() { return tiles + 4 * R_HALVES + C_HALVES; };
 
   const int qi = q0 + 32 * qb + l31;
   const bool qvalid = qi < qlen;
@@ -689,13 +687,12 @@ __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void k_attn_bwd_dq_h(const At
   {
     Stage rk;
     fetchK(rk, 0, false);
-    stage_store<PL>(rk, sk, KRh(0), KRl(0), nullptr, nullptr);
+    stage_store<PL>(rk, sk, KRh(), KRl(), nullptr, nullptr);
     __syncthreads();
     for (int it = 0; it < ntile; ++it) {
-      const int buf = it & (NB - 1), nbuf = (it + 1) & (NB - 1);
       const bool more = it + 1 < ntile;
       if (more) fetchK(rk, (it + 1) * BT, false);
-      const f32x16 s = mm_rows_h(KRh(buf), KRl(buf), 32 * kb, l31, h, qh, ql);       // S'^T[key][query]
+      const f32x16 s = mm_rows_h(KRh(), KRl(), 32 * kb, l31, h, qh, ql);   // S'^T[key][query]
       float x[16], mx = -INFINITY;
       if (more) {                 // only the last tile of a segment can hold rows past its end
 #pragma unroll
@@ -719,8 +716,8 @@ __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void k_attn_bwd_dq_h(const At
         l_run = l_run * __builtin_amdgcn_exp2f(m_run - m_new) + sum;
         m_run = m_new;
       }
-      if (NB == 1) __syncthreads();
-      if (more) stage_store<PL>(rk, sk, KRh(nbuf), KRl(nbuf), nullptr, nullptr);
+      __syncthreads();   // every wave has read the tile
+      if (more) stage_store<PL>(rk, sk, KRh(), KRl(), nullptr, nullptr);
       __syncthreads();
     }
   }
@@ -759,18 +756,17 @@ __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void k_attn_bwd_dq_h(const At
     Stage rk, rv;
     fetchK(rk, 0, true);
     fetchV(rv, 0);
-    stage_store<PL>(rk, sk, KRh(0), KRl(0), KCh(0), KCl(0));
-    stage_store<PL>(rv, sv, VRh(0), VRl(0), nullptr, nullptr);
+    stage_store<PL>(rk, sk, KRh(), KRl(), KCh(), KCl());
+    stage_store<PL>(rv, sv, VRh(), VRl(), nullptr, nullptr);
     __syncthreads();
     for (int it = 0; it < ntile; ++it) {
-      const int buf = it & (NB - 1), nbuf = (it + 1) & (NB - 1);
       const bool more = it + 1 < ntile;
       if (more) {
         fetchK(rk, (it + 1) * BT, true);
         fetchV(rv, (it + 1) * BT);
       }
-      const f32x16 s = mm_rows_h(KRh(buf), KRl(buf), 32 * kb, l31, h, qh, ql);       // S'^T
-      const f32x16 dp = mm_rows_h(VRh(buf), VRl(buf), 32 * kb, l31, h, doh, dol);    // dP'^T = V dO^T
+      const f32x16 s = mm_rows_h(KRh(), KRl(), 32 * kb, l31, h, qh, ql);        // S'^T
+      const f32x16 dp = mm_rows_h(VRh(), VRl(), 32 * kb, l31, h, doh, dol);     // dP'^T = V dO^T
       f32x16 ds;
       if (more) {
 #pragma unroll
@@ -785,11 +781,11 @@ __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void k_attn_bwd_dq_h(const At
       }
       h16x8 bh[2], bl[2];
       acc_planes(ds, DS_MUL, bh, bl);
-      mm_cols_acc_h(acc, KCh(buf), KCl(buf), kb, l31, h, bh, bl);
-      if (NB == 1) __syncthreads();
+      mm_cols_acc_h(acc, KCh(), KCl(), kb, l31, h, bh, bl);
+      __syncthreads();   // every wave has read the tile
       if (more) {
-        stage_store<PL>(rk, sk, KRh(nbuf), KRl(nbuf), KCh(nbuf), KCl(nbuf));
-        stage_store<PL>(rv, sv, VRh(nbuf), VRl(nbuf), nullptr, nullptr);
+        stage_store<PL>(rk, sk, KRh(), KRl(), KCh(), KCl());
+        stage_store<PL>(rv, sv, VRh(), VRl(), nullptr, nullptr);
       }
       __syncthreads();
     }
@@ -816,14 +812,14 @@ __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void k_attn_bwd_dq_h(const At
   }
 }
 
-// grid (key tile, head, key segment); dynamic LDS: 2 x DKV_BUF_HALVES halves + 4 x 64 floats
+// grid (key tile, head, key segment); dynamic LDS: DKV_BUF_HALVES halves + 4 x 64 floats
 template <bool PL>
-__global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void k_attn_bwd_dkv_h(const AttnBwdArgs a, const float* __restrict__ scales,
+__global__ __launch_bounds__(256, 3) void k_attn_bwd_dkv_h(const AttnBwdArgs a, const float* __restrict__ scales,
                                                            const BwdPlanes pl) {
   extern __shared__ __align__(16) unsigned char dkv_smem[];
   _Float16* tiles = reinterpret_cast<_Float16*>(dkv_smem);
-  float* Lt = reinterpret_cast<float*>(dkv_smem + (size_t)NB * DKV_BUF_HALVES * 2);     // [2][BT]
-  float* Dt = Lt + 2 * BT;                                                               // [2][BT]
+  float* Lt = reinterpret_cast<float*>(dkv_smem + (size_t)DKV_BUF_HALVES * 2);   // [BT] of a 2 BT slot
+  float* Dt = Lt + 2 * BT;                                                       // [BT] of a 2 BT slot
   const int head = blockIdx.y, ksg = blockIdx.z;
   const int kbeg = a.cu[ksg], klen = a.cu[ksg + 1] - kbeg;
   const int k0 = blockIdx.x * BT;
@@ -837,14 +833,15 @@ __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void k_attn_bwd_dkv_h(const A
   const float sq = scales[0], sk = scales[1], sv = scales[2], sdo = scales[3];
   const float c = a.scale * kLog2e / (sq * sk);
   const float dmul = sv * sdo;
-  auto QRh = [&](int b) { return tiles + b * DKV_BUF_HALVES; };
-  auto QRl = [&](int b) { return tiles + b * DKV_BUF_HALVES + R_HALVES; };
-  auto ORh = [&](int b) { return tiles + b * DKV_BUF_HALVES + 2 * R_HALVES; };
-  auto ORl = [&](int b) { return tiles + b * DKV_BUF_HALVES + 3 * R_HALVES; };
-  auto QCh = [&](int b) { return tiles + b * DKV_BUF_HALVES + 4 * R_HALVES; };
-  auto QCl = [&](int b) { return tiles + b * DKV_BUF_HALVES + 4 * R_HALVES + C_HALVES; };
-  auto OCh = [&](int b) { return tiles + b * DKV_BUF_HALVES + 4 * R_HALVES + 2 * C_HALVES; };
-  auto OCl = [&](int b) { return tiles + b * DKV_BUF_HALVES + 4 * R_HALVES + 3 * C_HALVES; };
+  // the planes inside the tile buffer
+  auto QRh = [&]() { return tiles; };
+  auto QRl = [&]() { return tiles + R_HALVES; };
+  auto ORh = [&]() { return tiles + 2 * R_HALVES; };
+  auto ORl = [&]() { return tiles + 3 * R_HALVES; };
+  auto QCh = [&]() { return tiles + 4 * R_HALVES; };
+  auto QCl = [&]() { return tiles + 4 * R_HALVES + C_HALVES; };
+  auto OCh = [&]() { return tiles + 4 * R_HALVES + 2 * C_HALVES; };
+  auto OCl = [&]() { return tiles + 4 * R_HALVES + 3 * C_HALVES; };
 
   const int ki = k0 + 32 * kb + l31;
   const bool kvalid = ki < klen;
@@ -871,35 +868,34 @@ __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void k_attn_bwd_dkv_h(const A
       rd = r < qlen ? a.dsum[(size_t)(qbeg + r) * a.nhead + head] * dmul : 0.f;
     }
   };
-  auto store_stats = [&](int buf) {
+  auto store_stats = [&]() {
     if (tid < BT) {
-      Lt[buf * BT + tid] = rl;
-      Dt[buf * BT + tid] = rd;
+      Lt[tid] = rl;
+      Dt[tid] = rd;
     }
   };
   Stage rq, ro;
   fetchQ(rq, 0);
   fetchO(ro, 0);
   fetch_stats(0);
-  stage_store<PL>(rq, sq, QRh(0), QRl(0), QCh(0), QCl(0));
-  stage_store<PL>(ro, sdo, ORh(0), ORl(0), OCh(0), OCl(0));
-  store_stats(0);
+  stage_store<PL>(rq, sq, QRh(), QRl(), QCh(), QCl());
+  stage_store<PL>(ro, sdo, ORh(), ORl(), OCh(), OCl());
+  store_stats();
   __syncthreads();
   for (int it = 0; it < ntile; ++it) {
-    const int buf = it & (NB - 1), nbuf = (it + 1) & (NB - 1);
     const bool more = it + 1 < ntile;
     if (more) {
       fetchQ(rq, (it + 1) * BT);
       fetchO(ro, (it + 1) * BT);
       fetch_stats((it + 1) * BT);
     }
-    const f32x16 s = mm_rows_h(QRh(buf), QRl(buf), 32 * qb, l31, h, kh, kl);      // S'[query][key]
-    const f32x16 dp = mm_rows_h(ORh(buf), ORl(buf), 32 * qb, l31, h, vh, vl);     // dP' = dO V^T
+    const f32x16 s = mm_rows_h(QRh(), QRl(), 32 * qb, l31, h, kh, kl);      // S'[query][key]
+    const f32x16 dp = mm_rows_h(ORh(), ORl(), 32 * qb, l31, h, vh, vl);     // dP' = dO V^T
     f32x16 p, ds;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      const float4 l4 = *reinterpret_cast<const float4*>(&Lt[buf * BT + 32 * qb + 8 * g + 4 * h]);
-      const float4 d4 = *reinterpret_cast<const float4*>(&Dt[buf * BT + 32 * qb + 8 * g + 4 * h]);
+      const float4 l4 = *reinterpret_cast<const float4*>(&Lt[32 * qb + 8 * g + 4 * h]);
+      const float4 d4 = *reinterpret_cast<const float4*>(&Dt[32 * qb + 8 * g + 4 * h]);
       const float lv[4] = {l4.x, l4.y, l4.z, l4.w}, dv[4] = {d4.x, d4.y, d4.z, d4.w};
       // (rows past the segment's end exist in the last tile only; an invalid key lane is never stored)
       if (more) {
@@ -924,15 +920,15 @@ __global__ __launch_bounds__(256, NB == 1 ? 3 : 2) void k_attn_bwd_dkv_h(const A
     {
       h16x8 bh[2], bl[2];
       acc_planes(p, P_MUL, bh, bl);
-      mm_cols_acc_h(acc_v, OCh(buf), OCl(buf), qb, l31, h, bh, bl);      // dV^T[d][key] += dO^T P
+      mm_cols_acc_h(acc_v, OCh(), OCl(), qb, l31, h, bh, bl);      // dV^T[d][key] += dO^T P
       acc_planes(ds, DS_MUL, bh, bl);
-      mm_cols_acc_h(acc_k, QCh(buf), QCl(buf), qb, l31, h, bh, bl);      // dK^T[d][key] += Q^T dS
+      mm_cols_acc_h(acc_k, QCh(), QCl(), qb, l31, h, bh, bl);      // dK^T[d][key] += Q^T dS
     }
-    if (NB == 1) __syncthreads();
+    __syncthreads();   // every wave has read the tile
     if (more) {
-      stage_store<PL>(rq, sq, QRh(nbuf), QRl(nbuf), QCh(nbuf), QCl(nbuf));
-      stage_store<PL>(ro, sdo, ORh(nbuf), ORl(nbuf), OCh(nbuf), OCl(nbuf));
-      store_stats(nbuf);
+      stage_store<PL>(rq, sq, QRh(), QRl(), QCh(), QCl());
+      stage_store<PL>(ro, sdo, ORh(), ORl(), OCh(), OCl());
+      store_stats();
     }
     __syncthreads();
   }
@@ -1061,7 +1057,7 @@ extern "C" int spr_attn_varlen_bwd(const float* q, int q_stride, const float* k,
                                 stream))
       return rc;
     hipLaunchKernelGGL(k_attn_bwd_scales, dim3(1), dim3(256), 0, stream, parts, scales);
-    constexpr size_t dkv_lds = (size_t)NB * DKV_BUF_HALVES * 2 + 4 * BT * sizeof(float);
+    constexpr size_t dkv_lds = (size_t)DKV_BUF_HALVES * 2 + 4 * BT * sizeof(float);
     static_assert(dkv_lds >= sizeof(float) * 2 * 2 * 16 * 64, "the final reduction reuses the tile buffers");
     if (planes) {
       // operand planes written once (k_attn_bwd_pack), staged by 16-byte copies

@@ -27,6 +27,7 @@
 // Pre-kernels per call: k_rowflag (flag = sum_c x[i,c] > 0 and the packed
 // support records), k_w_prep (weights -> fragment-order hi/lo planes).
 // cin == 1 (the first block) has its own kernel, k_kpconv_cin1.
+#include "lds_dma.h"
 #include "spr_common.h"
 
 namespace spr {
@@ -257,18 +258,9 @@ __global__ __launch_bounds__(256) void k_w_prep(const float* __restrict__ W, int
   Wl[i] = (_Float16)(w - (float)h);
 }
 
-__device__ __forceinline__ void wait_vm(int n) {   // n folds to a constant after unrolling
-  switch (n) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-    case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-    case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-    case 16: asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-  }
-}
+// the tile kernel's counted wait (lds_dma.h): n = (k-steps in flight) * LPB folds to a constant after unrolling
+#define KP_TILE_COUNTS(W) W(0) W(2) W(4) W(6) W(8) W(12) W(16)
+SPR_DEFINE_WAIT_VM_ANY(wait_vm_tile, KP_TILE_COUNTS)
 
 typedef _Float16 kh8 __attribute__((ext_vector_type(8)));
 template <int N> struct VecF;
@@ -551,13 +543,13 @@ __global__ __launch_bounds__(64 * P1W) void k_kpconv_mfma(
           }
         }
       };
-      wait_vm(0);
+      wait_vm<0>();
 #pragma unroll
       for (int d = 0; d < D; ++d) load_step(d, bh[d], bl[d]);
       for (int b0 = 0; b0 < NBATCH - D; b0 += D) {
 #pragma unroll
         for (int d = 0; d < D; ++d) {
-          wait_vm((D - 1) * LPB);
+          wait_vm_tile((D - 1) * LPB);
           __builtin_amdgcn_sched_barrier(0);
           mma_step(b0 + d, bh[d], bl[d]);
           __builtin_amdgcn_sched_barrier(0);
@@ -566,7 +558,7 @@ __global__ __launch_bounds__(64 * P1W) void k_kpconv_mfma(
       }
 #pragma unroll
       for (int d = 0; d < D; ++d) {   // drain
-        wait_vm((D - 1 - d) * LPB);
+        wait_vm_tile((D - 1 - d) * LPB);
         __builtin_amdgcn_sched_barrier(0);
         mma_step(NBATCH - D + d, bh[d], bl[d]);
       }
@@ -691,9 +683,6 @@ int launch_mfma(const float* q_xyz, int nq, const float* s_xyz, int ns, const in
 // Covers Cin in {32, 64} with Cin * Cout <= 4096 (the 32->32 and 64->64 layers:
 // every KPConv of levels 0 and 1); other shapes keep k_kpconv_mfma.
 constexpr int kRingTQ = 16;
-#ifndef SPR_KP_NS64
-#define SPR_KP_NS64 4   // ring depth of the 64 -> 64 instantiation (experiment builds override it)
-#endif
 
 // Tile descriptors: one wave per tile of 16 queries (in `order` if given).  Entry [tile][w] =
 // {query A, query B, items A, items B} for wave w (-1 / 0 beyond nq).  An item = 8 neighbour
@@ -739,104 +728,11 @@ __global__ __launch_bounds__(256) void k_kp_tiles(const int* __restrict__ nbr, i
   }
 }
 
-// LDS-DMA: 16 bytes per active lane from base + off (per-lane byte offset) to LDS at dst_s + 16 * lane.
-// The wait in front orders the write behind every ds_read this wave has issued (the slot being refilled).
-__device__ __forceinline__ void ring_dma16(const void* base, unsigned off, unsigned dst_s) {
-  unsigned keep;
-  asm volatile(
-      "s_waitcnt lgkmcnt(0)\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep) : "v"(off), "s"(base), "s"(dst_s) : "memory");
-}
-__device__ __forceinline__ void ring_dma16_nw(const void* base, unsigned off, unsigned dst_s) {   // no LDS wait
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep) : "v"(off), "s"(base), "s"(dst_s) : "memory");
-}
-// m0 is not preserved (declared as a clobber: the compiler keeps nothing in it across the statement)
-__device__ __forceinline__ void ring_dma16_m0(const void* base, unsigned off, unsigned dst_s) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-               : : "v"(off), "s"(base), "s"(dst_s) : "memory", "m0");
-}
-// lanes 0..7 only (8 records of 16 bytes -> dst_s .. dst_s + 128); exec is restored inside the statement
-__device__ __forceinline__ void ring_dma16_rec8(const void* base, unsigned off, unsigned dst_s) {
-  unsigned long long keep;
-  asm volatile(
-      "s_mov_b64 %0, exec\n\ts_mov_b64 exec, 0xff\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, %2\n\ts_mov_b64 exec, %0"
-      : "=&s"(keep) : "v"(off), "s"(base), "s"(dst_s) : "memory", "m0");
-}
-// All DMA instructions of one ring item behind ONE M0 setup (round 5): the instruction's immediate offset moves the
-// global AND the LDS address, so the second row piece (LDS slot + 1 KiB) and the record piece (slot + 8 RB) are issued
-// against bases moved DOWN by their LDS displacement.  PPI = row pieces per item (1: 32 channels, 2: 64 channels).
-template <int PPI, int RB>
-__device__ __forceinline__ void ring_item_dma(const void* x, const void* x_m1k, const void* sx_m, unsigned off0,
-                                              unsigned off1, unsigned off_rec, unsigned dst_s) {
-  unsigned long long keep;
-  if constexpr (PPI == 2) {
-    asm volatile(
-        "s_mov_b32 m0, %7\n\ts_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, %4\n\t"
-        "global_load_lds_dwordx4 %2, %5 offset:1024\n\t"
-        "s_mov_b64 %0, exec\n\ts_mov_b64 exec, 0xff\n\t"
-        "global_load_lds_dwordx4 %3, %6 offset:%8\n\t"
-        "s_mov_b64 exec, %0"
-        : "=&s"(keep) : "v"(off0), "v"(off1), "v"(off_rec), "s"(x), "s"(x_m1k), "s"(sx_m), "s"(dst_s), "n"(8 * RB)
-        : "memory", "m0");
-  } else {
-    asm volatile(
-        "s_mov_b32 m0, %5\n\ts_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, %3\n\t"
-        "s_mov_b64 %0, exec\n\ts_mov_b64 exec, 0xff\n\t"
-        "global_load_lds_dwordx4 %2, %4 offset:%6\n\t"
-        "s_mov_b64 exec, %0"
-        : "=&s"(keep) : "v"(off0), "v"(off_rec), "s"(x), "s"(sx_m), "s"(dst_s), "n"(8 * RB)
-        : "memory", "m0");
-  }
-}
-__device__ __forceinline__ void ring_dma4(const void* base, unsigned off, unsigned dst_s) {
-  unsigned keep;
-  asm volatile(
-      "s_waitcnt lgkmcnt(0)\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-      "global_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
-      : "=&s"(keep) : "v"(off), "s"(base), "s"(dst_s) : "memory");
-}
-__device__ __forceinline__ void wait_vm_any(int n) {   // n is wave uniform
-  switch (n) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1: asm volatile("s_waitcnt vmcnt(1)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); break;
-    case 5: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-    case 6: asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); break;
-    case 7: asm volatile("s_waitcnt vmcnt(7)" ::: "memory"); break;
-    case 8: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-    case 9: asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); break;
-    case 10: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-    case 11: asm volatile("s_waitcnt vmcnt(11)" ::: "memory"); break;
-    case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;
-    case 13: asm volatile("s_waitcnt vmcnt(13)" ::: "memory"); break;
-    case 14: asm volatile("s_waitcnt vmcnt(14)" ::: "memory"); break;
-    case 15: asm volatile("s_waitcnt vmcnt(15)" ::: "memory"); break;
-    case 16: asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); break;
-    case 17: asm volatile("s_waitcnt vmcnt(17)" ::: "memory"); break;
-    case 18: asm volatile("s_waitcnt vmcnt(18)" ::: "memory"); break;
-    case 19: asm volatile("s_waitcnt vmcnt(19)" ::: "memory"); break;
-    case 20: asm volatile("s_waitcnt vmcnt(20)" ::: "memory"); break;
-    case 21: asm volatile("s_waitcnt vmcnt(21)" ::: "memory"); break;
-    case 22: asm volatile("s_waitcnt vmcnt(22)" ::: "memory"); break;
-    case 23: asm volatile("s_waitcnt vmcnt(23)" ::: "memory"); break;
-    case 24: asm volatile("s_waitcnt vmcnt(24)" ::: "memory"); break;
-    case 25: asm volatile("s_waitcnt vmcnt(25)" ::: "memory"); break;
-    case 26: asm volatile("s_waitcnt vmcnt(26)" ::: "memory"); break;
-    case 27: asm volatile("s_waitcnt vmcnt(27)" ::: "memory"); break;
-    case 28: asm volatile("s_waitcnt vmcnt(28)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-  }
-}
+// the ring's counted wait: n = DPI * (items that may stay in flight, <= NS - 2) is wave uniform
+#define KP_RING_COUNTS(W)                                                                                      \
+  W(0) W(1) W(2) W(3) W(4) W(5) W(6) W(7) W(8) W(9) W(10) W(11) W(12) W(13) W(14) W(15) W(16) W(17) W(18) W(19) \
+  W(20) W(21) W(22) W(23) W(24) W(25) W(26) W(27) W(28)
+SPR_DEFINE_WAIT_VM_ANY(wait_vm_ring, KP_RING_COUNTS)
 
 template <int CC, int COUT, int NS>
 struct RingShape {
@@ -947,7 +843,7 @@ __global__ __launch_bounds__(512, (RingShape<CC, COUT, NS>::MINW)) void k_kpconv
       for (int e = 0; e < 8; ++e) { bh[k][e] = (_Float16)0.f; bl[k][e] = (_Float16)0.f; }
     }
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // everything the compiler issued so far has landed
+  wait_vm<0>();   // everything the compiler issued so far has landed
 
   // ---- per-wave item stream ------------------------------------------------------------------
   // Index rows of a tile, staged by LDS-DMA into idxbuf[par]: query A's row at int 0, query B's row
@@ -963,8 +859,8 @@ __global__ __launch_bounds__(512, (RingShape<CC, COUT, NS>::MINW)) void k_kpconv
         const int k = h + lane;
         const unsigned dst = __builtin_amdgcn_readfirstlane(idx_s + (par * idxb + (sel ? 8 * d.z : 0) + h) * 4);
         // two masked instructions, each with a uniform base; both write dst + 4 * lane
-        if (q >= 0 && k < kmax) ring_dma4(nbr, (unsigned)(((size_t)q * nbr_stride + k) * 4), dst);
-        else ring_dma4(pad_word, 0u, dst);
+        if (q >= 0 && k < kmax) lds_dma4(nbr, (unsigned)(((size_t)q * nbr_stride + k) * 4), dst);
+        else lds_dma4(pad_word, 0u, dst);
       }
     }
   };
@@ -980,36 +876,18 @@ __global__ __launch_bounds__(512, (RingShape<CC, COUT, NS>::MINW)) void k_kpconv
     r.rec = *reinterpret_cast<const unsigned*>(base + a_idc);
     return r;
   };
-  // No LDS wait in front of these DMAs: a slot is refilled only after the item that lived in it has
-  // been moved to registers and its first influence computed, and the LDS retires a wave's reads in
-  // order, hundreds of cycles before a DMA can return.
   const unsigned a_dma = (lane % LPR) * 16;
   auto issue_ids = [&](unsigned slot_off, const Ids& ids) {
-#ifdef SPR_KP_ABL_NODMA
-    return;
-#endif
     const unsigned slot = __builtin_amdgcn_readfirstlane(ring_s + slot_off);
-#ifndef SPR_KP_RING_NO_LGKM
-    // Every ds_read of the slot's previous item has RETURNED before the refill is issued (the
-    // ordering used to rest on timing alone -- the LDS retires a wave's reads in order, hundreds of cycles before
-    // a DMA can land -- which no ISA rule guarantees).  A/B against -DSPR_KP_RING_NO_LGKM: scripts/kp_lgkm_ab.sh.
+    // Every ds_read of the slot's previous item has RETURNED before the refill is issued (the ordering used to rest
+    // on timing alone -- the LDS retires a wave's reads in order, hundreds of cycles before a DMA can land -- which
+    // no ISA rule guarantees; the wait costs nothing measurable: DESIGN.md).
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
-#ifdef SPR_KP_ITEM_DMA_OLD
-#pragma unroll
-    for (int pc = 0; pc < PPI; ++pc) {
-      const unsigned rid = min(ids.row[pc], (unsigned)(ns - 1));   // shadow slots fetch a real (finite) row
-      ring_dma16_m0(x, rid * RB + a_dma, slot + pc * 1024);
-    }
-    ring_dma16_rec8(sxf, min(ids.rec, (unsigned)ns) * 16, slot + 8 * RB);   // record ns = the shadow record
-#else
-    static_assert(PPI == 1 || PPI == 2, "ring item: one or two row pieces");
     const unsigned o0 = min(ids.row[0], (unsigned)(ns - 1)) * RB + a_dma;      // shadow slots fetch a real (finite) row
     const unsigned o1 = min(ids.row[PPI - 1], (unsigned)(ns - 1)) * RB + a_dma;
     const unsigned orec = min(ids.rec, (unsigned)ns) * 16;                       // record ns = the shadow record
-    ring_item_dma<PPI, RB>(x, reinterpret_cast<const char*>(x) - 1024, reinterpret_cast<const char*>(sxf) - 8 * RB, o0, o1,
-                           orec, slot);
-#endif
+    lds_dma_ring_item<PPI, RB>(x, reinterpret_cast<const char*>(x) - 1024, reinterpret_cast<const char*>(sxf) - 8 * RB, o0,
+                               o1, orec, slot);
   };
   // first min(NS, n) items of a tile: all ids first, then all gathers
   auto prime = [&](const int4 d, int par) {
@@ -1022,9 +900,6 @@ __global__ __launch_bounds__(512, (RingShape<CC, COUT, NS>::MINW)) void k_kpconv
       if (i < n) issue_ids(i * SLOT, ids[i]);
   };
 
-#ifdef SPR_KP_PRIO
-  if (wave >= 4) __builtin_amdgcn_s_setprio(1);   // the later-dispatched half loses every issue arbitration otherwise
-#endif
   // Tile walk: tiles are handed out by one device-wide counter (zeroed by k_rowflag ahead of this
   // launch) instead of blockIdx + k * gridDim.  The kernel shares the chip with the pyramid builder and
   // the shortcut branches of the same forward (other HIP streams): a workgroup that becomes resident
@@ -1045,7 +920,7 @@ __global__ __launch_bounds__(512, (RingShape<CC, COUT, NS>::MINW)) void k_kpconv
   if (tile_nxt < ntiles) d_nxt = desc[(size_t)tile_nxt * 8 + wave];
   if (tile < ntiles) {
     stage_idx(d_cur, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     if (tile_nxt < ntiles) stage_idx(d_nxt, 1);
     prime(d_cur, 0);
   }
@@ -1099,12 +974,12 @@ __global__ __launch_bounds__(512, (RingShape<CC, COUT, NS>::MINW)) void k_kpconv
     // register set is ever copied, and the gathers of items i + 2 .. i + NS - 1 stay in flight.
     auto wait_item = [&](int i) {   // item i has landed: at most the younger items may be outstanding
       const int younger = n_items - 1 - i;
-      if (younger >= NS - 2) wait_vm_any(DPI * (NS - 2));
-      else wait_vm_any(DPI * max(younger, 0));
+      if (younger >= NS - 2) wait_vm_ring(DPI * (NS - 2));
+      else wait_vm_ring(DPI * max(younger, 0));
     };
     KStep R0, R1;
     if (n_items == 0) {
-      wait_vm_any(0);
+      wait_vm_ring(0);
     } else {
       wait_item(0);
       R0 = ld_kstep(0, 0);
@@ -1157,13 +1032,8 @@ __global__ __launch_bounds__(512, (RingShape<CC, COUT, NS>::MINW)) void k_kpconv
         const float dx = (R0.rec.x - qx) - kx, dy = (R0.rec.y - qy) - ky, dz = (R0.rec.z - qz) - kz;
         const float w = fmaxf(0.f, 1.f - __builtin_amdgcn_sqrtf(dx * dx + dy * dy + dz * dz) * inv_extent);
         cnt += __float_as_int(R0.rec.w);
-#ifndef SPR_KP_ABL_NOMFMA1
 #pragma unroll
         for (int t = 0; t < NTC; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w, R0.xv[t], acc[t], 0, 0, 0);
-#else
-#pragma unroll
-        for (int t = 0; t < NTC; ++t) acc[t][0] += w * R0.xv[t];
-#endif
       }
       wait_item(i + 1);                   // (the last item of the tile: everything has landed)
       R0 = ld_kstep(nslot, 0);
@@ -1173,13 +1043,8 @@ __global__ __launch_bounds__(512, (RingShape<CC, COUT, NS>::MINW)) void k_kpconv
         const float dx = (R1.rec.x - qx) - kx, dy = (R1.rec.y - qy) - ky, dz = (R1.rec.z - qz) - kz;
         const float w = fmaxf(0.f, 1.f - __builtin_amdgcn_sqrtf(dx * dx + dy * dy + dz * dz) * inv_extent);
         cnt += __float_as_int(R1.rec.w);
-#ifndef SPR_KP_ABL_NOMFMA1
 #pragma unroll
         for (int t = 0; t < NTC; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(w, R1.xv[t], acc[t], 0, 0, 0);
-#else
-#pragma unroll
-        for (int t = 0; t < NTC; ++t) acc[t][0] += w * R1.xv[t];
-#endif
       }
       R1 = ld_kstep(nslot, 1);
       ids_next = load_ids(par, i + NS + 1);   // (past the tile's last item: unused ints of the buffer)
@@ -1225,9 +1090,6 @@ __global__ __launch_bounds__(512, (RingShape<CC, COUT, NS>::MINW)) void k_kpconv
     {
       const _Float16* ah_row = wfh + p16 * SH + 8 * j4;
       const _Float16* al_row = wfl + p16 * SH + 8 * j4;
-#ifdef SPR_KP_ABL_NOP2
-      if (ntiles < 0)
-#endif
 #pragma unroll
       for (int k = 0; k < KSW; ++k) {
         const int ks = min(ks0 + k, KS - 1);            // a slice short of KSW steps meets zero weights
@@ -1268,7 +1130,7 @@ __global__ __launch_bounds__(512, (RingShape<CC, COUT, NS>::MINW)) void k_kpconv
     tile_nn = __builtin_amdgcn_readfirstlane(ltile[1 + par]);   // published before barrier 1 of this tile
   }
   if (sp == 0) flush_pending();
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vm<0>();
 #ifdef SPR_KP_RING_PROF
   if (blockIdx.x == 0) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1488,7 +1350,7 @@ extern "C" int spr_kpconv_fwd(const float* q_xyz, int nq, const float* s_xyz, in
 #define SPR_RING_ARGS                                                                                       \
   q_xyz, nq, ns, nbr, nbr_stride, kmax, x, wh, wl, kernel_points, inv_extent, sxf, desc, pad_word, xp, wp, \
       n_xp, n_wp, tile_ctr, out, stream
-      if (cin == 64 && cout == 64) return launch_ring<64, 64, SPR_KP_NS64>(SPR_RING_ARGS);
+      if (cin == 64 && cout == 64) return launch_ring<64, 64, 4>(SPR_RING_ARGS);
       if (cin == 64 && cout == 32) return launch_ring<64, 32, 4>(SPR_RING_ARGS);
       if (cin == 32 && cout == 32) return launch_ring<32, 32, 3>(SPR_RING_ARGS);
       if (cin == 32 && cout == 64) return launch_ring<32, 64, 8>(SPR_RING_ARGS);

@@ -22,6 +22,7 @@
 #include <atomic>
 
 #include "attn_planes.h"
+#include "lds_dma.h"
 #include "spr_common.h"
 
 namespace spr {
@@ -116,7 +117,7 @@ __global__ __launch_bounds__(WM* WN * 64) void k_gemm_nt(
     }
   };
   auto store_slab = [&]() {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int i = 0; i < A_PT; ++i) {
@@ -168,7 +169,7 @@ __global__ __launch_bounds__(WM* WN * 64) void k_gemm_nt(
     __builtin_amdgcn_sched_barrier(0);
     __syncthreads();
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vm<0>();
   const int col = n0 + wn * 32 + l31;
   const float bv = (bias && col < N) ? bias[col] : 0.f;
   store_tile<ACT, RES>(acc, m0 + wm * 32, col, M, N, bv, residual, out, lh);
@@ -288,7 +289,7 @@ __global__ __launch_bounds__(WM* WN * 64) void k_gemm_nt_h3(
     *reinterpret_cast<u32x2*>(lo) = (u32x2){l0, l1};
   };
   auto store_slab = [&]() {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int i = 0; i < A_PT; ++i) {
@@ -347,7 +348,7 @@ __global__ __launch_bounds__(WM* WN * 64) void k_gemm_nt_h3(
     __builtin_amdgcn_sched_barrier(0);
     __syncthreads();
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vm<0>();
   if (PLANES) {
     // ---- attention operand planes (attn_planes.h) straight from the accumulators ----
     // accumulator (i, j): lane column = token m0 + (wm TM + i) 32 + l31, register r = feature
@@ -581,8 +582,8 @@ __global__ __launch_bounds__(512) void k_gemm_nt_h3p(
     auto slab = [&](auto stag) {
       constexpr int S = decltype(stag)::value;
       // operand slab S was prefetched one iteration ago; the 8 stores issued after it may stay in flight
-      if (young) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (young) wait_vm<8>();
+      else wait_vm<0>();
       __builtin_amdgcn_sched_barrier(0);
       store_slab();
       __syncthreads();

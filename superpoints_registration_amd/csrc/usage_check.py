@@ -1,10 +1,10 @@
-"""Build check for xenc.hip (csrc/Makefile): no scratch and no SGPR spills in the fused chains.
+"""Build check (csrc/Makefile) for every kernel that issues LDS-DMA (lds_dma.h): no scratch and no SGPR spills.
 
 Reads the compiler's -Rpass-analysis=kernel-resource-usage remarks (a text file) and fails if any kernel whose
 name contains NAME reports `ScratchSize [bytes/lane]` != 0 or `SGPRs Spill` != 0, or if fewer than COUNT such
 kernels are found (a renamed kernel must not pass by not being looked at).
 
-    python3 xenc_usage_check.py build/xenc.usage.txt k_xenc_chain 5
+    python3 usage_check.py build/xenc.usage.txt k_xenc_chain 5
 """
 import re
 import sys
@@ -61,8 +61,9 @@ def main(argv):
         return 1
     if bad:
         print(f"error: {name}: scratch memory or SGPR spills in {len(bad)} instantiation(s) (see above and {path}).\n"
-              "  The weight ring of these kernels is counted by hand; every scratch reload drains it (vmcnt(0)).\n"
-              "  Shorten live ranges (xenc.hip, \"Arguments\") until the compiler reports 0 for both.", file=sys.stderr)
+              "  These kernels issue LDS-DMA from scalar operands and count its waits by hand (lds_dma.h): a spilled\n"
+              "  SGPR next to those operands is unsafe, and every scratch reload drains the queue (vmcnt(0)).\n"
+              "  Shorten live ranges until the compiler reports 0 for both.", file=sys.stderr)
         return 1
     return 0
 

@@ -52,6 +52,7 @@
 #include <vector>
 
 #include "attn_planes.h"
+#include "lds_dma.h"
 #include "spr_common.h"
 
 namespace spr {
@@ -63,7 +64,6 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 constexpr int XD = 256;            // d_model
 constexpr int XCHUNK = 32768;      // bytes per weight chunk (32 fragments of 1 KiB)
 constexpr int XSLOTS = 4;          // ring depth (chunks)
-constexpr int XAHEAD = 2;          // an acquire of chunk g (at step 8 of chunk g - 1) issues chunk g + XAHEAD
 constexpr int XDMA = 8;            // LDS-DMA instructions per wave and chunk (32 KiB / 4 waves / 1 KiB)
 constexpr int XTOK = 128;          // tokens per workgroup tile
 
@@ -111,38 +111,6 @@ __device__ __forceinline__ ChainArgsP opaque_s(ChainArgsP p) {
   return p;
 }
 
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void wait_vm_any(int n) {   // n wave uniform, a multiple of 4 in 0..60
-#define SPR_W(k) case k: wait_vm<k>(); break;
-  switch (n) {
-    SPR_W(4) SPR_W(8) SPR_W(12) SPR_W(16) SPR_W(20) SPR_W(24) SPR_W(28) SPR_W(32) SPR_W(36) SPR_W(40) SPR_W(44)
-    SPR_W(48) SPR_W(52) SPR_W(56) SPR_W(60)
-    default: wait_vm<0>(); break;
-  }
-#undef SPR_W
-}
-
-// LDS-DMA: 16 bytes per lane from base + off (per-lane byte offset) to LDS at M0 + offset + 16 * lane.
-// Four 1-KiB pieces behind ONE M0 / address setup: the instruction's immediate offset moves the global AND the LDS
-// address, so piece q of a 4-KiB group is the same instruction with offset q KiB.
-// dma_first() is piece 0 of a group: it loads M0, spends the wait state an LDS-DMA needs behind an M0 write and issues
-// the piece in ONE statement, so nothing can come between the M0 write and its first use.  dma_q<Q>() (Q = 1 .. 3) are
-// the bare instruction and name M0 as clobbered: they rely on nothing having written M0 since the group's dma_first()
-// (the chunk loops hold no instruction that uses M0: LDS instructions of this architecture do not, and the kernel is
-// built -- and checked at build time, csrc/Makefile -- without SGPR spills, whose lane writes could).
-// `base` is the weight stream's address as a wave-uniform 64-bit value (k_xenc_chain builds it from two
-// readfirstlane results, so it is an SGPR pair by construction and never a value the compiler reloads from a lane).
-__device__ __forceinline__ void dma_first(unsigned long long base, unsigned off, unsigned dst_s) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-               : : "v"(off), "s"(base), "s"(dst_s) : "memory", "m0");
-}
-template <int Q>
-__device__ __forceinline__ void dma_q(unsigned long long base, unsigned off) {
-  asm volatile("global_load_lds_dwordx4 %0, %1 offset:%2" : : "v"(off), "s"(base), "n"(Q * 1024) : "memory", "m0");
-}
 // (the trailing s_nop keeps the compiler's next instruction from overwriting the data registers of a
 // wide store before it has read them)
 __device__ __forceinline__ void store16(void* p, const u32x4& v) {
@@ -278,11 +246,8 @@ __device__ __forceinline__ f32x16 ln_block(const f32x16& v, int b, int h, float 
 // steps ahead through a ring of four register pairs carried from chunk to chunk: the last three steps of a
 // chunk read the first fragments of the NEXT chunk, which is acquired (counted DMA wait + barrier) at step 8.
 #define XSB() __builtin_amdgcn_sched_barrier(0)
-#ifndef SPR_XENC_PF
-#define SPR_XENC_PF 3            // fragment reads run this many steps ahead of their MFMAs
-#endif
-constexpr int XPF = SPR_XENC_PF;
-constexpr int XRING = XPF < 4 ? 4 : 8;     // register pairs of the fragment ring (a power of two > XPF)
+constexpr int XPF = 3;           // fragment reads run this many steps ahead of their MFMAs
+constexpr int XRING = 4;         // register pairs of the fragment ring (a power of two > XPF)
 struct Carry {
   f16x8 h[XRING], l[XRING];
 };
@@ -367,7 +332,8 @@ __global__ __launch_bounds__(256, 1) void k_xenc_chain(ChainArgs args_by_value) 
   __shared__ int s_tile[2];
   int nch, nseg, ntiles;
   int *cu_s, *tf_s;
-  unsigned long long w_s;              // the weight stream: chunks of XCHUNK bytes in consumption order
+  const void* w_s;                     // the weight stream: chunks of XCHUNK bytes in consumption order; an SGPR pair by
+                                       // construction (two readfirstlane results), never a value reloaded from a lane
   {
     const ChainArgsP k = ka;
     const int nf = k->c.nf, d_ff = 32 * nf;
@@ -376,8 +342,8 @@ __global__ __launch_bounds__(256, 1) void k_xenc_chain(ChainArgs args_by_value) 
     tf_s = cu_s + nseg + 1;                                        // tiles in front of every segment [nseg + 1]
     nch = (HEAD ? 8 : 0) + (FFN ? 2 * nf : 0) + (TAIL == 2 ? 24 : 0);   // chunks per tile
     const unsigned long long w = (unsigned long long)(uintptr_t)k->c.w;
-    w_s = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(w >> 32)) << 32) |
-          (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)w);
+    w_s = reinterpret_cast<const void*>(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(w >> 32)) << 32) |
+                                        (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)w));
     // ---- parameter tables and cu_seqlens into LDS (the steady state reads its operands from LDS only) ----
     const float *bo = k->c.bo, *b1 = k->c.b1, *b2 = k->c.b2, *bin = k->c.bin, *g_mid = k->c.g_mid, *b_mid = k->c.b_mid,
                 *g_tail = k->c.g_tail, *b_tail = k->c.b_tail;
@@ -419,20 +385,20 @@ __global__ __launch_bounds__(256, 1) void k_xenc_chain(ChainArgs args_by_value) 
     if (++i_slot == XSLOTS) i_slot = 0;
   };
   // piece j of the armed chunk (j is a constant after unrolling): pieces 0 and 4 set M0 for their group of four
-  // (dma_first), the others are ONE instruction
+  // (lds_dma16_first), the others are ONE instruction (lds_dma.h; the chunk loops hold nothing that writes M0)
   auto piece = [&](int j) __attribute__((always_inline)) {
 #ifdef SPR_XENC_STAMP
     if (stamp_on & 2) return;             // ablation: no weight DMA (garbage results)
 #endif
     switch (j) {
-      case 0: dma_first(w_s, dma_off, dma_dst); break;
-      case 1: dma_q<1>(w_s, dma_off); break;
-      case 2: dma_q<2>(w_s, dma_off); break;
-      case 3: dma_q<3>(w_s, dma_off); break;
-      case 4: dma_first(w_s, dma_off4, dma_dst + 4096); break;
-      case 5: dma_q<1>(w_s, dma_off4); break;
-      case 6: dma_q<2>(w_s, dma_off4); break;
-      default: dma_q<3>(w_s, dma_off4); break;
+      case 0: lds_dma16_first(w_s, dma_off, dma_dst); break;
+      case 1: lds_dma16_more<1>(w_s, dma_off); break;
+      case 2: lds_dma16_more<2>(w_s, dma_off); break;
+      case 3: lds_dma16_more<3>(w_s, dma_off); break;
+      case 4: lds_dma16_first(w_s, dma_off4, dma_dst + 4096); break;
+      case 5: lds_dma16_more<1>(w_s, dma_off4); break;
+      case 6: lds_dma16_more<2>(w_s, dma_off4); break;
+      default: lds_dma16_more<3>(w_s, dma_off4); break;
     }
   };
   auto acquire = [&]() __attribute__((always_inline)) -> const unsigned char* {
@@ -470,11 +436,13 @@ __global__ __launch_bounds__(256, 1) void k_xenc_chain(ChainArgs args_by_value) 
   a_slot = 1;
 #pragma unroll
   for (int i = 0; i < XPF; ++i) frag_ld(slot, lane, i, cy.h[i], cy.l[i]);
+#ifdef SPR_XENC_STAMP
+  int stamp_it = 0;
+  int step_stamp = -1;       // >= 0 = stamp every step of the next chunk at step_stamp + i
+#endif
   // chunk with accumulator `acc`, activation planes xh / xl (one fragment per step), side slices side(0..31).
   // SWAP = false: acc[feature][token] (weights are the A operand); true: acc[token][feature] (activations are the A
   // operand: the lane is a FEATURE and holds 16 tokens -- the V blocks, whose planes are stored transposed)
-  int stamp_it = 0;
-  int step_stamp = -1;       // diagnostic build: >= 0 = stamp every step of the next chunk at step_stamp + i
   auto chunk_f = [&](auto swap_tag, f32x16& acc, const f16x8 (&xh)[16], const f16x8 (&xl)[16], auto&& side)
       __attribute__((always_inline)) {
     constexpr bool SW = decltype(swap_tag)::value;
@@ -552,7 +520,9 @@ __global__ __launch_bounds__(256, 1) void k_xenc_chain(ChainArgs args_by_value) 
 
 #pragma unroll 1
   for (int it = 0; tile < ntiles; ++it) {
+#ifdef SPR_XENC_STAMP
     stamp_it = it;
+#endif
     if (tid == 0) s_tile[(it + 1) & 1] = atomicAdd(args()->tile_ctr, 1);   // the next tile (read at the end of this one)
     // Tiles never straddle a segment (cloud): tile = (segment, 128-token slice of it).  A wave's 32 tokens then sit in
     // 32 consecutive, 32-byte aligned columns of the transposed V planes (one segment, vstart is a multiple of 16).
