@@ -935,6 +935,45 @@ int spr_pair_gather(const float* x, int t_in, int c, const int* cu, int n_clouds
                     const int* src_idx, const int* tgt_idx, int npairs, const int* cu_out,
                     int t_out, float* y, void* stream);
 
+/* ---- training over shared clouds: the pair assembly's backward and the labels in pair layout ------
+ * RegTR.forward on a batch of clouds and pairs (shared_clouds.py): a cloud is encoded once per step,
+ * with gradients, and used by any number of the step's pairs.
+ *
+ * spr_pair_gather_bwd: gx [t_in, c] from gy [t_out, c], the backward of spr_pair_gather (same cu
+ *   [n_clouds + 1], cu_out [2 * npairs + 1], t_in, t_out, c).  The segments that copied a cloud come as
+ *   a use list in CSR form: use_seg[use_ptr[k] .. use_ptr[k + 1]) are the output segments (0 ..
+ *   2 * npairs - 1) that are copies of cloud k, in ascending order; use_ptr [n_clouds + 1], use_seg
+ *   [2 * npairs], both built on the host.  Row i of cloud k (input row cu[k] + i) is the sum over k's
+ *   uses s, in the stored order, of gy row cu_out[s] + i, accumulated in registers and stored once: a
+ *   fixed order whatever the launch geometry, no atomics.  EVERY row of gx is written (the caller
+ *   clears nothing): rows of a cloud without uses, and rows behind cu[n_clouds], are zeros.  A use whose
+ *   segment is shorter than its cloud contributes zeros for the rows it lacks, a segment index outside
+ *   [0, 2 * npairs) contributes nothing, use_ptr entries are clamped to [0, 2 * npairs]: zeros, never
+ *   foreign memory.  16-byte accesses when c % 4 == 0 and gy, gx are 16-byte aligned, 4-byte otherwise.
+ *
+ * spr_overlap_pool_pairs: one level of compute_overlaps (spr_overlap_pool below; backbone_kpconv/
+ *   kpconv.py:552-578) for labels in PAIR layout over a pool matrix in CLOUD layout.  ov_prev [n_prev]:
+ *   the previous level's values, segment after segment (cu_out_prev [2 * npairs + 1]); pool
+ *   [n_pool_rows, w] with row stride pool_stride: the encode call's pool matrix of this level, whose
+ *   entries index the previous level's rows of all clouds (cu_prev [n_clouds + 1]) and whose rows are
+ *   this level's rows of all clouds (cu_cur [n_clouds + 1]); seg_cloud [2 * npairs]: the cloud each
+ *   segment copies; out [nq], segment after segment (cu_out_cur [2 * npairs + 1]).  Output row r of
+ *   segment s, a copy of cloud k, reads pool row cu_cur[k] + (r - cu_out_cur[s]); an entry id counts
+ *   when cu_prev[k] <= id < cu_prev[k + 1] and then reads ov_prev[cu_out_prev[s] + id - cu_prev[k]].
+ *   out[r] = clamp(sum / count, 0, 1) with the columns in ascending order and 0 / 0 = NaN: the
+ *   arithmetic of spr_overlap_pool, bit for bit.  Nothing outside the segment's own labels is read: a
+ *   cloud index outside [0, n_clouds), a pool row outside the cloud's, a label outside the segment's
+ *   (or outside ov_prev) does not count, and a row left without a counted entry is NaN like a row of
+ *   shadow entries.  No workspace.
+ */
+int spr_pair_gather_bwd(const float* gy, int t_out, int c, const int* cu, int n_clouds,
+                        const int* use_ptr, const int* use_seg, int npairs, const int* cu_out,
+                        int t_in, float* gx, void* stream);
+int spr_overlap_pool_pairs(const float* ov_prev, int n_prev, const int* pool, int pool_stride, int w,
+                           int n_pool_rows, const int* cu_prev, const int* cu_cur, int n_clouds,
+                           const int* seg_cloud, int npairs, const int* cu_out_prev,
+                           const int* cu_out_cur, int nq, float* out, void* stream);
+
 /* ---- losses (forward) of RegTR.compute_loss -- SURVEY 8f row 1 --------------
  * models/qk_regtr_full.py:313-368.  Deterministic reductions (fixed partition,
  * float64 accumulation).  Scalars are written to device memory (out[0]).

@@ -132,6 +132,8 @@ SIGNATURES = {
     "spr_sum_scaled": (_i, [_vp, _i, _f, _vp, _vp]),
     "spr_gather_rows": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp]),
     "spr_pair_gather": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp]),
+    "spr_pair_gather_bwd": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp]),
+    "spr_overlap_pool_pairs": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp]),
     "spr_bgemm": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _l, _l, _l, _l, _l, _l, _f, _f, _vp]),
     "spr_tn_product_split_workspace_bytes": (_sz, []),
     "spr_tn_product_split": (_i, [_vp, _vp, _l, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _sz, _vp]),

@@ -20,7 +20,9 @@ Differences by design (documented in DESIGN.md):
   * training: with gradients enabled every operator runs through its explicit HIP backward
     (autograd.py), so `compute_loss(model(batch), batch)['total'].backward()` fills the
     same parameter gradients as the reference's training_step (generic_reg_model.py:82-84);
-    under torch.no_grad() the forward is the plain inference path.
+    under torch.no_grad() the forward is the plain inference path;
+  * a batch may hold `clouds` and `pairs` (indices into the clouds) instead of `src_xyz` / `tgt_xyz`: every cloud is
+    then encoded once for all the pairs that use it, in training as well (shared_clouds.py).
 """
 import os
 
@@ -28,7 +30,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _concurrency, ops
+from . import _concurrency, ops, shared_clouds
 from .kpconv import NEIGHBOR_SELECT, KPFEncoder, Preprocessor
 from .transformers import (PositionEmbeddingCoordsSine, PositionEmbeddingLearned, TransformerCrossEncoder,
                            TransformerCrossEncoderLayer, make_segments)
@@ -160,19 +162,46 @@ class RegTR(nn.Module):
     def forward(self, batch):
         """model.train() + gradients enabled: differentiable (HIP backward, autograd.py).
         model.eval() (the reference's test loop, trainer.py:216-260) or torch.no_grad():
-        the inference path -- fused in-projection, no tape, nothing saved."""
+        the inference path -- fused in-projection, no tape, nothing saved.
+        batch: `src_xyz` / `tgt_xyz` lists, or `clouds` and `pairs` (shared_clouds.py): every cloud is encoded once
+        and used by any number of the batch's pairs, in training as well."""
+        shared = None
+        if 'clouds' in batch:
+            shared = shared_clouds.check_batch(batch)       # raises on the host, before any launch
         if not self.training and torch.is_grad_enabled():
             with torch.no_grad():
-                return self._forward(batch)
+                return self._forward(batch, shared)
         if self.training and torch.is_grad_enabled():
             ops.prime_weight_ranges(self.parameters())      # one measuring launch for every weight the step moved
-        return self._forward(batch)
+        return self._forward(batch, shared)
 
-    def _forward(self, batch):
+    def _forward(self, batch, shared=None):
+        if shared is not None:
+            return self._forward_shared(batch, *shared)
         B = len(batch['src_xyz'])
         tokens, xyz_c, lens_c, meta = self._encode(list(batch['src_xyz']) + list(batch['tgt_xyz']))
         batch['kpconv_meta'] = meta                      # qk_regtr_full.py:153
         return self._register(tokens, xyz_c, lens_c[:B], lens_c[B:], pair_keys=batch.get('pair_key'))
+
+    def _forward_shared(self, batch, clouds, src, tgt):
+        """forward() on a batch of clouds and pairs: _encode once over the clouds (on the tape when training), tokens
+        and points laid out per pair by the pair gather (differentiable over the tokens; the points carry no
+        gradient), then the unchanged _register.  Leaves in the batch what compute_loss, overlap.label_batch and
+        training.compute_metrics read: the encode call's kpconv_meta, the per-pair views of the clouds as src_xyz /
+        tgt_xyz (the cloud tensors themselves) and the pair layout under '_pair_layout'."""
+        tokens, xyz_c, _, meta = self._encode(clouds)
+        batch['kpconv_meta'] = meta
+        layout = shared_clouds.PairLayout(src, tgt, meta['_lens_host'], tokens.device)   # host lengths: no read-back
+        batch['_pair_layout'] = layout
+        batch['src_xyz'], batch['tgt_xyz'] = shared_clouds.pair_views(batch)
+        P = len(src)
+        cu = meta['_cu'][len(meta['points']) - 1]
+        src_lens, tgt_lens = layout.seg_lens[-1][:P], layout.seg_lens[-1][P:]
+        segments = make_segments(src_lens, tgt_lens, tokens.device)
+        tok = shared_clouds.pair_gather(tokens, cu, layout)
+        with torch.no_grad():
+            xyz = shared_clouds.pair_gather(xyz_c, cu, layout)
+        return self._register(tok, xyz, src_lens, tgt_lens, segments, batch.get('pair_key'))
 
     def _encode(self, clouds):
         """The per-cloud half of the forward: pyramid, KPConv encoder, feat_proj.  Nothing here looks across clouds.
@@ -383,10 +412,15 @@ class RegTR(nn.Module):
         # compute_overlaps (kpconv.py:552-578): average the per-point masks up the pyramid
         with torch.no_grad():   # ground-truth side: no gradient
             ov = torch.cat([o.to(device) for o in list(batch['src_overlap']) + list(batch['tgt_overlap'])]).float()
-            pyr = {'pyr_0': ov}
-            for p in range(1, len(meta['points'])):
-                ov = ops.overlap_pool(ov, meta['_i32'][('pools', p - 1)], meta['points'][p - 1].shape[0])
-                pyr[f'pyr_{p}'] = ov
+            layout = batch.get('_pair_layout') if 'clouds' in batch else None
+            if layout is not None:   # a batch of clouds and pairs: the pools index the cloud layout, the masks are per pair
+                pyr = shared_clouds.overlap_pyramid(ov, meta, layout)
+                ov = pyr[f"pyr_{len(meta['points']) - 1}"]
+            else:
+                pyr = {'pyr_0': ov}
+                for p in range(1, len(meta['points'])):
+                    ov = ops.overlap_pool(ov, meta['_i32'][('pools', p - 1)], meta['points'][p - 1].shape[0])
+                    pyr[f'pyr_{p}'] = ov
             batch['overlap_pyr'] = pyr
 
         # overlap loss: the (already sigmoided) predictions go through BCEWithLogits (:248, :329)

@@ -35,6 +35,7 @@ from typing import Callable, Dict, Iterable, List, Optional
 
 import torch
 
+from . import shared_clouds
 from .augment import TrainAugmentation
 from .overlap import label_batch
 from .se3 import se3_compare
@@ -358,9 +359,10 @@ class CheckpointManager:
 class Trainer:
     """fit() / validate() with the reference's step order.  `batches` are dicts as produced by the
     reference's collate_pair (src_xyz / tgt_xyz lists, pose, src_overlap / tgt_overlap) already on
-    the device; data loading itself is out of the hot-path scope.  augment=True applies the reference's training
-    augmentation (augment.py: cfg.perturb_pose, cfg.augment_noise, shuffle, swap) to every training batch on the
-    device, with draws keyed on (seed, global_step, rank, position in the batch); validate() never augments."""
+    the device, or the cloud / pair form of shared_clouds.py (`clouds`, `pairs`, pose: a cloud encoded once per step for
+    all the pairs that use it; not with augment=True); data loading itself is out of the hot-path scope.  augment=True
+    applies the reference's training augmentation (augment.py: cfg.perturb_pose, cfg.augment_noise, shuffle, swap) to
+    every training batch on the device, with draws keyed on (seed, global_step, rank, position in the batch); validate() never augments."""
 
     def __init__(self, cfg, ckpt_dir: Optional[str] = None, grad_clip: Optional[float] = None, rank: int = 0,
                  world: int = 1, process_group=None, bucket_bytes: int = 16 << 20, augment: bool = False,
@@ -387,8 +389,17 @@ class Trainer:
     def _ensure_labels(self, batch) -> None:
         """A batch of clouds and poses that comes without ground-truth overlap masks (all a dataset gives) is
         labelled on the device; the reference's loaders do this per pair on the CPU (threedmatch.py:78-84).
+        A batch of `clouds` and `pairs` (shared_clouds.py) is labelled per pair on the per-pair views of its clouds.
         Batches of another shape (a stand-in model's) pass through untouched."""
-        if 'src_overlap' not in batch and all(k in batch for k in ('src_xyz', 'tgt_xyz', 'pose')):
+        if 'src_overlap' in batch:
+            return
+        if all(k in batch for k in ('clouds', 'pairs', 'pose')):
+            shared_clouds.check_batch(batch)
+            src, tgt = shared_clouds.pair_views(batch)
+            labels = label_batch({'src_xyz': src, 'tgt_xyz': tgt, 'pose': batch['pose']}, self.cfg.overlap_radius)
+            for k in ('src_overlap', 'tgt_overlap', 'correspondences'):
+                batch[k] = labels[k]
+        elif all(k in batch for k in ('src_xyz', 'tgt_xyz', 'pose')):
             label_batch(batch, self.cfg.overlap_radius)
 
     def _pair_keys(self, n: int) -> List[int]:
@@ -398,6 +409,10 @@ class Trainer:
 
     def train_step(self, model, batch) -> dict:
         """trainer.py:107-146 for one batch."""
+        if self.augment and 'clouds' in batch:
+            # the reference's augmentation perturbs and shuffles per pair: a cloud shared by two pairs would have to be
+            # two different clouds
+            raise ValueError("Trainer(augment=True) cannot train on a batch of shared 'clouds': the augmentation is per pair")
         self.global_step += 1
         model.train()
         augment = self.augment and all(k in batch for k in ('src_xyz', 'tgt_xyz', 'pose'))
