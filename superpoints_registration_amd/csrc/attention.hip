@@ -22,6 +22,7 @@
 #include "attn_planes.h"
 #include "lds_dma.h"
 #include "spr_common.h"
+#include "split_mma.h"
 #include <atomic>
 #include <type_traits>
 
@@ -146,14 +147,14 @@ __global__ __launch_bounds__(256) void k_attn(
     for (int s = 0; s < 16; ++s)
       st = __builtin_amdgcn_mfma_f32_32x32x2f32(ka[s], qreg[s], st, 0, 0, 0);
 #pragma unroll
-    for (int r = 0; r < 16; ++r) va[r] = vp[((r & 3) + 8 * (r >> 2) + 4 * lh) * HD];
+    for (int r = 0; r < 16; ++r) va[r] = vp[acc_row32(r, lh, 0) * HD];
     __builtin_amdgcn_sched_barrier(0);
 
     // lane holds, for its query, the 16 keys  j(r) = (r&3) + 8*(r>>2) + 4*lh
     float mx = -INFINITY;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int j = kt + (r & 3) + 8 * (r >> 2) + 4 * lh;
+      const int j = acc_row32(r, lh, kt);
       if (j >= klen) st[r] = -INFINITY;  // tail of the key segment
       mx = fmaxf(mx, st[r]);
     }
@@ -229,11 +230,6 @@ __global__ __launch_bounds__(256) void k_attn(
 //         in place -- registers 8s..8s+7 of a lane are exactly the B fragment
 //         of k-step s with key order kappa(s,h,j) = 16s + 8(j>>2) + 4h + (j&3);
 //         the V^T A-fragment is read with the same order.
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 constexpr int KT2 = 64;  // keys per tile (two 32-key MFMA sub-tiles)
 constexpr int PT = 64;   // token columns per pack workgroup
 constexpr int PS = 72;   // pack transposition row stride (halves)
@@ -313,8 +309,8 @@ __global__ __launch_bounds__(256) void k_attn_pack(
       }
       split_pk_s(vv.x, vv.y, vmul, ha, la);
       split_pk_s(vv.z, vv.w, vmul, hb, lb);
-      const h16x4 vh4 = __builtin_bit_cast(h16x4, (u32x2){ha, hb});
-      const h16x4 vl4 = __builtin_bit_cast(h16x4, (u32x2){la, lb});
+      const f16x4 vh4 = __builtin_bit_cast(f16x4, (u32x2){ha, hb});
+      const f16x4 vl4 = __builtin_bit_cast(f16x4, (u32x2){la, lb});
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         Lh[(c4 + e) * PS + r] = vh4[e];
@@ -431,14 +427,14 @@ __global__ __launch_bounds__(256, WPS) void k_attn_s(
   // K / V^T DMA, wait and barrier -- the other waves' tiles depend on them -- and nothing else: no Q loads, no tile().
   const bool has_q = q0 + wave * 32 < qlen;
 
-  h16x8 qh[2] = {}, ql[2] = {};
+  f16x8 qh[2] = {}, ql[2] = {};
   if (has_q) {
     const int qi = min(q0 + wave * 32 + l31, qlen - 1);
     const size_t row = ((size_t)head * t_total + qbeg + qi) * HD + 8 * lh;
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      qh[s] = *reinterpret_cast<const h16x8*>(qh_g + row + 16 * s);
-      if constexpr (H3) ql[s] = *reinterpret_cast<const h16x8*>(ql_g + row + 16 * s);
+      qh[s] = *reinterpret_cast<const f16x8*>(qh_g + row + 16 * s);
+      if constexpr (H3) ql[s] = *reinterpret_cast<const f16x8*>(ql_g + row + 16 * s);
     }
   }
   // The Q fragments are first USED inside the tile loop: without this the compiler's own wait for their loads
@@ -502,13 +498,13 @@ __global__ __launch_bounds__(256, WPS) void k_attn_s(
     for (;;) {
       // ---- S^T = K Q^T + (off - m_ref)   (rows = keys, cols = queries) ----
       __builtin_amdgcn_s_setprio(2);
-      h16x8 kfh[2][2], kfl[2][2];
+      f16x8 kfh[2][2], kfl[2][2];
       auto load_kf = [&](int kk) __attribute__((always_inline)) {
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
           const int kpos = (32 * kk + l31) * HD + 8 * ((2 * s + lh) ^ ((l31 >> 2) & 3));
-          kfh[kk][s] = *reinterpret_cast<const h16x8*>(Kh[buf] + kpos);
-          if constexpr (H3) kfl[kk][s] = *reinterpret_cast<const h16x8*>(Kl[buf] + kpos);
+          kfh[kk][s] = *reinterpret_cast<const f16x8*>(Kh[buf] + kpos);
+          if constexpr (H3) kfl[kk][s] = *reinterpret_cast<const f16x8*>(Kl[buf] + kpos);
         }
       };
 #pragma unroll
@@ -517,11 +513,8 @@ __global__ __launch_bounds__(256, WPS) void k_attn_s(
         sc[kk] = negm;
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-          if constexpr (H3) {
-            sc[kk] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kfh[kk][s], ql[s], sc[kk], 0, 0, 0);
-            sc[kk] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kfl[kk][s], qh[s], sc[kk], 0, 0, 0);
-          }
-          sc[kk] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kfh[kk][s], qh[s], sc[kk], 0, 0, 0);
+          if constexpr (H3) sc[kk] = mma3_32(kfh[kk][s], kfl[kk][s], qh[s], ql[s], sc[kk]);
+          else sc[kk] = mma1_32(kfh[kk][s], qh[s], sc[kk]);
         }
         if (kk == 0) __builtin_amdgcn_sched_barrier(0);
       }
@@ -531,7 +524,7 @@ __global__ __launch_bounds__(256, WPS) void k_attn_s(
         for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int j = kt + 32 * kk + (r & 3) + 8 * (r >> 2) + 4 * lh;
+            const int j = acc_row32(r, lh, kt + 32 * kk);
             if (j >= klen) sc[kk][r] = -INFINITY;
           }
       }
@@ -557,11 +550,10 @@ __global__ __launch_bounds__(256, WPS) void k_attn_s(
       float ta = 0.f, tb = 0.f;
       if constexpr (ADAPT) {
         // per 32-key sub-tile (the decision needs that sub-tile's probabilities only: 16 live registers, not 32)
-        typedef _Float16 h16x2_ __attribute__((ext_vector_type(2)));
         const float thr = kSig * psum;                                    // (first tile: psum = 0 -> significant)
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
-          h16x2_ m2 = {(_Float16)0.f, (_Float16)0.f};
+          f16x2 m2 = {(_Float16)0.f, (_Float16)0.f};
 #pragma unroll
           for (int r = 0; r < 16; r += 2) {
             const float p0 = __builtin_amdgcn_exp2f(sc[kk][r]);
@@ -575,9 +567,9 @@ __global__ __launch_bounds__(256, WPS) void k_attn_s(
             // (through the compiler, not inline asm: a VALU instruction that reads the result of a transcendental needs
             // a wait state the hazard pass only inserts for instructions it can see -- the asm form produced NaNs in
             // the lanes the quarter-rate unit finishes last)
-            const unsigned int hi_u = __builtin_bit_cast(unsigned int, __builtin_convertvector((f32x2){p0, p1}, h16x2_));
+            const unsigned int hi_u = __builtin_bit_cast(unsigned int, __builtin_convertvector((f32x2){p0, p1}, f16x2));
             ph_u[kk][r >> 1] = hi_u;
-            m2 = __builtin_elementwise_max(m2, __builtin_bit_cast(h16x2_, hi_u));
+            m2 = __builtin_elementwise_max(m2, __builtin_bit_cast(f16x2, hi_u));
           }
           const float mxp = (float)(m2[0] > m2[1] ? m2[0] : m2[1]);
           sigk[kk] = __builtin_amdgcn_ballot_w64(!(mxp < thr)) != 0;
@@ -636,24 +628,24 @@ __global__ __launch_bounds__(256, WPS) void k_attn_s(
     // ---- O^T += V^T P^T ----
     auto pv = [&](auto lo_tag, int kk) __attribute__((always_inline)) {
       constexpr bool LO = decltype(lo_tag)::value;
-      h16x8 vfh[2], vfl[2];
+      f16x8 vfh[2], vfl[2];
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         const int vpos = l31 * KT2 + 8 * ((4 * kk + 2 * s + lh) ^ ((l31 >> 1) & 7));
-        vfh[s] = *reinterpret_cast<const h16x8*>(Vth[buf] + vpos);
-        if constexpr (H3) vfl[s] = *reinterpret_cast<const h16x8*>(Vtl[buf] + vpos);
+        vfh[s] = *reinterpret_cast<const f16x8*>(Vth[buf] + vpos);
+        if constexpr (H3) vfl[s] = *reinterpret_cast<const f16x8*>(Vtl[buf] + vpos);
       }
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         const u32x4 pa = {ph_u[kk][4 * s], ph_u[kk][4 * s + 1], ph_u[kk][4 * s + 2], ph_u[kk][4 * s + 3]};
-        const h16x8 pbh = __builtin_bit_cast(h16x8, pa);
+        const f16x8 pbh = __builtin_bit_cast(f16x8, pa);
         if constexpr (LO) {
           const u32x4 pb = {pl_u[kk][4 * s], pl_u[kk][4 * s + 1], pl_u[kk][4 * s + 2], pl_u[kk][4 * s + 3]};
-          const h16x8 pbl = __builtin_bit_cast(h16x8, pb);
-          o = __builtin_amdgcn_mfma_f32_32x32x16_f16(vfh[s], pbl, o, 0, 0, 0);
+          const f16x8 pbl = __builtin_bit_cast(f16x8, pb);
+          o = mma1_32(vfh[s], pbl, o);
         }
-        if constexpr (H3) o = __builtin_amdgcn_mfma_f32_32x32x16_f16(vfl[s], pbh, o, 0, 0, 0);
-        o = __builtin_amdgcn_mfma_f32_32x32x16_f16(vfh[s], pbh, o, 0, 0, 0);
+        if constexpr (H3) o = mma1_32(vfl[s], pbh, o);
+        o = mma1_32(vfh[s], pbh, o);
       }
     };
 #pragma unroll

@@ -21,6 +21,7 @@
 // over queries).
 #include "attn_planes.h"
 #include "spr_common.h"
+#include "split_mma.h"
 
 namespace spr {
 namespace {
@@ -41,8 +42,6 @@ struct AttnBwdArgs {
   float *lse, *dsum;             // [T, nhead]
   float *dq, *dk, *dv;           // [T, nhead * 32] contiguous
 };
-
-__device__ __forceinline__ int crow(int r, int h) { return 8 * (r >> 2) + 4 * h + (r & 3); }
 
 __global__ __launch_bounds__(256) void k_attn_bwd_rowdot(const float* __restrict__ out, int os, const float* __restrict__ dout,
                                                          int dos, int t_total, int nhead, float* __restrict__ dsum) {
@@ -105,11 +104,11 @@ __device__ __forceinline__ f32x16 mm_rows(const float* tile, int row0, int l31, 
   return c;
 }
 // acc += X^T . B where B is a C-layout tile (contraction over its rows): A[m = l31][k = (r, h)] =
-// tile[row0 + crow(r, h)][l31]
+// tile[row0 + acc_row32(r, h)][l31]
 __device__ __forceinline__ void mm_cols_acc(f32x16& acc, const float* tile, int row0, int l31, int h, const f32x16& b) {
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const float a = tile[(row0 + crow(r, h)) * LS + l31];
+    const float a = tile[(row0 + acc_row32(r, h)) * LS + l31];
     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b[r], acc, 0, 0, 0);
   }
 }
@@ -162,7 +161,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_dq(const AttnBwdArgs a) {
       float x[16], mx = -INFINITY;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int key = it * BT + 32 * kb + crow(r, h);
+        const int key = it * BT + 32 * kb + acc_row32(r, h);
         x[r] = key < klen ? s[r] * c : -INFINITY;
         mx = fmaxf(mx, x[r]);
       }
@@ -228,7 +227,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_dq(const AttnBwdArgs a) {
       f32x16 ds;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int key = it * BT + 32 * kb + crow(r, h);
+        const int key = it * BT + 32 * kb + acc_row32(r, h);
         const float p = key < klen ? __builtin_amdgcn_exp2f(s[r] * c - lse) : 0.f;
         ds[r] = p * (dp[r] - dq_row);
       }
@@ -380,22 +379,18 @@ __global__ __launch_bounds__(256) void k_attn_bwd_dkv(const AttnBwdArgs a) {
 
 
 // ======================================================================================================
-// Split-fp16 form (every attention mode but 0; the default is 4): the same two kernels with every product on
-// v_mfma_f32_32x32x16_f16 over range-scaled hi/lo operand planes (3 matrix instructions per product and k-step, fp32
-// accumulation -- the forward's arithmetic, spr_common.h split_pk_s), 5.3x less matrix time than the f32 form.
+// Split-fp16 form (every attention mode but 0; the default is 4): the same two kernels with every product as a
+// split-fp16 product over range-scaled hi/lo operand planes (the forward's arithmetic, split_mma.h), 5.3x less matrix
+// time than the f32 form.
 //   operand scales (powers of two, measured per call): sq, sk, sv, sdo bring max|q|, |k|, |v|, |dO| into
 //   [2^14, 2^15).  S' = sq sk S and dP' = sv sdo dP stay in fp32.  The probabilities are split as P 2^14 (<= 2^14),
 //   dS as P (dP' - D') 2^-21: |dP' - D'| <= 2 . 32 . 2^15 . 2^15 = 2^36 by Cauchy-Schwarz (D' is a convex
 //   combination of the dP' of its row), so no operand can overflow fp16 whatever the data.
 // The staged tiles live in LDS as fp16 planes in two forms: R[row][d] (A operand of the products that contract
-// over d: 8 consecutive d per lane) and C[d][pos(row)] (A operand of the products that contract over the tile's
+// over d: split_mma.h's 40-half planes) and C[d][pos(row)] (A operand of the products that contract over the tile's
 // rows), pos() = the order in which a 32x32 accumulator tile holds its rows, so that the accumulator registers
-// of S / dS are the B operand of the next product as they are: k-step s of a 32-row block contracts the rows
-// 16 s + 8 (j >> 2) + 4 h + (j & 3), j = 0..7, of lane half h = registers 8 s + j.
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int bu32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int bu32x2 __attribute__((ext_vector_type(2)));
-constexpr int RS = 40;                    // R-form row stride in halves (80 B: 16-byte aligned, spreads the banks)
+// of S / dS are the B operand of the next product as they are (split_mma.h, Fragments).
+constexpr int RS = kPlaneStride;           // R-form row stride in halves
 constexpr int CS = 72;                    // C-form row stride in halves (144 B)
 constexpr int R_HALVES = BT * RS;         // one R plane of a 64-row tile
 constexpr int C_HALVES = BHD * CS;        // one C plane
@@ -416,8 +411,8 @@ __device__ __forceinline__ void tile_store_split(const TileRegs& t, float s, _Fl
     unsigned int h0, l0, h1, l1;
     split_pk_s(v.x, v.y, s, h0, l0);
     split_pk_s(v.z, v.w, s, h1, l1);
-    *reinterpret_cast<bu32x2*>(rh + row * RS + dc) = (bu32x2){h0, h1};
-    *reinterpret_cast<bu32x2*>(rl + row * RS + dc) = (bu32x2){l0, l1};
+    *reinterpret_cast<u32x2*>(rh + row * RS + dc) = (u32x2){h0, h1};
+    *reinterpret_cast<u32x2*>(rl + row * RS + dc) = (u32x2){l0, l1};
     if (ch != nullptr) {
       const int pos = 32 * (row >> 5) + cpos(row & 31);
       unsigned short* ph = reinterpret_cast<unsigned short*>(ch) + dc * CS + pos;
@@ -434,7 +429,7 @@ __device__ __forceinline__ void tile_store_split(const TileRegs& t, float s, _Fl
   }
 }
 // the lane's 16 values x[16 h' ..] of a row as B-operand planes: b?[s] = x[16 s + 8 h + j], j = 0..7
-__device__ __forceinline__ void row_planes(const float* __restrict__ row, int h, float s, h16x8 (&bh)[2], h16x8 (&bl)[2]) {
+__device__ __forceinline__ void row_planes(const float* __restrict__ row, int h, float s, f16x8 (&bh)[2], f16x8 (&bl)[2]) {
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks) {
     const float4 x = *reinterpret_cast<const float4*>(row + 16 * ks + 8 * h);
@@ -444,50 +439,48 @@ __device__ __forceinline__ void row_planes(const float* __restrict__ row, int h,
     split_pk_s(x.z, x.w, s, hi[1], lo[1]);
     split_pk_s(y.x, y.y, s, hi[2], lo[2]);
     split_pk_s(y.z, y.w, s, hi[3], lo[3]);
-    bh[ks] = __builtin_bit_cast(h16x8, (bu32x4){hi[0], hi[1], hi[2], hi[3]});
-    bl[ks] = __builtin_bit_cast(h16x8, (bu32x4){lo[0], lo[1], lo[2], lo[3]});
+    bh[ks] = __builtin_bit_cast(f16x8, (u32x4){hi[0], hi[1], hi[2], hi[3]});
+    bl[ks] = __builtin_bit_cast(f16x8, (u32x4){lo[0], lo[1], lo[2], lo[3]});
   }
 }
-__device__ __forceinline__ f32x16 mfma_h(const h16x8& a, const h16x8& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-// C = X[row0 + m][.] . B (contraction over d), X in R form
+// C = X[row0 + m][.] . B (contraction over d), X in R form.  The three terms of mma3_32 one by one, here and in
+// mm_cols_acc_h: inside these helpers the combined call compiles to other code (profiles/split_mma_header.txt)
 __device__ __forceinline__ f32x16 mm_rows_h(const _Float16* rh, const _Float16* rl, int row0, int l31, int h,
-                                            const h16x8 (&bh)[2], const h16x8 (&bl)[2]) {
+                                            const f16x8 (&bh)[2], const f16x8 (&bl)[2]) {
   f32x16 c;
 #pragma unroll
   for (int r = 0; r < 16; ++r) c[r] = 0.f;
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks) {
-    const h16x8 ah = *reinterpret_cast<const h16x8*>(rh + (row0 + l31) * RS + 16 * ks + 8 * h);
-    const h16x8 al = *reinterpret_cast<const h16x8*>(rl + (row0 + l31) * RS + 16 * ks + 8 * h);
-    c = mfma_h(ah, bl[ks], c);
-    c = mfma_h(al, bh[ks], c);
-    c = mfma_h(ah, bh[ks], c);
+    const f16x8 ah = *reinterpret_cast<const f16x8*>(rh + (row0 + l31) * RS + 16 * ks + 8 * h);
+    const f16x8 al = *reinterpret_cast<const f16x8*>(rl + (row0 + l31) * RS + 16 * ks + 8 * h);
+    c = mma1_32(ah, bl[ks], c);
+    c = mma1_32(al, bh[ks], c);
+    c = mma1_32(ah, bh[ks], c);
   }
   return c;
 }
 // the accumulator tile b (scaled by s) as B-operand planes of a product that contracts over its rows
-__device__ __forceinline__ void acc_planes(const f32x16& b, float s, h16x8 (&bh)[2], h16x8 (&bl)[2]) {
+__device__ __forceinline__ void acc_planes(const f32x16& b, float s, f16x8 (&bh)[2], f16x8 (&bl)[2]) {
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks) {
     unsigned int hi[4], lo[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) split_pk_s(b[8 * ks + 2 * i], b[8 * ks + 2 * i + 1], s, hi[i], lo[i]);
-    bh[ks] = __builtin_bit_cast(h16x8, (bu32x4){hi[0], hi[1], hi[2], hi[3]});
-    bl[ks] = __builtin_bit_cast(h16x8, (bu32x4){lo[0], lo[1], lo[2], lo[3]});
+    bh[ks] = __builtin_bit_cast(f16x8, (u32x4){hi[0], hi[1], hi[2], hi[3]});
+    bl[ks] = __builtin_bit_cast(f16x8, (u32x4){lo[0], lo[1], lo[2], lo[3]});
   }
 }
 // acc += X^T . B, X in C form (32-row block blk), B = acc_planes of a C-layout tile
 __device__ __forceinline__ void mm_cols_acc_h(f32x16& acc, const _Float16* ch, const _Float16* cl, int blk, int l31, int h,
-                                              const h16x8 (&bh)[2], const h16x8 (&bl)[2]) {
+                                              const f16x8 (&bh)[2], const f16x8 (&bl)[2]) {
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks) {
-    const h16x8 ah = *reinterpret_cast<const h16x8*>(ch + l31 * CS + 32 * blk + 16 * ks + 8 * h);
-    const h16x8 al = *reinterpret_cast<const h16x8*>(cl + l31 * CS + 32 * blk + 16 * ks + 8 * h);
-    acc = mfma_h(ah, bl[ks], acc);
-    acc = mfma_h(al, bh[ks], acc);
-    acc = mfma_h(ah, bh[ks], acc);
+    const f16x8 ah = *reinterpret_cast<const f16x8*>(ch + l31 * CS + 32 * blk + 16 * ks + 8 * h);
+    const f16x8 al = *reinterpret_cast<const f16x8*>(cl + l31 * CS + 32 * blk + 16 * ks + 8 * h);
+    acc = mma1_32(ah, bl[ks], acc);
+    acc = mma1_32(al, bh[ks], acc);
+    acc = mma1_32(ah, bh[ks], acc);
   }
 }
 
@@ -515,7 +508,7 @@ struct BwdPlanes {
 };
 struct Stage {
   TileRegs f;                  // fp32 route
-  bu32x4 rh, rl, ch, cl;       // plane route
+  u32x4 rh, rl, ch, cl;       // plane route
 };
 template <bool PL>
 __device__ __forceinline__ void stage_fetch(Stage& st, const float* __restrict__ x, int stride, int hoff,
@@ -525,17 +518,17 @@ __device__ __forceinline__ void stage_fetch(Stage& st, const float* __restrict__
     st.f = tile_fetch(x, stride, seg_beg, len, row0, hoff);
   } else {
     const int row = row0 + (threadIdx.x >> 2), chunk = threadIdx.x & 3;
-    st.rh = st.rl = (bu32x4){0u, 0u, 0u, 0u};
+    st.rh = st.rl = (u32x4){0u, 0u, 0u, 0u};
     if (row < len) {
       const size_t o = ((size_t)head * T + seg_beg + row) * BHD + 8 * chunk;
-      st.rh = *reinterpret_cast<const bu32x4*>(rp[0] + o);
-      st.rl = *reinterpret_cast<const bu32x4*>(rp[1] + o);
+      st.rh = *reinterpret_cast<const u32x4*>(rp[0] + o);
+      st.rl = *reinterpret_cast<const u32x4*>(rp[1] + o);
     }
     if (want_c) {
       const int d = threadIdx.x >> 3, c8 = threadIdx.x & 7;
       const size_t o = ((size_t)head * BHD + d) * tc + ccol0 + 8 * c8;
-      st.ch = *reinterpret_cast<const bu32x4*>(cp[0] + o);
-      st.cl = *reinterpret_cast<const bu32x4*>(cp[1] + o);
+      st.ch = *reinterpret_cast<const u32x4*>(cp[0] + o);
+      st.cl = *reinterpret_cast<const u32x4*>(cp[1] + o);
     }
   }
 }
@@ -546,26 +539,26 @@ __device__ __forceinline__ void stage_store(const Stage& st, float s, _Float16* 
     tile_store_split(st.f, s, rh, rl, ch, cl);
   } else {
     const int row = threadIdx.x >> 2, chunk = threadIdx.x & 3;
-    *reinterpret_cast<bu32x4*>(rh + row * RS + 8 * chunk) = st.rh;
-    *reinterpret_cast<bu32x4*>(rl + row * RS + 8 * chunk) = st.rl;
+    *reinterpret_cast<u32x4*>(rh + row * RS + 8 * chunk) = st.rh;
+    *reinterpret_cast<u32x4*>(rl + row * RS + 8 * chunk) = st.rl;
     if (ch != nullptr) {
       const int d = threadIdx.x >> 3, c8 = threadIdx.x & 7;
-      *reinterpret_cast<bu32x4*>(ch + d * CS + 8 * c8) = st.ch;
-      *reinterpret_cast<bu32x4*>(cl + d * CS + 8 * c8) = st.cl;
+      *reinterpret_cast<u32x4*>(ch + d * CS + 8 * c8) = st.ch;
+      *reinterpret_cast<u32x4*>(cl + d * CS + 8 * c8) = st.cl;
     }
   }
 }
 // the lane's B-operand planes of one row, from the fp32 tensor (split here) or from the R planes
 template <bool PL>
 __device__ __forceinline__ void row_operand(const float* __restrict__ x, size_t xoff, float s, _Float16* const (&rp)[2],
-                                            size_t prow, int h, h16x8 (&bh)[2], h16x8 (&bl)[2]) {
+                                            size_t prow, int h, f16x8 (&bh)[2], f16x8 (&bl)[2]) {
   if constexpr (!PL) {
     row_planes(x + xoff, h, s, bh, bl);
   } else {
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      bh[ks] = *reinterpret_cast<const h16x8*>(rp[0] + prow * BHD + 16 * ks + 8 * h);
-      bl[ks] = *reinterpret_cast<const h16x8*>(rp[1] + prow * BHD + 16 * ks + 8 * h);
+      bh[ks] = *reinterpret_cast<const f16x8*>(rp[0] + prow * BHD + 16 * ks + 8 * h);
+      bl[ks] = *reinterpret_cast<const f16x8*>(rp[1] + prow * BHD + 16 * ks + 8 * h);
     }
   }
 }
@@ -609,8 +602,8 @@ __global__ __launch_bounds__(256) void k_attn_bwd_pack(const AttnBwdArgs a, cons
   split_pk_s(v1.z, v1.w, s, hi[3], lo[3]);
   if (r < len) {
     const size_t o = ((size_t)head * pl.t + beg + r) * BHD + 8 * chunk;
-    *reinterpret_cast<bu32x4*>(rp[0] + o) = (bu32x4){hi[0], hi[1], hi[2], hi[3]};
-    *reinterpret_cast<bu32x4*>(rp[1] + o) = (bu32x4){lo[0], lo[1], lo[2], lo[3]};
+    *reinterpret_cast<u32x4*>(rp[0] + o) = (u32x4){hi[0], hi[1], hi[2], hi[3]};
+    *reinterpret_cast<u32x4*>(rp[1] + o) = (u32x4){lo[0], lo[1], lo[2], lo[3]};
   }
   if (which == 2) return;      // V is only ever contracted over d
   const int pos = 32 * (row >> 5) + cpos(row & 31);
@@ -626,8 +619,8 @@ __global__ __launch_bounds__(256) void k_attn_bwd_pack(const AttnBwdArgs a, cons
   __syncthreads();
   const int d = threadIdx.x >> 3, c8 = threadIdx.x & 7;
   const size_t o = ((size_t)head * BHD + d) * pl.tc + pl.cst[seg] + row0 + 8 * c8;
-  *reinterpret_cast<bu32x4*>(cp[0] + o) = *reinterpret_cast<const bu32x4*>(th + d * CS + 8 * c8);
-  *reinterpret_cast<bu32x4*>(cp[1] + o) = *reinterpret_cast<const bu32x4*>(tl + d * CS + 8 * c8);
+  *reinterpret_cast<u32x4*>(cp[0] + o) = *reinterpret_cast<const u32x4*>(th + d * CS + 8 * c8);
+  *reinterpret_cast<u32x4*>(cp[1] + o) = *reinterpret_cast<const u32x4*>(tl + d * CS + 8 * c8);
 }
 
 // ONE tile buffer in the two kernels below: two barriers per iteration, half the LDS of a double buffer, THREE
@@ -665,7 +658,7 @@ __global__ __launch_bounds__(256, 3) void k_attn_bwd_dq_h(const AttnBwdArgs a, c
   const int qi = q0 + 32 * qb + l31;
   const bool qvalid = qi < qlen;
   const int qic = qvalid ? qi : qlen - 1;
-  h16x8 qh[2], ql[2], doh[2], dol[2];
+  f16x8 qh[2], ql[2], doh[2], dol[2];
   row_operand<PL>(a.q, (size_t)(qbeg + qic) * a.qs + hoff, sq, pl.rq, (size_t)head * pl.t + qbeg + qic, h, qh, ql);
   row_operand<PL>(a.dout, (size_t)(qbeg + qic) * a.dos + hoff, sdo, pl.ro, (size_t)head * pl.t + qbeg + qic, h, doh, dol);
   const int kc0 = PL ? pl.cst[ksg] : 0;
@@ -703,7 +696,7 @@ __global__ __launch_bounds__(256, 3) void k_attn_bwd_dq_h(const AttnBwdArgs a, c
       } else {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int key = it * BT + 32 * kb + crow(r, h);
+          const int key = it * BT + 32 * kb + acc_row32(r, h);
           x[r] = key < klen ? s[r] * c : -INFINITY;
           mx = fmaxf(mx, x[r]);
         }
@@ -774,12 +767,12 @@ __global__ __launch_bounds__(256, 3) void k_attn_bwd_dq_h(const AttnBwdArgs a, c
       } else {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int key = it * BT + 32 * kb + crow(r, h);
+          const int key = it * BT + 32 * kb + acc_row32(r, h);
           const float p = key < klen ? __builtin_amdgcn_exp2f(s[r] * c - lse) : 0.f;
           ds[r] = p * (dp[r] - dq_row);
         }
       }
-      h16x8 bh[2], bl[2];
+      f16x8 bh[2], bl[2];
       acc_planes(ds, DS_MUL, bh, bl);
       mm_cols_acc_h(acc, KCh(), KCl(), kb, l31, h, bh, bl);
       __syncthreads();   // every wave has read the tile
@@ -846,7 +839,7 @@ __global__ __launch_bounds__(256, 3) void k_attn_bwd_dkv_h(const AttnBwdArgs a, 
   const int ki = k0 + 32 * kb + l31;
   const bool kvalid = ki < klen;
   const int kic = kvalid ? ki : klen - 1;
-  h16x8 kh[2], kl[2], vh[2], vl[2];
+  f16x8 kh[2], kl[2], vh[2], vl[2];
   row_operand<PL>(a.k, (size_t)(kbeg + kic) * a.ks + hoff, sk, pl.rk, (size_t)head * pl.t + kbeg + kic, h, kh, kl);
   row_operand<PL>(a.v, (size_t)(kbeg + kic) * a.vs + hoff, sv, pl.rv, (size_t)head * pl.t + kbeg + kic, h, vh, vl);
   const int qc0 = PL ? pl.cst[seg] : 0;
@@ -918,7 +911,7 @@ __global__ __launch_bounds__(256, 3) void k_attn_bwd_dkv_h(const AttnBwdArgs a, 
       }
     }
     {
-      h16x8 bh[2], bl[2];
+      f16x8 bh[2], bl[2];
       acc_planes(p, P_MUL, bh, bl);
       mm_cols_acc_h(acc_v, OCh(), OCl(), qb, l31, h, bh, bl);      // dV^T[d][key] += dO^T P
       acc_planes(ds, DS_MUL, bh, bl);

@@ -21,6 +21,7 @@
 //                   through LDS and written as rows with 16-byte stores (4 rows x 256 bytes per wave
 //                   instruction).  Fixed summation order everywhere: bitwise reproducible.
 #include "spr_common.h"
+#include "split_mma.h"
 
 namespace spr {
 namespace {
@@ -29,9 +30,6 @@ constexpr int HD = 32;         // head dim
 constexpr int QB = 128;        // queries per workgroup (4 waves x 32)
 constexpr int KR = 64;         // keys per workgroup of the store pass (2 sub-tiles of 32)
 constexpr int LSR = KR + 4;    // LDS row stride (floats) of the store staging: 16-byte rows 4 banks apart
-
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 // scales[0] = log2(e) scale 2^-ek (Q planes), scales[1] = 2^ek (K planes), ek = half the exponent gap of the bounds
 __global__ __launch_bounds__(256) void k_probs_scales(const float* __restrict__ q_parts,
@@ -65,15 +63,8 @@ __global__ __launch_bounds__(256) void k_probs_pack(const float* __restrict__ q,
   const float4 vq = *reinterpret_cast<const float4*>(q + (size_t)tok * q_stride + f);
   const float4 vk = *reinterpret_cast<const float4*>(k + (size_t)tok * k_stride + f);
   const size_t hm = ((size_t)(f / HD) * t_total + tok) * HD + f % HD;
-  unsigned int ha, hb, la, lb;
-  split_pk_s(vq.x, vq.y, scales[0], ha, la);
-  split_pk_s(vq.z, vq.w, scales[0], hb, lb);
-  *reinterpret_cast<u32x2*>(qh + hm) = (u32x2){ha, hb};
-  *reinterpret_cast<u32x2*>(ql + hm) = (u32x2){la, lb};
-  split_pk_s(vk.x, vk.y, scales[1], ha, la);
-  split_pk_s(vk.z, vk.w, scales[1], hb, lb);
-  *reinterpret_cast<u32x2*>(kh + hm) = (u32x2){ha, hb};
-  *reinterpret_cast<u32x2*>(kl + hm) = (u32x2){la, lb};
+  split_store4(vq, scales[0], qh + hm, ql + hm);
+  split_store4(vk, scales[1], kh + hm, kl + hm);
 }
 
 // Block id -> (group, tile) with all tiles of one group on one XCD (ids b and b + 8 share an L2) when the group
@@ -91,28 +82,26 @@ __device__ __forceinline__ void group_tile(int b, int ngrp, int ntile, int& g, i
 
 // S^T = K Q^T of one 32-key x 32-query sub-tile in split fp16 (rows = keys, lane = query), C = c0.
 __device__ __forceinline__ f32x16 scores_t(const _Float16* __restrict__ kh_g, const _Float16* __restrict__ kl_g,
-                                           size_t krow, const h16x8 (&qh)[2], const h16x8 (&ql)[2], f32x16 c) {
-  h16x8 kfh[2], kfl[2];
+                                           size_t krow, const f16x8 (&qh)[2], const f16x8 (&ql)[2], f32x16 c) {
+  f16x8 kfh[2], kfl[2];
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
-    kfh[s] = *reinterpret_cast<const h16x8*>(kh_g + krow + 16 * s);
-    kfl[s] = *reinterpret_cast<const h16x8*>(kl_g + krow + 16 * s);
+    kfh[s] = *reinterpret_cast<const f16x8*>(kh_g + krow + 16 * s);
+    kfl[s] = *reinterpret_cast<const f16x8*>(kl_g + krow + 16 * s);
   }
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(kfh[s], ql[s], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(kfl[s], qh[s], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(kfh[s], qh[s], c, 0, 0, 0);
+    c = mma3_32(kfh[s], kfl[s], qh[s], ql[s], c);
   }
   return c;
 }
 
 __device__ __forceinline__ void load_q(const _Float16* __restrict__ qh_g, const _Float16* __restrict__ ql_g,
-                                       size_t row, h16x8 (&qh)[2], h16x8 (&ql)[2]) {
+                                       size_t row, f16x8 (&qh)[2], f16x8 (&ql)[2]) {
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
-    qh[s] = *reinterpret_cast<const h16x8*>(qh_g + row + 16 * s);
-    ql[s] = *reinterpret_cast<const h16x8*>(ql_g + row + 16 * s);
+    qh[s] = *reinterpret_cast<const f16x8*>(qh_g + row + 16 * s);
+    ql[s] = *reinterpret_cast<const f16x8*>(ql_g + row + 16 * s);
   }
 }
 
@@ -135,7 +124,7 @@ __global__ __launch_bounds__(256) void k_probs_stats(const _Float16* __restrict_
   if (q0 >= qlen) return;
   const int ks = kv_seg[seg];
   const int kbeg = cu[ks], klen = cu[ks + 1] - kbeg;
-  h16x8 qh[2], ql[2];
+  f16x8 qh[2], ql[2];
   load_q(qh_g, ql_g, ((size_t)head * t_total + qbeg + min(q0 + l31, qlen - 1)) * HD + 8 * lh, qh, ql);
   float m = kNegBig, l = 0.f;
   for (int kt = 0; kt < klen; kt += 64) {   // two 32-key sub-tiles per step: both fragment loads in flight at once
@@ -151,7 +140,7 @@ __global__ __launch_bounds__(256) void k_probs_stats(const _Float16* __restrict_
       for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-          if (kt + 32 * kk + (r & 3) + 8 * (r >> 2) + 4 * lh >= klen) sc[kk][r] = -INFINITY;
+          if (acc_row32(r, lh, kt + 32 * kk) >= klen) sc[kk][r] = -INFINITY;
     }
     float mx = fmaxf(sc[0][0], sc[1][0]);
 #pragma unroll
@@ -218,7 +207,7 @@ __global__ __launch_bounds__(256) void k_probs_write(const _Float16* __restrict_
   };
   // p = 2^(s - m) / l of one head, added to acc
   auto head_probs = [&](int head) {
-    h16x8 qh[2], ql[2];
+    f16x8 qh[2], ql[2];
     const size_t qrow = (size_t)head * t_total + qbeg + qi;
     load_q(qh_g, ql_g, qrow * HD + 8 * lh, qh, ql);
     const float m = m_in[qrow], rl = rl_in[qrow];
@@ -231,7 +220,7 @@ __global__ __launch_bounds__(256) void k_probs_write(const _Float16* __restrict_
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float p = __builtin_amdgcn_exp2f(c[r] - m);
-        const bool kvalid = kt + (r & 3) + 8 * (r >> 2) + 4 * lh < klen;
+        const bool kvalid = acc_row32(r, lh, kt) < klen;
         acc[kk][r] = kvalid ? fmaf(p, rl, acc[kk][r]) : acc[kk][r];
       }
     }

@@ -25,6 +25,7 @@
 // the operand strides; the global side walks whichever operand dimension is
 // contiguous with consecutive lanes.
 #include "spr_common.h"
+#include "split_mma.h"
 
 #include <cstdlib>
 
@@ -98,7 +99,7 @@ __global__ __launch_bounds__(256) void k_bgemm_f32(const float* __restrict__ A, 
   if (j < d.n) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int i = i0 + wi + (r & 3) + 8 * (r >> 2) + 4 * lh;
+      const int i = acc_row32(r, lh, i0 + wi);
       if (i < d.m) {
         float* c = Cb + (long)i * sc_i + (long)j * sc_j;
         const float v = alpha * acc[r];
@@ -225,7 +226,7 @@ __global__ __launch_bounds__(256) void k_bgemm_f32_t(const float* __restrict__ A
       if (j >= d.n) continue;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int i = i0 + wi + 32 * mi + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        const int i = acc_row32(r, lh, i0 + wi + 32 * mi);
         if (i < d.m) {
           float* c = Cb + (long)i * sc_i + (long)j * sc_j;
           const float v = alpha * acc[mi][nj][r];
@@ -332,20 +333,18 @@ extern "C" int spr_tn_product_f64(const float* Lm, const float* Rm, long rows, i
 
 // ---------------------------------------------------------------------------
 // Weight gradients in the forward's arithmetic (round 3): parts[b][i][j] = sum over the rows t of batch b of
-// L[t, i] R[t, j]  (L = dY [rows, nl], R = X [rows, nr], both row-major) with range-scaled split-fp16 operands
-// and v_mfma_f32_32x32x16_f16 -- three MFMAs per product, fp32 accumulation -- instead of the exact-f32 MFMA
-// of spr_bgemm (1/5 of its matrix-pipe time).  The contraction runs over the ROW index of both operands, so a
-// slab of 32 rows is transposed on its way into LDS: a thread loads a 4 (rows) x 4 (columns) block, splits it
-// and writes, per column, the 4 consecutive-row halves as one 8-byte word into the [column][row] image the
-// MFMA fragments read (8 consecutive k per lane); lanes are mapped row-quad fastest so that the 16 lanes of a
-// ds_write_b64 group cover all banks.  128 x 128 outputs per workgroup of 4 waves (64 x 64 each), slab-deep
-// register prefetch, one workgroup per (tile, row batch); the batches are summed by spr_reduce_parts.
+// L[t, i] R[t, j]  (L = dY [rows, nl], R = X [rows, nr], both row-major) as a split-fp16 product (split_mma.h)
+// instead of the exact-f32 MFMA of spr_bgemm (1/5 of its matrix-pipe time).  The contraction runs over the ROW index
+// of both operands, so a slab of 32 rows is transposed on its way into LDS: a thread loads a 4 (rows) x 4 (columns)
+// block, splits it and writes, per column, the 4 consecutive-row halves as one 8-byte word into the [column][row]
+// planes the MFMA fragments read; lanes are mapped row-quad fastest so that the 16 lanes of a ds_write_b64 group cover
+// all banks.  128 x 128 outputs per workgroup of 4 waves (64 x 64 each), slab-deep register prefetch, one workgroup
+// per (tile, row batch); the batches are summed by spr_reduce_parts.
 namespace spr {
 namespace {
-typedef _Float16 th8 __attribute__((ext_vector_type(8)));
-constexpr int TNT = 128;       // output tile edge
-constexpr int TNK = 32;        // rows (contraction) per slab
-constexpr int TNS = 40;        // LDS row stride in halves (32 + 8 pad: conflict-free ds_read_b128)
+constexpr int TNT = 128;            // output tile edge
+constexpr int TNK = kPlaneK;        // rows (contraction) per slab
+constexpr int TNS = kPlaneStride;   // LDS row stride in halves
 
 __global__ __launch_bounds__(256) void k_gemm_tn_h3(const float* __restrict__ Lm, const float* __restrict__ Rm, long rows,
                                                     int nl, int nr, int chunk, const float* __restrict__ l_parts,
@@ -393,12 +392,8 @@ __global__ __launch_bounds__(256) void k_gemm_tn_h3(const float* __restrict__ Lm
                            {v[0].z, v[1].z, v[2].z, v[3].z}, {v[0].w, v[1].w, v[2].w, v[3].w}};
 #pragma unroll
     for (int q = 0; q < 4; ++q) {       // column 4 n4 + q: its four consecutive rows
-      unsigned int h0, l0, h1, l1;
-      split_pk_s(c[q][0], c[q][1], sc, h0, l0);
-      split_pk_s(c[q][2], c[q][3], sc, h1, l1);
       const int o = (4 * n4 + q) * TNS + 4 * tq;
-      *reinterpret_cast<uint2*>(hi + o) = make_uint2(h0, h1);
-      *reinterpret_cast<uint2*>(lo + o) = make_uint2(l0, l1);
+      split_store4((f32x4){c[q][0], c[q][1], c[q][2], c[q][3]}, sc, hi + o, lo + o);
     }
   };
   fetch(r_beg);
@@ -410,26 +405,19 @@ __global__ __launch_bounds__(256) void k_gemm_tn_h3(const float* __restrict__ Lm
 #pragma unroll
     for (int s2 = 0; s2 < TNK / 16; ++s2) {
       const int ko = 16 * s2 + 8 * lh;
-      th8 ah[2], al[2], bh[2], bl[2];
+      f16x8 ah[2], al[2], bh[2], bl[2];
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        ah[i] = *reinterpret_cast<const th8*>(Ah + (wi + 32 * i + l31) * TNS + ko);
-        al[i] = *reinterpret_cast<const th8*>(Al + (wi + 32 * i + l31) * TNS + ko);
-        bh[i] = *reinterpret_cast<const th8*>(Bh + (wj + 32 * i + l31) * TNS + ko);
-        bl[i] = *reinterpret_cast<const th8*>(Bl + (wj + 32 * i + l31) * TNS + ko);
+        frag_ld40(Ah, Al, wi + 32 * i + l31, ko, ah[i], al[i]);
+        frag_ld40(Bh, Bl, wj + 32 * i + l31, ko, bh[i], bl[i]);
       }
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-        }
+        for (int j = 0; j < 2; ++j) acc[i][j] = mma3_32(ah[i], al[i], bh[j], bl[j], acc[i][j]);
     }
     __syncthreads();
   }
-  // C layout: col = l31, row = (r & 3) + 8 (r >> 2) + 4 lh
   float* P = parts + (size_t)blockIdx.y * nl * nr;
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -439,7 +427,7 @@ __global__ __launch_bounds__(256) void k_gemm_tn_h3(const float* __restrict__ Lm
       if (col >= nr) continue;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int row = i0 + wi + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        const int row = acc_row32(r, lh, i0 + wi + 32 * i);
         if (row < nl) P[(size_t)row * nr + col] = acc[i][j][r] * unscale;
       }
     }

@@ -28,13 +28,11 @@
 // pass 2 swaps the MFMA operands (C^T: four consecutive output columns per lane) so that the result
 // leaves as 16-byte stores.
 #include "spr_common.h"
+#include "split_mma.h"
 
 namespace spr {
 int gemm_mode();
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kTailThreads = 512;
 constexpr int kTailWaves = 8;
@@ -245,15 +243,8 @@ __global__ __launch_bounds__(kTailThreads) void k_block_tail(const TailArgs a) {
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
           f32x4& c = (KB > 0 && ks >= KSA) ? acc_b[KB > 0 ? rt : 0][nt] : acc_a[rt][nt];
-          if constexpr (PASS == 1) {     // C[row = 4 kg + r][col = p16]
-            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wl[nt][ks], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(xl, wh[nt][ks], c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wh[nt][ks], c, 0, 0, 0);
-          } else {                       // C^T[col = 4 kg + r][row = p16]
-            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[nt][ks], xh, c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[nt][ks], xl, c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[nt][ks], xh, c, 0, 0, 0);
-          }
+          if constexpr (PASS == 1) c = mma3_16(xh, xl, wh[nt][ks], wl[nt][ks], c);   // C[row = 4 kg + r][col = p16]
+          else c = mma3_16<true>(wh[nt][ks], wl[nt][ks], xh, xl, c);                 // C^T[col = 4 kg + r][row = p16]
         }
       }
     }

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "spr_common.h"
+#include "split_mma.h"
 
 namespace spr {
 
@@ -105,10 +106,10 @@ __global__ void k_test_16x16x4(const float* A, const float* B, float* D) {
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   acc = __builtin_amdgcn_mfma_f32_16x16x4f32(A[(l & 15) * 4 + (l >> 4)], B[(l >> 4) * 16 + (l & 15)],
                                              acc, 0, 0, 0);
-  for (int r = 0; r < 4; ++r) D[(4 * (l >> 4) + r) * 16 + (l & 15)] = acc[r];
+  for (int r = 0; r < 4; ++r) D[acc_row16(r, l >> 4) * 16 + (l & 15)] = acc[r];
 }
 // D[32x32] = A[32x2] B[2x32] with A[l&31][l>>5], B[l>>5][l&31];
-// D: col = l&31, row = (r&3) + 8*(r>>2) + 4*(l>>5)
+// D: col = l&31, row = acc_row32(r, l>>5)
 __global__ void k_test_32x32x2(const float* A, const float* B, float* D) {
   const int l = threadIdx.x;
   f32x16 acc;
@@ -116,7 +117,7 @@ __global__ void k_test_32x32x2(const float* A, const float* B, float* D) {
   acc = __builtin_amdgcn_mfma_f32_32x32x2f32(A[(l & 31) * 2 + (l >> 5)], B[(l >> 5) * 32 + (l & 31)],
                                              acc, 0, 0, 0);
   for (int r = 0; r < 16; ++r)
-    D[((r & 3) + 8 * (r >> 2) + 4 * (l >> 5)) * 32 + (l & 31)] = acc[r];
+    D[acc_row32(r, l >> 5, 0) * 32 + (l & 31)] = acc[r];
 }
 }  // namespace
 }  // namespace spr

@@ -29,6 +29,7 @@
 // cin == 1 (the first block) has its own kernel, k_kpconv_cin1.
 #include "lds_dma.h"
 #include "spr_common.h"
+#include "split_mma.h"
 
 namespace spr {
 namespace {
@@ -262,13 +263,12 @@ __global__ __launch_bounds__(256) void k_w_prep(const float* __restrict__ W, int
 #define KP_TILE_COUNTS(W) W(0) W(2) W(4) W(6) W(8) W(12) W(16)
 SPR_DEFINE_WAIT_VM_ANY(wait_vm_tile, KP_TILE_COUNTS)
 
-typedef _Float16 kh8 __attribute__((ext_vector_type(8)));
 template <int N> struct VecF;
-template <> struct VecF<2> { typedef float type __attribute__((ext_vector_type(2))); };
-template <> struct VecF<4> { typedef float type __attribute__((ext_vector_type(4))); };
+template <> struct VecF<2> { typedef f32x2 type; };
+template <> struct VecF<4> { typedef f32x4 type; };
 template <int N> struct VecH;
-template <> struct VecH<2> { typedef _Float16 type __attribute__((ext_vector_type(2))); };
-template <> struct VecH<4> { typedef _Float16 type __attribute__((ext_vector_type(4))); };
+template <> struct VecH<2> { typedef f16x2 type; };
+template <> struct VecH<4> { typedef f16x4 type; };
 
 // ---------------------------------------------------------------------------
 // Fused MFMA kernel.
@@ -462,7 +462,7 @@ __global__ __launch_bounds__(64 * P1W) void k_kpconv_mfma(
         // C/D layout: row (kernel point) = 4*j4 + r, col = p16 <-> channels NTC*p16 + t
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int p = 4 * j4 + r;
+          const int p = acc_row16(r, j4);
           typedef typename VecH<NTC>::type hv_t;
           hv_t hh, ll;
           if constexpr (NTC == 2) {
@@ -472,12 +472,11 @@ __global__ __launch_bounds__(64 * P1W) void k_kpconv_mfma(
             ll = __builtin_bit_cast(hv_t, lu);
           } else {
             static_assert(NTC == 4, "NTC is 2 or 4");
-            typedef unsigned int u2_t __attribute__((ext_vector_type(2)));
             unsigned int h0, l0, h1, l1;
             split_pk_s(acc1[0][r], acc1[1][r], sa, h0, l0);
             split_pk_s(acc1[2][r], acc1[3][r], sa, h1, l1);
-            hh = __builtin_bit_cast(hv_t, (u2_t){h0, h1});
-            ll = __builtin_bit_cast(hv_t, (u2_t){l0, l1});
+            hh = __builtin_bit_cast(hv_t, (u32x2){h0, h1});
+            ll = __builtin_bit_cast(hv_t, (u32x2){l0, l1});
           }
           if (p < kKP) {
             *reinterpret_cast<hv_t*>(wfh + ql * SH + p * CC + NTC * p16) = hh;
@@ -519,8 +518,8 @@ __global__ __launch_bounds__(64 * P1W) void k_kpconv_mfma(
       constexpr int KS = KW / 32;                                  // k-steps per channel chunk
       // fragment-order planes (k_w_prep): 512 halves per (chunk, n-tile, k-step)
       const size_t wofs = ((size_t)(c0 / CC) * (cout / 16) + ng * NTW) * KS * 512 + lane * 8;
-      kh8 bh[D][NTW], bl[D][NTW];
-      auto load_step = [&](int ks, kh8 (&dh)[NTW], kh8 (&dl)[NTW]) {
+      f16x8 bh[D][NTW], bl[D][NTW];
+      auto load_step = [&](int ks, f16x8 (&dh)[NTW], f16x8 (&dl)[NTW]) {
         const size_t gk = wofs + (size_t)(ks0 + ks) * 512;
 #pragma unroll
         for (int t = 0; t < NTW; ++t) {
@@ -530,16 +529,14 @@ __global__ __launch_bounds__(64 * P1W) void k_kpconv_mfma(
           asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(dl[t]) : "v"(pl));
         }
       };
-      auto mma_step = [&](int ks, const kh8 (&sh)[NTW], const kh8 (&sl)[NTW]) {
+      auto mma_step = [&](int ks, const f16x8 (&sh)[NTW], const f16x8 (&sl)[NTW]) {
 #pragma unroll
         for (int m = 0; m < MTW; ++m) {
-          const kh8 ah = *reinterpret_cast<const kh8*>(ah_row + m * 16 * SH + 32 * (ks0 + ks));
-          const kh8 al = *reinterpret_cast<const kh8*>(al_row + m * 16 * SH + 32 * (ks0 + ks));
+          const f16x8 ah = *reinterpret_cast<const f16x8*>(ah_row + m * 16 * SH + 32 * (ks0 + ks));
+          const f16x8 al = *reinterpret_cast<const f16x8*>(al_row + m * 16 * SH + 32 * (ks0 + ks));
 #pragma unroll
           for (int t = 0; t < NTW; ++t) {
-            acc2[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, sl[t], acc2[m][t], 0, 0, 0);
-            acc2[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, sh[t], acc2[m][t], 0, 0, 0);
-            acc2[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, sh[t], acc2[m][t], 0, 0, 0);
+            acc2[m][t] = mma3_16(ah, al, sh[t], sl[t], acc2[m][t]);
           }
         }
       };
@@ -830,14 +827,14 @@ __global__ __launch_bounds__(512, (RingShape<CC, COUT, NS>::MINW)) void k_kpconv
   // phase-2 role and the wave's slice of W, resident in registers for the whole launch
   const int ng = wave % NG, sp = wave / NG;
   const int ks0 = sp * KSW;
-  kh8 bh[KSW], bl[KSW];
+  f16x8 bh[KSW], bl[KSW];
 #pragma unroll
   for (int k = 0; k < KSW; ++k) {
     const int ks = ks0 + k;
     if (ks < KS) {
       const size_t o = ((size_t)ng * KS + ks) * 512 + lane * 8;
-      bh[k] = *reinterpret_cast<const kh8*>(Wh + o);
-      bl[k] = *reinterpret_cast<const kh8*>(Wl + o);
+      bh[k] = *reinterpret_cast<const f16x8*>(Wh + o);
+      bl[k] = *reinterpret_cast<const f16x8*>(Wl + o);
     } else {
 #pragma unroll
       for (int e = 0; e < 8; ++e) { bh[k][e] = (_Float16)0.f; bl[k][e] = (_Float16)0.f; }
@@ -993,7 +990,7 @@ __global__ __launch_bounds__(512, (RingShape<CC, COUT, NS>::MINW)) void k_kpconv
       // C/D layout: row (kernel point) = 4*j4 + r, col = p16 <-> channels NTC*p16 + t
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int p = 4 * j4 + r;
+        const int p = acc_row16(r, j4);
         typedef typename VecH<NTC>::type hv_t;
         hv_t hh, ll;
         if constexpr (NTC == 2) {
@@ -1002,12 +999,11 @@ __global__ __launch_bounds__(512, (RingShape<CC, COUT, NS>::MINW)) void k_kpconv
           hh = __builtin_bit_cast(hv_t, hu);
           ll = __builtin_bit_cast(hv_t, lu);
         } else {
-          typedef unsigned int u2_t __attribute__((ext_vector_type(2)));
           unsigned int h0, l0, h1, l1;
           split_pk_s(acc[0][r], acc[1][r], sa, h0, l0);
           split_pk_s(acc[2][r], acc[3][r], sa, h1, l1);
-          hh = __builtin_bit_cast(hv_t, (u2_t){h0, h1});
-          ll = __builtin_bit_cast(hv_t, (u2_t){l0, l1});
+          hh = __builtin_bit_cast(hv_t, (u32x2){h0, h1});
+          ll = __builtin_bit_cast(hv_t, (u32x2){l0, l1});
         }
         if (p < kKP) {
           *reinterpret_cast<hv_t*>(wfh + ql * SH + p * CC + NTC * p16) = hh;
@@ -1093,11 +1089,9 @@ __global__ __launch_bounds__(512, (RingShape<CC, COUT, NS>::MINW)) void k_kpconv
 #pragma unroll
       for (int k = 0; k < KSW; ++k) {
         const int ks = min(ks0 + k, KS - 1);            // a slice short of KSW steps meets zero weights
-        const kh8 ah = *reinterpret_cast<const kh8*>(ah_row + 32 * ks);
-        const kh8 al = *reinterpret_cast<const kh8*>(al_row + 32 * ks);
-        acc2 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl[k], acc2, 0, 0, 0);
-        acc2 = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[k], acc2, 0, 0, 0);
-        acc2 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[k], acc2, 0, 0, 0);
+        const f16x8 ah = *reinterpret_cast<const f16x8*>(ah_row + 32 * ks);
+        const f16x8 al = *reinterpret_cast<const f16x8*>(al_row + 32 * ks);
+        acc2 = mma3_16(ah, al, bh[k], bl[k], acc2);
       }
     }
     if (sp > 0) {
@@ -1116,7 +1110,7 @@ __global__ __launch_bounds__(512, (RingShape<CC, COUT, NS>::MINW)) void k_kpconv
       // C layout: row (query of the tile) = 4*j4 + r, col = p16
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int ql = 4 * j4 + r;
+        const int ql = acc_row16(r, j4);
         pend_n[r] = lqid[par * kRingTQ + ql];
         const float inv = unscale / (float)max(lcnt[par * kRingTQ + ql], 1);   // unscale: exact power of two
         pend_v[r] = acc2[r] * inv;

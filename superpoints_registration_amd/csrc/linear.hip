@@ -24,11 +24,13 @@
 #include "attn_planes.h"
 #include "lds_dma.h"
 #include "spr_common.h"
+#include "split_mma.h"
 
 namespace spr {
 namespace {
 
 constexpr int BK = 32;
+static_assert(BK == kPlaneK, "the split kernels stage split_mma.h's slabs");
 constexpr int LDSK = BK + 1;
 
 // Epilogue of one 32x32 accumulator tile (C/D layout, dtype independent:
@@ -46,13 +48,13 @@ __device__ __forceinline__ float store_tile(const f32x16& acc, int row0, int col
   if (RES) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int row = min(row0 + (r & 3) + 8 * (r >> 2) + 4 * lh, M - 1);
+      const int row = min(row0 + acc_row32(r, lh), M - 1);
       res[r] = residual[(size_t)row * N + col];
     }
   }
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int row = row0 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+    const int row = row0 + acc_row32(r, lh);
     float v = acc[r] * unscale + bv;   // unscale: exact power of two (1 in the exact-f32 kernel)
     if (RES) v += res[r];
     if (ACT == SPR_ACT_RELU) v = fmaxf(v, 0.f);
@@ -176,29 +178,9 @@ __global__ __launch_bounds__(WM* WN * 64) void k_gemm_nt(
 }
 
 // ---------------------------------------------------------------------------
-// Split-fp16 GEMM ("h3"): fp32-level accuracy at ~5x the exact-f32 MFMA rate.
-//   x' = x s_x (s_x = per-tensor power of two, max |x'| in [2^14, 2^15))
-//   x' = hi + lo,  hi = fp16(x'),  lo = fp16(x' - hi)
-//   a.b ~= (ah.bh + ah.bl + al.bh) / (s_a s_b)        (al.bl ~ 2^-22 |a.b| dropped)
-// The matrix cores honour fp16 subnormals on both operands (measured with
-// scripts/abl/denorm.hip), so all three products share ONE fp32 accumulator.
-// Range safety (spr_common.h, split_pk_s): max |x| of each operand comes from a
-// pre-pass (launch_absmax -> 512 partials, reduced in this kernel's prologue), so
-// no operand can overflow fp16 and every element within 2^-18 of its tensor's
-// maximum keeps 22 significand bits; smaller ones keep an absolute error of
-// 2^-39 max|x|.  Products are exact in the MFMA and accumulate in fp32.  Three
-// v_mfma_f32_32x32x16_f16 per 16-deep k-step (32 cycles each) replace eight
-// v_mfma_f32_32x32x2_f32 (64 cycles each).  Operands are scaled + split on the
-// fly while a K-slab is staged into LDS (fp16 rows of 32+8 halves: 80-byte stride
-// -> conflict-free ds_read_b128 fragment reads).  spr_set_gemm_mode(0) selects the
-// exact-f32 kernel.
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int HS = 40;                 // LDS row stride in halves (BK = 32 + 8 pad)
-
+// Split-fp16 GEMM ("h3"): fp32-level accuracy at ~5x the exact-f32 MFMA rate.  The arithmetic, the fragment
+// conventions and the slab staging (slab_load / slab_store: operands are scaled + split on the fly while a K-slab
+// is staged into LDS) are those of split_mma.h.  spr_set_gemm_mode(0) selects the exact-f32 kernel.
 template <int BM, int BN, int WM, int WN, int ACT, bool RES, bool PLANES = false>
 __global__ __launch_bounds__(WM* WN * 64) void k_gemm_nt_h3(
     const float* __restrict__ Xp, int Mp, int K, const float* __restrict__ Wp, int Np,
@@ -226,14 +208,11 @@ __global__ __launch_bounds__(WM* WN * 64) void k_gemm_nt_h3(
     bid -= beg;
   }
   constexpr int TM = BM / (WM * 32), TN = BN / (WN * 32);   // 32x32 sub-tiles per wave
-  constexpr int A_F4 = BM * BK / 4, B_F4 = BN * BK / 4;
-  constexpr int A_PT = A_F4 / NT, B_PT = B_F4 / NT;
-  static_assert(A_F4 % NT == 0 && B_F4 % NT == 0, "slab must divide over the threads");
   extern __shared__ __align__(16) unsigned char gemm_smem[];
   _Float16* Ah = reinterpret_cast<_Float16*>(gemm_smem);
-  _Float16* Al = Ah + BM * HS;
-  _Float16* Bh = Al + BM * HS;
-  _Float16* Bl = Bh + BN * HS;
+  _Float16* Al = Ah + BM * kPlaneStride;
+  _Float16* Bh = Al + BM * kPlaneStride;
+  _Float16* Bl = Bh + BN * kPlaneStride;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int wm = wave / WN, wn = wave % WN;
   // 1-D grid, XCD-swizzled: the column tiles of one row panel share an L2
@@ -262,47 +241,16 @@ __global__ __launch_bounds__(WM* WN * 64) void k_gemm_nt_h3(
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-  f32x4 ra[A_PT], rb[B_PT];
+  f32x4 ra[BM * BK / 4 / NT], rb[BN * BK / 4 / NT];
   auto load_slab = [&](int k0) {
-#pragma unroll
-    for (int i = 0; i < A_PT; ++i) {
-      const int f = tid + i * NT;
-      const int r = f / (BK / 4), c4 = f % (BK / 4);
-      const float* p = X + (size_t)min(m0 + r, M - 1) * K + k0 + c4 * 4;
-      asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(ra[i]) : "v"(p));
-    }
-#pragma unroll
-    for (int i = 0; i < B_PT; ++i) {
-      const int f = tid + i * NT;
-      const int r = f / (BK / 4), c4 = f % (BK / 4);
-      const float* p = Wt + (size_t)min(n0 + r, N - 1) * K + k0 + c4 * 4;
-      asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(rb[i]) : "v"(p));
-    }
-  };
-  // rows past M / N are clamped on the load side: they produce finite garbage
-  // in accumulator rows / columns that store_tile never writes
-  auto split_store = [&](const f32x4& v, float sc, _Float16* hi, _Float16* lo) {
-    unsigned int h0, h1, l0, l1;
-    split_pk_s(v[0], v[1], sc, h0, l0);
-    split_pk_s(v[2], v[3], sc, h1, l1);
-    *reinterpret_cast<u32x2*>(hi) = (u32x2){h0, h1};
-    *reinterpret_cast<u32x2*>(lo) = (u32x2){l0, l1};
+    slab_load<BM, NT>(ra, X, M, K, tid, m0, k0);
+    slab_load<BN, NT>(rb, Wt, N, K, tid, n0, k0);
   };
   auto store_slab = [&]() {
     wait_vm<0>();
     __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int i = 0; i < A_PT; ++i) {
-      const int f = tid + i * NT;
-      const int r = f / (BK / 4), c4 = f % (BK / 4);
-      split_store(ra[i], sa, Ah + r * HS + c4 * 4, Al + r * HS + c4 * 4);
-    }
-#pragma unroll
-    for (int i = 0; i < B_PT; ++i) {
-      const int f = tid + i * NT;
-      const int r = f / (BK / 4), c4 = f % (BK / 4);
-      split_store(rb[i], sb, Bh + r * HS + c4 * 4, Bl + r * HS + c4 * 4);
-    }
+    slab_store<BM, NT>(ra, sa, Ah, Al, tid);
+    slab_store<BN, NT>(rb, sb, Bh, Bl, tid);
   };
 
   load_slab(0);
@@ -317,32 +265,17 @@ __global__ __launch_bounds__(WM* WN * 64) void k_gemm_nt_h3(
       const int ko = 16 * s + 8 * lh;
       f16x8 ah[TM], al[TM], bh[TN], bl[TN];
 #pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const int row = (wm * TM + i) * 32 + l31;
-        ah[i] = *reinterpret_cast<const f16x8*>(Ah + row * HS + ko);
-        al[i] = *reinterpret_cast<const f16x8*>(Al + row * HS + ko);
-      }
+      for (int i = 0; i < TM; ++i) frag_ld40(Ah, Al, (wm * TM + i) * 32 + l31, ko, ah[i], al[i]);
 #pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int row = (wn * TN + j) * 32 + l31;
-        bh[j] = *reinterpret_cast<const f16x8*>(Bh + row * HS + ko);
-        bl[j] = *reinterpret_cast<const f16x8*>(Bl + row * HS + ko);
-      }
+      for (int j = 0; j < TN; ++j) frag_ld40(Bh, Bl, (wn * TN + j) * 32 + l31, ko, bh[j], bl[j]);
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-          // small terms first, then the dominant one
-          if (PLANES) {
-            // transposed product: lane = token (X row), registers = features (W rows)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[j], ah[i], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[j], al[i], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[j], ah[i], acc[i][j], 0, 0, 0);
-          } else {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-          }
+          // small terms first, then the dominant one.  PLANES: transposed product (lane = token (X row),
+          // registers = features (W rows)) with the bits of the untransposed one
+          if (PLANES) acc[i][j] = mma3_32<true>(bh[j], bl[j], ah[i], al[i], acc[i][j]);
+          else acc[i][j] = mma3_32(ah[i], al[i], bh[j], bl[j], acc[i][j]);
         }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -374,7 +307,7 @@ __global__ __launch_bounds__(WM* WN * 64) void k_gemm_nt_h3(
 #pragma unroll
           for (int r = 0; r < 16; r += 2) {
             // registers r, r+1 = adjacent features (two plane rows), same token column
-            const int d = (r & 3) + 8 * (r >> 2) + 4 * lh;
+            const int d = acc_row32(r, lh);
             const float a = acc[i][j][r] * unscale + bias[fl + d];
             const float b = acc[i][j][r + 1] * unscale + bias[fl + d + 1];
             unsigned int hu, lu;
@@ -393,14 +326,10 @@ __global__ __launch_bounds__(WM* WN * 64) void k_gemm_nt_h3(
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
             const int d0 = 8 * g + 4 * lh;                      // registers 4g..4g+3 = features d0..d0+3
-            float v[4];
+            f32x4 v;
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * g + e] * unscale + bias[fl + d0 + e];
-            unsigned int h0, h1, l0, l1;
-            split_pk_s(v[0], v[1], pmul, h0, l0);
-            split_pk_s(v[2], v[3], pmul, h1, l1);
-            *reinterpret_cast<u32x2*>(ph + row + d0) = (u32x2){h0, h1};
-            *reinterpret_cast<u32x2*>(pw + row + d0) = (u32x2){l0, l1};
+            split_store4(v, pmul, ph + row + d0, pw + row + d0);
           }
         }
       }
@@ -453,13 +382,12 @@ __global__ __launch_bounds__(512) void k_gemm_nt_h3p(
     float* __restrict__ out_parts, int ntiles) {
   constexpr int K = 256, NSLAB = K / BK;
   constexpr int BM = 128, BN = 256, WN = 4, NT = 512, TM = 2, TN = 2;
-  constexpr int A_PT = BM * BK / 4 / NT, B_PT = BN * BK / 4 / NT;   // 2, 4 float4 per thread and slab
   constexpr int QPS = 16 / NSLAB;                                   // quarters leaving per slab: 2
   extern __shared__ __align__(16) unsigned char gemm_smem[];
   _Float16* Ah = reinterpret_cast<_Float16*>(gemm_smem);
-  _Float16* Al = Ah + BM * HS;
-  _Float16* Bh = Al + BM * HS;
-  _Float16* Bl = Bh + BN * HS;
+  _Float16* Al = Ah + BM * kPlaneStride;
+  _Float16* Bh = Al + BM * kPlaneStride;
+  _Float16* Bl = Bh + BN * kPlaneStride;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int wm = wave / WN, wn = wave % WN;
   const int l31 = lane & 31, lh = lane >> 5;
@@ -477,43 +405,14 @@ __global__ __launch_bounds__(512) void k_gemm_nt_h3p(
   }
 
   f32x16 acc[TM][TN], prev[TM][TN];
-  f32x4 ra[A_PT], rb[B_PT];
+  f32x4 ra[BM * BK / 4 / NT], rb[BN * BK / 4 / NT];   // 2, 4 float4 per thread and slab
   auto load_slab = [&](int m0, int n0, int k0) {
-#pragma unroll
-    for (int i = 0; i < A_PT; ++i) {
-      const int f = tid + i * NT;
-      const int r = f / (BK / 4), c4 = f % (BK / 4);
-      const float* p = X + (size_t)min(m0 + r, M - 1) * K + k0 + c4 * 4;
-      asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(ra[i]) : "v"(p));
-    }
-#pragma unroll
-    for (int i = 0; i < B_PT; ++i) {
-      const int f = tid + i * NT;
-      const int r = f / (BK / 4), c4 = f % (BK / 4);
-      const float* p = Wt + (size_t)min(n0 + r, N - 1) * K + k0 + c4 * 4;
-      asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(rb[i]) : "v"(p));
-    }
+    slab_load<BM, NT>(ra, X, M, K, tid, m0, k0);
+    slab_load<BN, NT>(rb, Wt, N, K, tid, n0, k0);
   };
-  auto split_store = [&](const f32x4& v, float sc, _Float16* hi, _Float16* lo) {
-    unsigned int h0, h1, l0, l1;
-    split_pk_s(v[0], v[1], sc, h0, l0);
-    split_pk_s(v[2], v[3], sc, h1, l1);
-    *reinterpret_cast<u32x2*>(hi) = (u32x2){h0, h1};
-    *reinterpret_cast<u32x2*>(lo) = (u32x2){l0, l1};
-  };
-  auto store_slab = [&]() {
-#pragma unroll
-    for (int i = 0; i < A_PT; ++i) {
-      const int f = tid + i * NT;
-      const int r = f / (BK / 4), c4 = f % (BK / 4);
-      split_store(ra[i], sa, Ah + r * HS + c4 * 4, Al + r * HS + c4 * 4);
-    }
-#pragma unroll
-    for (int i = 0; i < B_PT; ++i) {
-      const int f = tid + i * NT;
-      const int r = f / (BK / 4), c4 = f % (BK / 4);
-      split_store(rb[i], sb, Bh + r * HS + c4 * 4, Bl + r * HS + c4 * 4);
-    }
+  auto store_slab = [&]() {   // the caller has counted its waits
+    slab_store<BM, NT>(ra, sa, Ah, Al, tid);
+    slab_store<BN, NT>(rb, sb, Bh, Bl, tid);
   };
 
   // deferred tile
@@ -595,25 +494,13 @@ __global__ __launch_bounds__(512) void k_gemm_nt_h3p(
         const int ko = 16 * ks + 8 * lh;
         f16x8 ah[TM], al[TM], bh[TN], bl[TN];
 #pragma unroll
-        for (int i = 0; i < TM; ++i) {
-          const int row = (wm * TM + i) * 32 + l31;
-          ah[i] = *reinterpret_cast<const f16x8*>(Ah + row * HS + ko);
-          al[i] = *reinterpret_cast<const f16x8*>(Al + row * HS + ko);
-        }
+        for (int i = 0; i < TM; ++i) frag_ld40(Ah, Al, (wm * TM + i) * 32 + l31, ko, ah[i], al[i]);
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          const int row = (wn * TN + j) * 32 + l31;
-          bh[j] = *reinterpret_cast<const f16x8*>(Bh + row * HS + ko);
-          bl[j] = *reinterpret_cast<const f16x8*>(Bl + row * HS + ko);
-        }
+        for (int j = 0; j < TN; ++j) frag_ld40(Bh, Bl, (wn * TN + j) * 32 + l31, ko, bh[j], bl[j]);
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
-          for (int j = 0; j < TN; ++j) {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-          }
+          for (int j = 0; j < TN; ++j) acc[i][j] = mma3_32(ah[i], al[i], bh[j], bl[j], acc[i][j]);
       }
       __builtin_amdgcn_sched_barrier(0);
       young = false;
@@ -861,7 +748,7 @@ int launch_gemm(const float* x, int m, int k, const float* w, int n, const float
   if (spr::g_gemm_mode.load(std::memory_order_relaxed) == 1) {
     SPR_REQUIRE(a_parts != nullptr && w_parts != nullptr, "linear: split-fp16 mode needs the absmax partials");
     // LDS bytes of a BM x BN tile's slab (hi + lo planes of both operands)
-    auto lds = [](int bm, int bn) { return (size_t)(bm + bn) * spr::HS * 2 * sizeof(_Float16); };
+    auto lds = [](int bm, int bn) { return (size_t)(bm + bn) * spr::kPlaneStride * 2 * sizeof(_Float16); };
     if (!RES && ACT <= SPR_ACT_SIGMOID && n >= 256 && k == 256 && m >= 1024 && m < 32768) {
       // persistent 128x256 tiles (k_gemm_nt_h3p): for a few thousand rows the finer tiles fill the
       // chip better (27 vs 43 us at 5 000 x 256 x 300); at 60 k rows both forms sit on the CU's
@@ -921,7 +808,7 @@ int spr::launch_inproj_planes(const float* x, int m, int k, const float* w, int 
               "in-projection planes: bad shape (m=%d k=%d n=%d)", m, k, n);
   SPR_REQUIRE(a_parts && w_parts && planes.scales, "in-projection planes: missing scale inputs");
   auto kern = spr::k_gemm_nt_h3<256, 256, 4, 2, SPR_ACT_NONE, false, true>;
-  const size_t lds = (size_t)(256 + 256) * spr::HS * 2 * sizeof(_Float16);
+  const size_t lds = (size_t)(256 + 256) * spr::kPlaneStride * 2 * sizeof(_Float16);
   if (int rc = ensure_dyn_lds((const void*)kern, (int)lds)) return rc;
   hipLaunchKernelGGL(kern, dim3(cdiv(n, 256) * cdiv(m, 256)), dim3(512), lds, stream, x, m, k, w, n, bias,
                      (const float*)nullptr, (float*)nullptr, planes, f0, a_parts, n_aparts, w_parts, (float*)nullptr,
@@ -954,7 +841,7 @@ template <int ACT>
 int launch_grouped_act(const float* a, int k, const float* b, float* c, const spr::GemmGroup* groups_dev,
                        int total_tiles, int max_n, const float* a_parts, const float* w_parts, const float* epi,
                        hipStream_t stream) {
-  auto lds = [](int bm, int bn) { return (size_t)(bm + bn) * spr::HS * 2 * sizeof(_Float16); };
+  auto lds = [](int bm, int bn) { return (size_t)(bm + bn) * spr::kPlaneStride * 2 * sizeof(_Float16); };
   int bm, bn;
   spr::gemm_group_tile(max_n, &bm, &bn);
   if (bn == 256) {

@@ -24,6 +24,7 @@
 // spr_reduce_parts, the bias gradients through spr_colsum: fixed partitions, fixed summation order, no atomics --
 // two calls give the same bits.  Tokens are processed in groups of 16 384 so that the workspace stays bounded.
 #include "spr_common.h"
+#include "split_mma.h"
 
 namespace spr {
 namespace {
@@ -37,9 +38,6 @@ struct PmParams {
   const float* w[5];
   const float* b[5];
 };
-
-// row of the 32 x 32 accumulator that register r of lane half lh holds (column = lane & 31)
-__device__ __forceinline__ int acc_row(int r, int lh) { return (r & 3) + 8 * (r >> 2) + 4 * lh; }
 
 // acc[mi] = A B over K.  A(token, k) = src[k * LDA + token] in LDS (LDA = 32 MI + 1); B(k, n) = W[n * K + k]
 // (TRANS = false: y = h W^T of nn.Linear) or W[k * N + n] (TRANS = true: the backward's delta W).  Contains barriers:
@@ -134,7 +132,7 @@ __device__ __forceinline__ void layer1(const PmParams& p, const float* xs, float
   for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int t = 32 * mi + acc_row(r, lh);
+      const int t = acc_row32(r, lh, 32 * mi);
       const float v = relu(((w0 * xs[3 * t] + w1 * xs[3 * t + 1]) + w2 * xs[3 * t + 2]) + b);
       dst[c * LDA + t] = v;
       if (v > 0.f) mask |= 1u << (16 * mi + r);
@@ -156,7 +154,7 @@ __device__ __forceinline__ void epilogue_fwd(const f32x16 (&acc)[MI], const floa
   for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int t = 32 * mi + acc_row(r, lh);
+      const int t = acc_row32(r, lh, 32 * mi);
       const float v = relu(acc[mi][r] + b);
       if (dst != nullptr) dst[n * LDA + t] = v;
       if (v > 0.f) mask |= 1u << (16 * mi + r);
@@ -174,7 +172,7 @@ __device__ __forceinline__ void epilogue_bwd(const f32x16 (&acc)[1], unsigned ma
   const int n = wave * 32 + l31;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int t = acc_row(r, lh);
+    const int t = acc_row32(r, lh);
     const float v = (mask >> r) & 1u ? acc[0][r] : 0.f;
     if (dst != nullptr) dst[n * LDA + t] = v;
     if (t < valid) dl[(size_t)t * N + n] = v;
@@ -217,7 +215,7 @@ __global__ __launch_bounds__(NT) void k_posemb_mlp_fwd(const float* __restrict__
   for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int t = t0 + 32 * mi + acc_row(r, lh);
+      const int t = acc_row32(r, lh, t0 + 32 * mi);
       if (t < T) pe[(size_t)t * 256 + n] = acc[mi][r] + b;
     }
 }

@@ -128,8 +128,10 @@ int launch_absmax2(const float* x0, long rows0, int cols0, long stride0, float* 
 
 // ---- device helpers --------------------------------------------------------
 #ifdef __HIPCC__
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));   // the wider fp16 / packed-integer types: split_mma.h
 
 // Largest s in [0, nseg) with cu[s] <= i  (cu[0] = 0, cu non-decreasing).
 __device__ __forceinline__ int find_segment(const int* __restrict__ cu, int nseg,
@@ -163,9 +165,8 @@ __device__ __forceinline__ int xcd_swizzle(int b, int nwg) {
 // hi_u / lo_u hold (a, b) as packed halves.  UNSCALED form: only for operands
 // whose magnitude is known to sit in fp16's comfortable range (softmax
 // probabilities); everything else goes through split_pk_s.
-typedef _Float16 spr_h16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void split_pk(float a, float b, unsigned int& hi_u, unsigned int& lo_u) {
-  const spr_h16x2 hi = {(_Float16)a, (_Float16)b};
+  const f16x2 hi = {(_Float16)a, (_Float16)b};
   hi_u = __builtin_bit_cast(unsigned int, hi);
   asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]\n\t"
       "v_fma_mixhi_f16 %0, %1, -1.0, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]"

@@ -54,12 +54,11 @@
 #include "attn_planes.h"
 #include "lds_dma.h"
 #include "spr_common.h"
+#include "split_mma.h"
 
 namespace spr {
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int XD = 256;            // d_model
 constexpr int XCHUNK = 32768;      // bytes per weight chunk (32 fragments of 1 KiB)
@@ -256,9 +255,6 @@ __device__ __forceinline__ void frag_ld(const unsigned char* slot, int lane, int
   h = fr[(2 * i) * 64];
   l = fr[(2 * i + 1) * 64];
 }
-__device__ __forceinline__ f32x16 mfma1(const f16x8& a, const f16x8& b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
 
 // LDS: [ring XSLOTS x XCHUNK] [tables] [cu]
 constexpr int T_BO = 0, T_B2 = 256, T_GM = 512, T_BM = 768, T_GT = 1024, T_BT = 1280, T_BIN = 1536, T_B1 = 2304;
@@ -453,15 +449,15 @@ __global__ __launch_bounds__(256, 1) void k_xenc_chain(ChainArgs args_by_value) 
       if (step_stamp >= 0) XSTAMP_IT(step_stamp + i);
 #endif
       if (i == 8) nxt = acquire();
-      acc = SW ? mfma1(xh[i], cy.l[i & (XRING - 1)], acc) : mfma1(cy.l[i & (XRING - 1)], xh[i], acc);
+      acc = SW ? mma1_32(xh[i], cy.l[i & (XRING - 1)], acc) : mma1_32(cy.l[i & (XRING - 1)], xh[i], acc);
       XSB();
       side(2 * i);
       XSB();
-      acc = SW ? mfma1(xl[i], cy.h[i & (XRING - 1)], acc) : mfma1(cy.h[i & (XRING - 1)], xl[i], acc);
+      acc = SW ? mma1_32(xl[i], cy.h[i & (XRING - 1)], acc) : mma1_32(cy.h[i & (XRING - 1)], xl[i], acc);
       XSB();
       side(2 * i + 1);
       XSB();
-      acc = SW ? mfma1(xh[i], cy.h[i & (XRING - 1)], acc) : mfma1(cy.h[i & (XRING - 1)], xh[i], acc);
+      acc = SW ? mma1_32(xh[i], cy.h[i & (XRING - 1)], acc) : mma1_32(cy.h[i & (XRING - 1)], xh[i], acc);
       XSB();
       if (i + XPF < 16) frag_ld(slot, lane, i + XPF, cy.h[(i + XPF) & (XRING - 1)], cy.l[(i + XPF) & (XRING - 1)]);
       else frag_ld(nxt, lane, i + XPF - 16, cy.h[(i + XPF) & (XRING - 1)], cy.l[(i + XPF) & (XRING - 1)]);
@@ -480,15 +476,15 @@ __global__ __launch_bounds__(256, 1) void k_xenc_chain(ChainArgs args_by_value) 
       if (step_stamp >= 0) XSTAMP_IT(step_stamp + i);
 #endif
       if (i == 8) nxt = acquire();
-      y[i >> 1] = mfma1(cy.l[i & (XRING - 1)], hh[i & 1], y[i >> 1]);
+      y[i >> 1] = mma1_32(cy.l[i & (XRING - 1)], hh[i & 1], y[i >> 1]);
       XSB();
       side(2 * i);
       XSB();
-      y[i >> 1] = mfma1(cy.h[i & (XRING - 1)], hl[i & 1], y[i >> 1]);
+      y[i >> 1] = mma1_32(cy.h[i & (XRING - 1)], hl[i & 1], y[i >> 1]);
       XSB();
       side(2 * i + 1);
       XSB();
-      y[i >> 1] = mfma1(cy.h[i & (XRING - 1)], hh[i & 1], y[i >> 1]);
+      y[i >> 1] = mma1_32(cy.h[i & (XRING - 1)], hh[i & 1], y[i >> 1]);
       XSB();
       if (i + XPF < 16) frag_ld(slot, lane, i + XPF, cy.h[(i + XPF) & (XRING - 1)], cy.l[(i + XPF) & (XRING - 1)]);
       else frag_ld(nxt, lane, i + XPF - 16, cy.h[(i + XPF) & (XRING - 1)], cy.l[(i + XPF) & (XRING - 1)]);
