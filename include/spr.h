@@ -920,6 +920,35 @@ int spr_match_sinkhorn(const float* feat, int d, const float* xyz, const int* cu
 int spr_gather_rows(const float* x, int n_src, int c, const int* idx, int n,
                     float* out, void* stream);
 
+/* ---- decoder: nearest upsample + skip concatenation + unary projection in one GEMM ----------
+ * Replaces NearestUpsampleBlock.forward -> closest_pool (kpconv_blocks.py:757-768, :112-124), the torch.cat of
+ * KPFDecoder.forward (kpconv.py:156-158) and the UnaryBlock.mlp behind it (kpconv_blocks.py:549,:557):
+ *   y[i, :] = [ xc[idx0[i], :] | xs[i, :] ] . w^T        (no bias, no activation, no norm)
+ * xc [nc, kc] coarse features, xs [n, ks] skip features, w [n_out, kc + ks] = UnaryBlock.mlp.weight, y [n, n_out],
+ * all f32 row-major.  idx0[i] = idx[i * idx_stride]: column 0 of an i32 [n, idx_stride] matrix (idx_stride >= 1), so
+ * the int32 upsamples matrix of the pyramid goes in as it is.  A row whose index is >= nc (the shadow index) or < 0
+ * contributes a zero coarse row (closest_pool's appended zero row, spr_gather_rows' rule); the call never reads
+ * outside xc.  The gathered and the concatenated rows are never written: the tiles gather while they are staged.
+ * nc >= 1; n = 0 is legal (nothing is launched).  kc and ks multiples of 32, n_out >= 32 (status 2 otherwise).
+ * Arithmetic follows spr_set_gemm_mode.  Mode 1: xc and xs share ONE power-of-two scale, taken from the larger of
+ *   their two ranges, so the result has the error bound of spr_linear on the concatenated tensor; mode 0: exact f32,
+ *   one fmaf chain over the kc + ks columns.  The reduction order is fixed and there are no atomics: a row's bits
+ *   depend on that row's operands (and, in mode 1, on the two scales) only -- not on its position or on the batch.
+ * xc_range / xs_range / w_range (+ counts): operand ranges as in spr_linear (NULL = measured here; a range of xc
+ *   bounds all of its rows, gathered or not).  out_range / out_range_cap / out_range_n_host: published like
+ *   spr_linear's without residual (one partial per workgroup in mode 1 when they fit, else *out_range_n_host = 0).
+ * ws: spr_upsample_unary_workspace_size() bytes of device scratch (the three ranges' partials; unused in mode 0).
+ * spr_upsample_unary_supported: 1 where the fused call is the host layer's default for the shape, 0 where it takes
+ *   gather + two spr_linear calls instead (no kernel for the shape, or none that measured faster).
+ */
+int spr_upsample_unary_supported(int kc, int ks, int n_out);
+size_t spr_upsample_unary_workspace_size(void);
+int spr_upsample_unary(const float* xc, int nc, int kc, const float* xs, int n, int ks, const int* idx,
+                       int idx_stride, const float* w, int n_out, float* y, const float* xc_range, int xc_range_n,
+                       const float* xs_range, int xs_range_n, const float* w_range, int w_range_n,
+                       float* out_range, int out_range_cap, int* out_range_n_host, void* ws, size_t ws_bytes,
+                       void* stream);
+
 /* ---- pair assembly: encoded clouds -> the token layout of a list of pairs ---------
  * RegTR.register (regtr.py): a cloud is encoded once (pyramid, KPConv encoder, feat_proj) and used by
  * any number of pairs.  x [t_in, c] holds the packed rows of n_clouds clouds (cu [n_clouds + 1]);

@@ -131,6 +131,10 @@ SIGNATURES = {
     "spr_transform_l1_pair": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _sz, _vp]),
     "spr_sum_scaled": (_i, [_vp, _i, _f, _vp, _vp]),
     "spr_gather_rows": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp]),
+    "spr_upsample_unary_supported": (_i, [_i, _i, _i]),
+    "spr_upsample_unary_workspace_size": (_sz, []),
+    "spr_upsample_unary": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i,
+                                _vp, _vp, _sz, _vp]),
     "spr_pair_gather": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp]),
     "spr_pair_gather_bwd": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp]),
     "spr_overlap_pool_pairs": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp]),

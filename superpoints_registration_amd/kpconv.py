@@ -1,7 +1,7 @@
-"""KPConv pyramid preprocessing and encoder on the HIP library.
+"""KPConv pyramid preprocessing, encoder and decoder on the HIP library.
 
 Public names follow the reference's ``src/models/backbone_kpconv/kpconv.py`` so
-that RegTR-style callers keep working: KPFEncoder (:22-92), Preprocessor
+that RegTR-style callers keep working: KPFEncoder (:22-92), KPFDecoder (:95-168), Preprocessor
 (:295-418) / PreprocessorGPU (:421-549), batch_grid_subsampling_kpconv (:174),
 batch_neighbors_kpconv (:247) and their *_gpu aliases (:217, :265),
 calibrate_neighbors (:714, defined in calibration.py).
@@ -31,9 +31,9 @@ from typing import List, Optional
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import decoder, ops
 from . import tie_order as _tie
-from .kpconv_blocks import block_decider
+from .kpconv_blocks import NearestUpsampleBlock, UnaryBlock, _cu_of, _idx_of, _maxlen_of, block_decider
 
 NEIGHBOR_SELECT = {'nearest': ops.SELECT_NEAREST, 'index': ops.SELECT_INDEX}
 
@@ -113,8 +113,16 @@ class KPFEncoder(nn.Module):
         # skip taps: the input of every strided block, plus the final features
         self.encoder_skips = [i for i, b in enumerate(blocks) if b.down]
         self.encoder_skip_dims = [b.in_dim for b in blocks if b.down]
-        self.encoder_skips.append(len(blocks) - 1)
-        self.encoder_skip_dims.append(final_dim)
+        arch = list(config.architecture)
+        if len(blocks) < len(arch) and 'upsample' in arch[len(blocks)]:
+            # a decoder follows (kpconv.py:44-50, :74): the upsample block's own index and input width are listed
+            # and the final tap is not added; forward() never reaches that index, so skip_x holds one tensor per
+            # strided block
+            self.encoder_skips.append(len(blocks))
+            self.encoder_skip_dims.append(final_dim)
+        else:
+            self.encoder_skips.append(len(blocks) - 1)
+            self.encoder_skip_dims.append(final_dim)
 
     def forward(self, x, batch):
         skip_x = []
@@ -142,6 +150,74 @@ class KPFEncoder(nn.Module):
                 i += 1
         assert i == len(self.encoder_blocks), "pyramid ended before the encoder"
         return x, skip_x, meta
+
+
+class KPFDecoder(nn.Module):
+    """Upsampling half of the backbone (kpconv.py:95-168; Predator's dense descriptors -- RegTR itself never builds
+    it).  Attributes `decoder_blocks`, `decoder_concats`, the state-dict names and the (x, x_all) return value match
+    the reference.  A NearestUpsampleBlock followed by a UnaryBlock runs as ONE projection that gathers while it
+    stages its tiles (decoder.upsample_unary): the upsampled and the concatenated tensors are never produced."""
+
+    def __init__(self, config, in_dim, encoder_skip_dims, reduce_channel_when_upsample=True):
+        super().__init__()
+        out_dim = in_dim
+        self.decoder_blocks = nn.ModuleList()
+        self.decoder_concats = []
+        arch = list(config.architecture)
+        # first upsampling block, and the level / radius the encoder ends on
+        octave, start_i = 0, 0
+        r = config.first_subsampling_dl * config.conv_radius
+        for block_i, block in enumerate(arch):
+            if 'upsample' in block:
+                start_i = block_i
+                break
+            elif 'pool' in block or 'strided' in block:
+                octave += 1
+                r *= 2
+        for block_i, block in enumerate(arch[start_i:]):
+            # a block behind an upsample reads the skip tensor of its level as well
+            if block_i > 0 and 'upsample' in arch[start_i + block_i - 1]:
+                in_dim += encoder_skip_dims[octave]
+                self.decoder_concats.append(block_i)
+            self.decoder_blocks.append(block_decider(block, r, in_dim, out_dim, octave, config))
+            in_dim = out_dim
+            if 'upsample' in block:
+                octave -= 1
+                r *= 0.5
+                if reduce_channel_when_upsample:
+                    out_dim = out_dim // 2
+
+    def forward(self, x, skip_x, batch):
+        x_all = []
+        pyr = len(batch['stack_lengths']) - 1
+        blocks = self.decoder_blocks
+        i = 0
+        while i < len(blocks):
+            block = blocks[i]
+            nxt = blocks[i + 1] if i + 1 < len(blocks) else None
+            if (isinstance(block, NearestUpsampleBlock) and isinstance(nxt, UnaryBlock)
+                    and i not in self.decoder_concats):
+                # upsample + unary: block i + 1 is in decoder_concats by construction
+                pyr -= 1
+                y = decoder.upsample_unary(x, skip_x.pop(), _idx_of(batch, 'upsamples', block.layer_ind - 1),
+                                           nxt.mlp.weight)
+                x = nxt.batch_norm(y, batch['stack_lengths'][pyr], cu=_cu_of(batch, pyr),
+                                   slope=1.0 if nxt.no_relu else 0.1, max_len=_maxlen_of(batch, pyr))
+                x_all.append(x)
+                i += 2
+                continue
+            if i in self.decoder_concats:
+                pyr -= 1
+            if isinstance(block, UnaryBlock):
+                y = decoder.concat_unary(x, skip_x.pop(), block.mlp.weight)
+                x = block.batch_norm(y, batch['stack_lengths'][pyr], cu=_cu_of(batch, pyr),
+                                     slope=1.0 if block.no_relu else 0.1, max_len=_maxlen_of(batch, pyr))
+            else:
+                x = block(x, batch)
+            if i in self.decoder_concats:
+                x_all.append(x)
+            i += 1
+        return x, x_all
 
 
 # --------------------------------------------------------------------------- #

@@ -4,9 +4,14 @@ arguments, forward signatures and state-dict names), computing through the HIP
 library.  Under torch.no_grad() (inference) the calls are plain C-ABI launches; with
 gradients enabled they go through the explicit HIP backward of autograd.py.
 
+The decoder's blocks are here as well: NearestUpsampleBlock, and the UnaryBlock
+that KPFDecoder (kpconv.py) feeds with the upsampled features and a skip tensor.
+
 Not mirrored (never selected by a shipped config):
 deformable / modulated KPConv, 'closest' aggregation, 'constant'/'gaussian'
-influence, GlobalAverage / NearestUpsample / MaxPool blocks.
+influence, and the blocks 'unary2', 'global_average', 'max_pool*' and the
+deformable / equivariant / invariant names: block_decider raises ValueError
+for them.
 """
 import math
 
@@ -129,6 +134,8 @@ def block_decider(block_name, radius, in_dim, out_dim, layer_ind, config):
         return SimpleBlock(block_name, in_dim, out_dim, radius, layer_ind, config)
     elif block_name in ['resnetb', 'resnetb_strided']:
         return ResnetBottleneckBlock(block_name, in_dim, out_dim, radius, layer_ind, config)
+    elif block_name == 'nearest_upsample':
+        return NearestUpsampleBlock(layer_ind)
     else:
         raise ValueError('Unknown / unsupported block name in the architecture definition : ' + block_name)
 
@@ -331,3 +338,19 @@ class ResnetBottleneckBlock(nn.Module):
         # unary2 (no relu) + shortcut, then LeakyReLU: fused into unary2's norm pass
         return self.unary2(x, stack_lengths_post, cu=cu_post, add=shortcut, final_slope=0.1,
                            max_len=ml_post)
+
+
+class NearestUpsampleBlock(nn.Module):
+    """kpconv_blocks.py:757-772: every point of level layer_ind - 1 takes the features of its nearest point of level
+    layer_ind (column 0 of the upsamples matrix; the shadow index reads a zero row).  KPFDecoder runs this block and
+    a UnaryBlock behind it as one projection that never writes the gathered tensor (decoder.upsample_unary)."""
+
+    def __init__(self, layer_ind):
+        super().__init__()
+        self.layer_ind = layer_ind
+
+    def forward(self, x, batch):
+        return closest_pool(x, _idx_of(batch, 'upsamples', self.layer_ind - 1))
+
+    def __repr__(self):
+        return 'NearestUpsampleBlock(layer: {:d} -> {:d})'.format(self.layer_ind, self.layer_ind - 1)
