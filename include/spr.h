@@ -436,6 +436,23 @@ int spr_kpconv_fwd(const float* q_xyz, int nq, const float* s_xyz, int ns, const
                    const float* w_range, int w_range_n, const void* plan, const void* wplanes,
                    void* ws, size_t ws_bytes, void* stream);
 
+/* Encoder stem in inference: the first block's KPConv (cin = 1, x [ns,1]) + per-cloud InstanceNorm + LeakyReLU,
+ *   out [nq,cout] = lrelu(IN(spr_kpconv_fwd(...)), slope)
+ * without the raw [nq,cout] tensor: only the 16 normalised influence sums per query are kept (in ws) and the rows
+ * are formed twice from them, for the statistics and for the output.  Row values have spr_kpconv_fwd's bits; the
+ * statistics are summed in float64 over 512-row slices from each cloud's first row (batch invariant) in another order
+ * than spr_instnorm's, so a mean or rstd may be the adjacent float32.  cu [nb+1] over the nq rows, max_len_host, eps,
+ * out_range / out_range_n as in spr_instnorm; mean_out / rstd_out (or NULL): [nb,cout], receive the statistics.
+ * spr_kpconv_stem_supported: cin == 1, cout a multiple of 16, at most 16
+ * kernel points; other shapes are refused (the caller uses spr_kpconv_fwd + spr_instnorm). */
+int spr_kpconv_stem_supported(int cin, int cout, int n_kp);
+size_t spr_kpconv_stem_workspace_size(int nq, int ns, int nb, int max_len_host, int cout);
+int spr_kpconv_stem(const float* q_xyz, int nq, const float* s_xyz, int ns, const int* nbr, int nbr_stride,
+                    int kmax, int rows_sorted, const float* x, const float* weights, int cout,
+                    const float* kernel_points, int n_kp, float kp_extent, const int* cu, int nb,
+                    int max_len_host, float eps, float slope, float* out, float* out_range, int out_range_n,
+                    float* mean_out, float* rstd_out, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- a5: per-cloud InstanceNorm (+ residual add) (+ LeakyReLU) ------------
  * Replaces BatchNormBlock.forward (kpconv_blocks.py:497-525: per-cloud
  * nn.InstanceNorm1d, affine=False, eps, biased variance) fused with the
@@ -570,7 +587,8 @@ int spr_layernorm(const float* x, int m, int c, const float* gamma, const float*
 
 /* ---- a7: sine positional embedding -----------------------------------------
  * Replaces PositionEmbeddingCoordsSine.forward (transformer/
- * position_embedding.py:29-50).  xyz [n,3] -> out [n,d_model].
+ * position_embedding.py:29-50).  xyz [n,3] -> out [n,d_model].  The distinct frequencies of an axis
+ * (d_model / 6) are held in a table of 1024: d_model of 6150 and more is refused.
  */
 int spr_posemb_sine(const float* xyz, int n, int d_model, float scale,
                     float temperature, float* out, void* stream);

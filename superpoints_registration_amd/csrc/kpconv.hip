@@ -163,15 +163,37 @@ __global__ __launch_bounds__(256) void k_records_cin1(const float* __restrict__ 
 // exactly the A-operand layout of v_mfma_f32_16x16x4_f32 (row = query, k = g) --
 // so the [16 q x 16 kp] x [16 kp x Cout] product that follows needs no
 // transposition, and its C layout (lane = channel) stores 64-byte row pieces.
-__global__ __launch_bounds__(256) void k_kpconv_cin1(
-    const float* __restrict__ q_xyz, int nq, const float* __restrict__ s_xyz, int ns,
-    const int* __restrict__ nbr, int nbr_stride, int kmax, int rows_sorted,
-    const float4* __restrict__ sxf, const float* __restrict__ W, int cout,
-    const float* __restrict__ kpts, int n_kp, float inv_extent, float* __restrict__ out) {
+//
+// How the data arrives (the arithmetic and its order are those of a lane that walks its row one
+// neighbour at a time: per (query, kernel point) the influences are added in ascending position):
+//   indices  the wave's 16 index rows are staged in LDS, kCin1Chunk columns per pass: 16 lanes take
+//            64 contiguous bytes of a row, and all loads of a pass are issued before the first LDS write;
+//   stop     with rows_sorted a query's valid count is its first shadow position in the staged row
+//            (otherwise the whole row); the wave walks up to its largest count, no ballot per step;
+//   records  B 16-byte records per lane are requested before the first is consumed.  Positions past
+//            the wave's stop inside the last batch read record 0, as a shadow entry does, and add +0.
+// kCin1Batch and the five waves per SIMD of the launch bound come from the sweep in profiles/stem_bench.txt: with
+// the gathers batched the loop is bound by its vector arithmetic (about 200 issue cycles per neighbour and wave, a
+// sixth of them v_sqrt_f32), so waves per SIMD count for more than records in flight beyond eight.
+constexpr int kCin1Chunk = 64;                  // index columns staged per pass (kmax <= 64: one pass)
+constexpr int kCin1RowStride = kCin1Chunk + 1;  // odd: the 16 queries' reads of one column hit 16 banks
+// Records in flight per lane.  The loop was specified with at least eight; four at 8 waves per SIMD measured 0.52
+// against 0.557 ms per 2.1 M-query call (same bits) and is the setting to take if that floor is dropped.
+constexpr int kCin1Batch = 8;
+// LDS of the staged index rows: 4 waves x 16 rows, and the last batch's overshoot behind the last row
+constexpr int kCin1LdsInts = 4 * 16 * kCin1RowStride + 32;
+
+template <int B>
+__device__ __forceinline__ void cin1_gather(const float* __restrict__ q_xyz, int nq, int ns,
+                                            const int* __restrict__ nbr, int nbr_stride, int kmax, int rows_sorted,
+                                            const float4* __restrict__ sxf, const float* __restrict__ kpts, int n_kp,
+                                            float inv_extent, int* __restrict__ lrows, float (&wf)[4]) {
+  // a last batch reads up to B - 1 words past the wave's stop: the row's stale tail, the next row, the next wave's
+  // rows or, behind the very last row, the slack -- always inside lrows, and masked (k0 + b < kstop) before use
+  static_assert(B >= 1 && B <= 32, "the last batch's reads past the last staged row stay inside the slack");
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int qv = lane & 15, g = lane >> 4;
   const int q0 = blockIdx.x * 64 + wave * 16;
-  if (q0 >= nq) return;
   const int n = min(q0 + qv, nq - 1);
   const float qx = q_xyz[3 * (size_t)n], qy = q_xyz[3 * (size_t)n + 1], qz = q_xyz[3 * (size_t)n + 2];
   float kx[4], ky[4], kz[4];
@@ -184,29 +206,91 @@ __global__ __launch_bounds__(256) void k_kpconv_cin1(
     ky[s] = kok[s] ? kpts[3 * p + 1] : 0.f;
     kz[s] = kok[s] ? kpts[3 * p + 2] : 0.f;
   }
-  float wf[4] = {0.f, 0.f, 0.f, 0.f};
-  int cnt = 0;
-  const int* row = nbr + (size_t)n * nbr_stride;
-  for (int k = 0; k < kmax; ++k) {
-    const int idx = row[k];
-    const bool ok = idx >= 0 && idx < ns;
-    if (rows_sorted && __ballot(ok) == 0ull) break;   // only trailing shadow entries left
-    const size_t id = ok ? (size_t)idx : 0;
-    const float4 rec = sxf[id];          // {x, y, z, feature}: one 16-byte load (the four kernel-point groups of a query share it)
-    const float xv = ok ? rec.w : 0.f;
-    cnt += xv > 0.f ? 1 : 0;
-    const float rx = rec.x - qx, ry = rec.y - qy, rz = rec.z - qz;
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      const float dx = rx - kx[s], dy = ry - ky[s], dz = rz - kz[s];
-      // v_sqrt_f32 (1 ulp), like the fused kernel
-      const float w = fmaxf(0.f, 1.f - __builtin_amdgcn_sqrtf(dx * dx + dy * dy + dz * dz) * inv_extent);
-      wf[s] += kok[s] ? w * xv : 0.f;
+  for (int s = 0; s < 4; ++s) wf[s] = 0.f;
+  int cnt = 0;
+  int* lrow = lrows + wave * 16 * kCin1RowStride;  // this wave's 16 staged rows
+  // Wave uniform.  A wave past the end (the last workgroup only) does not return: it loads its clamped query and the
+  // kernel points like the others, issues no index or record load, and keeps every chunk's two barriers.
+  bool done = q0 >= nq;
+  for (int c0 = 0; c0 < kmax; c0 += kCin1Chunk) {
+    const int kc = min(kCin1Chunk, kmax - c0);
+    if (c0 > 0) __syncthreads();                   // the previous pass's reads are done
+    {
+      // lane -> (row g + 4 i, column qv + 16 j)
+      int v[4][kCin1Chunk / 16];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int* src = nbr + (size_t)min(q0 + g + 4 * i, nq - 1) * nbr_stride + c0;
+#pragma unroll
+        for (int j = 0; j < kCin1Chunk / 16; ++j) {
+          const int c = qv + 16 * j;
+          v[i][j] = (!done && c < kc) ? src[c] : -1;
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < kCin1Chunk / 16; ++j) lrow[(g + 4 * i) * kCin1RowStride + qv + 16 * j] = v[i][j];
+    }
+    __syncthreads();
+    if (done) continue;
+    int kstop = kc;
+    if (rows_sorted) {
+      // first shadow position of query qv (its four g lanes take every fourth column), then the wave's largest
+      int first = kc;
+      for (int k = g; k < kc; k += 4) {
+        const int idx = lrow[qv * kCin1RowStride + k];
+        if (!(idx >= 0 && idx < ns)) first = min(first, k);
+      }
+      first = min(first, __shfl_xor(first, 16, 64));
+      first = min(first, __shfl_xor(first, 32, 64));
+#pragma unroll
+      for (int o = 8; o > 0; o >>= 1) first = max(first, __shfl_xor(first, o, 64));
+      kstop = first;
+      done = kstop < kc;                           // only trailing shadow entries left
+    }
+    for (int k0 = 0; k0 < kstop; k0 += B) {
+      float4 rec[B];
+      bool ok[B];
+#pragma unroll
+      for (int b = 0; b < B; ++b) {
+        const int idx = lrow[qv * kCin1RowStride + k0 + b];   // past kstop: a stale word or the slack, masked here
+        ok[b] = k0 + b < kstop && idx >= 0 && idx < ns;
+        rec[b] = sxf[ok[b] ? (size_t)idx : 0];     // {x, y, z, feature}: one 16-byte load (the four kernel-point groups of a query share it)
+      }
+#pragma unroll
+      for (int b = 0; b < B; ++b) {
+        const float xv = ok[b] ? rec[b].w : 0.f;
+        cnt += xv > 0.f ? 1 : 0;
+        const float rx = rec[b].x - qx, ry = rec[b].y - qy, rz = rec[b].z - qz;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          const float dx = rx - kx[s], dy = ry - ky[s], dz = rz - kz[s];
+          // v_sqrt_f32 (1 ulp), like the fused kernel
+          const float w = fmaxf(0.f, 1.f - __builtin_amdgcn_sqrtf(dx * dx + dy * dy + dz * dz) * inv_extent);
+          wf[s] += kok[s] ? w * xv : 0.f;
+        }
+      }
     }
   }
   const float inv = 1.f / (float)max(cnt, 1);
 #pragma unroll
   for (int s = 0; s < 4; ++s) wf[s] *= inv;
+}
+
+__global__ __launch_bounds__(256, 5) void k_kpconv_cin1(
+    const float* __restrict__ q_xyz, int nq, const float* __restrict__ s_xyz, int ns,
+    const int* __restrict__ nbr, int nbr_stride, int kmax, int rows_sorted,
+    const float4* __restrict__ sxf, const float* __restrict__ W, int cout,
+    const float* __restrict__ kpts, int n_kp, float inv_extent, float* __restrict__ out) {
+  __shared__ int lrows[kCin1LdsInts];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int qv = lane & 15, g = lane >> 4;
+  const int q0 = blockIdx.x * 64 + wave * 16;
+  float wf[4];
+  cin1_gather<kCin1Batch>(q_xyz, nq, ns, nbr, nbr_stride, kmax, rows_sorted, sxf, kpts, n_kp, inv_extent, lrows, wf);
+  if (q0 >= nq) return;
   for (int o0 = 0; o0 < cout; o0 += 16) {
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -222,6 +306,128 @@ __global__ __launch_bounds__(256) void k_kpconv_cin1(
       if (qn < nq && o0 + qv < cout) out[(size_t)qn * cout + o0 + qv] = acc[r];
     }
   }
+}
+
+// ---------------------------------------------------------------------------
+// Encoder stem in inference (spr_kpconv_stem): Cin == 1 KPConv + per-cloud InstanceNorm + LeakyReLU without the raw
+// [Nq, Cout] tensor.  An output row is S[q][0..15] . W[16 x Cout], so only S (64 bytes per row) is kept:
+//   k_stem_sums   the gather loop above, stores the sixteen influence sums of a query (after the 1 / cnt scaling);
+//   k_stem_stats  grid (cloud, 512-row slice from the cloud's first row): y = S W per 16-row group by the four
+//                 v_mfma_f32_16x16x4_f32 steps of k_kpconv_cin1 (an element's bits do not depend on its group mates),
+//                 sums of y and y^2 per channel in float64 in a fixed order -> the partial layout of k_in_final;
+//   k_stem_apply  y once more with the operands swapped (y^T = W^T S^T: the same products in the same k order, and a
+//                 lane holds four adjacent channels of one row), k_in_apply's float operations, 16-byte stores,
+//                 max |out| into the range slots.
+constexpr int kStemSliceRows = 512;   // = instnorm_slice_rows(), checked by the entry point
+
+__global__ __launch_bounds__(256, 5) void k_stem_sums(
+    const float* __restrict__ q_xyz, int nq, int ns, const int* __restrict__ nbr, int nbr_stride, int kmax,
+    int rows_sorted, const float4* __restrict__ sxf, const float* __restrict__ kpts, int n_kp, float inv_extent,
+    float* __restrict__ S /*[nq][16]*/) {
+  __shared__ int lrows[kCin1LdsInts];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int qv = lane & 15, g = lane >> 4;
+  const int q = blockIdx.x * 64 + wave * 16 + qv;
+  float wf[4];
+  cin1_gather<kCin1Batch>(q_xyz, nq, ns, nbr, nbr_stride, kmax, rows_sorted, sxf, kpts, n_kp, inv_extent, lrows, wf);
+  if (q >= nq) return;
+#pragma unroll
+  for (int s = 0; s < 4; ++s) S[(size_t)q * 16 + 4 * s + g] = wf[s];   // kernel points >= n_kp: 0
+}
+
+// A operand of the 16-row group that starts at `row0`: lane (qv, g) takes S[row0 + qv][4 s + g]; rows from `end` on: 0
+__device__ __forceinline__ void stem_load_group(const float* __restrict__ S, int row0, int end, int qv, int g,
+                                                float (&a)[4]) {
+  const int row = row0 + qv;
+#pragma unroll
+  for (int s = 0; s < 4; ++s) a[s] = row < end ? S[(size_t)row * 16 + 4 * s + g] : 0.f;
+}
+
+__global__ __launch_bounds__(256) void k_stem_stats(const float* __restrict__ S, const int* __restrict__ cu,
+                                                    const float* __restrict__ W, int cout, int n_kp, int nsplit,
+                                                    double* __restrict__ part /*[nb][nsplit][2][cout]*/) {
+  constexpr int kGroups = kStemSliceRows / 16 / 4;   // 16-row groups per wave
+  const int cloud = blockIdx.x, split = blockIdx.y;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int qv = lane & 15, g = lane >> 4;
+  const int end = cu[cloud + 1];
+  const int r0 = cu[cloud] + split * kStemSliceRows;
+  __shared__ double red[2][4][4][16];                // [sum | sum of squares][wave][g][channel of the tile]
+  float a[kGroups][4];
+#pragma unroll
+  for (int i = 0; i < kGroups; ++i) stem_load_group(S, r0 + (wave + 4 * i) * 16, end, qv, g, a[i]);
+  double* p = part + (((size_t)cloud * nsplit + split) * 2) * cout;
+  for (int o0 = 0; o0 < cout; o0 += 16) {
+    float bv[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) bv[s] = 4 * s + g < n_kp ? W[(size_t)(4 * s + g) * cout + o0 + qv] : 0.f;
+    double sm = 0.0, sq = 0.0;                       // channel o0 + qv over the rows 4 g + r of this wave's groups
+#pragma unroll
+    for (int i = 0; i < kGroups; ++i) {
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int s = 0; s < 4; ++s) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i][s], bv[s], acc, 0, 0, 0);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {                  // rows past the cloud's end are exact zeros: they add nothing
+        const double y = acc[r];
+        sm += y;
+        sq += y * y;
+      }
+    }
+    red[0][wave][g][qv] = sm;
+    red[1][wave][g][qv] = sq;
+    __syncthreads();
+    if (threadIdx.x < 32) {
+      const int which = threadIdx.x >> 4, ch = threadIdx.x & 15;
+      double t = 0.0;
+      for (int w = 0; w < 4; ++w)
+        for (int gg = 0; gg < 4; ++gg) t += red[which][w][gg][ch];
+      p[(size_t)which * cout + o0 + ch] = t;
+    }
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(256) void k_stem_apply(const float* __restrict__ S, int nq, const int* __restrict__ cu,
+                                                    int nb, const float* __restrict__ W, int cout, int n_kp,
+                                                    const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                    float slope, float* __restrict__ out,
+                                                    float* __restrict__ out_range, int nslots) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int qv = lane & 15, g = lane >> 4;
+  const int q0 = blockIdx.x * 64 + wave * 16;
+  const int q = q0 + qv;
+  float mx = 0.f;
+  if (q0 < nq) {                                     // wave uniform; every wave reaches publish_range's barrier
+    float b[4];
+    stem_load_group(S, q0, nq, qv, g, b);
+    const int cloud = find_segment(cu, nb, min(q, nq - 1));
+    for (int o0 = 0; o0 < cout; o0 += 16) {
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        const float av = 4 * s + g < n_kp ? W[(size_t)(4 * s + g) * cout + o0 + qv] : 0.f;
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b[s], acc, 0, 0, 0);
+      }
+      // C layout of the swapped product: row (channel) = o0 + 4 g + r, col (query) = qv
+      if (q < nq) {
+        const float4 m = *reinterpret_cast<const float4*>(mean + (size_t)cloud * cout + o0 + 4 * g);
+        const float4 r = *reinterpret_cast<const float4*>(rstd + (size_t)cloud * cout + o0 + 4 * g);
+        float4 w;
+        w.x = (acc[0] - m.x) * r.x;
+        w.y = (acc[1] - m.y) * r.y;
+        w.z = (acc[2] - m.z) * r.z;
+        w.w = (acc[3] - m.w) * r.w;
+        w.x = w.x >= 0.f ? w.x : w.x * slope;
+        w.y = w.y >= 0.f ? w.y : w.y * slope;
+        w.z = w.z >= 0.f ? w.z : w.z * slope;
+        w.w = w.w >= 0.f ? w.w : w.w * slope;
+        *reinterpret_cast<float4*>(out + (size_t)q * cout + o0 + 4 * g) = w;
+        mx = fmaxf(mx, fmaxf(fmaxf(fabsf(w.x), fabsf(w.y)), fmaxf(fabsf(w.z), fabsf(w.w))));
+      }
+    }
+  }
+  if (out_range != nullptr) publish_range(mx, out_range, nslots);
 }
 
 // ---------------------------------------------------------------------------
@@ -1275,6 +1481,72 @@ extern "C" int spr_kpconv_prep_weights(const float* weights, int n_kp, int cin, 
 
 extern "C" size_t spr_kpconv_workspace_bytes(int nq, int ns, int cin, int cout) {
   return measure(kpconv_layout, nq, ns, cin, cout);
+}
+
+// ---- encoder stem (k_stem_sums / k_stem_stats / k_in_final / k_stem_apply) ----
+namespace {
+struct StemWs {
+  float4* sxf;          // [ns] support records
+  float* S;             // [nq][16] influence sums
+  double* part;         // [nb][nsplit][2][cout]
+  float *mean, *rstd;   // [nb][cout]
+};
+StemWs stem_layout(Workspace& w, int nq, int ns, int nb, int max_len, int cout) {
+  const size_t Q = (size_t)(nq > 0 ? nq : 1), N = (size_t)(ns > 0 ? ns : 1), B = (size_t)(nb > 0 ? nb : 1),
+               C = (size_t)(cout > 0 ? cout : 1);
+  StemWs l{};
+  l.sxf = w.take<float4>(N);
+  l.S = w.take<float>(Q * 16);
+  l.part = w.take<double>(B * instnorm_nsplit(max_len) * 2 * C);
+  l.mean = w.take<float>(B * C);
+  l.rstd = w.take<float>(B * C);
+  return l;
+}
+}  // namespace
+
+extern "C" int spr_kpconv_stem_supported(int cin, int cout, int n_kp) {
+  return cin == 1 && cout >= 16 && cout % 16 == 0 && n_kp >= 1 && n_kp <= 16;
+}
+
+extern "C" size_t spr_kpconv_stem_workspace_size(int nq, int ns, int nb, int max_len, int cout) {
+  return measure(stem_layout, nq, ns, nb, max_len, cout);
+}
+
+extern "C" int spr_kpconv_stem(const float* q_xyz, int nq, const float* s_xyz, int ns, const int* nbr, int nbr_stride,
+                               int kmax, int rows_sorted, const float* x, const float* weights, int cout,
+                               const float* kernel_points, int n_kp, float kp_extent, const int* cu, int nb,
+                               int max_len_host, float eps, float slope, float* out, float* out_range,
+                               int out_range_n, float* mean_out, float* rstd_out, void* ws, size_t ws_bytes,
+                               void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SPR_REQUIRE(nq > 0 && ns > 0 && nb >= 1, "kpconv_stem: empty input");
+  SPR_REQUIRE(kmax >= 1 && kmax <= nbr_stride, "kpconv_stem: bad kmax=%d stride=%d", kmax, nbr_stride);
+  SPR_REQUIRE(spr_kpconv_stem_supported(1, cout, n_kp), "kpconv_stem: no kernel for cout=%d, %d kernel points", cout,
+              n_kp);
+  SPR_REQUIRE(kp_extent > 0.f, "kpconv_stem: KP_extent must be > 0");
+  SPR_REQUIRE(max_len_host >= 1 && max_len_host <= nq, "kpconv_stem: bad max_len_host=%d", max_len_host);
+  SPR_REQUIRE(out_range == nullptr || (out_range_n >= 1 && (out_range_n & (out_range_n - 1)) == 0),
+              "kpconv_stem: out_range_n must be a power of two");
+  SPR_REQUIRE(instnorm_slice_rows() == kStemSliceRows, "kpconv_stem: statistics slices differ from the InstanceNorm's");
+  Workspace w(ws, ws_bytes);
+  const StemWs l = stem_layout(w, nq, ns, nb, max_len_host, cout);
+  SPR_REQUIRE(ws != nullptr && w.ok(), "kpconv_stem: workspace too small");
+  const int nsplit = instnorm_nsplit(max_len_host);
+  float* mean = mean_out != nullptr ? mean_out : l.mean;   // [nb][cout], the caller's if it wants the statistics
+  float* rstd = rstd_out != nullptr ? rstd_out : l.rstd;
+  hipLaunchKernelGGL(k_records_cin1, dim3(cdiv(ns, 256)), dim3(256), 0, stream, x, s_xyz, ns, l.sxf);
+  {
+    ProfScope prof(stream, 100000 + cout, nq);
+    hipLaunchKernelGGL(k_stem_sums, dim3(cdiv(nq, 64)), dim3(256), 0, stream, q_xyz, nq, ns, nbr, nbr_stride, kmax,
+                       rows_sorted, l.sxf, kernel_points, n_kp, 1.0f / kp_extent, l.S);
+  }
+  hipLaunchKernelGGL(k_stem_stats, dim3(nb, nsplit), dim3(256), 0, stream, l.S, cu, weights, cout, n_kp, nsplit,
+                     l.part);
+  launch_in_final(l.part, cu, nb, cout, nsplit, eps, mean, rstd, stream);
+  hipLaunchKernelGGL(k_stem_apply, dim3(cdiv(nq, 64)), dim3(256), 0, stream, l.S, nq, cu, nb, weights, cout, n_kp,
+                     mean, rstd, slope, out, out_range, out_range_n);
+  SPR_LAUNCH_CHECK();
+  return 0;
 }
 
 // x_range / w_range: operand ranges handed in (see spr_linear); NULL = measured here.

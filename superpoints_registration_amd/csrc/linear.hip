@@ -717,21 +717,49 @@ __global__ __launch_bounds__(256) void k_layernorm256(const float* __restrict__ 
 }
 
 // position_embedding.py:29-50
-__global__ void k_posemb(const float* __restrict__ xyz, int n, int d_model, int npf, float scale,
-                         float temperature, float* __restrict__ out) {
-  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (gid >= (long)n * d_model) return;
-  const int row = (int)(gid / d_model), ch = (int)(gid % d_model);
-  float v = 0.f;
-  if (ch < 3 * npf) {
-    const int axis = ch / npf, i = ch % npf;
-    // dim_t[i] = temperature ** (2 * (i // 2) / npf)
-    const float e = (float)(2 * (i / 2)) / (float)npf;
-    const float dim_t = powf(temperature, e);
-    const float a = (xyz[3 * (size_t)row + axis] * scale) / dim_t;
-    v = (i & 1) ? cosf(a) : sinf(a);
+// One thread per (token, channel pair 2 s, 2 s + 1): inside the 3 * npf embedding channels (npf is even) a pair is
+// the sine and the cosine of ONE argument (xyz * scale) / dim_t, formed once; behind them the pair is zeros.  The
+// npf / 2 distinct dim_t are computed once per workgroup into LDS (by the device's powf: its bits are the
+// contract), a workgroup covers kPosembTokens tokens, and a wave stores 512 contiguous bytes per step.
+constexpr int kPosembTokens = 16;
+constexpr int kPosembMaxFreq = 1024;  // npf / 2 of the widest d_model the entry point takes
+
+__global__ __launch_bounds__(256) void k_posemb(const float* __restrict__ xyz, int n, int d_model, int npf,
+                                                float scale, float temperature, float* __restrict__ out) {
+  __shared__ float dim_t[kPosembMaxFreq];
+  // dim_t[i] = temperature ** (2 * (i // 2) / npf)
+  for (int f = threadIdx.x; f < npf / 2; f += 256) dim_t[f] = powf(temperature, (float)(2 * f) / (float)npf);
+  __syncthreads();
+  const int slots = (d_model + 1) >> 1;          // channel pairs per token (the last one half empty if d_model is odd)
+  const bool vec = (d_model & 1) == 0;           // then every pair is 8-byte aligned
+  const int row0 = blockIdx.x * kPosembTokens;
+  const int rows = min(kPosembTokens, n - row0);
+  // the thread's (token, pair) advances by 256 pairs per step
+  const int dr = 256 / slots, ds = 256 % slots;
+  int r = (int)threadIdx.x / slots, s = (int)threadIdx.x % slots;
+  while (r < rows) {
+    const int row = row0 + r, ch = 2 * s;
+    float v0 = 0.f, v1 = 0.f;
+    if (ch < 3 * npf) {
+      const int axis = (ch >= npf ? 1 : 0) + (ch >= 2 * npf ? 1 : 0), i = ch - axis * npf;
+      const float a = (xyz[3 * (size_t)row + axis] * scale) / dim_t[i >> 1];
+      v0 = sinf(a);
+      v1 = cosf(a);
+    }
+    float* o = out + (size_t)row * d_model + ch;
+    if (vec) {
+      *reinterpret_cast<float2*>(o) = make_float2(v0, v1);
+    } else {
+      o[0] = v0;
+      if (ch + 1 < d_model) o[1] = v1;
+    }
+    s += ds;
+    r += dr;
+    if (s >= slots) {
+      s -= slots;
+      ++r;
+    }
   }
-  out[gid] = v;
 }
 
 }  // namespace
@@ -986,8 +1014,8 @@ extern "C" int spr_posemb_sine(const float* xyz, int n, int d_model, float scale
   hipStream_t stream = (hipStream_t)stream_;
   SPR_REQUIRE(n > 0 && d_model >= 6, "posemb: bad sizes");
   const int npf = d_model / 3 / 2 * 2;  // position_embedding.py:21
-  const long total = (long)n * d_model;
-  hipLaunchKernelGGL(k_posemb, dim3(cdiv(total, 256)), dim3(256), 0, stream, xyz, n, d_model, npf,
+  SPR_REQUIRE(npf / 2 <= kPosembMaxFreq, "posemb: d_model=%d is wider than the frequency table", d_model);
+  hipLaunchKernelGGL(k_posemb, dim3(cdiv(n, kPosembTokens)), dim3(256), 0, stream, xyz, n, d_model, npf,
                      scale, temperature, out);
   SPR_LAUNCH_CHECK();
   return 0;

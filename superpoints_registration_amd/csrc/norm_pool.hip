@@ -114,20 +114,6 @@ __global__ void k_in_final(const double* __restrict__ part, const int* __restric
   rstd[i] = (float)(1.0 / sqrt(var + (double)eps));
 }
 
-// Operand-range hand-over (spr.h): the workgroup's max |out| joins one of kRangeSlots slots by
-// integer atomic max on the bit pattern (non-negative floats order like unsigned ints; the result
-// does not depend on the order of arrival).  The caller zero-initialises the slots.  Called by
-// every thread of a 256-thread block.
-__device__ __forceinline__ void publish_range(float mx, float* __restrict__ slots, int nslots) {
-  __shared__ float shr[4];
-  mx = wave_max(mx);
-  if ((threadIdx.x & 63) == 0) shr[threadIdx.x >> 6] = mx;
-  __syncthreads();
-  if (threadIdx.x == 0)
-    atomicMax(reinterpret_cast<unsigned int*>(slots) + (blockIdx.x & (nslots - 1)),
-              __float_as_uint(fmaxf(fmaxf(shr[0], shr[1]), fmaxf(shr[2], shr[3]))));
-}
-
 // Streaming pass, one float4 (4 channels of one row) per thread and step; every thread takes
 // kInApplyUnroll steps a whole grid apart (all loads of a thread issued up front), so that a
 // workgroup publishes its range once per kInApplyUnroll * 256 float4s.
@@ -380,6 +366,16 @@ __global__ void k_gather_rows(const float* __restrict__ x, int n_src, int c,
 }
 
 }  // namespace
+
+// For a producer of the [cloud][slice][2][c] partial sums other than k_in_stats (the encoder stem, kpconv.hip): the
+// slice grid of a longest cloud, and the k_in_final launch over the partials.
+int instnorm_slice_rows() { return kSliceRows; }
+int instnorm_nsplit(int max_len) { return in_nsplit(max_len); }
+void launch_in_final(const double* part, const int* cu, int nb, int c, int nsplit, float eps, float* mean,
+                     float* rstd, hipStream_t stream) {
+  hipLaunchKernelGGL(k_in_final, dim3(cdiv((long)nb * c, 256)), dim3(256), 0, stream, part, cu, nb, c, nsplit, eps,
+                     mean, rstd);
+}
 }  // namespace spr
 
 using namespace spr;

@@ -126,6 +126,13 @@ int launch_absmax(const float* x, long rows, int cols, long stride, float* parts
 int launch_absmax2(const float* x0, long rows0, int cols0, long stride0, float* parts0, const float* x1,
                    long rows1, int cols1, long stride1, float* parts1, hipStream_t stream);
 
+// InstanceNorm statistics for producers of the [cloud][slice][2][c] float64 partial sums (norm_pool.hip): rows per
+// slice, slices of a longest cloud, and the k_in_final launch (mean / rstd [nb][c]).
+int instnorm_slice_rows();
+int instnorm_nsplit(int max_len);
+void launch_in_final(const double* part, const int* cu, int nb, int c, int nsplit, float eps, float* mean,
+                     float* rstd, hipStream_t stream);
+
 // ---- device helpers --------------------------------------------------------
 #ifdef __HIPCC__
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -291,6 +298,19 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
+}
+// Operand-range hand-over (spr.h): the workgroup's max |out| joins one of kRangeSlots slots by
+// integer atomic max on the bit pattern (non-negative floats order like unsigned ints; the result
+// does not depend on the order of arrival).  The caller zero-initialises the slots.  Called by
+// every thread of a 256-thread block.
+__device__ __forceinline__ void publish_range(float mx, float* __restrict__ slots, int nslots) {
+  __shared__ float shr[4];
+  mx = wave_max(mx);
+  if ((threadIdx.x & 63) == 0) shr[threadIdx.x >> 6] = mx;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    atomicMax(reinterpret_cast<unsigned int*>(slots) + (blockIdx.x & (nslots - 1)),
+              __float_as_uint(fmaxf(fmaxf(shr[0], shr[1]), fmaxf(shr[2], shr[3]))));
 }
 #endif
 

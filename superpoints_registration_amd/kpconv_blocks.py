@@ -20,7 +20,7 @@ import torch.nn as nn
 from torch.nn.init import kaiming_uniform_
 from torch.nn.parameter import Parameter
 
-from . import _concurrency, ops
+from . import _concurrency, ops, stem
 from .kernel_points import load_kernels
 
 
@@ -229,6 +229,12 @@ class SimpleBlock(nn.Module):
             neighb_inds = _idx_of(batch, 'neighbors', li)
             stack_lengths, cu, ml = batch['stack_lengths'][li], _cu_of(batch, li), _maxlen_of(batch, li)
         self.KPConv.rows_sorted = bool(batch.get('_rows_sorted', False))
+        if stem.stem_route(x, self.KPConv.weights, self.use_bn):
+            # the encoder's first block in inference: one call, the raw KPConv output is never written
+            return stem.kpconv_stem(q_pts, s_pts, neighb_inds, x, self.KPConv.weights,
+                                    self.KPConv.kernel_points.detach(), self.KPConv.KP_extent, cu,
+                                    eps=self.batch_norm.eps, slope=0.1, rows_sorted=self.KPConv.rows_sorted,
+                                    max_len=ml)
         x = self.KPConv(q_pts, s_pts, neighb_inds, x)
         return self.batch_norm(x, stack_lengths, cu=cu, slope=0.1, max_len=ml)
 
