@@ -436,6 +436,46 @@ int spr_kpconv_fwd(const float* q_xyz, int nq, const float* s_xyz, int ns, const
                    const float* w_range, int w_range_n, const void* plan, const void* wplanes,
                    void* ws, size_t ws_bytes, void* stream);
 
+/* KPConv in the reference's other modes (kpconv_blocks.py:361-385; rigid kernel points; csrc/kpconv_modes.hip):
+ *   influence    SPR_KP_CONSTANT  w = 1
+ *                SPR_KP_LINEAR    w = max(0, 1 - sqrt(d2) / kp_extent)                  (spr_kpconv_fwd's rule)
+ *                SPR_KP_GAUSSIAN  w = exp(-d2 / (2 sigma^2 + 1e-9)), sigma = 0.3 kp_extent   (no cut-off)
+ *   aggregation  SPR_KP_SUM       every kernel point weighs on a neighbour
+ *                SPR_KP_CLOSEST   only p = argmin_p d2 does (the lowest p on a tie, torch.argmin)
+ * with d2[n,k,p] = |s[nbr[n,k]] - q[n] - kernel_points[p]|^2 in float32.  An index outside [0, ns) contributes nothing
+ * and is not counted; the output is divided by max(1, #{k : sum_c x[nbr[n,k],c] > 0}), counted from the flags
+ * spr_kpconv_fwd counts from (one summation order).  An unknown influence / aggregation returns status 2.
+ * linear / sum is valid here and agrees with spr_kpconv_fwd to rounding, not to the bit (another kernel, another order).
+ * spr_kpconv_modes_fwd takes spr_kpconv_fwd's arguments without rows_sorted and plan (the kernel compacts each row
+ *   itself and has no tile plan); impl: 0 = fused tile kernel for 15 kernel points with cin, cout multiples of 32 and
+ *   cout <= 256, one thread per output element otherwise; 1 = the latter for every shape.  wplanes:
+ *   spr_kpconv_prep_weights of THESE weights with THIS w_range, as for spr_kpconv_fwd (NULL = built here, per call).
+ * spr_kpconv_modes_weighted_features / spr_kpconv_modes_bwd_dx: spr_kpconv_weighted_features / spr_kpconv_bwd_dx in
+ *   the given mode (declared with the backward below for the default mode): wf [nq, n_kp * cin] un-normalised and
+ *   cnt [nq] = max(1, count); dx [ns, cin] fully written, 64-bit fixed-point sums (bitwise reproducible),
+ *   ws: spr_scatter_workspace_bytes(ns, cin).  The influences and the arg-min are constants of the backward (kernel
+ *   points are not trained); with two GEMMs in between = the KPConv backward.  n_kp <= 16. */
+#define SPR_KP_CONSTANT 0
+#define SPR_KP_LINEAR 1
+#define SPR_KP_GAUSSIAN 2
+#define SPR_KP_SUM 0
+#define SPR_KP_CLOSEST 1
+size_t spr_kpconv_modes_workspace_size(int nq, int ns, int cin, int cout);
+int spr_kpconv_modes_fwd(const float* q_xyz, int nq, const float* s_xyz, int ns, const int* nbr, int nbr_stride,
+                         int kmax, const float* x, int cin, const float* weights, int cout,
+                         const float* kernel_points, int n_kp, float kp_extent, int influence, int aggregation,
+                         float* out, int impl, const float* x_range, int x_range_n, const float* w_range,
+                         int w_range_n, const void* wplanes, void* ws, size_t ws_bytes, void* stream);
+size_t spr_kpconv_modes_weighted_features_workspace_size(int ns);
+int spr_kpconv_modes_weighted_features(const float* q_xyz, int nq, const float* s_xyz, int ns, const int* nbr,
+                                       int nbr_stride, int kmax, const float* x, int cin, const float* kernel_points,
+                                       int n_kp, float kp_extent, int influence, int aggregation, float* wf,
+                                       float* cnt, void* ws, size_t ws_bytes, void* stream);
+int spr_kpconv_modes_bwd_dx(const float* q_xyz, int nq, const float* s_xyz, int ns, const int* nbr, int nbr_stride,
+                            int kmax, int cin, const float* kernel_points, int n_kp, float kp_extent, int influence,
+                            int aggregation, const float* dwf, const float* dwf_range, int dwf_range_n, float* dx,
+                            void* ws, size_t ws_bytes, void* stream);
+
 /* Encoder stem in inference: the first block's KPConv (cin = 1, x [ns,1]) + per-cloud InstanceNorm + LeakyReLU,
  *   out [nq,cout] = lrelu(IN(spr_kpconv_fwd(...)), slope)
  * without the raw [nq,cout] tensor: only the 16 normalised influence sums per query are kept (in ws) and the rows

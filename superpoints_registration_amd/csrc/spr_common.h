@@ -126,6 +126,12 @@ int launch_absmax(const float* x, long rows, int cols, long stride, float* parts
 int launch_absmax2(const float* x0, long rows0, int cols0, long stride0, float* parts0, const float* x1,
                    long rows1, int cols1, long stride1, float* parts1, hipStream_t stream);
 
+// KPConv's per-support flags (kpconv.hip, k_rowflag): flag[i] = (sum_c x[i, c] > 0) in ONE summation order for every
+// caller -- the forward kernels, the backward's recomputation and the mode-aware kernels (kpconv_modes.hip) count
+// neighbours from it.  Writes flag[ns], the support records sxf[ns + 1] and tile_ctr[0].
+void launch_rowflag(const float* x, const float* s_xyz, int ns, int cin, unsigned char* flag, float4* sxf,
+                    int* tile_ctr, hipStream_t stream);
+
 // InstanceNorm statistics for producers of the [cloud][slice][2][c] float64 partial sums (norm_pool.hip): rows per
 // slice, slices of a longest cloud, and the k_in_final launch (mean / rstd [nb][c]).
 int instnorm_slice_rows();

@@ -7,11 +7,14 @@ gradients enabled they go through the explicit HIP backward of autograd.py.
 The decoder's blocks are here as well: NearestUpsampleBlock, and the UnaryBlock
 that KPFDecoder (kpconv.py) feeds with the upsampled features and a skip tensor.
 
+KPConv runs every rigid mode of the reference: KP_influence 'constant' / 'linear' /
+'gaussian' x aggregation_mode 'sum' / 'closest'.  linear / sum (every shipped config)
+goes through ops.kpconv, the other five through kpconv_modes.kpconv.
+
 Not mirrored (never selected by a shipped config):
-deformable / modulated KPConv, 'closest' aggregation, 'constant'/'gaussian'
-influence, and the blocks 'unary2', 'global_average', 'max_pool*' and the
-deformable / equivariant / invariant names: block_decider raises ValueError
-for them.
+deformable / modulated KPConv, and the blocks 'unary2', 'global_average',
+'max_pool*' and the deformable / equivariant / invariant names: block_decider
+raises ValueError for them.
 """
 import math
 
@@ -20,7 +23,7 @@ import torch.nn as nn
 from torch.nn.init import kaiming_uniform_
 from torch.nn.parameter import Parameter
 
-from . import _concurrency, ops, stem
+from . import _concurrency, kpconv_modes, ops, stem
 from .kernel_points import load_kernels
 
 
@@ -78,7 +81,7 @@ def closest_pool(x, inds):
 
 
 class KPConv(nn.Module):
-    """kpconv_blocks.py:175-420 (rigid, 'linear' influence, 'sum' aggregation)."""
+    """kpconv_blocks.py:175-420 (rigid: every influence function and both aggregation rules)."""
 
     def __init__(self, kernel_size, p_dim, in_channels, out_channels, KP_extent, radius,
                  fixed_kernel_points='center', KP_influence='linear', aggregation_mode='sum',
@@ -86,9 +89,7 @@ class KPConv(nn.Module):
         super().__init__()
         if deformable or modulated:
             raise NotImplementedError("deformable / modulated KPConv is outside the hot-path scope")
-        if KP_influence != 'linear' or aggregation_mode != 'sum':
-            raise NotImplementedError("only KP_influence='linear', aggregation_mode='sum' "
-                                      "(the only mode the shipped configs use)")
+        kpconv_modes.mode_codes(KP_influence, aggregation_mode)     # ValueError for an unknown string
         self.K = kernel_size
         self.p_dim = p_dim
         self.in_channels = in_channels
@@ -117,9 +118,12 @@ class KPConv(nn.Module):
         return Parameter(torch.tensor(K_points_numpy, dtype=torch.float32), requires_grad=False)
 
     def forward(self, q_pts, s_pts, neighb_inds, x):
-        return ops.kpconv(q_pts, s_pts, neighb_inds, x, self.weights,
-                          self.kernel_points.detach(), self.KP_extent,
-                          rows_sorted=self.rows_sorted, impl=self.impl)
+        if kpconv_modes.is_default_mode(self.KP_influence, self.aggregation_mode):
+            return ops.kpconv(q_pts, s_pts, neighb_inds, x, self.weights,
+                              self.kernel_points.detach(), self.KP_extent,
+                              rows_sorted=self.rows_sorted, impl=self.impl)
+        return kpconv_modes.kpconv(q_pts, s_pts, neighb_inds, x, self.weights, self.kernel_points.detach(),
+                                   self.KP_extent, self.KP_influence, self.aggregation_mode)
 
     def __repr__(self):
         return 'KPConv(radius: {:.2f}, extent: {:.2f}, in_feat: {:d}, out_feat: {:d})'.format(
@@ -218,6 +222,12 @@ class SimpleBlock(nn.Module):
         self.batch_norm = BatchNormBlock(out_dim // 2, self.use_bn, self.bn_momentum)
         self.leaky_relu = nn.LeakyReLU(0.1)
 
+    def stem_route(self, x) -> bool:
+        """Whether forward(x, ...) runs as the fused stem call: stem.stem_route's rule, in the linear / sum mode
+        only (the stem kernel has no other)."""
+        return (kpconv_modes.is_default_mode(self.KPConv.KP_influence, self.KPConv.aggregation_mode)
+                and stem.stem_route(x, self.KPConv.weights, self.use_bn))
+
     def forward(self, x, batch):
         li = self.layer_ind
         if 'strided' in self.block_name:
@@ -229,7 +239,7 @@ class SimpleBlock(nn.Module):
             neighb_inds = _idx_of(batch, 'neighbors', li)
             stack_lengths, cu, ml = batch['stack_lengths'][li], _cu_of(batch, li), _maxlen_of(batch, li)
         self.KPConv.rows_sorted = bool(batch.get('_rows_sorted', False))
-        if stem.stem_route(x, self.KPConv.weights, self.use_bn):
+        if self.stem_route(x):
             # the encoder's first block in inference: one call, the raw KPConv output is never written
             return stem.kpconv_stem(q_pts, s_pts, neighb_inds, x, self.KPConv.weights,
                                     self.KPConv.kernel_points.detach(), self.KPConv.KP_extent, cu,
