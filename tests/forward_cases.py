@@ -255,11 +255,12 @@ def lattice_kernel_points(ext):
     return np.asarray(pts, np.float32)
 
 
-def random_kernel_points(ext, seed):
-    """Centre at the origin + 14 points in the ball of radius 1.5 ext (the disposition's scale: radius = 1.5 extent)."""
+def random_kernel_points(ext, seed, n_kp=15):
+    """Centre at the origin + n_kp - 1 points in the ball of radius 1.5 ext (the disposition's scale: radius = 1.5
+    extent)."""
     r = rng_of(501, seed)
-    v = r.standard_normal((14, 3))
-    v = v / np.linalg.norm(v, axis=1, keepdims=True) * (r.uniform(0.5, 1.0, (14, 1)) * 1.5 * ext)
+    v = r.standard_normal((n_kp - 1, 3))
+    v = v / np.linalg.norm(v, axis=1, keepdims=True) * (r.uniform(0.5, 1.0, (n_kp - 1, 1)) * 1.5 * ext)
     return np.concatenate([np.zeros((1, 3)), v], 0).astype(np.float32)
 
 
@@ -270,8 +271,8 @@ def kp_features(ns, cin, seed, integer=False):
     return (r.random((ns, cin)) - 0.4).astype(np.float32)
 
 
-def kp_weights(cin, cout, seed):
-    return ((rng_of(503, seed, cin, cout).random((15, cin, cout)) - 0.5) * 0.5).astype(np.float32)
+def kp_weights(cin, cout, seed, n_kp=15):
+    return ((rng_of(503, seed, cin, cout).random((n_kp, cin, cout)) - 0.5) * 0.5).astype(np.float32)
 
 
 def kp_cloud_case(nq, ns, kmax, offset, ext, seed, rows_sorted=True, fill=0.7):

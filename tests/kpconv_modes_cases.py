@@ -168,3 +168,275 @@ def golden_case():
 
 def golden_go():
     return _rng_float(np.random.default_rng(GOLDEN_GO_SEED), (GOLDEN['nq'], GOLDEN['cout']), -1.0, 1.0)
+
+
+# ---- range and edge cases (tests/test_gpu_kpconv_modes_range.py, tests/test_kpconv_modes_range_host.py) -------------------
+# route name -> (impl, cin, cout, n_kp): the kernels spr_kpconv_modes_fwd dispatches to, and the shapes that tell them apart
+ROUTES = {
+    "tile32": (0, 32, 64, 15), "tile64": (0, 64, 64, 15), "tile128x256": (0, 128, 256, 15), "simple48": (0, 48, 40, 15),
+    "cin1": (0, 1, 32, 15), "kp7": (0, 32, 32, 7), "kp16": (0, 32, 32, 16), "impl1": (1, 32, 32, 15),
+}
+ROUTE_KERNEL = {"tile32": "tile32", "tile64": "tile64", "tile128x256": "tile64", "simple48": "simple", "cin1": "simple",
+                "kp7": "simple", "kp16": "simple", "impl1": "simple"}
+TILE_KP = 15            # kKP: the tile kernel's kernel-point count
+AUX_KP_MAX = 16         # kKPmax: the most the one-wave-per-query kernels (weighted features, d x) take
+FWD_KP_MAX = 32         # the most spr_kpconv_modes_fwd takes (the one-thread-per-output kernel)
+
+
+def modes_route(impl, cin, cout, n_kp):
+    """The forward kernel a call reaches, restated from spr_kpconv_modes_fwd's dispatch (csrc/kpconv_modes.hip):
+    'tile64' / 'tile32' (k_kpconv_modes_tile at 64- / 32-channel chunks) or 'simple' (k_kpconv_modes_simple)."""
+    planes = cin > 0 and cin % 32 == 0 and cout > 0 and cout % 32 == 0 and cout <= 256       # modes_plane_shape
+    if impl == 0 and n_kp == TILE_KP and planes:
+        return "tile64" if cin % 64 == 0 else "tile32"
+    return "simple"
+
+
+def case_from_numpy(q, s, nb, x, w, kp, ext, index_dtype=torch.int32):
+    """The dict of make_case from the numpy arrays of tests/forward_cases.py."""
+    f = lambda a: torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float32)))
+    return dict(q=f(q), s=f(s), idx=torch.from_numpy(np.asarray(nb, np.int64)).to(index_dtype), x=f(x), w=f(w), kp=f(kp),
+                extent=float(ext))
+
+
+def _d2_64(case):
+    q, s, kp = case['q'].double(), case['s'].double(), case['kp'].double()
+    idx = case['idx'].long()
+    valid = (idx >= 0) & (idx < s.shape[0])
+    safe = torch.where(valid, idx, torch.zeros_like(idx))
+    return (((s[safe] - q.unsqueeze(1)).unsqueeze(2) - kp) ** 2).sum(3), valid
+
+
+def near_tie_rows(case):
+    """bool [nq]: the query rows that hold a real neighbour whose two lowest d2 (float64) are within GAP_MIN of each
+    other, relative to the larger -- there float32 and float64 may pick different kernel points in `closest`.  An exact
+    tie (gap 0) is NOT a near-tie: both arithmetics see it and both take the lowest p."""
+    d2, valid = _d2_64(case)
+    if d2.shape[2] < 2:
+        return torch.zeros(d2.shape[0], dtype=torch.bool)
+    two = torch.sort(d2, dim=2)[0][:, :, :2]
+    gap = (two[:, :, 1] - two[:, :, 0]) / two[:, :, 1].clamp(min=1e-300)
+    return ((gap < GAP_MIN) & (gap > 0) & valid).any(1)
+
+
+NEAR_TIE_CAP = 0.10
+
+
+def near_tie_share(case):
+    """(rows that leave the strict comparison in `closest`, live rows): float64 values alone."""
+    idx, ns = case['idx'].long(), case['s'].shape[0]
+    live = ((idx >= 0) & (idx < ns)).any(1)
+    return int((near_tie_rows(case) & live).sum()), int(live.sum())
+
+
+def kernel_points_n(ext, seed, n_kp, lattice=False):
+    """n_kp kernel points: forward_cases.random_kernel_points, or its 15-point lattice cut to n_kp / continued with
+    points at (+-ext, ext, ext), (ext, -ext, ext) (lattice positions outside the 15)."""
+    import forward_cases as fc
+    if not lattice:
+        return fc.random_kernel_points(ext, seed, n_kp)
+    pts = fc.lattice_kernel_points(ext)
+    more = np.asarray([(ext, ext, ext), (-ext, ext, ext), (ext, -ext, ext)], np.float32)
+    return np.concatenate([pts, more], 0)[:n_kp].copy()
+
+
+def cloud_case(route, nq, ns, kmax, offset, ext, seed, rows_sorted=True, fill=0.7, n_kp=None, cin=None, cout=None):
+    """forward_cases.kp_cloud_case with the section-5 features, weights and kernel points at a route's shape; seeds
+    seed, seed + 1 (features), seed + 2 (weights), seed + 3 (kernel points) as tests/test_gpu_forward_range.py."""
+    import forward_cases as fc
+    _, rcin, rcout, rkp = ROUTES[route]
+    cin, cout, n_kp = cin or rcin, cout or rcout, n_kp or rkp
+    q, s, nb = fc.kp_cloud_case(nq, ns, kmax, offset, ext, seed, rows_sorted=rows_sorted, fill=fill)
+    return case_from_numpy(q, s, nb, fc.kp_features(ns, cin, seed + 1), fc.kp_weights(cin, cout, seed + 2, n_kp),
+                           fc.random_kernel_points(ext, seed + 3, n_kp), ext)
+
+
+OFFSETS = [(1e2, 0.03), (1e3, 0.03), (1e2, 0.6), (1e3, 5.0)]
+ROW_WIDTHS = [1, 8, 9, 63, 64, 65, 128, 129]
+BACKWARD_WIDTHS = [64, 65, 129]
+QUERY_COUNTS = [1, 15, 16, 17, 31, 32, 33, 65]
+ODD_COUNTS = [1, 3, 7, 9]
+
+
+def offset_case(route, offset, ext, rows_sorted):
+    return cloud_case(route, 300, 350, 20, offset, ext, 41, rows_sorted=rows_sorted)
+
+
+def width_case(route, kmax, rows_sorted=True):
+    """Sorted rows hold ~0.9 kmax leading entries (the columns behind a staging boundary are then mostly shadow);
+    unsorted rows have real neighbours in every column, the last one included."""
+    return cloud_case(route, 150, 200, kmax, 1e2, 0.25, 45, rows_sorted=rows_sorted, fill=0.9)
+
+
+def count_case(route, nq, rows_sorted):
+    return cloud_case(route, nq, 120, 12, 1e2, 0.125, 49, rows_sorted=rows_sorted)
+
+
+def odd_valid_case(route):
+    """Rows with exactly 1, 3, 7 and 9 valid entries (row r: ODD_COUNTS[r % 4]; row 3 is all shadow), leading -- the
+    half-waves of the 32-channel tile kernel take the even and the odd staged neighbours, so the last even one has no
+    partner."""
+    case = cloud_case(route, 40, 120, 12, 1e2, 0.125, 61, fill=1.0)
+    idx, ns = case['idx'], case['s'].shape[0]
+    for r in range(idx.shape[0]):
+        idx[r, ODD_COUNTS[r % 4]:] = ns
+    return case
+
+
+def valid_counts(case):
+    idx, ns = case['idx'].long(), case['s'].shape[0]
+    return ((idx >= 0) & (idx < ns)).sum(1)
+
+
+def exact_case(route, offset, ext):
+    """forward_cases.kp_exact_case on the lattice kernel points, positive features; (case, names)."""
+    import forward_cases as fc
+    _, cin, cout, n_kp = ROUTES[route]
+    q, s, nb, names = fc.kp_exact_case(offset, ext)
+    x = np.abs(fc.kp_features(s.shape[0], cin, 53)) + 0.5
+    w = fc.kp_weights(cin, cout, 54, n_kp)
+    return case_from_numpy(q, s, nb, x, w, kernel_points_n(ext, 0, n_kp, lattice=True), ext), names
+
+
+# the twelve neighbour positions (in units of ext / 8) at distance sqrt(18) / 8 ext from the centre kernel point AND
+# from at least two axis points of the lattice (3/4 ext) -- and, with 15 points, from two cube corners (1/2 ext)
+TIE_OFFSETS = [(a * 3, b * 3, 0) for a in (1, -1) for b in (1, -1)] + [(a * 3, 0, b * 3) for a in (1, -1) for b in (1, -1)] + \
+              [(0, a * 3, b * 3) for a in (1, -1) for b in (1, -1)]
+TIE_EXT = 0.25
+
+
+def tie_case(route, nq=33, offset=1e2, seed=67):
+    """Exact arg-min ties.  Query i sits on the lattice; its neighbours are a seeded subset of the twelve TIE_OFFSETS
+    positions (3/8, 3/8, 0) ext and their images, in random order between shadow entries.  Every difference, square and
+    sum of d2 is exact in float32 (multiples of ext / 8 below 2^10), so d2 to the centre, to two axis points and (with
+    15 or more points) to two corners are the SAME float32 number, the minimum: torch.argmin and the kernels must take
+    p = 0.  The weights differ by 0.25 p per kernel point, the features are positive: another pick moves the output by
+    O(1) of its scale."""
+    import forward_cases as fc
+    _, cin, cout, n_kp = ROUTES[route]
+    ext, kmax = TIE_EXT, 14
+    r = fc.rng_of(601, seed, nq)
+    base = np.array([offset, -offset, 0.5 * offset], np.float32).astype(np.float64)
+    q = base[None] + np.arange(nq)[:, None] * np.array([2 * ext, 0.0, 0.0])[None]
+    off = np.asarray(TIE_OFFSETS, np.float64) * (ext / 8)
+    s = (q[:, None, :] + off[None]).reshape(-1, 3)
+    assert np.array_equal(s.astype(np.float32).astype(np.float64), s), "lattice not representable"
+    ns = s.shape[0]
+    nb = np.full((nq, kmax), ns, np.int64)
+    for i in range(nq):
+        take = r.permutation(12)[:r.integers(1, 13)]
+        cols = np.sort(r.permutation(kmax)[:take.size])
+        nb[i, cols] = 12 * i + take
+    x = np.abs(fc.kp_features(ns, cin, seed + 1)) + 0.5
+    w = fc.kp_weights(cin, cout, seed + 2, n_kp) + 0.25 * np.arange(n_kp, dtype=np.float32)[:, None, None]
+    return case_from_numpy(q, s, nb, x, w, kernel_points_n(ext, 0, n_kp, lattice=True), ext)
+
+
+def d2_float32(case):
+    """d2 [nq, k, p] as the kernels form it: float32 differences, squares and sums, in numpy (no contraction)."""
+    q, s, kp = case['q'].numpy(), case['s'].numpy(), case['kp'].numpy()
+    idx, ns = case['idx'].long().numpy(), case['s'].shape[0]
+    valid = (idx >= 0) & (idx < ns)
+    rel = s[np.where(valid, idx, 0)] - q[:, None, :]
+    d = rel[:, :, None, :] - kp[None, None]
+    return (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2], valid
+
+
+def count_edge_case(route):
+    """The integer-feature construction of test_gpu_forward_range.py::test_kpconv_neighbour_count_edges: support rows
+    0..39 sum to exactly 0, rows 40..79 to -1, queries 5..24 see only those (count clamps at 1), row 3 is all shadow."""
+    import forward_cases as fc
+    _, cin, cout, n_kp = ROUTES[route]
+    ext, ns, nq, kmax = 0.125, 160, 90, 10
+    q, s, nb = fc.kp_cloud_case(nq, ns, kmax, 1e2, ext, 55, rows_sorted=True, fill=0.8)
+    x = fc.kp_features(ns, cin, 56, integer=True)
+    if cin > 1:
+        x[:40, 0] -= x[:40].sum(1)
+        x[40:80, 0] -= x[40:80].sum(1) + 1
+    else:
+        x[:40], x[40:80] = 0.0, -1.0
+    nb[5:25] = np.where(nb[5:25] < ns, nb[5:25] % 80, ns)
+    nb[3] = ns
+    return case_from_numpy(q, s, nb, x, fc.kp_weights(cin, cout, 57, n_kp), fc.random_kernel_points(ext, 58, n_kp), ext)
+
+
+def ref_counts(case):
+    """max(1, #{valid neighbours whose feature sum is > 0}) [nq], float64 sums."""
+    idx, ns = case['idx'].long(), case['s'].shape[0]
+    valid = (idx >= 0) & (idx < ns)
+    pos = case['x'].double().sum(1)[torch.where(valid, idx, torch.zeros_like(idx))] > 0
+    return (pos & valid).sum(1).clamp(min=1)
+
+
+UNDERFLOW_EXT = 2.0 ** -10
+
+
+def underflow_case(route):
+    """The geometry of count_case(33) under a kernel of extent 2^-10 (cloud spacing ~0.05): neighbours closer than 16
+    extents to their query are made shadow, so every Gaussian influence is below the smallest float32 denormal and
+    every linear influence is 0."""
+    import forward_cases as fc
+    case = cloud_case(route, 33, 120, 12, 1e2, 0.125, 49)
+    ext = UNDERFLOW_EXT
+    idx, ns = case['idx'].long(), case['s'].shape[0]
+    valid = (idx >= 0) & (idx < ns)
+    d = (case['s'].double()[torch.where(valid, idx, torch.zeros_like(idx))] - case['q'].double().unsqueeze(1)).norm(dim=2)
+    case['idx'] = torch.where(valid & (d < 16 * ext), torch.full_like(idx, ns), idx).to(case['idx'].dtype)
+    case['kp'] = torch.from_numpy(fc.random_kernel_points(ext, 52, case['kp'].shape[0]))
+    case['extent'] = float(ext)
+    return case
+
+
+def influences_64(case, KP_influence):
+    """The float64 influences [nq, k, p] of the valid items (others 0)."""
+    d2, valid = _d2_64(case)
+    if KP_influence == 'linear':
+        w = torch.clamp(1 - torch.sqrt(d2) / case['extent'], min=0.0)
+    else:
+        w = torch.exp(-d2 / (2 * (case['extent'] * 0.3) ** 2 + 1e-9))
+    return w * valid.unsqueeze(2)
+
+
+# ---- operand magnitudes -------------------------------------------------------------------------------------------------
+MAG_ROUTES = ("tile32", "tile64")
+MAG_MODES = [('gaussian', 'sum'), ('linear', 'closest'), ('constant', 'closest')]
+MAG_KMAX = 16            # a power of two: kmax * max|x| is then exact in float32
+X_SCALES = [2.0 ** -20, 1.0, 2.0 ** 13]
+W_SCALES = [2.0 ** -10, 1.0, 2.0 ** 7]
+POW2_EDGES = ("below", "at", "above")
+
+
+def magnitude_case(route):
+    """65 queries (three tiles, the last with one live row), rows of MAG_KMAX; max|x| is below 1."""
+    return cloud_case(route, 65, 120, MAG_KMAX, 1e2, 0.125, 71)
+
+
+def pow2_edge_x(x, edge):
+    """x with its largest |entry| replaced so that max|x| is 4, or the float32 next below / above 4: kmax * max|x| is
+    then 2^6 exactly or one float32 step from it -- the edges of pow2_exp_for (the exponent field changes AT a power of
+    two).  x must stay below 4 elsewhere."""
+    x = x.clone()
+    four = np.float32(4.0)
+    v = {"at": four, "below": np.nextafter(four, np.float32(0)), "above": np.nextafter(four, np.float32(8))}[edge]
+    flat = x.view(-1)
+    flat[int(flat.abs().argmax())] = float(v)
+    return x
+
+
+def mixed_x(x):
+    """The second half of the support rows (the second cloud of a batch) 2^12 larger than the first."""
+    x = x.clone()
+    x[x.shape[0] // 2:] *= 2.0 ** 12
+    return x
+
+
+def saturating_case(route, edge):
+    """Every feature equal to the pow2_edge_x value (4, or one float32 step from it) and every row full (fill 1, row 3
+    all shadow): in constant / sum every weighted-feature sum of a live row IS kmax * max|x| -- the operand bound the
+    tile kernel scales by, reached, not merely bounded.  A scale one power of two too large overflows fp16 here (just
+    below 2^6 the operands sit just below 2^15 after scaling); one too small costs a bit everywhere."""
+    case = cloud_case(route, 65, 120, MAG_KMAX, 1e2, 0.125, 71, fill=1.0)
+    four = np.float32(4.0)
+    v = {"at": four, "below": np.nextafter(four, np.float32(0)), "above": np.nextafter(four, np.float32(8))}[edge]
+    case["x"] = torch.full_like(case["x"], float(v))
+    return case

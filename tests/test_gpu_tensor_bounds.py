@@ -18,8 +18,8 @@ a copy: the augmentation case therefore also hands them over as uint8, which is 
 of autograd.bgemm, int64 or non-contiguous tensors that ops._dev converts, and the parameters of a module (the
 cross-encoder's weights: its plan packs them).
 
-The last test checks that the cases called every spr_* entry point that ops.py, autograd.py, tie_order.py, augment.py
-and overlap.py reference, under the arena: a new operator fails it until it has a case here.  Run the module as a
+The last test checks that the cases called every spr_* entry point that any module of the package references, under
+the arena: a new operator fails it until it has a case here.  Run the module as a
 whole."""
 import os
 import re
@@ -53,7 +53,8 @@ CALLED = set()           # spr_* entry points called while a tensor arena was in
 
 
 # entry points with a host-only form beside the one that takes device operands: only the latter counts
-DEVICE_FORM = {"spr_augment_draw": lambda args: args[7] is not None and args[13] is not None}    # pair keys / keys out
+DEVICE_FORM = {"spr_augment_draw": lambda args: args[7] is not None and args[13] is not None,    # pair keys / keys out
+               "spr_modelnet_draw": lambda args: args[7] is not None and args[11] is not None}   # pair keys / rkeys out
 
 
 class _Recorder:
@@ -699,21 +700,84 @@ def test_weight_ranges_in_one_launch(device, monkeypatch):
         assert float(m) == float(t.abs().max())
 
 
+# ---- operators of the other host modules ---------------------------------------------------------------------------------
+def test_decoder_upsample_unary(device, monkeypatch):
+    """W.decoder_case: the gathered rows' index column, both feature tensors and the weights end at a band."""
+    f, check = W.decoder_case(device)
+    check(bounded(monkeypatch, f, "upsample_unary"))
+
+
+def test_kpconv_stem(device, monkeypatch):
+    f, check = W.stem_case(device)
+    check(bounded(monkeypatch, f, "kpconv_stem"))
+
+
+@pytest.mark.parametrize("name,mode", W.MODES_CASES, ids=lambda v: v if isinstance(v, str) else "-".join(v))
+def test_kpconv_modes(device, monkeypatch, name, mode):
+    f, check = W.kpconv_modes_case(device, name, mode)
+    check(bounded(monkeypatch, f, f"kpconv_modes {name} {mode}"))
+
+
+def test_modelnet_draw_and_pairs(device, monkeypatch):
+    f, check = W.modelnet_case(device)
+    check(bounded(monkeypatch, f, "modelnet_pairs"))
+
+
+@pytest.mark.parametrize("npairs", [1, 7])
+@pytest.mark.parametrize("c", [256, 3])
+def test_pair_gather_bwd(device, monkeypatch, c, npairs):
+    """The inputs and the criterion (the ordered float32 sum, bit for bit) of
+    test_gpu_shared_clouds.py::test_pair_gather_bwd_is_the_ordered_sum.  No workspace: only tensors."""
+    import test_gpu_shared_clouds as SC
+    from superpoints_registration_amd import shared_clouds
+    gy, lay, cu, ref = SC._bwd_case(c, npairs, device)
+
+    def f(put):
+        ins = [put(t) for t in (gy.to(device), cu.clone(), lay.use_ptr.clone(), lay.use_seg.clone(), lay.cu_out[0].clone())]
+        return shared_clouds.pair_gather_bwd(*ins, rows=sum(SC.LENS))
+    got = bounded(monkeypatch, f, f"pair_gather_bwd c={c} pairs={npairs}")
+    assert torch.equal(got.cpu().view(torch.int32), ref.view(torch.int32))
+
+
+@pytest.mark.parametrize("npairs", [1, 7])
+def test_overlap_pool_pairs(device, monkeypatch, npairs):
+    """test_gpu_shared_clouds.py::test_overlap_pool_pairs_is_overlap_pool_on_the_pair_layout: ops.overlap_pool on the
+    materialised pair-layout pool matrix, bit for bit (NaN rows -- a mean of nothing -- included)."""
+    import test_gpu_shared_clouds as SC
+    from superpoints_registration_amd import shared_clouds
+    lay, pool, ov, pool_pairs = SC._pool_case(npairs, device)
+    ref = ops.overlap_pool(ov.to(device), pool_pairs.to(device), lay.rows[0])
+
+    def f(put):
+        ins = [put(t) for t in (ov.to(device), pool.to(device), ops.lengths_to_cu(SC.LENS0, device),
+                                ops.lengths_to_cu(SC.LENS, device), lay.seg_cloud.clone(), lay.cu_out[0].clone(),
+                                lay.cu_out[1].clone())]
+        return shared_clouds.overlap_pool_pairs(*ins, rows=lay.rows[1])
+    got = bounded(monkeypatch, f, f"overlap_pool_pairs pairs={npairs}")
+    assert torch.equal(got.view(torch.int32), ref.view(torch.int32))
+
+
 # ---- coverage: keep this test last ---------------------------------------------------------------------------------------
 # entry points that are host-only or take no device operand
 EXEMPT = (r"_bytes$", r"_len$", r"_size$", r"_slots$", r"_tile_rows$", r"^spr_range_parts$", r"^spr_layernorm_range_count$",
           r"_host$", r"^spr_version$", r"^spr_selftest$", r"^spr_set_[a-z]+_mode$", r"^spr_prof_",
-          r"^spr_ransac_draw$")     # its draw table is written to a host array; it has no device operand
+          r"^spr_ransac_draw$",     # its draw table is written to a host array; it has no device operand
+          r"_supported$",           # spr_kpconv_stem_supported, spr_upsample_unary_supported: three ints in, one int out
+          r"^spr_last_error$")      # returns the thread's message string
 # entry points that no case can reach at small size, with the reason (none so far)
 UNREACHED = {}
 
 
 def test_every_entry_point_was_called_under_the_arena(device):
+    """Every module of the package is scanned (all but _lib.py, which names every entry point in its signature table):
+    an spr_* name referenced anywhere in them fails this test until a case above calls it under the arena."""
     pkg = os.path.dirname(ops.__file__)
-    text = "".join(open(os.path.join(pkg, n)).read() for n in ("ops.py", "autograd.py", "tie_order.py", "augment.py",
-                                                               "overlap.py"))
+    names = sorted(n for n in os.listdir(pkg) if n.endswith(".py") and n != "_lib.py")
+    assert {"ops.py", "autograd.py", "tie_order.py", "augment.py", "overlap.py", "decoder.py", "stem.py", "kpconv_modes.py",
+            "shared_clouds.py", "modelnet.py"} <= set(names)
+    text = "".join(open(os.path.join(pkg, n)).read() for n in names)
     referenced = {n for n in _lib.SIGNATURES if re.search(rf"\b{n}\b", text)}
     wanted = {n for n in referenced if not any(re.search(p, n) for p in EXEMPT)}
-    assert len(wanted) >= 70, len(wanted)
+    assert len(wanted) >= 80, len(wanted)
     missing = sorted(n for n in wanted if n not in CALLED and n not in UNREACHED)
     assert not missing, f"no case of this module called {missing} with guarded tensors"

@@ -17,8 +17,8 @@ also show a store outside a tensor, a returned element that was never written (t
 production last call's correct value there) and scratch read before it is written.  Regions of a returned tensor
 that include/spr.h declares not written are cut away inside the case (_owned).
 
-The last test of the module checks that the cases above reached every `_workspace(` / `_loss_ws(` call site of ops.py
-and autograd.py: a new operator fails it until it has a case here.  Run the module as a whole."""
+The last test of the module checks that the cases above reached every `_workspace(` / `_loss_ws(` call site of every
+module of the package: a new operator fails it until it has a case here.  Run the module as a whole."""
 import math
 import os
 import re
@@ -701,6 +701,152 @@ def test_whole_inference_forward(device, monkeypatch):
     run_three(monkeypatch, f, "inference forward", guard=1 << 16, verify_every=256)
 
 
+# ---- operators of the other host modules: decoder.py, stem.py, kpconv_modes.py, modelnet.py, tie_order.py --------------
+# Each builder returns (f, check): f(put) builds its inputs anew, passes every device operand through put and runs the
+# operator; check(production) applies the criterion of the test it names.  tests/test_gpu_tensor_bounds.py runs the
+# same builders with placed inputs.  (The test modules that import this one are imported inside the builders.)
+def decoder_case(device):
+    """decoder.upsample_unary, fused route: the widest-tail shape of
+    test_gpu_decoder.py::test_fused_call_inside_its_tensors_and_workspace (two whole tiles + 3 rows, shadow and negative
+    indices), under the float64 bound of ::test_upsample_unary_against_float64."""
+    import test_gpu_decoder as D
+    from superpoints_registration_amd import decoder
+    kc, ks, n_out, n, nc = 64, 32, 64, 2 * D.TILE + 3, 5
+    xc, xs = synthetic.rand((nc, kc), 71, -3.0, 3.0), synthetic.rand((n, ks), 72, -3.0, 3.0)
+    w = synthetic.rand((n_out, kc + ks), 73, -0.2, 0.2)
+    idx = D._indices("shadow", n, nc)
+
+    def f(put):
+        ins = [put(t) for t in (xc.to(device), xs.to(device), D._matrix(idx, 1, device), w.to(device))]
+        return decoder.upsample_unary(*ins, route="fused")
+
+    def check(y):
+        D._check(y, D._ref64(xc, xs, idx, w), 2e-6 * max(1, (kc + ks) // 256), "upsample_unary")
+    return f, check
+
+
+def stem_case(device):
+    """stem.kpconv_stem on the ragged batch of test_gpu_stem.py (cout 64, random features), statistics included: the
+    bits of that module's production call (::test_stem_inside_exactly_its_workspace's criterion); the float64 check
+    of these shapes is tests/test_gpu_stem_range.py."""
+    import test_gpu_stem as S
+    from superpoints_registration_amd import stem
+    d = S._stem_case(device, 64, "random")
+
+    def f(put):
+        q, s, nb, x, w, kp, cu = (put(d[k].clone()) for k in ("q", "s", "nb", "x", "w", "kp", "cu"))
+        return stem.kpconv_stem(q, s, nb, x, w, kp, S.EXT, cu, slope=0.1, rows_sorted=True, max_len=d["ml"],
+                                return_stats=True)
+
+    def check(out):
+        for got, want in zip(out, (d["out"], d["smean"], d["srstd"])):
+            assert torch.equal(_bits(got), _bits(want))
+    return f, check
+
+
+def kpconv_modes_case(device, name, mode):
+    """kpconv_modes forward, weighted features and d x (KPConvModesFn) on a case of tests/test_gpu_kpconv_modes.py,
+    under ::test_backward_matches_float64_autograd's bounds."""
+    import test_gpu_kpconv_modes as M
+    case = M.case_of(name)
+    go, ref, dx_ref, dw_ref = M.ref_of(name, mode)
+
+    def f(put):
+        d = M.on_device(case, device, put)
+        x, w = d["x"].requires_grad_(True), d["w"].requires_grad_(True)
+        out = M.run_forward(dict(d, x=x, w=w), mode)
+        out.backward(put(go.clone().to(device)))
+        return out.detach(), x.grad, w.grad
+
+    def check(res):
+        out, dx, dw = res
+        assert M.scale_err(out, ref) <= 1e-5 and _rel(dx, dx_ref) <= 2e-5 and _rel(dw, dw_ref) <= 2e-5
+    return f, check
+
+
+MODES_CASES = [("tile strided nq37 ns130 k33 32-64", ('gaussian', 'closest')), ("tile nq37 k5 64-64", ('constant', 'sum')),
+               ("simple 48-40", ('linear', 'closest'))]
+
+
+def modelnet_case(device):
+    """modelnet.modelnet_draw (device form) and modelnet.modelnet_pairs with inline and with explicit draws, the batch
+    of test_gpu_modelnet_pairs.py::test_every_tensor_and_the_workspace_between_poisoned_guard_bands; the two forms
+    agree in every bit (::test_inline_draws_equal_explicit_buffers_and_the_numpy_philox)."""
+    import test_gpu_modelnet_pairs as MP
+    from superpoints_registration_amd import modelnet
+    seed, keys, lens, k = 77, [5, 6, 7], [700, 2048, 333], 717
+    xyz = T(np.concatenate([MP.shape_cloud(n, 20 + b) for b, n in enumerate(lens)])).to(device)
+
+    def owned(r):
+        cnt = r["corr_count"].tolist()                 # columns past a pair's count are not written (include/spr.h)
+        cols = torch.cat([torch.arange(i * k, i * k + c) for i, c in enumerate(cnt)]).to(r["corr"].device)
+        return dict(r, corr=r["corr"][:, cols])
+
+    def f(put):
+        pts, cu = put(xyz.clone()), put(ops.lengths_to_cu(lens, device))
+        dirs, tf, rk, ex, nz, sk = modelnet.modelnet_draw(seed, keys, 45.0, 0.5, cu, sum(lens), k)
+        tf_d, dirs_d = put(T(tf).to(device)), put(T(dirs).to(device))
+        inline = modelnet.modelnet_pairs(pts, cu, max(lens), MP.P07, k, tf_d, dirs_d, seed=seed, pair_keys=keys)
+        explicit = modelnet.modelnet_pairs(pts, cu, max(lens), MP.P07, k, tf_d, dirs_d, rkeys=rk, extra=ex, noise=nz, skeys=sk)
+        return owned(inline), owned(explicit), rk, ex, nz, sk
+
+    def check(res):
+        inline, explicit = res[0], res[1]
+        assert not bool(inline["status"].any()) and int(inline["corr_count"].sum()) > 0
+        for key in inline:
+            assert torch.equal(_bits(inline[key]), _bits(explicit[key])), f"inline and explicit draws differ in {key}"
+    return f, check
+
+
+def tie_order_case(device, name, limit):
+    """ops.radius_neighbors(tie_order='reference'): the kd-tree replay and spr_tie_order on a case of
+    test_gpu_tie_order.py::test_radius_neighbors_gives_the_reference_rows, held against the reference's rows."""
+    import tie_order_cases as tc
+    c, gold = tc.cases()[name], tc.load_golden()
+    sup, qry = T(np.array(c.sup)).to(device), T(np.array(c.qry)).to(device)
+
+    def f(put):
+        s, scu = put(sup.clone()), put(ops.lengths_to_cu(list(c.s_lens), device))
+        q, qcu = (s, scu) if c.qry is c.sup else (put(qry.clone()), put(ops.lengths_to_cu(list(c.q_lens), device)))
+        rows, mc = ops.radius_neighbors(q, s, qcu, scu, c.radius, limit, tie_order='reference')
+        return rows, torch.tensor([mc])
+
+    def check(res):
+        assert np.array_equal(res[0].cpu().numpy(), tc.reference_rows(gold, name, limit))
+    return f, check
+
+
+def _unplaced(f):
+    return lambda: f(lambda t: t)
+
+
+def test_decoder_upsample_unary(device, monkeypatch):
+    f, check = decoder_case(device)
+    check(run_three(monkeypatch, _unplaced(f), "upsample_unary"))
+
+
+def test_kpconv_stem(device, monkeypatch):
+    f, check = stem_case(device)
+    check(run_three(monkeypatch, _unplaced(f), "kpconv_stem"))
+
+
+@pytest.mark.parametrize("name,mode", MODES_CASES, ids=lambda v: v if isinstance(v, str) else "-".join(v))
+def test_kpconv_modes(device, monkeypatch, name, mode):
+    f, check = kpconv_modes_case(device, name, mode)
+    check(run_three(monkeypatch, _unplaced(f), f"kpconv_modes {name} {mode}"))
+
+
+def test_modelnet_pairs(device, monkeypatch):
+    f, check = modelnet_case(device)
+    check(run_three(monkeypatch, _unplaced(f), "modelnet_pairs"))
+
+
+@pytest.mark.parametrize("name,limit", [("batch3", 17), ("n1", 5)])
+def test_tie_order(device, monkeypatch, name, limit):
+    f, check = tie_order_case(device, name, limit)
+    check(run_three(monkeypatch, _unplaced(f), f"tie order {name}"))
+
+
 # ---- one byte short is refused -------------------------------------------------------------------------------------------
 class _OneByteShort(Arena):
     """Hands out [GUARD, GUARD + nbytes - 1): the guards still stand around the nbytes the caller asked for."""
@@ -842,6 +988,37 @@ def test_one_byte_short_is_refused(device, monkeypatch):
     cfs, cft, cxs, cxt = circle_case(seed=sorted(CIRCLE_REGIMES).index("ragged") + 1, **CIRCLE_REGIMES["ragged"])
     case("circle_loss", lambda _: circle_run(device, cfs, cft, cxs, cxt)[0])
 
+    # the other host modules: one case per workspace layout (the builders above, inputs as they come)
+    for what, builder in (("upsample_unary", decoder_case), ("kpconv_stem", stem_case), ("modelnet_pairs", modelnet_case)):
+        case(what, lambda _, f=builder(device)[0]: f(lambda t: t))
+    import test_gpu_kpconv_modes as M
+    md = M.on_device(M.case_of("simple 48-40"), device)
+    case("kpconv_modes forward", lambda _: M.run_forward(md, ('gaussian', 'closest')))
+    # the two backward sites of kpconv_modes.py, as test_gpu_kpconv_modes.py::test_one_byte_short_is_refused calls them
+    from superpoints_registration_amd import kpconv_modes, tie_order
+    infl, agg = kpconv_modes.mode_codes('gaussian', 'closest')
+    dwf = synthetic.rand((md["q"].shape[0], md["kp"].shape[0] * md["x"].shape[1]), 5).to(device)
+    case("kpconv_modes weighted features", lambda _: kpconv_modes.weighted_features(md["q"], md["s"], md["idx"], md["x"], md["kp"],
+                                                                                     md["extent"], infl, agg))
+    case("kpconv_modes bwd_dx", lambda _: kpconv_modes.bwd_dx(md["q"], md["s"], md["idx"], md["x"].shape[1], md["kp"],
+                                                              md["extent"], infl, agg, dwf))
+    # the tie-order fix-up alone (ops.radius_neighbors would ask for the search's workspace first): the nearest-rule
+    # rows of tie_order_cases' "batch3", built anew per run since the fix-up rewrites them in place
+    import tie_order_cases as tc
+    c = tc.cases()["batch3"]
+    sup, scu = T(np.array(c.sup)).to(device), ops.lengths_to_cu(list(c.s_lens), device)
+    tree = tie_order.ReplayTree(sup, scu)
+
+    def tie_rows():
+        rows, mc = ops.radius_neighbors(sup, sup, scu, scu, c.radius, 17)
+        return rows, mc
+
+    def tie_fix(state):
+        rows, mc = state
+        tree.apply(rows, sup, scu, c.radius, mc)
+        return rows
+    case("tie_order", tie_fix, tie_rows)
+
     assert set(FALLS_BACK) <= {c[0] for c in cases}
     for what, prepare, run in cases:
         _one_byte_short(monkeypatch, what, prepare, run)
@@ -853,12 +1030,16 @@ EXCLUDED = {}
 
 
 def test_every_workspace_call_site_was_reached(device):
+    """Every module of the package is scanned (all but _lib.py, the binding itself): a `_workspace(` / `_loss_ws(` call
+    site in any of them fails this test until a case above reaches it."""
     pkg = os.path.dirname(ops.__file__)
     sites = []
-    for name in ("ops.py", "autograd.py"):
+    names = sorted(n for n in os.listdir(pkg) if n.endswith(".py") and n != "_lib.py")
+    assert {"ops.py", "autograd.py", "decoder.py", "stem.py", "kpconv_modes.py", "modelnet.py", "tie_order.py"} <= set(names)
+    for name in names:
         for no, line in enumerate(open(os.path.join(pkg, name)).read().splitlines(), 1):
             if re.search(r"_workspace\(|_loss_ws\(", line) and not re.match(r"\s*def (_workspace|_loss_ws)\(", line):
                 sites.append((name, no))
-    assert len(sites) >= 36
+    assert len(sites) >= 45, len(sites)
     missing = [s for s in sites if s not in SEEN and s not in EXCLUDED]
     assert not missing, f"no case of this module reached {missing}"
