@@ -68,6 +68,44 @@ int spr_grid_subsample(const float* xyz, const int* cu, int n, int nb, float dl,
                        int max_p, int order_mode, float* out_xyz, int* out_lens,
                        int* out_total, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- a1 with attributes: features averaged, labels voted per voxel -----------
+ * Replaces grid_subsampling.subsample_batch(points, batches, features=, classes=, sampleDl=, max_p=)
+ * (cpp_subsampling/wrapper.cpp:62-82, :199-206 -> grid_subsampling.cpp:109 batch_grid_subsampling), called from
+ * models/backbone_kpconv/kpconv.py:187-214.
+ *   Points.   out_xyz, out_lens, out_total, the row order in both order modes, the max_p cut and the -1 code are bit
+ *             for bit what spr_grid_subsample gives for the same arguments; the attribute rows follow the same row
+ *             order and the same cut (grid_subsampling.cpp:181-204).
+ *   Features. feat [n, fdim] f32 -> out_feat [n, fdim] f32, first *out_total rows valid.  Per voxel and column: the
+ *             float32 sum of the voxel's points in original point order, starting from +0 (grid_subsampling.h:46,
+ *             :59), then ONE IEEE division by (float)count (grid_subsampling.cpp:90-94) -- not the multiplication by
+ *             (float)(1.0 / count) of the barycentre (:87).  No reassociation, no contraction.
+ *   Labels.   lab [n, ldim] i32 -> out_lab [n, ldim] i32: per voxel and column the label with the largest count
+ *             (grid_subsampling.h:50, :69; grid_subsampling.cpp:99-101).  Any int32 is a label; there is no cap on
+ *             the number of distinct labels in a voxel.
+ *   Ties.     max_element returns the FIRST maximum in the iteration order of the std::unordered_map<int, int> that
+ *             received the voxel's labels in point order (grid_subsampling.cpp:100-101).  That order is a list rule:
+ *             hash = the label sign-extended to size_t, bucket = hash % bucket_count; the bucket count grows
+ *             1 -> 13 -> 29 -> 59 -> 127 -> ... when the 1st, 14th, 30th, 60th, 128th ... distinct label arrives (the
+ *             schedule is measured on a real std::unordered_map<int, int> at run time, not tabulated); a new label
+ *             whose bucket is empty goes to the front of the list, otherwise directly in front of the first list
+ *             element of its bucket; a growth re-inserts the old list, front to back, by the same rule under the
+ *             new bucket count.
+ *   Arguments. fdim == 0: feat and out_feat are NULL (not read, not written); likewise ldim.  Both 0 is the plain
+ *             call.  A negative dimension, or a NULL where the dimension is positive, is refused, status 2, before
+ *             anything is enqueued; so is a workspace below spr_grid_subsample_attrs_workspace_size(n, nb, fdim,
+ *             ldim), which is never below spr_grid_subsample_workspace_bytes(n, nb) and does not depend on fdim.
+ *   ldim > 1 with nb > 1.  The reference slices the class vector of cloud b wrongly there
+ *             (grid_subsampling.cpp:157-158: the slice ends at sum_b + len * ldim instead of (sum_b + len) * ldim),
+ *             so for every cloud after the first the range is too short and can end before it begins, an invalid
+ *             iterator pair for the vector constructor: undefined behaviour, nothing to reproduce.  This
+ *             library applies the single-cloud rule to every cloud, with lab row i belonging to point i.  It is
+ *             compared against the reference only for ldim == 1 or nb == 1.
+ */
+size_t spr_grid_subsample_attrs_workspace_size(int n, int nb, int fdim, int ldim);
+int spr_grid_subsample_attrs(const float* xyz, const int* cu, int n, int nb, float dl, int max_p, int order_mode,
+                             const float* feat, int fdim, const int* lab, int ldim, float* out_xyz, float* out_feat,
+                             int* out_lab, int* out_lens, int* out_total, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- voxel pre-downsampling, one point per voxel ------------
  * Replaces voxel_down_sample of the KITTI loader (data_loaders/kitti_pred.py:12-14,
  * :203-204 -> kiss_icp): voxel = trunc(p / voxel_size) per axis in float64, the first point of

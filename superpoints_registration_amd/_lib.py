@@ -26,6 +26,9 @@ SIGNATURES = {
     "spr_last_error": (ctypes.c_char_p, []),
     "spr_grid_subsample_workspace_bytes": (_sz, [_i, _i]),
     "spr_grid_subsample": (_i, [_vp, _vp, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "spr_grid_subsample_attrs_workspace_size": (_sz, [_i, _i, _i, _i]),
+    "spr_grid_subsample_attrs": (_i, [_vp, _vp, _i, _i, _f, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                      _vp]),
     "spr_voxel_downsample_workspace_bytes": (_sz, [_i]),
     "spr_voxel_downsample": (_i, [_vp, _i, ctypes.c_double, _vp, _vp, _vp, _sz, _vp]),
     "spr_prepare_scans_scratch_len": (_sz, [_i, _i]),

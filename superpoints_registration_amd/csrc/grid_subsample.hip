@@ -56,22 +56,43 @@ struct SchedArg {
 struct Schedule {
   std::vector<unsigned int> buckets;  // [0] = 1 (initial), then each growth
 };
+template <class Map>
+std::vector<unsigned int> measure_schedule(size_t upto) {
+  std::vector<unsigned int> out;
+  Map m;
+  size_t bc = m.bucket_count();
+  out.push_back((unsigned int)bc);
+  for (size_t i = 0; i < upto; ++i) {
+    m.emplace((typename Map::key_type)i, 0);
+    if (m.bucket_count() != bc) {
+      bc = m.bucket_count();
+      out.push_back((unsigned int)bc);
+    }
+  }
+  return out;
+}
 const Schedule& host_schedule() {
   static Schedule s;
   static std::once_flag once;
   std::call_once(once, [] {
-    std::unordered_map<size_t, char> m;
-    size_t bc = m.bucket_count();
-    s.buckets.push_back((unsigned int)bc);
-    const size_t kMax = (size_t)1 << 22;  // clouds up to 4M voxels
-    for (size_t i = 0; i < kMax; ++i) {
-      m.emplace(i, 0);
-      if (m.bucket_count() != bc) {
-        bc = m.bucket_count();
-        s.buckets.push_back((unsigned int)bc);
-      }
-    }
+    s.buckets = measure_schedule<std::unordered_map<size_t, char>>((size_t)1 << 22);  // clouds up to 4M voxels
   });
+  return s;
+}
+// The same measurement on the container of the label vote, std::unordered_map<int, int> (grid_subsampling.h:20), for
+// voxels of up to `keys` distinct labels.  A voxel holds at most n labels, so the caller asks for n: measured once per
+// power of two, the largest kept.
+Schedule label_schedule(size_t keys) {
+  static Schedule s;
+  static size_t covered = 0;
+  static std::mutex mu;
+  std::lock_guard<std::mutex> lock(mu);
+  if (keys > covered) {
+    size_t upto = (size_t)1 << 16;
+    while (upto < keys) upto <<= 1;
+    s.buckets = measure_schedule<std::unordered_map<int, int>>(upto);
+    covered = upto;
+  }
   return s;
 }
 
@@ -238,13 +259,14 @@ __global__ void k_emit_canonical(const float* __restrict__ bary,
                                  const int* __restrict__ nvox_p,
                                  const int* __restrict__ vcu,
                                  const int* __restrict__ out_cu,
-                                 const int* __restrict__ out_lens, float* out) {
+                                 const int* __restrict__ out_lens, float* out, int* __restrict__ rowvox) {
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= *nvox_p) return;
   const int c = (int)((vkey[v] & ~kKeyWrapped) >> kKeyBits);
   const int r = v - vcu[c];
   if (r >= out_lens[c]) return;
   const size_t o = (size_t)(out_cu[c] + r);
+  if (rowvox) rowvox[o] = v;   // output row -> voxel, for the attribute passes (NULL: plain call)
   out[3 * o + 0] = bary[3 * (size_t)v + 0];
   out[3 * o + 1] = bary[3 * (size_t)v + 1];
   out[3 * o + 2] = bary[3 * (size_t)v + 2];
@@ -325,7 +347,7 @@ __global__ __launch_bounds__(1024) void k_umap_order(
     const int* __restrict__ vcu, const int* __restrict__ cu, int nsched, SchedArg sched,
     int* listA, int* listB, int* tfirst, int* tcnt, int* thead, int* nxt,
     int* scan, int* bucket, const float* __restrict__ bary, const int* __restrict__ out_cu,
-    const int* __restrict__ out_lens, float* out) {
+    const int* __restrict__ out_lens, float* out, int* __restrict__ rowvox) {
   __shared__ int lds[1024];
   extern __shared__ int lds_tab[];
   const int c = blockIdx.x;
@@ -404,6 +426,7 @@ __global__ __launch_bounds__(1024) void k_umap_order(
     out[3 * (ob + p) + 0] = bary[3 * v + 0];
     out[3 * (ob + p) + 1] = bary[3 * v + 1];
     out[3 * (ob + p) + 2] = bary[3 * v + 2];
+    if (rowvox) rowvox[ob + p] = (int)v;
   }
 }
 
@@ -462,29 +485,25 @@ SubsampleWs subsample_layout(Workspace& w, int n, int nb) {
   return l;
 }
 
-}  // namespace
-}  // namespace spr
-
-using namespace spr;
-
-extern "C" size_t spr_grid_subsample_workspace_bytes(int n, int nb) {
-  return measure(subsample_layout, n, nb);
+SchedArg sched_arg(const Schedule& s, int* nsched) {
+  SchedArg sched;
+  for (int i = 0; i < kMaxSched; ++i)
+    sched.v[i] = i < (int)s.buckets.size() ? s.buckets[i] : 0xffffffffu;
+  *nsched = (int)(s.buckets.size() < (size_t)kMaxSched ? s.buckets.size() : kMaxSched);
+  return sched;
 }
 
-extern "C" int spr_grid_subsample(const float* xyz, const int* cu, int n, int nb,
-                                  float dl, int max_p, int order_mode,
-                                  float* out_xyz, int* out_lens, int* out_total,
-                                  void* ws, size_t ws_bytes, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
-  SPR_REQUIRE(n >= 0 && nb >= 1, "grid_subsample: bad sizes n=%d nb=%d", n, nb);
-  SPR_REQUIRE(dl > 0.f, "grid_subsample: sampleDl must be > 0");
-  SPR_REQUIRE(nb < (1 << 23), "grid_subsample: too many clouds");
-  // reference: subsampling an empty batch is an error (wrapper.cpp:266-270)
-  SPR_REQUIRE(n > 0, "grid_subsample: empty input");
-  Workspace w(ws, ws_bytes);
+// Everything both entry points enqueue, up to the emitted points; the caller ends with k_check_err.  Left behind for
+// the attribute passes: vals2 (point indices sorted by voxel, original order inside a voxel), scalars[0] (voxel
+// count), out_cu, and -- only when the caller hands in `rank` and `rowvox` -- vstart (segment starts) and rowvox
+// (output row -> voxel, after the order mode and the max_p cut).  The plain call passes NULL for both: the insertion
+// ranks then overwrite vstart, as they always have.
+int subsample_enqueue(const SubsampleWs& l, const float* xyz, const int* cu, int n, int nb, float dl, int max_p,
+                      int order_mode, float* out_xyz, int* out_lens, int* out_total, int* rank, int* rowvox,
+                      hipStream_t stream) {
   const auto [info, keys, keys2, vkey, vals, vals2, flags, vid, vstart, vfirst, sval, sval2, listA, listB, nxt, scan, bary,
-              tfirst, tcnt, thead, cloud_cnt, vcu, out_cu, scalars, temp_bytes, temp] = subsample_layout(w, n, nb);
-  SPR_REQUIRE(ws != nullptr && w.ok(), "grid_subsample: workspace too small");
+              tfirst, tcnt, thead, cloud_cnt, vcu, out_cu, scalars, temp_bytes, temp] = l;
+  if (!rank) rank = vstart;
   const size_t N = (size_t)n;
   int* nvox = scalars;
   int* err = scalars + 1;
@@ -518,26 +537,235 @@ extern "C" int spr_grid_subsample(const float* xyz, const int* cu, int n, int nb
   SPR_LAUNCH_CHECK();
   if (order_mode == SPR_ORDER_CANONICAL) {
     hipLaunchKernelGGL(k_emit_canonical, dim3(cdiv(n, TB)), dim3(TB), 0, stream, bary,
-                       vkey, nvox, vcu, out_cu, out_lens, out_xyz);
+                       vkey, nvox, vcu, out_cu, out_lens, out_xyz, rowvox);
   } else {
-    const Schedule& s = host_schedule();
-    SchedArg sched;
-    for (int i = 0; i < kMaxSched; ++i)
-      sched.v[i] = i < (int)s.buckets.size() ? s.buckets[i] : 0xffffffffu;
-    const int nsched = (int)(s.buckets.size() < (size_t)kMaxSched ? s.buckets.size() : kMaxSched);
+    int nsched;
+    const SchedArg sched = sched_arg(host_schedule(), &nsched);
     // insertion order: flags / vid / vstart are free again after k_bary (mark, who, rank)
     SPR_HIP_CHECK(hipMemsetAsync(flags, 0, N * sizeof(int), stream));
     hipLaunchKernelGGL(k_mark_first, dim3(cdiv(n, TB)), dim3(TB), 0, stream, vfirst, nvox, flags, vid);
     tb = temp_bytes;
-    SPR_HIP_CHECK(rocprim::exclusive_scan(temp, tb, flags, vstart, 0, (size_t)n, rocprim::plus<int>(), stream));
-    hipLaunchKernelGGL(k_compact_first, dim3(cdiv(n, TB)), dim3(TB), 0, stream, flags, vstart, vid, n, sval2);
+    SPR_HIP_CHECK(rocprim::exclusive_scan(temp, tb, flags, rank, 0, (size_t)n, rocprim::plus<int>(), stream));
+    hipLaunchKernelGGL(k_compact_first, dim3(cdiv(n, TB)), dim3(TB), 0, stream, flags, rank, vid, n, sval2);
     const int umap_lds = kUmapLdsInts * (int)sizeof(int);
     if (int rc = ensure_dyn_lds((const void*)k_umap_order, umap_lds)) return rc;
     hipLaunchKernelGGL(k_umap_order, dim3(nb), dim3(1024), umap_lds, stream, vkey, sval2, vcu, cu,
                        nsched, sched, listA, listB, tfirst, tcnt, thead, nxt, scan, sval, bary, out_cu,
-                       out_lens, out_xyz);
+                       out_lens, out_xyz, rowvox);
   }
-  hipLaunchKernelGGL(k_check_err, dim3(1), dim3(1), 0, stream, err, out_total);
+  SPR_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- attributes: feature average and label vote per voxel -------------------------------------------------------------
+// One thread per (output row, column), the column fastest: the threads of a row read one point's attribute row together.
+// Each walks its voxel's segment of vals2 in order, which is the original point order (stable sort), as k_bary does.
+struct Segment {
+  int beg, end;
+};
+__device__ __forceinline__ Segment segment_of(int v, const int* __restrict__ vstart, int nvox, int n) {
+  return {vstart[v], (v + 1 < nvox) ? vstart[v + 1] : n};
+}
+
+// grid_subsampling.h:46,59 (float32 sum in point order, from +0) and grid_subsampling.cpp:90-94 (one division by
+// (float)count -- not the barycentre's multiplication by a reciprocal).
+__global__ void k_attr_features(const float* __restrict__ feat, int fdim, const int* __restrict__ vals,
+                                const int* __restrict__ vstart, const int* __restrict__ nvox_p, int n,
+                                const int* __restrict__ rowvox, const int* __restrict__ out_cu, int nb,
+                                float* __restrict__ out_feat) {
+  const size_t total = (size_t)out_cu[nb] * (size_t)fdim;
+  const int nvox = *nvox_p;
+  for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+    const size_t row = t / (size_t)fdim;
+    const size_t col = t - row * (size_t)fdim;
+    const Segment s = segment_of(rowvox[row], vstart, nvox, n);
+    float sum = 0.f;
+    for (int j = s.beg; j < s.end; ++j) sum = __fadd_rn(sum, feat[(size_t)vals[j] * (size_t)fdim + col]);
+    out_feat[t] = __fdiv_rn(sum, (float)(s.end - s.beg));
+  }
+}
+
+// std::hash<int> is the value converted to size_t, i.e. sign extended; the bucket is hash % bucket_count.
+__device__ __forceinline__ int label_bucket(int label, unsigned int nbk) {
+  return (int)((unsigned long long)(long long)label % (unsigned long long)nbk);
+}
+// One insertion into the node list of a libstdc++ hashtable (hashtable.h _M_insert_bucket_begin, and _M_rehash_aux,
+// which re-inserts by the same rule): the node goes to the list's front if its bucket is empty, else directly in front
+// of the first node of its bucket.  list: key numbers (first-arrival rank), bkt: bucket per key number.
+__device__ __forceinline__ int list_insert(int* __restrict__ list, int len, int id, const int* __restrict__ bkt) {
+  const int b = bkt[id];
+  int at = 0;
+  while (at < len && bkt[list[at]] != b) ++at;
+  if (at == len) at = 0;
+  for (int j = len; j > at; --j) list[j] = list[j - 1];
+  list[at] = id;
+  return len + 1;
+}
+
+// grid_subsampling.h:50,69 (labels[i][*it] += 1 in point order) and grid_subsampling.cpp:99-101 (max_element over the
+// map's iteration order with `<` on the counts: the first maximum in that order wins).
+// The thread keeps its voxel's distinct labels and their counts in first-arrival order in its segment's slice of
+// dist / cnt (a segment of k points has at most k distinct labels); only a tied maximum needs the iteration order,
+// and then the container's node list is replayed in the same slice of la / lb / bkt: epoch e of the bucket schedule
+// re-inserts the list front to back under sched[e] buckets and appends the keys that arrive before the next growth
+// (the k-th distinct key, k counted from 0, arrives when the table has sched[e] > k buckets: k_umap_order's epochs).
+__global__ void k_attr_labels(const int* __restrict__ lab, int ldim, const int* __restrict__ vals,
+                              const int* __restrict__ vstart, const int* __restrict__ nvox_p, int n,
+                              const int* __restrict__ rowvox, const int* __restrict__ out_cu, int nb, int nsched,
+                              SchedArg sched, int* __restrict__ dist, int* __restrict__ cnt, int* __restrict__ la,
+                              int* __restrict__ lb, int* __restrict__ bkt, int* __restrict__ out_lab, int* err) {
+  const size_t total = (size_t)out_cu[nb] * (size_t)ldim;
+  const int nvox = *nvox_p;
+  for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+    const size_t row = t / (size_t)ldim;
+    const size_t col = t - row * (size_t)ldim;
+    const Segment s = segment_of(rowvox[row], vstart, nvox, n);
+    const size_t slice = col * (size_t)n + (size_t)s.beg;
+    int* d = dist + slice;
+    int* c = cnt + slice;
+    int m = 0;
+    for (int j = s.beg; j < s.end; ++j) {
+      const int l = lab[(size_t)vals[j] * (size_t)ldim + col];
+      int k = 0;
+      while (k < m && d[k] != l) ++k;
+      if (k == m) {
+        d[m] = l;
+        c[m] = 1;
+        ++m;
+      } else {
+        c[k] += 1;
+      }
+    }
+    int best = 0, tied = 1;
+    for (int k = 1; k < m; ++k) {
+      if (c[k] > c[best]) {
+        best = k;
+        tied = 1;
+      } else if (c[k] == c[best]) {
+        ++tied;
+      }
+    }
+    if (tied > 1) {
+      const int top = c[best];
+      int* cur = la + slice;
+      int* other = lb + slice;
+      int* bk = bkt + slice;
+      int len = 0, done = 0, e = 0;
+      while (done < m) {
+        e += 1;
+        if (e >= nsched) {   // cannot happen: the host measured the schedule for n keys
+          atomicOr(err, 1);
+          break;
+        }
+        const unsigned int nbk = sched.v[e];
+        const int upto = (unsigned int)m < nbk ? m : (int)nbk;
+        for (int k = 0; k < upto; ++k) bk[k] = label_bucket(d[k], nbk);
+        int relen = 0;
+        for (int i = 0; i < len; ++i) relen = list_insert(other, relen, cur[i], bk);
+        int* tmp = cur;
+        cur = other;
+        other = tmp;
+        for (int k = done; k < upto; ++k) len = list_insert(cur, len, k, bk);
+        done = upto;
+      }
+      for (int i = 0; i < len; ++i) {
+        if (c[cur[i]] == top) {
+          best = cur[i];
+          break;
+        }
+      }
+    }
+    out_lab[t] = d[best];
+  }
+}
+
+// The plain layout, then what the attribute passes add: rank (the insertion ranks, so that vstart survives), rowvox,
+// and five ints per (point, label column) for the vote.  Nothing depends on fdim.
+struct AttrsWs {
+  SubsampleWs sub;
+  int *rank, *rowvox, *dist, *cnt, *la, *lb, *bkt;
+};
+AttrsWs attrs_layout(Workspace& w, int n, int nb, int fdim, int ldim) {
+  const size_t N = (size_t)(n > 0 ? n : 1), L = (size_t)(ldim > 0 ? ldim : 0);
+  (void)fdim;
+  AttrsWs l;
+  l.sub = subsample_layout(w, n, nb);
+  l.rank = w.take<int>(N);
+  l.rowvox = w.take<int>(N);
+  for (int** p : {&l.dist, &l.cnt, &l.la, &l.lb, &l.bkt}) *p = w.take<int>(N * L);
+  return l;
+}
+
+}  // namespace
+}  // namespace spr
+
+using namespace spr;
+
+extern "C" size_t spr_grid_subsample_workspace_bytes(int n, int nb) {
+  return measure(subsample_layout, n, nb);
+}
+
+extern "C" int spr_grid_subsample(const float* xyz, const int* cu, int n, int nb,
+                                  float dl, int max_p, int order_mode,
+                                  float* out_xyz, int* out_lens, int* out_total,
+                                  void* ws, size_t ws_bytes, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SPR_REQUIRE(n >= 0 && nb >= 1, "grid_subsample: bad sizes n=%d nb=%d", n, nb);
+  SPR_REQUIRE(dl > 0.f, "grid_subsample: sampleDl must be > 0");
+  SPR_REQUIRE(nb < (1 << 23), "grid_subsample: too many clouds");
+  // reference: subsampling an empty batch is an error (wrapper.cpp:266-270)
+  SPR_REQUIRE(n > 0, "grid_subsample: empty input");
+  Workspace w(ws, ws_bytes);
+  const SubsampleWs l = subsample_layout(w, n, nb);
+  SPR_REQUIRE(ws != nullptr && w.ok(), "grid_subsample: workspace too small");
+  if (int rc = subsample_enqueue(l, xyz, cu, n, nb, dl, max_p, order_mode, out_xyz, out_lens, out_total, nullptr, nullptr,
+                                 stream))
+    return rc;
+  hipLaunchKernelGGL(k_check_err, dim3(1), dim3(1), 0, stream, l.scalars + 1, out_total);
+  SPR_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" size_t spr_grid_subsample_attrs_workspace_size(int n, int nb, int fdim, int ldim) {
+  return measure(attrs_layout, n, nb, fdim, ldim);
+}
+
+extern "C" int spr_grid_subsample_attrs(const float* xyz, const int* cu, int n, int nb, float dl, int max_p,
+                                        int order_mode, const float* feat, int fdim, const int* lab, int ldim,
+                                        float* out_xyz, float* out_feat, int* out_lab, int* out_lens, int* out_total,
+                                        void* ws, size_t ws_bytes, void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  SPR_REQUIRE(n >= 0 && nb >= 1, "grid_subsample_attrs: bad sizes n=%d nb=%d", n, nb);
+  SPR_REQUIRE(dl > 0.f, "grid_subsample_attrs: sampleDl must be > 0");
+  SPR_REQUIRE(nb < (1 << 23), "grid_subsample_attrs: too many clouds");
+  SPR_REQUIRE(n > 0, "grid_subsample_attrs: empty input");
+  SPR_REQUIRE(fdim >= 0 && ldim >= 0, "grid_subsample_attrs: negative dimension fdim=%d ldim=%d", fdim, ldim);
+  SPR_REQUIRE(fdim == 0 || (feat && out_feat), "grid_subsample_attrs: fdim=%d without features in and out", fdim);
+  SPR_REQUIRE(ldim == 0 || (lab && out_lab), "grid_subsample_attrs: ldim=%d without labels in and out", ldim);
+  Workspace w(ws, ws_bytes);
+  const AttrsWs l = attrs_layout(w, n, nb, fdim, ldim);
+  SPR_REQUIRE(ws != nullptr && w.ok(), "grid_subsample_attrs: workspace too small");
+  int nsched = 0;
+  SchedArg sched;
+  if (ldim > 0) sched = sched_arg(label_schedule((size_t)n), &nsched);   // host work: before anything is enqueued
+  if (int rc = subsample_enqueue(l.sub, xyz, cu, n, nb, dl, max_p, order_mode, out_xyz, out_lens, out_total, l.rank,
+                                 l.rowvox, stream))
+    return rc;
+  const int TB = 256;
+  const long kMaxBlocks = 1 << 20;   // grid-stride beyond: n * dim has no int bound
+  int* nvox = l.sub.scalars;
+  if (fdim > 0) {
+    const long blocks = ((long)n * fdim + TB - 1) / TB;
+    hipLaunchKernelGGL(k_attr_features, dim3((unsigned int)(blocks < kMaxBlocks ? blocks : kMaxBlocks)), dim3(TB), 0,
+                       stream, feat, fdim, l.sub.vals2, l.sub.vstart, nvox, n, l.rowvox, l.sub.out_cu, nb, out_feat);
+  }
+  if (ldim > 0) {
+    const long blocks = ((long)n * ldim + TB - 1) / TB;
+    hipLaunchKernelGGL(k_attr_labels, dim3((unsigned int)(blocks < kMaxBlocks ? blocks : kMaxBlocks)), dim3(TB), 0,
+                       stream, lab, ldim, l.sub.vals2, l.sub.vstart, nvox, n, l.rowvox, l.sub.out_cu, nb, nsched, sched,
+                       l.dist, l.cnt, l.la, l.lb, l.bkt, out_lab, l.sub.scalars + 1);
+  }
+  hipLaunchKernelGGL(k_check_err, dim3(1), dim3(1), 0, stream, l.sub.scalars + 1, out_total);
   SPR_LAUNCH_CHECK();
   return 0;
 }

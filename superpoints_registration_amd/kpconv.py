@@ -31,7 +31,7 @@ from typing import List, Optional
 import torch
 import torch.nn as nn
 
-from . import decoder, ops
+from . import decoder, ops, subsample_attrs
 from . import tie_order as _tie
 from .kpconv_blocks import NearestUpsampleBlock, UnaryBlock, _cu_of, _idx_of, _maxlen_of, block_decider
 
@@ -225,11 +225,18 @@ def batch_grid_subsampling_kpconv(points, batches_len, features=None, labels=Non
                                   max_p=0, verbose=0, random_grid_orient=True,
                                   order=ops.ORDER_REFERENCE):
     """Replaces cpp_subsampling.subsample_batch behind kpconv.py:174-214.
-    points [N,3] on the device, batches_len [B] -> (sub_points, sub_lengths)."""
+    points [N,3] on the device, batches_len [B] -> (sub_points, sub_lengths).
+    With features [N, d] and / or labels [N] or [N, d]: the reference's 3- or 4-tuple (kpconv.py:187-214), (sub_points,
+    sub_lengths[, sub_features][, sub_labels]) on the device; sub_labels is int32 [M, ldim] as the reference's wrapper
+    returns it (wrapper.cpp:282-284, :309), also for labels of shape [N]."""
+    cu = ops.lengths_to_cu(batches_len, points.device)
     if features is not None or labels is not None:
-        raise NotImplementedError('subsampling with features / labels is not on the RegTR path')
-    return ops.grid_subsample(points, ops.lengths_to_cu(batches_len, points.device), sampleDl,
-                              max_p=max_p, order=order)
+        res = list(subsample_attrs.grid_subsample(points, cu, sampleDl, max_p=max_p, order=order, features=features,
+                                                  labels=labels))
+        if labels is not None:
+            res[-1] = res[-1].reshape(res[0].shape[0], -1).to(torch.int32)
+        return tuple(res)
+    return ops.grid_subsample(points, cu, sampleDl, max_p=max_p, order=order)
 
 
 def batch_neighbors_kpconv(queries, supports, q_batches, s_batches, radius, max_neighbors,
