@@ -514,6 +514,11 @@ int spr_kpconv_modes_bwd_dx(const float* q_xyz, int nq, const float* s_xyz, int 
                             int aggregation, const float* dwf, const float* dwf_range, int dwf_range_n, float* dx,
                             void* ws, size_t ws_bytes, void* stream);
 
+/* Per-point input features: spr_kpconv_fwd (impl 0 and 2) runs 2 <= cin <= 8 with any cout >= 1 and at most 16
+ * kernel points on the small-Cin kernel (k_kpconv_few: exact f32, the cin = 1 kernel's influence and data movement);
+ * spr_kpconv_workspace_bytes covers its support records.  Host only: the dispatch rule, for callers and tests. */
+int spr_kpconv_few_supported(int cin, int cout, int n_kp);
+
 /* Encoder stem in inference: the first block's KPConv (cin = 1, x [ns,1]) + per-cloud InstanceNorm + LeakyReLU,
  *   out [nq,cout] = lrelu(IN(spr_kpconv_fwd(...)), slope)
  * without the raw [nq,cout] tensor: only the 16 normalised influence sums per query are kept (in ws) and the rows

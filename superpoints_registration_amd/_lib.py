@@ -73,6 +73,7 @@ SIGNATURES = {
                                                 _vp, _sz, _vp]),
     "spr_kpconv_modes_bwd_dx": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _f, _i, _i, _vp, _vp, _i, _vp, _vp,
                                      _sz, _vp]),
+    "spr_kpconv_few_supported": (_i, [_i, _i, _i]),
     "spr_kpconv_stem_supported": (_i, [_i, _i, _i]),
     "spr_kpconv_stem_workspace_size": (_sz, [_i, _i, _i, _i, _i]),
     "spr_kpconv_stem": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _i, _f, _vp, _i, _i, _f, _f, _vp,

@@ -34,6 +34,12 @@ def augment_batch(batch: dict, cfg, seed: int, pair_keys, max_pts: int = 30000) 
     correspondences (list of [2,K] integer tensors, local indices) and src_path / tgt_path.  cfg.perturb_pose
     ('none' | 'small' | 'large') and cfg.augment_noise select the perturbation and the jitter scale; pair_keys [B]
     (ints below 2^63, e.g. dataset index + epoch * dataset size) and seed select the draws.
+    Per-point input features (src_point_feats / tgt_point_feats: lists of [N, C] tensors row-aligned with the clouds)
+    follow their points through ShufflePoints and RandomSwap -- gathered by the permutation the library call returns
+    and exchanged where the pair swaps -- with their values untouched: every column is treated as a scalar per point
+    (colour, intensity, height).  Direction-valued columns such as normals are NOT rotated with the perturbation; that
+    is the caller's to do.  With features the returned dict also holds 'src_perm' / 'tgt_perm' (lists of int64 [n]:
+    the row of every output point in the cloud it came from, i.e. the caller's tgt cloud where the pair swapped).
     Returns a NEW dict (other entries are carried over by reference); the caller's is not modified.  One library
     call for all pairs and one small device-to-host read (per-pair status and surviving correspondence counts)."""
     src_list, tgt_list = list(batch['src_xyz']), list(batch['tgt_xyz'])
@@ -48,6 +54,14 @@ def augment_batch(batch: dict, cfg, seed: int, pair_keys, max_pts: int = 30000) 
     scale = float(cfg.get('augment_noise', 0.0))
     src_lens = [int(s.shape[0]) for s in src_list]
     tgt_lens = [int(t.shape[0]) for t in tgt_list]
+    has_feats = batch.get('src_point_feats') is not None or batch.get('tgt_point_feats') is not None
+    if has_feats:
+        if batch.get('src_point_feats') is None or batch.get('tgt_point_feats') is None:
+            raise ValueError("augment_batch: 'src_point_feats' and 'tgt_point_feats' come together")
+        feats = list(batch['src_point_feats']) + list(batch['tgt_point_feats'])
+        if len(feats) != 2 * nb or any(f.dim() != 2 or int(f.shape[0]) != n or f.shape[1] != feats[0].shape[1]
+                                       for f, n in zip(feats, src_lens + tgt_lens)):
+            raise ValueError("augment_batch: point features must be one [n, C] tensor per cloud, row-aligned with it")
     perturb_src, swap, perturb = ops.augment_draw(seed, pair_keys, mode)
     out_s, out_t = output_lengths(src_lens, tgt_lens, swap, max_pts)
 
@@ -91,11 +105,33 @@ def augment_batch(batch: dict, cfg, seed: int, pair_keys, max_pts: int = 30000) 
     if has_corr:
         new_counts, corr64 = host[nb:], r['corr'].long()          # one conversion; the per-pair entries are views
         out['correspondences'] = [corr64[:, int(o):int(o) + k] for o, k in zip(kw['corr_off'], new_counts)]
+    if has_feats:
+        out.update(permute_point_feats(feats, r['src_perm'], r['tgt_perm'], src_lens, tgt_lens, out_s, out_t, swap))
     if 'src_path' in batch and 'tgt_path' in batch:
         sp, tp = list(batch['src_path']), list(batch['tgt_path'])
         out['src_path'] = [tp[b] if swap[b] else sp[b] for b in range(nb)]
         out['tgt_path'] = [sp[b] if swap[b] else tp[b] for b in range(nb)]
     return out
+
+
+def permute_point_feats(feats, src_perm, tgt_perm, src_lens, tgt_lens, out_s, out_t, swap) -> dict:
+    """ShufflePoints and RandomSwap on per-point features.  feats: [src_0.., tgt_0..] tensors [n, C]; src_perm /
+    tgt_perm: packed per OUTPUT side, each entry the local row of that output point in the cloud it came from
+    (ops.augment_pairs' contract: on a swap the permutations change sides with the clouds).  One gather per side over
+    the packed features; works on any device.  Returns the four batch entries."""
+    nb = len(src_lens)
+    packed = torch.cat(feats)
+    dev = packed.device
+    starts = np.concatenate([[0], np.cumsum(list(src_lens) + list(tgt_lens))]).astype(np.int64)
+    res = {}
+    for side, perm, lens in (('src', src_perm, out_s), ('tgt', tgt_perm, out_t)):
+        # where each output cloud of this side came from in `packed`: the other side's cloud where the pair swapped
+        origin = [(b + nb if bool(swap[b]) else b) if side == 'src' else (b if bool(swap[b]) else b + nb) for b in range(nb)]
+        base = torch.from_numpy(np.repeat(starts[origin], np.asarray(lens, dtype=np.int64))).to(dev)
+        local = perm.to(device=dev, dtype=torch.int64)
+        res[f'{side}_point_feats'] = list(torch.split(packed.index_select(0, local + base), list(lens)))
+        res[f'{side}_perm'] = list(torch.split(local, list(lens)))
+    return res
 
 
 class TrainAugmentation:

@@ -245,8 +245,9 @@ class KPConvFn(torch.autograd.Function):
                                            _ops._ptr(dwf), _ops._ptr(dr), int(dr_n), _ops._ptr(dx), _ops._ptr(ws),
                                            ws.numel(), _ops._stream(x)), "spr_kpconv_bwd_dx")
         if ctx.needs_input_grad[4]:
-            # the first layer (cin = 1: constant input) is the ill-conditioned sum: float64 accumulation
-            dw = _tn_product(wf, g, nq, n_kp * cin, cout, f64=(cin == 1)).view(n_kp, cin, cout)
+            # the first layer (cin = 1: constant input; cin <= 8: per-point input features, the same sum over all
+            # level-0 rows of a batch) is the ill-conditioned sum: float64 accumulation
+            dw = _tn_product(wf, g, nq, n_kp * cin, cout, f64=(cin <= 8)).view(n_kp, cin, cout)
         return None, None, None, dx, dw, None, None, None, None
 
 

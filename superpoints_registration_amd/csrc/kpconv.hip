@@ -26,7 +26,8 @@
 //   workgroup); phase-2 accumulators persist across chunks.
 // Pre-kernels per call: k_rowflag (flag = sum_c x[i,c] > 0 and the packed
 // support records), k_w_prep (weights -> fragment-order hi/lo planes).
-// cin == 1 (the first block) has its own kernel, k_kpconv_cin1.
+// cin == 1 (the first block) has its own kernel, k_kpconv_cin1; 2 <= cin <= 8 (a first block fed per-point input
+// features) has k_kpconv_few<C>, which packs its own support records.
 #include "lds_dma.h"
 #include "spr_common.h"
 #include "split_mma.h"
@@ -304,6 +305,177 @@ __global__ __launch_bounds__(256, 5) void k_kpconv_cin1(
     for (int r = 0; r < 4; ++r) {
       const int qn = q0 + 4 * g + r;
       if (qn < nq && o0 + qv < cout) out[(size_t)qn * cout + o0 + qv] = acc[r];
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// 2 <= Cin <= 8 (a first block fed per-point input features: colour, intensity, height).  k_kpconv_cin1's data
+// movement -- 16 queries per wave, lane (q, g) owns kernel points g, g + 4, g + 8, g + 12 of query q, index rows
+// staged in LDS, the stop from the first shadow position, records requested in batches -- with C features per
+// neighbour: a lane keeps wf[s][c], the influence-weighted sum of feature c on its kernel point 4 s + g (added in
+// ascending neighbour position, exact f32), and the product is 4 C steps of v_mfma_f32_16x16x4_f32 per 16 output
+// columns against W[(p C + c) cout + o].
+//
+// Records: k_records_few packs {x, y, z, counted, f_0 .. f_{C-1}} per support point, padded to whole 16-byte pieces
+// (two for C <= 4, three for C <= 8).  `counted` is k_rowflag's flag, (sum_c x[i,c]) > 0 in k_rowflag's summation
+// order (restated in k_records_few: the one-wave-per-row pass costs more than this whole call at 2 M points), so the
+// divisor counts the neighbours spr_kpconv_weighted_features counts in the backward; a neighbour that is not
+// counted still adds its features.
+//
+// kFewBatch: records in flight per lane, the most that keeps four waves per SIMD (128 registers) without scratch.
+// Eight 2-piece records are 64 registers: C <= 3.  C = 4 beside its 16 accumulators spilled 8 bytes at eight and takes
+// six (48); eight 3-piece records are 96, so C >= 5 requests four (48).  Resource table: DESIGN.md 4.
+template <int C> struct FewRec { static constexpr int kPieces = C <= 4 ? 2 : 3; };
+template <int C> constexpr int kFewBatch = C <= 3 ? 8 : C == 4 ? 6 : 4;
+
+template <int C>
+__global__ __launch_bounds__(256) void k_records_few(const float* __restrict__ x, const float* __restrict__ s_xyz,
+                                                     int ns, float4* __restrict__ rec) {
+  constexpr int P = FewRec<C>::kPieces;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= ns) return;
+  float f[8];
+#pragma unroll
+  for (int c = 0; c < 8; ++c) f[c] = c < C ? x[(size_t)i * C + c] : 0.f;
+  // k_rowflag's flag for this width, in its summation order: the wave butterfly of its one-wave-per-row form over
+  // lanes 0 .. 7 (offsets 4, 2, 1; the lanes beyond hold 0 and add nothing), which is also what its float4 layouts
+  // compute at C = 4 and C = 8.  The backward counts with k_rowflag (spr_kpconv_weighted_features); a row whose sum
+  // sits at 0 must not be counted by one and not by the other.
+  const float t = ((f[0] + f[4]) + (f[2] + f[6])) + ((f[1] + f[5]) + (f[3] + f[7]));
+  float4* r = rec + (size_t)i * P;
+  r[0] = make_float4(s_xyz[3 * (size_t)i], s_xyz[3 * (size_t)i + 1], s_xyz[3 * (size_t)i + 2],
+                     __int_as_float(t > 0.f ? 1 : 0));
+  r[1] = make_float4(f[0], f[1], f[2], f[3]);
+  if (P == 3) r[2] = make_float4(f[4], f[5], f[6], f[7]);
+}
+
+template <int C>
+__global__ __launch_bounds__(256, 4) void k_kpconv_few(
+    const float* __restrict__ q_xyz, int nq, int ns, const int* __restrict__ nbr, int nbr_stride, int kmax,
+    int rows_sorted, const float4* __restrict__ rec, const float* __restrict__ W, int cout,
+    const float* __restrict__ kpts, int n_kp, float inv_extent, float* __restrict__ out) {
+  constexpr int P = FewRec<C>::kPieces;
+  constexpr int B = kFewBatch<C>;
+  // as in cin1_gather: a last batch's reads past the last staged row stay inside the slack behind it
+  static_assert(B >= 1 && B <= 32 && C >= 2 && C <= 8, "k_kpconv_few: 2 <= C <= 8");
+  __shared__ int lrows[kCin1LdsInts];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int qv = lane & 15, g = lane >> 4;
+  const int q0 = blockIdx.x * 64 + wave * 16;
+  const int n = min(q0 + qv, nq - 1);
+  const float qx = q_xyz[3 * (size_t)n], qy = q_xyz[3 * (size_t)n + 1], qz = q_xyz[3 * (size_t)n + 2];
+  float kx[4], ky[4], kz[4];
+  bool kok[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    const int p = 4 * s + g;
+    kok[s] = p < n_kp;
+    kx[s] = kok[s] ? kpts[3 * p] : 0.f;
+    ky[s] = kok[s] ? kpts[3 * p + 1] : 0.f;
+    kz[s] = kok[s] ? kpts[3 * p + 2] : 0.f;
+  }
+  float wf[4][C];
+#pragma unroll
+  for (int s = 0; s < 4; ++s)
+#pragma unroll
+    for (int c = 0; c < C; ++c) wf[s][c] = 0.f;
+  int cnt = 0;
+  int* lrow = lrows + wave * 16 * kCin1RowStride;  // this wave's 16 staged rows
+  // Wave uniform; a wave past the end keeps every chunk's two barriers and issues no index or record load.
+  bool done = q0 >= nq;
+  for (int c0 = 0; c0 < kmax; c0 += kCin1Chunk) {
+    const int kc = min(kCin1Chunk, kmax - c0);
+    if (c0 > 0) __syncthreads();                   // the previous pass's reads are done
+    {
+      // lane -> (row g + 4 i, column qv + 16 j)
+      int v[4][kCin1Chunk / 16];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int* src = nbr + (size_t)min(q0 + g + 4 * i, nq - 1) * nbr_stride + c0;
+#pragma unroll
+        for (int j = 0; j < kCin1Chunk / 16; ++j) {
+          const int c = qv + 16 * j;
+          v[i][j] = (!done && c < kc) ? src[c] : -1;
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < kCin1Chunk / 16; ++j) lrow[(g + 4 * i) * kCin1RowStride + qv + 16 * j] = v[i][j];
+    }
+    __syncthreads();
+    if (done) continue;
+    int kstop = kc;
+    if (rows_sorted) {
+      // first shadow position of query qv (its four g lanes take every fourth column), then the wave's largest
+      int first = kc;
+      for (int k = g; k < kc; k += 4) {
+        const int idx = lrow[qv * kCin1RowStride + k];
+        if (!(idx >= 0 && idx < ns)) first = min(first, k);
+      }
+      first = min(first, __shfl_xor(first, 16, 64));
+      first = min(first, __shfl_xor(first, 32, 64));
+#pragma unroll
+      for (int o = 8; o > 0; o >>= 1) first = max(first, __shfl_xor(first, o, 64));
+      kstop = first;
+      done = kstop < kc;                           // only trailing shadow entries left
+    }
+    for (int k0 = 0; k0 < kstop; k0 += B) {
+      float4 r[B][P];
+      bool ok[B];
+#pragma unroll
+      for (int b = 0; b < B; ++b) {
+        const int idx = lrow[qv * kCin1RowStride + k0 + b];   // past kstop: a stale word or the slack, masked here
+        ok[b] = k0 + b < kstop && idx >= 0 && idx < ns;
+        const float4* src = rec + (ok[b] ? (size_t)idx : 0) * P;
+#pragma unroll
+        for (int i = 0; i < P; ++i) r[b][i] = src[i];
+      }
+#pragma unroll
+      for (int b = 0; b < B; ++b) {
+        cnt += ok[b] ? __float_as_int(r[b][0].w) : 0;
+        const float f8[8] = {r[b][1].x, r[b][1].y, r[b][1].z, r[b][1].w,
+                             r[b][P - 1].x, r[b][P - 1].y, r[b][P - 1].z, r[b][P - 1].w};   // [4..7] read for C > 4 only
+        float f[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) f[c] = ok[b] ? f8[c] : 0.f;
+        const float rx = r[b][0].x - qx, ry = r[b][0].y - qy, rz = r[b][0].z - qz;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          const float dx = rx - kx[s], dy = ry - ky[s], dz = rz - kz[s];
+          // the Cin == 1 kernel's influence: v_sqrt_f32 (1 ulp)
+          float w = fmaxf(0.f, 1.f - __builtin_amdgcn_sqrtf(dx * dx + dy * dy + dz * dz) * inv_extent);
+          w = kok[s] ? w : 0.f;
+#pragma unroll
+          for (int c = 0; c < C; ++c) wf[s][c] += w * f[c];
+        }
+      }
+    }
+  }
+  if (q0 >= nq) return;
+  const float inv = 1.f / (float)max(cnt, 1);
+#pragma unroll
+  for (int s = 0; s < 4; ++s)
+#pragma unroll
+    for (int c = 0; c < C; ++c) wf[s][c] *= inv;
+  for (int o0 = 0; o0 < cout; o0 += 16) {
+    const bool col = o0 + qv < cout;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const int p = 4 * s + g;
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        const float bv = (p < n_kp && col) ? W[((size_t)p * C + c) * cout + o0 + qv] : 0.f;
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(wf[s][c], bv, acc, 0, 0, 0);
+      }
+    }
+    // C layout: row (query) = 4 g + r, col (channel) = qv
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int qn = q0 + 4 * g + r;
+      if (qn < nq && col) out[(size_t)qn * cout + o0 + qv] = acc[r];
     }
   }
 }
@@ -1419,7 +1591,9 @@ struct KpWs {
   float *x_parts, *w_parts;
   KpPlan plan;
   int* tile_ctr;
+  float4* few_rec;     // k_records_few's records of a 2 <= cin <= 8 call: 2 (cin <= 4) or 3 16-byte pieces per support point
 };
+static inline bool few_cin(int cin) { return cin >= 2 && cin <= 8; }
 static KpWs kpconv_layout(Workspace& w, int nq, int ns, int cin, int cout) {
   const size_t n = (size_t)(ns > 0 ? ns : 1);
   KpWs l;
@@ -1430,6 +1604,10 @@ static KpWs kpconv_layout(Workspace& w, int nq, int ns, int cin, int cout) {
   l.w_parts = w.take<float>(kAmaxParts);
   l.plan = plan_view(w, nq);
   l.tile_ctr = w.take<int>(64);
+  // Last: the carve in front is what every cin had before.  A size query never falls when an argument grows (a drop is
+  // how a wrapped product shows, tests/test_workspace_sizes_host.py), so inputs wider than 8 channels keep the
+  // three-piece region of cin = 8 although only 2 <= cin <= 8 fills it; cin = 1 has none.
+  l.few_rec = w.take<float4>(cin >= 2 ? n * (cin <= 4 ? 2 : 3) : 0);
   return l;
 }
 static inline int w_chunk(int cin) { return cin % 64 == 0 ? 64 : 32; }
@@ -1504,6 +1682,11 @@ StemWs stem_layout(Workspace& w, int nq, int ns, int nb, int max_len, int cout) 
 }
 }  // namespace
 
+// the shapes spr_kpconv_fwd sends to k_kpconv_few (impl 0 and 2)
+extern "C" int spr_kpconv_few_supported(int cin, int cout, int n_kp) {
+  return few_cin(cin) && cout >= 1 && n_kp >= 1 && n_kp <= 16;
+}
+
 extern "C" int spr_kpconv_stem_supported(int cin, int cout, int n_kp) {
   return cin == 1 && cout >= 16 && cout % 16 == 0 && n_kp >= 1 && n_kp <= 16;
 }
@@ -1567,7 +1750,7 @@ extern "C" int spr_kpconv_fwd(const float* q_xyz, int nq, const float* s_xyz, in
   SPR_REQUIRE(cin >= 1 && cout >= 1 && n_kp >= 1 && n_kp <= 32, "kpconv: bad dims");
   SPR_REQUIRE(kp_extent > 0.f, "kpconv: KP_extent must be > 0");
   Workspace w(ws, ws_bytes);
-  const auto [flag, sxf, own_wplanes, x_parts, w_parts, own_plan, tile_ctr] = kpconv_layout(w, nq, ns, cin, cout);
+  const auto [flag, sxf, own_wplanes, x_parts, w_parts, own_plan, tile_ctr, few_rec] = kpconv_layout(w, nq, ns, cin, cout);
   SPR_REQUIRE(ws != nullptr && w.ok(), "kpconv: workspace too small");
   SPR_REQUIRE(wplanes == nullptr || w_range != nullptr, "kpconv: prepared weight planes come with the range they were scaled by");
   // buffers handed in were sized when they were filled (spr_kpconv_prep_weights, spr_kpconv_plan)
@@ -1580,6 +1763,23 @@ extern "C" int spr_kpconv_fwd(const float* q_xyz, int nq, const float* s_xyz, in
     ProfScope prof(stream, cin * 100000 + cout, nq);
     hipLaunchKernelGGL(k_kpconv_cin1, dim3(cdiv(nq, 64)), dim3(256), 0, stream, q_xyz, nq, s_xyz, ns, nbr,
                        nbr_stride, kmax, rows_sorted, sxf, weights, cout, kernel_points, n_kp, inv_extent, out);
+    SPR_LAUNCH_CHECK();
+    return 0;
+  }
+
+  if ((impl == 0 || impl == 2) && spr_kpconv_few_supported(cin, cout, n_kp)) {
+    // per-point input features, in front of launch_rowflag's consumers: the record pass computes that flag itself
+    switch (cin) {
+#define SPR_FEW_CASE(C)                                                                                              \
+  case C: {                                                                                                          \
+    hipLaunchKernelGGL(k_records_few<C>, dim3(cdiv(ns, 256)), dim3(256), 0, stream, x, s_xyz, ns, few_rec);          \
+    ProfScope prof(stream, cin * 100000 + cout, nq);                                                                 \
+    hipLaunchKernelGGL(k_kpconv_few<C>, dim3(cdiv(nq, 64)), dim3(256), 0, stream, q_xyz, nq, ns, nbr, nbr_stride,    \
+                       kmax, rows_sorted, few_rec, weights, cout, kernel_points, n_kp, inv_extent, out);             \
+  } break;
+      SPR_FEW_CASE(2) SPR_FEW_CASE(3) SPR_FEW_CASE(4) SPR_FEW_CASE(5) SPR_FEW_CASE(6) SPR_FEW_CASE(7) SPR_FEW_CASE(8)
+#undef SPR_FEW_CASE
+    }
     SPR_LAUNCH_CHECK();
     return 0;
   }

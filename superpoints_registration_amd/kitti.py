@@ -13,14 +13,17 @@ from . import ops
 
 
 def prepare_pairs(src_scans: Sequence[torch.Tensor], tgt_scans: Sequence[torch.Tensor], cfg,
-                  pose: Optional[torch.Tensor] = None) -> dict:
+                  pose: Optional[torch.Tensor] = None, intensity: bool = False) -> dict:
     """src_scans / tgt_scans: B raw scans each, [n_i, 3] or [n_i, 4] float32 device tensors (4 columns:
     np.fromfile(...).reshape(-1, 4) as it is, x y z reflectance; all scans of a call have the same width).  cfg: the
     experiment's config (first_subsampling_dl; crop_radius and remove_ground default to 0.0 and False).  pose: [B,3,4]
     or [B,4,4] ground truth (src -> tgt), passed through.
     Returns the collate_pair dict RegTR.forward and Trainer.train_step read: 'src_xyz' / 'tgt_xyz' (lists of [m_i, 3],
     views of one packed tensor), 'pose', and 'src_index' / 'tgt_index' (lists of int64 [m_i]: each kept point's row in
-    its raw scan, to take reflectance or labels along).  A scan of which nothing survives raises ValueError."""
+    its raw scan, to take reflectance or labels along).  A scan of which nothing survives raises ValueError.
+    intensity=True (needs [n, 4] scans) adds 'src_point_feats' / 'tgt_point_feats': [m_i, 2] float32 = [1, reflectance]
+    per kept point, column 3 of the raw scan gathered by the returned index -- the in_feats_dim = 2 input of RegTR
+    (ones first, so that KPConv's neighbour count, which counts rows of positive feature sum, keeps its meaning)."""
     src, tgt = list(src_scans), list(tgt_scans)
     B = len(src)
     if B < 1 or len(tgt) != B:
@@ -30,6 +33,8 @@ def prepare_pairs(src_scans: Sequence[torch.Tensor], tgt_scans: Sequence[torch.T
     if len(widths) != 1 or next(iter(widths)) not in ((3,), (4,)):
         raise ValueError("prepare_pairs: scans must all be [n, 3] or all be [n, 4], got trailing shapes "
                          f"{sorted(map(str, widths))}")
+    if intensity and next(iter(widths)) != (4,):
+        raise ValueError("prepare_pairs: intensity=True needs [n, 4] scans (x y z reflectance)")
     lens = [int(s.shape[0]) for s in scans]
     if min(lens) < 1:
         b = lens.index(min(lens))
@@ -46,4 +51,9 @@ def prepare_pairs(src_scans: Sequence[torch.Tensor], tgt_scans: Sequence[torch.T
                              f"{cfg.get('remove_ground', False)})")
     clouds: List[torch.Tensor] = list(torch.split(xyz, out_lens))
     index: List[torch.Tensor] = list(torch.split(idx.long(), out_lens))
-    return {'src_xyz': clouds[:B], 'tgt_xyz': clouds[B:], 'pose': pose, 'src_index': index[:B], 'tgt_index': index[B:]}
+    out = {'src_xyz': clouds[:B], 'tgt_xyz': clouds[B:], 'pose': pose, 'src_index': index[:B], 'tgt_index': index[B:]}
+    if intensity:
+        kept = [s[:, 3].index_select(0, i).to(torch.float32) for s, i in zip(scans, index)]
+        feats = [torch.stack([torch.ones_like(v), v], dim=1) for v in kept]
+        out['src_point_feats'], out['tgt_point_feats'] = feats[:B], feats[B:]
+    return out

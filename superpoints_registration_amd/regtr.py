@@ -106,6 +106,49 @@ class EncodedClouds:
                              [n for e in encodings for n in e.lens])
 
 
+def check_point_feats(in_dim: int, clouds, feats, names):
+    """Per-point input features of an encode call, checked on the host: `feats` is None (then cfg.in_feats_dim must
+    be 1: the encoder runs on a column of ones) or one [n_i, in_dim] float32 tensor per cloud, row-aligned with it and
+    on its device.  names[i] says which pair or cloud entry i is, for the message.  Returns the list (or None)."""
+    in_dim = int(in_dim)
+    if feats is None:
+        if in_dim != 1:
+            raise ValueError(f"cfg.in_feats_dim = {in_dim}: the batch must carry per-point input features "
+                             f"('src_point_feats' / 'tgt_point_feats', 'cloud_point_feats' or encode(point_feats=...)), "
+                             f"one [n, {in_dim}] float32 tensor per cloud")
+        return None
+    feats = list(feats)
+    if len(feats) != len(clouds):
+        raise ValueError(f"point features: {len(feats)} entries for {len(clouds)} clouds")
+    for c, f, name in zip(clouds, feats, names):
+        if not isinstance(f, torch.Tensor) or f.dim() != 2 or int(f.shape[1]) != in_dim:
+            shape = tuple(f.shape) if isinstance(f, torch.Tensor) else type(f).__name__
+            raise ValueError(f"point features of {name}: expected [n, {in_dim}] (cfg.in_feats_dim), got {shape}")
+        if int(f.shape[0]) != int(c.shape[0]):
+            raise ValueError(f"point features of {name}: {int(f.shape[0])} rows for a cloud of {int(c.shape[0])} points")
+        if f.dtype != torch.float32:
+            raise ValueError(f"point features of {name}: dtype {f.dtype}, expected torch.float32")
+        if f.device != c.device:
+            raise ValueError(f"point features of {name}: on {f.device}, its cloud is on {c.device}")
+    return feats
+
+
+def batch_point_feats(in_dim: int, batch, shared=None):
+    """The input features of a batch in _encode's cloud order -- [src_0.., tgt_0..] of 'src_point_feats' /
+    'tgt_point_feats' on pair lists, 'cloud_point_feats' of a clouds-and-pairs batch -- or None; raises ValueError
+    (check_point_feats) on the host."""
+    if shared is not None:
+        clouds = shared[0]
+        return check_point_feats(in_dim, clouds, batch.get('cloud_point_feats'),
+                                 [f"clouds[{i}]" for i in range(len(clouds))])
+    src, tgt = list(batch['src_xyz']), list(batch['tgt_xyz'])
+    fs, ft = batch.get('src_point_feats'), batch.get('tgt_point_feats')
+    if (fs is None) != (ft is None):
+        raise ValueError("point features: 'src_point_feats' and 'tgt_point_feats' come together")
+    names = [f"the source of pair {b}" for b in range(len(src))] + [f"the target of pair {b}" for b in range(len(tgt))]
+    return check_point_feats(in_dim, src + tgt, None if fs is None else list(fs) + list(ft), names)
+
+
 class RegTR(nn.Module):
     def __init__(self, cfg, *args, compute_upsamples=True, order=ops.ORDER_REFERENCE,
                  return_attn=False, record_attn=False, **kwargs):
@@ -164,32 +207,36 @@ class RegTR(nn.Module):
         model.eval() (the reference's test loop, trainer.py:216-260) or torch.no_grad():
         the inference path -- fused in-projection, no tape, nothing saved.
         batch: `src_xyz` / `tgt_xyz` lists, or `clouds` and `pairs` (shared_clouds.py): every cloud is encoded once
-        and used by any number of the batch's pairs, in training as well."""
+        and used by any number of the batch's pairs, in training as well.
+        Per-point input features (cfg.in_feats_dim columns: colour, intensity, height ...): `src_point_feats` /
+        `tgt_point_feats`, lists of [n_i, C] float32 device tensors row-aligned with the clouds, or `cloud_point_feats`
+        aligned with `clouds`.  Without them (in_feats_dim = 1 only) the encoder runs on a column of ones."""
         shared = None
         if 'clouds' in batch:
             shared = shared_clouds.check_batch(batch)       # raises on the host, before any launch
+        feats = batch_point_feats(self.cfg.get('in_feats_dim', 1), batch, shared)   # likewise
         if not self.training and torch.is_grad_enabled():
             with torch.no_grad():
-                return self._forward(batch, shared)
+                return self._forward(batch, shared, feats)
         if self.training and torch.is_grad_enabled():
             ops.prime_weight_ranges(self.parameters())      # one measuring launch for every weight the step moved
-        return self._forward(batch, shared)
+        return self._forward(batch, shared, feats)
 
-    def _forward(self, batch, shared=None):
+    def _forward(self, batch, shared=None, feats=None):
         if shared is not None:
-            return self._forward_shared(batch, *shared)
+            return self._forward_shared(batch, *shared, feats=feats)
         B = len(batch['src_xyz'])
-        tokens, xyz_c, lens_c, meta = self._encode(list(batch['src_xyz']) + list(batch['tgt_xyz']))
+        tokens, xyz_c, lens_c, meta = self._encode(list(batch['src_xyz']) + list(batch['tgt_xyz']), feats)
         batch['kpconv_meta'] = meta                      # qk_regtr_full.py:153
         return self._register(tokens, xyz_c, lens_c[:B], lens_c[B:], pair_keys=batch.get('pair_key'))
 
-    def _forward_shared(self, batch, clouds, src, tgt):
+    def _forward_shared(self, batch, clouds, src, tgt, feats=None):
         """forward() on a batch of clouds and pairs: _encode once over the clouds (on the tape when training), tokens
         and points laid out per pair by the pair gather (differentiable over the tokens; the points carry no
         gradient), then the unchanged _register.  Leaves in the batch what compute_loss, overlap.label_batch and
         training.compute_metrics read: the encode call's kpconv_meta, the per-pair views of the clouds as src_xyz /
         tgt_xyz (the cloud tensors themselves) and the pair layout under '_pair_layout'."""
-        tokens, xyz_c, _, meta = self._encode(clouds)
+        tokens, xyz_c, _, meta = self._encode(clouds, feats)
         batch['kpconv_meta'] = meta
         layout = shared_clouds.PairLayout(src, tgt, meta['_lens_host'], tokens.device)   # host lengths: no read-back
         batch['_pair_layout'] = layout
@@ -203,8 +250,9 @@ class RegTR(nn.Module):
             xyz = shared_clouds.pair_gather(xyz_c, cu, layout)
         return self._register(tok, xyz, src_lens, tgt_lens, segments, batch.get('pair_key'))
 
-    def _encode(self, clouds):
+    def _encode(self, clouds, feats=None):
         """The per-cloud half of the forward: pyramid, KPConv encoder, feat_proj.  Nothing here looks across clouds.
+        feats: checked per-point input features, one [n_i, in_feats_dim] tensor per cloud, or None = a column of ones.
         Returns (tokens [sum L, d_embed], coarsest points [sum L, 3], host superpoint counts, kpconv_meta)."""
         # Pyramid (index work, never differentiated: qk_regtr_full.py:152) and KPConv encoder on a
         # column of ones (:157-166).  The pyramid is built on a SIDE stream and the blocks of a
@@ -213,7 +261,12 @@ class RegTR(nn.Module):
         # a size -- run beside the big convolutions of the shallower ones instead of in front of
         # them (SPR_NO_SIDE_STREAM=1: one stream, pyramid first).
         device = clouds[0].device
-        feats0 = torch.ones((sum(int(c.shape[0]) for c in clouds), 1), dtype=torch.float32, device=device)
+        if feats is None:
+            feats0 = torch.ones((sum(int(c.shape[0]) for c in clouds), 1), dtype=torch.float32, device=device)
+        else:
+            # level 0 is the input cloud: the features are never subsampled.  in_feats_dim 2..8 runs the first
+            # KPConv on the small-Cin kernel (stem.few_shape_ok), wider input on the generic one
+            feats0 = torch.cat(list(feats)).contiguous()
         if _concurrency.active(device):
             main = torch.cuda.current_stream(device)
             side = _concurrency.aux_stream(main, device, 'pyramid')
@@ -351,9 +404,10 @@ class RegTR(nn.Module):
         if self.training:
             raise RuntimeError(f"RegTR.{what} is an inference path: call model.eval() first (training goes through forward)")
 
-    def encode(self, clouds) -> EncodedClouds:
+    def encode(self, clouds, point_feats=None) -> EncodedClouds:
         """Pyramid, KPConv encoder and feat_proj of a list of [N_i, 3] float32 device clouds -- the part of forward()
-        that never looks across clouds -- kept for any number of register() calls."""
+        that never looks across clouds -- kept for any number of register() calls.  point_feats: per-point input
+        features, one [N_i, cfg.in_feats_dim] float32 device tensor per cloud (None: a column of ones)."""
         self._inference_only("encode")
         clouds = list(clouds)
         if not clouds:
@@ -361,8 +415,10 @@ class RegTR(nn.Module):
         clouds = [ops._dev(c, f"clouds[{i}]", torch.float32) for i, c in enumerate(clouds)]   # CPU tensor: raises
         if any(c.dim() != 2 or c.shape[1] != 3 or c.shape[0] == 0 for c in clouds):
             raise ValueError("encode: every cloud must be a non-empty [N, 3] tensor")
+        feats = check_point_feats(self.cfg.get('in_feats_dim', 1), clouds, point_feats,
+                                  [f"clouds[{i}]" for i in range(len(clouds))])
         with torch.no_grad():
-            tokens, xyz_c, lens_c, meta = self._encode(clouds)
+            tokens, xyz_c, lens_c, meta = self._encode(clouds, feats)
         return EncodedClouds(tokens, xyz_c, lens_c, cu=meta['_cu'][len(meta['points']) - 1], kpconv_meta=meta)
 
     def register(self, enc: EncodedClouds, pairs, pair_keys=None) -> dict:

@@ -20,6 +20,13 @@ def stem_shape_ok(cin: int, cout: int, n_kp: int) -> bool:
     return cin == 1 and cout >= 16 and cout % 16 == 0 and 1 <= n_kp <= 16
 
 
+def few_shape_ok(cin: int, cout: int, n_kp: int) -> bool:
+    """The shapes spr_kpconv_fwd (impl 0 and 2) runs on the small-Cin kernel k_kpconv_few (spr_kpconv_few_supported
+    restated): 2 to 8 input channels -- a first block fed per-point input features -- any Cout, at most 16 kernel
+    points.  Such a block is KPConv + instnorm; the fused stem stays Cin = 1."""
+    return 2 <= cin <= 8 and cout >= 1 and 1 <= n_kp <= 16
+
+
 def stem_predicate(on_gpu: bool, wants_grad: bool, use_bn: bool, x_channels: int, weights_shape) -> bool:
     """The routing rule itself, on plain values: features on the GPU, nothing asks for a gradient, the block
     normalises (use_batch_norm), and the shape has a kernel."""

@@ -362,7 +362,10 @@ class Trainer:
     the device, or the cloud / pair form of shared_clouds.py (`clouds`, `pairs`, pose: a cloud encoded once per step for
     all the pairs that use it; not with augment=True); data loading itself is out of the hot-path scope.  augment=True
     applies the reference's training augmentation (augment.py: cfg.perturb_pose, cfg.augment_noise, shuffle, swap) to
-    every training batch on the device, with draws keyed on (seed, global_step, rank, position in the batch); validate() never augments."""
+    every training batch on the device, with draws keyed on (seed, global_step, rank, position in the batch); validate() never augments.
+    Per-point input features (`src_point_feats` / `tgt_point_feats`, or `cloud_point_feats` beside `clouds`; see
+    RegTR.forward) ride in the batch dict through train_step / validate / fit; the augmentation shuffles and swaps them
+    with their points (augment.augment_batch)."""
 
     def __init__(self, cfg, ckpt_dir: Optional[str] = None, grad_clip: Optional[float] = None, rank: int = 0,
                  world: int = 1, process_group=None, bucket_bytes: int = 16 << 20, augment: bool = False,
