@@ -436,6 +436,47 @@ int spr_modelnet_pairs(const float* xyz, const int* cu, int n_total, int nb, int
                        int* src_index, int* tgt_index, int* corr, int* corr_count, int* status, void* ws,
                        size_t ws_bytes, void* stream);
 
+/* ---- surface normals as per-point input features: estimate, gather + rotate -----------
+ * Neither has a counterpart in the reference's hot path: its ModelNet files ship normals and its transform chain
+ * carries and rotates them (data_loaders/modelnet_transforms.py:285-289); estimating them is left to the user there.
+ *
+ * spr_estimate_normals: PCA normals over a neighbour matrix the caller already has.
+ *   xyz [n,3] f32 packed, cu [nb+1] i32; nbr [n, nbr_stride] i32, of which the first kmax columns are used.  Entries
+ *   are global rows of xyz; an entry outside [0, n) is a shadow, may sit at any column and contributes nothing.  This
+ *   is the matrix spr_radius_neighbors gives for queries = supports = xyz: it holds the point itself, and the kernel
+ *   adds nothing of its own.  viewpoint [nb,3] f32 (one per cloud) or NULL; cu is read only with a viewpoint.
+ *   normals [n,3] f32; curvature [n] f32 or NULL.  No workspace, no device-to-host read; n = 0 and kmax = 0 are legal.
+ *   Contract (float64 on the exactly converted float32 inputs), per point i with m valid entries j:
+ *     m < 3: normal (0, 0, 0), curvature 0.  Otherwise
+ *     d_j = p_j - p_i,  mu = sum d_j / m,  C = sum (d_j - mu)(d_j - mu)^T / m,  eigenvalues l0 <= l1 <= l2 of C;
+ *     n = the unit eigenvector of l0;  curvature = l0 / (l0 + l1 + l2), or 0 when the trace is 0.
+ *   Sign of n: with a viewpoint v of the point's cloud, n is flipped when n . (v - p_i) < 0.  Without one, or when
+ *     that product is exactly 0, it is flipped so that its component of largest magnitude is positive (the lowest
+ *     index among equal magnitudes).
+ *   The arithmetic is float32: the count and the nine moments sum d, sum d d^T relative to the query point (so a cloud
+ *   far from the origin is as well conditioned as one at it), C = E[d d^T] - mu mu^T, and a cyclic Jacobi on C / trace
+ *   in registers.  With u = 2^-24 the result is an exact eigenvector of a covariance within (kmax + 8) u |C| of C:
+ *     n^T C n <= l0 + 2 (kmax + 8) u l2,   |n x n_ref| <= (kmax + 8) u l2 / (l1 - l0),   | |n| - 1 | <= 4 * 2^-23,
+ *     |curvature - ref| <= (kmax + 8) u.
+ *   Where l0 = l1 (or all of C is 0) the eigenvector is not unique and any unit vector of the eigenspace is returned.
+ *   The sums are taken in a fixed order: results are reproducible bit for bit.
+ *
+ * spr_feats_gather_rotate: out[r, :] = feats[rows[r], :], with every listed column triple rotated.
+ *   feats [n_in, c] f32; rows [n_out] i32, global rows of feats (a row outside [0, n_in) gives zeros); cu_out [nb+1]
+ *   i32 over the OUTPUT rows; rot [nb,3,3] f32 row-major, one rotation per output cloud (identity where none);
+ *   dir_cols_host [n_dir] int, n_dir <= 4: the first column of every direction triple.  A triple running past c,
+ *   overlapping triples and n_dir > 4 are refused, status 2.  out [n_out, c] f32.  cu_out and rot are read only when
+ *   n_dir > 0.  n_out = 0 and empty clouds are legal.
+ *   Scalar columns are copied.  A triple (x, y, z) of a row of cloud b becomes, for k = 0, 1, 2,
+ *     f32((R_k0 x + R_k1 y) + R_k2 z),  R = rot[b],
+ *   evaluated in float64 with one rounding per operation (the convention of 8f-6): a float64 restatement is bit-equal.
+ *   Directions are not renormalised.
+ */
+int spr_estimate_normals(const float* xyz, const int* cu, int n, int nb, const int* nbr, int nbr_stride, int kmax,
+                         const float* viewpoint, float* normals, float* curvature, void* stream);
+int spr_feats_gather_rotate(const float* feats, int n_in, int c, const int* rows, int n_out, const int* cu_out, int nb,
+                            const float* rot, const int* dir_cols_host, int n_dir, float* out, void* stream);
+
 /* ---- a4: KPConv forward ---------------------------------------------------
  * Replaces KPConv.forward(q_pts, s_pts, neighb_inds, x)
  * (models/backbone_kpconv/kpconv_blocks.py:269-414; rigid kernel, linear

@@ -62,6 +62,8 @@ SIGNATURES = {
     "spr_modelnet_pairs_workspace_size": (_sz, [_i, _i, _i]),
     "spr_modelnet_pairs": (_i, [_vp, _vp, _i, _i, _i, _f, _f, _d, _d, _i, _f, _f, _vp, _vp, _u64, _vp, _vp, _vp, _vp,
                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "spr_estimate_normals": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "spr_feats_gather_rotate": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp]),
     "spr_kpconv_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "spr_kpconv_fwd": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _vp, _i, _vp, _i, _f, _vp, _i, _vp, _i, _vp,
                             _i, _vp, _vp, _vp, _sz, _vp]),

@@ -28,7 +28,7 @@ def output_lengths(src_lens: Sequence[int], tgt_lens: Sequence[int], swap: Seque
     return out_s, out_t
 
 
-def augment_batch(batch: dict, cfg, seed: int, pair_keys, max_pts: int = 30000) -> dict:
+def augment_batch(batch: dict, cfg, seed: int, pair_keys, max_pts: int = 30000, direction_cols=()) -> dict:
     """The reference's transforms_aug on a collate_pair dict: src_xyz / tgt_xyz (lists of [N,3] device tensors), pose
     ([B,3,4] or [B,4,4], src -> tgt) and, if present, src_overlap / tgt_overlap (lists of per-point bool masks),
     correspondences (list of [2,K] integer tensors, local indices) and src_path / tgt_path.  cfg.perturb_pose
@@ -37,8 +37,12 @@ def augment_batch(batch: dict, cfg, seed: int, pair_keys, max_pts: int = 30000) 
     Per-point input features (src_point_feats / tgt_point_feats: lists of [N, C] tensors row-aligned with the clouds)
     follow their points through ShufflePoints and RandomSwap -- gathered by the permutation the library call returns
     and exchanged where the pair swaps -- with their values untouched: every column is treated as a scalar per point
-    (colour, intensity, height).  Direction-valued columns such as normals are NOT rotated with the perturbation; that
-    is the caller's to do.  With features the returned dict also holds 'src_perm' / 'tgt_perm' (lists of int64 [n]:
+    (colour, intensity, height).  Direction-valued columns such as normals are named in direction_cols: every entry is
+    the first column of an (x, y, z) triple (at most 4, inside C, not overlapping), and RigidPerturb rotates that
+    triple by the rotation it applies to the cloud -- R of the drawn perturbation on the perturbed side, the identity
+    on the other and in mode 'none'; component k becomes f32((R_k0 x + R_k1 y) + R_k2 z) in float64, not renormalised
+    (normals.gather_rotate: one library call per side in place of the gather).  With the empty default no column is
+    rotated.  With features the returned dict also holds 'src_perm' / 'tgt_perm' (lists of int64 [n]:
     the row of every output point in the cloud it came from, i.e. the caller's tgt cloud where the pair swapped).
     Returns a NEW dict (other entries are carried over by reference); the caller's is not modified.  One library
     call for all pairs and one small device-to-host read (per-pair status and surviving correspondence counts)."""
@@ -62,6 +66,12 @@ def augment_batch(batch: dict, cfg, seed: int, pair_keys, max_pts: int = 30000) 
         if len(feats) != 2 * nb or any(f.dim() != 2 or int(f.shape[0]) != n or f.shape[1] != feats[0].shape[1]
                                        for f, n in zip(feats, src_lens + tgt_lens)):
             raise ValueError("augment_batch: point features must be one [n, C] tensor per cloud, row-aligned with it")
+    direction_cols = tuple(direction_cols)
+    if direction_cols:
+        if not has_feats:
+            raise ValueError("augment_batch: direction_cols without 'src_point_feats' / 'tgt_point_feats'")
+        from . import normals
+        direction_cols = tuple(normals.check_direction_cols(direction_cols, int(feats[0].shape[1]) if feats else 3))
     perturb_src, swap, perturb = ops.augment_draw(seed, pair_keys, mode)
     out_s, out_t = output_lengths(src_lens, tgt_lens, swap, max_pts)
 
@@ -106,7 +116,13 @@ def augment_batch(batch: dict, cfg, seed: int, pair_keys, max_pts: int = 30000) 
         new_counts, corr64 = host[nb:], r['corr'].long()          # one conversion; the per-pair entries are views
         out['correspondences'] = [corr64[:, int(o):int(o) + k] for o, k in zip(kw['corr_off'], new_counts)]
     if has_feats:
-        out.update(permute_point_feats(feats, r['src_perm'], r['tgt_perm'], src_lens, tgt_lens, out_s, out_t, swap))
+        rot = None
+        if direction_cols:      # per pair: (rotation of the caller's src cloud, of its tgt cloud)
+            eye = np.eye(3, dtype=np.float32)
+            rot = [(perturb[b, :, :3] if mode != 'none' and perturb_src[b] else eye,
+                    perturb[b, :, :3] if mode != 'none' and not perturb_src[b] else eye) for b in range(nb)]
+        out.update(permute_point_feats(feats, r['src_perm'], r['tgt_perm'], src_lens, tgt_lens, out_s, out_t, swap,
+                                       rot, direction_cols))
     if 'src_path' in batch and 'tgt_path' in batch:
         sp, tp = list(batch['src_path']), list(batch['tgt_path'])
         out['src_path'] = [tp[b] if swap[b] else sp[b] for b in range(nb)]
@@ -114,11 +130,15 @@ def augment_batch(batch: dict, cfg, seed: int, pair_keys, max_pts: int = 30000) 
     return out
 
 
-def permute_point_feats(feats, src_perm, tgt_perm, src_lens, tgt_lens, out_s, out_t, swap) -> dict:
+def permute_point_feats(feats, src_perm, tgt_perm, src_lens, tgt_lens, out_s, out_t, swap, rot=None,
+                        direction_cols=()) -> dict:
     """ShufflePoints and RandomSwap on per-point features.  feats: [src_0.., tgt_0..] tensors [n, C]; src_perm /
     tgt_perm: packed per OUTPUT side, each entry the local row of that output point in the cloud it came from
     (ops.augment_pairs' contract: on a swap the permutations change sides with the clouds).  One gather per side over
-    the packed features; works on any device.  Returns the four batch entries."""
+    the packed features; works on any device.  Returns the four batch entries.
+    With direction_cols, rot holds per pair the [3,3] rotations of the caller's (src, tgt) clouds, and the gather of a
+    side is one normals.gather_rotate call that rotates the listed triples by the rotation of each row's cloud of
+    origin (device only)."""
     nb = len(src_lens)
     packed = torch.cat(feats)
     dev = packed.device
@@ -129,7 +149,13 @@ def permute_point_feats(feats, src_perm, tgt_perm, src_lens, tgt_lens, out_s, ou
         origin = [(b + nb if bool(swap[b]) else b) if side == 'src' else (b if bool(swap[b]) else b + nb) for b in range(nb)]
         base = torch.from_numpy(np.repeat(starts[origin], np.asarray(lens, dtype=np.int64))).to(dev)
         local = perm.to(device=dev, dtype=torch.int64)
-        res[f'{side}_point_feats'] = list(torch.split(packed.index_select(0, local + base), list(lens)))
+        if direction_cols:
+            from . import normals
+            r_out = np.stack([rot[o % nb][o // nb] for o in origin]) if nb else np.zeros((0, 3, 3), np.float32)
+            moved = normals.gather_rotate(packed, local + base, ops.lengths_to_cu(list(lens), dev), r_out, direction_cols)
+        else:
+            moved = packed.index_select(0, local + base)
+        res[f'{side}_point_feats'] = list(torch.split(moved, list(lens)))
         res[f'{side}_perm'] = list(torch.split(local, list(lens)))
     return res
 
@@ -137,8 +163,8 @@ def permute_point_feats(feats, src_perm, tgt_perm, src_lens, tgt_lens, out_s, ou
 class TrainAugmentation:
     """Callable form: TrainAugmentation(cfg)(batch, seed, pair_keys) -> augmented copy of the batch."""
 
-    def __init__(self, cfg, max_pts: int = 30000):
-        self.cfg, self.max_pts = cfg, int(max_pts)
+    def __init__(self, cfg, max_pts: int = 30000, direction_cols=()):
+        self.cfg, self.max_pts, self.direction_cols = cfg, int(max_pts), tuple(direction_cols)
 
     def __call__(self, batch: dict, seed: int, pair_keys) -> dict:
-        return augment_batch(batch, self.cfg, seed, pair_keys, self.max_pts)
+        return augment_batch(batch, self.cfg, seed, pair_keys, self.max_pts, self.direction_cols)

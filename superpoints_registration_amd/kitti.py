@@ -13,7 +13,8 @@ from . import ops
 
 
 def prepare_pairs(src_scans: Sequence[torch.Tensor], tgt_scans: Sequence[torch.Tensor], cfg,
-                  pose: Optional[torch.Tensor] = None, intensity: bool = False) -> dict:
+                  pose: Optional[torch.Tensor] = None, intensity: bool = False, normals_radius: Optional[float] = None,
+                  normals_limit: int = 40) -> dict:
     """src_scans / tgt_scans: B raw scans each, [n_i, 3] or [n_i, 4] float32 device tensors (4 columns:
     np.fromfile(...).reshape(-1, 4) as it is, x y z reflectance; all scans of a call have the same width).  cfg: the
     experiment's config (first_subsampling_dl; crop_radius and remove_ground default to 0.0 and False).  pose: [B,3,4]
@@ -23,7 +24,12 @@ def prepare_pairs(src_scans: Sequence[torch.Tensor], tgt_scans: Sequence[torch.T
     its raw scan, to take reflectance or labels along).  A scan of which nothing survives raises ValueError.
     intensity=True (needs [n, 4] scans) adds 'src_point_feats' / 'tgt_point_feats': [m_i, 2] float32 = [1, reflectance]
     per kept point, column 3 of the raw scan gathered by the returned index -- the in_feats_dim = 2 input of RegTR
-    (ones first, so that KPConv's neighbour count, which counts rows of positive feature sum, keeps its meaning)."""
+    (ones first, so that KPConv's neighbour count, which counts rows of positive feature sum, keeps its meaning).
+    normals_radius (metres; None: no normals) appends the surface normal of every kept point, estimated over its
+    normals_limit nearest kept points within that radius (normals.estimate) and oriented towards the sensor, the
+    scan's origin: 'src_point_feats' / 'tgt_point_feats' are then [1, nx, ny, nz], or [1, reflectance, nx, ny, nz]
+    with intensity=True -- direction_cols (1,) or (2,) for the augmentation.  A point with fewer than 3 kept points
+    in range has the zero normal."""
     src, tgt = list(src_scans), list(tgt_scans)
     B = len(src)
     if B < 1 or len(tgt) != B:
@@ -52,8 +58,16 @@ def prepare_pairs(src_scans: Sequence[torch.Tensor], tgt_scans: Sequence[torch.T
     clouds: List[torch.Tensor] = list(torch.split(xyz, out_lens))
     index: List[torch.Tensor] = list(torch.split(idx.long(), out_lens))
     out = {'src_xyz': clouds[:B], 'tgt_xyz': clouds[B:], 'pose': pose, 'src_index': index[:B], 'tgt_index': index[B:]}
+    feats = None
     if intensity:
         kept = [s[:, 3].index_select(0, i).to(torch.float32) for s, i in zip(scans, index)]
         feats = [torch.stack([torch.ones_like(v), v], dim=1) for v in kept]
+    if normals_radius is not None:
+        from . import normals
+        nrm = normals.estimate(xyz, out_lens, float(normals_radius), int(normals_limit),
+                               viewpoint=torch.zeros((2 * B, 3), dtype=torch.float32, device=dev))
+        first = feats if feats is not None else [torch.ones((m, 1), dtype=torch.float32, device=dev) for m in out_lens]
+        feats = [torch.cat([f, n], dim=1) for f, n in zip(first, torch.split(nrm, out_lens))]
+    if feats is not None:
         out['src_point_feats'], out['tgt_point_feats'] = feats[:B], feats[B:]
     return out

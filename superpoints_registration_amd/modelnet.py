@@ -142,26 +142,40 @@ def modelnet_pairs(xyz: torch.Tensor, cu: torch.Tensor, max_len: int, p_keep: Se
             'corr_count': o_cnt, 'status': status}
 
 
-def make_pairs(points, cfg, seed: int, keys) -> dict:
+def make_pairs(points, cfg, seed: int, keys, normals: bool = False) -> dict:
     """The reference's ModelNet training transform on a batch of raw shapes: points [B, n, 3|6] or a list of [n_i, 3|6]
-    device tensors (normals are ignored), cfg = get_config('modelnet') (partial, num_points, noise_type, rot_mag,
-    trans_mag), keys [B] (ints below 2^63, e.g. dataset index + epoch * dataset size) and seed select the draws.
+    device tensors (columns 3:6, the dataset's normals, are ignored unless normals=True), cfg = get_config('modelnet')
+    (partial, num_points, noise_type, rot_mag, trans_mag), keys [B] (ints below 2^63, e.g. dataset index + epoch *
+    dataset size) and seed select the draws.
     Returns the collate_pair dict Trainer.train_step accepts: src_xyz / tgt_xyz (lists of [k,3]), pose [B,3,4]
     (source -> reference), src_overlap / tgt_overlap (lists of bool [k]), correspondences (list of [2,K] int64), idx
     (the keys) and src_index / tgt_index (lists: the raw row of every output point).  One library call for all pairs
-    and one small device-to-host read (per-pair status and correspondence counts)."""
+    and one small device-to-host read (per-pair status and correspondence counts).
+    normals=True (6-column shapes only) adds src_point_feats / tgt_point_feats, lists of [k, 4] = [1, nx, ny, nz] (the
+    in_feats_dim = 4 input): the raw normals of rows src_index / tgt_index, the source's rotated by the rotation of the
+    drawn transform as RandomTransformSE3.apply_transform does (modelnet_transforms.py:287-288), the reference's
+    untouched; one normals.gather_rotate call per side.  Every other entry is what normals=False returns."""
     noise_type = cfg.get('noise_type', 'crop')
     if noise_type != 'crop':
         raise NotImplementedError(f"make_pairs: noise_type {noise_type!r}; only 'crop' builds a pair with overlap masks")
+    raw_normals = None
     if isinstance(points, torch.Tensor):                     # [B, n, 3|6]: one slice, no per-shape work
         if points.dim() != 3:
             raise ValueError(f"make_pairs: points {tuple(points.shape)}, expected [B, n, 3|6]")
+        if normals and points.shape[2] != 6:
+            raise ValueError(f"make_pairs: normals=True needs [B, n, 6] shapes, got {tuple(points.shape)}")
         nb, lens = int(points.shape[0]), [int(points.shape[1])] * int(points.shape[0])
         xyz = _dev(points, "points")[:, :, :3].reshape(-1, 3).to(torch.float32)
+        if normals:
+            raw_normals = _dev(points, "points")[:, :, 3:6].reshape(-1, 3).to(torch.float32)
     else:
         clouds = list(points)
+        if normals and any(c.dim() != 2 or c.shape[1] != 6 for c in clouds):
+            raise ValueError("make_pairs: normals=True needs [n, 6] shapes")
         nb, lens = len(clouds), [int(c.shape[0]) for c in clouds]
         xyz = torch.cat([_dev(c, "points")[:, :3] for c in clouds]).to(torch.float32) if clouds else None
+        if normals and clouds:
+            raw_normals = torch.cat([_dev(c, "points")[:, 3:6] for c in clouds]).to(torch.float32)
     pk = _pair_keys(keys, nb, "make_pairs")
     if nb == 0:
         raise ValueError("make_pairs: no shapes")
@@ -176,7 +190,18 @@ def make_pairs(points, cfg, seed: int, keys) -> dict:
         raise RuntimeError(f"spr_modelnet_pairs: pairs without points {bad} (status 1: non-finite input, 2: a side is "
                            "empty after the crop)")
     corr64 = r['corr'].long()
+    feats = {}
+    if normals:
+        from . import normals as _normals
+        packed = torch.cat([torch.ones((raw_normals.shape[0], 1), dtype=torch.float32, device=dev), raw_normals], dim=1)
+        base = torch.from_numpy(np.repeat(np.concatenate([[0], np.cumsum(lens)])[:nb], k).astype(np.int32)).to(dev)
+        cu_out = lengths_to_cu([k] * nb, dev)
+        eye = np.broadcast_to(np.eye(3, dtype=np.float32), (nb, 3, 3))
+        for side, rot in (('src', tf[:, :, :3]), ('tgt', eye)):
+            moved = _normals.gather_rotate(packed, r[f'{side}_index'] + base, cu_out, rot, (1,))
+            feats[f'{side}_point_feats'] = list(torch.split(moved, k))
     return {
+        **feats,
         'src_xyz': list(torch.split(r['src_xyz'], k)), 'tgt_xyz': list(torch.split(r['tgt_xyz'], k)), 'pose': r['pose'],
         'src_overlap': list(torch.split(r['src_overlap'], k)), 'tgt_overlap': list(torch.split(r['tgt_overlap'], k)),
         'correspondences': [corr64[:, b * k:b * k + host[nb + b]] for b in range(nb)],

@@ -365,14 +365,15 @@ class Trainer:
     every training batch on the device, with draws keyed on (seed, global_step, rank, position in the batch); validate() never augments.
     Per-point input features (`src_point_feats` / `tgt_point_feats`, or `cloud_point_feats` beside `clouds`; see
     RegTR.forward) ride in the batch dict through train_step / validate / fit; the augmentation shuffles and swaps them
-    with their points (augment.augment_batch)."""
+    with their points (augment.augment_batch); direction_cols names the first column of every direction-valued
+    triple among them (normals: (1,) for [1, nx, ny, nz]), which the augmentation rotates with its cloud."""
 
     def __init__(self, cfg, ckpt_dir: Optional[str] = None, grad_clip: Optional[float] = None, rank: int = 0,
                  world: int = 1, process_group=None, bucket_bytes: int = 16 << 20, augment: bool = False,
-                 seed: int = 0):
+                 seed: int = 0, direction_cols=()):
         self.cfg = cfg
         self.augment, self.seed = bool(augment), int(seed)
-        self.augmentation = TrainAugmentation(cfg) if self.augment else None
+        self.augmentation = TrainAugmentation(cfg, direction_cols=direction_cols) if self.augment else None
         self.grad_clip = cfg.get('grad_clip', 0.0) if grad_clip is None else grad_clip
         self.rank, self.world, self.group = rank, world, process_group
         self.bucket_bytes = bucket_bytes
