@@ -555,6 +555,49 @@ int spr_kpconv_modes_bwd_dx(const float* q_xyz, int nq, const float* s_xyz, int 
                             int aggregation, const float* dwf, const float* dwf_range, int dwf_range_n, float* dx,
                             void* ws, size_t ws_bytes, void* stream);
 
+/* Deformable / modulated KPConv, linear influence and sum aggregation (kpconv_blocks.py:309-412 with deformable=True;
+ * csrc/kpconv_deform.hip).  offset_features [nq, of_stride >= (3 + modulated) n_kp] is the caller's offset convolution
+ * plus bias.  With K = n_kp, e = kp_extent, y = s[nbr[n,k]] - q[n], all float32:
+ *   D[n,p,:] = kernel_points[p] + e of[n, 3p:3p+3];   m[n,p] = 2 sigmoid(of[n, 3K+p]) when modulated, else 1
+ *   d2[n,k,p] = |y - D[n,p]|^2;   in_range[n,k] = any_p d2 < e^2 (an index outside [0, ns) is never in range)
+ *   h = max(0, 1 - sqrt(d2) / e) for in-range neighbours, 0 otherwise
+ *   out[n,:] = sum_p (m[n,p] sum_k h[n,k,p] x[nbr[n,k],:]) W[p] / max(1, #{k : in_range[n,k], sum_c x[nbr[n,k],c] > 0})
+ *   (the rigid kernels count every valid neighbour; the flags are spr_kpconv_fwd's, one summation order)
+ *   min_d2 [nq, K] (optional, NULL = not wanted) = min_k d2[n,k,p], a shadow entry taking part as (1e6, 1e6, 1e6).
+ * spr_kpconv_deform_fwd: spr_kpconv_modes_fwd's arguments without the mode pair; impl and wplanes as there (tile kernel
+ *   for 15 kernel points, cin and cout multiples of 32, cout <= 256).  n_kp <= 16 everywhere.
+ * The backward, with dwfm = (dout / cnt) W_flat^T [nq, K cin] from two GEMMs of the caller:
+ *   spr_kpconv_deform_weighted_features: wf [nq, K cin] UNmodulated and un-normalised, cnt [nq] = max(1, count) as above
+ *   spr_kpconv_deform_bwd_dx: dx[nbr[n,k], c] += sum_p h m dwfm[n,p,c]; dx [ns, cin] fully written, 64-bit fixed-point
+ *     sums (bitwise reproducible); ws: spr_scatter_workspace_bytes(ns, cin)
+ *   spr_kpconv_deform_bwd_offsets: d_offset_features [nq, (3 + modulated) K] contiguous, every element written, sums in a
+ *     fixed order (bitwise reproducible), no workspace; with g[n,k,p] = sum_c dwfm[n,p,c] x[nbr[n,k],c]:
+ *       d of[n, 3p:3p+3] = e m sum_k g (y - D[n,p]) / (sqrt(d2) e) over items with 0 < sqrt(d2) < e
+ *       d of[n, 3K+p]    = (sum_k h g) 2 s (1 - s),  s = sigmoid(of[n, 3K+p])
+ *     An item with d2 == 0 contributes 0 (the reference's sqrt yields NaN there).  No gradient reaches the points or
+ *     the count. */
+size_t spr_kpconv_deform_workspace_size(int nq, int ns, int cin, int cout);
+int spr_kpconv_deform_fwd(const float* q_xyz, int nq, const float* s_xyz, int ns, const int* nbr, int nbr_stride,
+                          int kmax, const float* x, int cin, const float* weights, int cout,
+                          const float* kernel_points, int n_kp, float kp_extent, const float* offset_features,
+                          int of_stride, int modulated, float* out, float* min_d2, int impl, const float* x_range,
+                          int x_range_n, const float* w_range, int w_range_n, const void* wplanes, void* ws,
+                          size_t ws_bytes, void* stream);
+size_t spr_kpconv_deform_weighted_features_workspace_size(int ns);
+int spr_kpconv_deform_weighted_features(const float* q_xyz, int nq, const float* s_xyz, int ns, const int* nbr,
+                                        int nbr_stride, int kmax, const float* x, int cin, const float* kernel_points,
+                                        int n_kp, float kp_extent, const float* offset_features, int of_stride,
+                                        float* wf, float* cnt, void* ws, size_t ws_bytes, void* stream);
+int spr_kpconv_deform_bwd_dx(const float* q_xyz, int nq, const float* s_xyz, int ns, const int* nbr, int nbr_stride,
+                             int kmax, int cin, const float* kernel_points, int n_kp, float kp_extent,
+                             const float* offset_features, int of_stride, int modulated, const float* dwfm,
+                             const float* dwfm_range, int dwfm_range_n, float* dx, void* ws, size_t ws_bytes,
+                             void* stream);
+int spr_kpconv_deform_bwd_offsets(const float* q_xyz, int nq, const float* s_xyz, int ns, const int* nbr,
+                                  int nbr_stride, int kmax, const float* x, int cin, const float* kernel_points,
+                                  int n_kp, float kp_extent, const float* offset_features, int of_stride,
+                                  int modulated, const float* dwfm, float* d_offset_features, void* stream);
+
 /* Per-point input features: spr_kpconv_fwd (impl 0 and 2) runs 2 <= cin <= 8 with any cout >= 1 and at most 16
  * kernel points on the small-Cin kernel (k_kpconv_few: exact f32, the cin = 1 kernel's influence and data movement);
  * spr_kpconv_workspace_bytes covers its support records.  Host only: the dispatch rule, for callers and tests. */

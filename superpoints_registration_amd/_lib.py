@@ -75,6 +75,16 @@ SIGNATURES = {
                                                 _vp, _sz, _vp]),
     "spr_kpconv_modes_bwd_dx": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _f, _i, _i, _vp, _vp, _i, _vp, _vp,
                                      _sz, _vp]),
+    "spr_kpconv_deform_workspace_size": (_sz, [_i, _i, _i, _i]),
+    "spr_kpconv_deform_fwd": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _i, _f, _vp, _i, _i, _vp, _vp,
+                                   _i, _vp, _i, _vp, _i, _vp, _vp, _sz, _vp]),
+    "spr_kpconv_deform_weighted_features_workspace_size": (_sz, [_i]),
+    "spr_kpconv_deform_weighted_features": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _f, _vp, _i, _vp,
+                                                 _vp, _vp, _sz, _vp]),
+    "spr_kpconv_deform_bwd_dx": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _f, _vp, _i, _i, _vp, _vp, _i, _vp,
+                                      _vp, _sz, _vp]),
+    "spr_kpconv_deform_bwd_offsets": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _f, _vp, _i, _i, _vp, _vp,
+                                           _vp]),
     "spr_kpconv_few_supported": (_i, [_i, _i, _i]),
     "spr_kpconv_stem_supported": (_i, [_i, _i, _i]),
     "spr_kpconv_stem_workspace_size": (_sz, [_i, _i, _i, _i, _i]),

@@ -85,7 +85,7 @@ def _chunk_hists(clouds, levels, config, hist_n: int) -> np.ndarray:
     out = np.zeros((len(levels), len(clouds), hist_n), np.int64)
     for l, lv in enumerate(levels):
         if lv.has_conv:
-            table = ops.RadiusTable(points, cu, lv.radius)
+            table = ops.RadiusTable(points, cu, lv.conv_radius)   # the conv search's radius (kpconv.py:631-634)
             _, hist = table.count(table.supports, table.s_cu, hist_n, counts=False)
             out[l] = hist.cpu().numpy()
         if lv.down:

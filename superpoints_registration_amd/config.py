@@ -47,6 +47,9 @@ _COMMON = dict(
     # the order inside an equal-distance run of a 'nearest' row: 'index' (ascending support index) or 'reference' (the
     # order cpp_neighbors' kd-tree search and std::sort leave it in: matrices equal to the reference's, index for index)
     tie_order='index',
+    # opt-in: only with it true does block_decider build the `*_deformable*` block names (deformable / modulated
+    # KPConv, the `deformable` subpackage; linear influence and sum aggregation only).  No shipped config sets it.
+    deformable_kpconv=False,
     # solver section of the YAML files (read by training.configure_optimizers / Trainer)
     optimizer='AdamW', base_lr=0.0001, weight_decay=0.0001, grad_clip=0.1, scheduler='step',
     scheduler_param=[127800, 0.5], reg_success_thresh_rot=10, reg_success_thresh_trans=0.1,

@@ -54,6 +54,10 @@ class BlockPlan:
 @dataclass
 class LevelPlan:
     radius: float    # r_normal of the level (kpconv.py:319, doubles per level :406)
+    conv_radius: float   # radius of the conv search (kpconv.py:349-352): the deformable radius when a deformable block
+                         # is among the level's non-strided blocks OTHER THAN THE LAST (the reference's layer_blocks[:-1])
+    pool_radius: float   # radius of the pool search (kpconv.py:374-377): the deformable radius when the strided block
+                         # itself is deformable; the up-sampling search uses twice this one (:385)
     has_conv: bool   # at least one non-strided block -> conv neighbours needed
     down: bool       # the level ends with a strided block -> subsample + pools
     limit: Optional[int]   # neighborhood_limits[level]; None when the config carries none (calibrate_neighbors)
@@ -90,7 +94,12 @@ def plan_pyramid(cfg):
         members.pop()
     levels = []
     for l, mem in enumerate(members):
-        levels.append(LevelPlan(radius=mem[0].radius,
+        r = mem[0].radius
+        r_deform = r * cfg.deform_radius / cfg.conv_radius if any('deformable' in b.name for b in mem) else r
+        convs = [b.name for b in mem if not b.down]
+        levels.append(LevelPlan(radius=r,
+                                conv_radius=r_deform if any('deformable' in n for n in convs[:-1]) else r,
+                                pool_radius=r_deform if mem[-1].down and 'deformable' in mem[-1].name else r,
                                 has_conv=any(not b.down for b in mem),
                                 down=mem[-1].down,
                                 limit=None if limits is None else int(limits[l])))
@@ -403,7 +412,7 @@ class Preprocessor(nn.Module):
             conv = pool = up = None
             plan_ns[0] = points.shape[0]
             if lv.has_conv:
-                conv = search((l, 'conv'), points, cu, points, cu, lv.radius, lv.limit)
+                conv = search((l, 'conv'), points, cu, points, cu, lv.conv_radius, lv.limit)
             publish('neighbors', l, conv)
             yield meta, 'conv', l
             if lv.down:
@@ -411,12 +420,12 @@ class Preprocessor(nn.Module):
                 sub_points, sub_lens = ops.grid_subsample(points, cu, dl, order=self.order)
                 sub_lens_host = sub_lens.tolist()
                 sub_cu = ops.lengths_to_cu(sub_lens_host, device)
-                pool = search((l, 'pool'), sub_points, sub_cu, points, cu, lv.radius, lv.limit)
+                pool = search((l, 'pool'), sub_points, sub_cu, points, cu, lv.pool_radius, lv.limit)
                 # spatial walk order of the level's pooled queries (kpconv_blocks.max_pool): one key + sort pass here,
                 # off the main stream, saves the max-pool most of its re-reads of the finer level's features
                 meta['pool_order'].append(ops.cell_order(sub_points, sub_cu, dl))
                 if self.compute_upsamples:
-                    up = search((l, 'up'), points, cu, sub_points, sub_cu, 2 * lv.radius, lv.limit)
+                    up = search((l, 'up'), points, cu, sub_points, sub_cu, 2 * lv.pool_radius, lv.limit)
             if not lv.down:
                 meta['pool_order'].append(None)
             publish('pools', l, pool)

@@ -11,10 +11,16 @@ KPConv runs every rigid mode of the reference: KP_influence 'constant' / 'linear
 'gaussian' x aggregation_mode 'sum' / 'closest'.  linear / sum (every shipped config)
 goes through ops.kpconv, the other five through kpconv_modes.kpconv.
 
+Deformable / modulated KPConv (linear / sum only) is opt-in: under
+config.deformable_kpconv block_decider builds 'simple_deformable[_strided]' and
+'resnetb_deformable[_strided]', whose .KPConv is a deformable.KPConvDeformable
+(the `deformable` subpackage, imported when such a block is built).  Without the
+key those names raise, and KPConv(deformable=True) / KPConv(modulated=True)
+raise in every config.
+
 Not mirrored (never selected by a shipped config):
-deformable / modulated KPConv, and the blocks 'unary2', 'global_average',
-'max_pool*' and the deformable / equivariant / invariant names: block_decider
-raises ValueError for them.
+the blocks 'unary2', 'global_average', 'max_pool*' and the equivariant /
+invariant names: block_decider raises ValueError for them.
 """
 import math
 
@@ -130,9 +136,37 @@ class KPConv(nn.Module):
             self.radius, self.KP_extent, self.in_channels, self.out_channels)
 
 
+DEFORMABLE_SIMPLE = ('simple_deformable', 'simple_deformable_strided')
+DEFORMABLE_RESNET = ('resnetb_deformable', 'resnetb_deformable_strided')
+
+
+def deformable_enabled(config) -> bool:
+    """The opt-in key of config.py (a config without it: off)."""
+    return bool(getattr(config, 'deformable_kpconv', False))
+
+
+def _block_kpconv(block_name, config, in_dim, out_dim, extent, radius):
+    """The .KPConv of a SimpleBlock / ResnetBottleneckBlock.  Under the opt-in a `*_deformable*` block gets a
+    KPConvDeformable (modulated = config.modulated) and every other block a rigid KPConv with modulated=False -- what
+    the reference's rigid path amounts to.  Without it: as ever, KPConv refuses deformable names and modulated."""
+    kw = dict(fixed_kernel_points=config.fixed_kernel_points, KP_influence=config.KP_influence,
+              aggregation_mode=config.aggregation_mode)
+    optin = deformable_enabled(config)
+    if optin and 'deform' in block_name:
+        from . import deformable
+        return deformable.KPConvDeformable(config.num_kernel_points, config.in_points_dim, in_dim, out_dim, extent,
+                                           radius, deformable=True, modulated=config.modulated, **kw)
+    return KPConv(config.num_kernel_points, config.in_points_dim, in_dim, out_dim, extent, radius,
+                  deformable='deform' in block_name, modulated=False if optin else config.modulated, **kw)
+
+
 def block_decider(block_name, radius, in_dim, out_dim, layer_ind, config):
     """kpconv_blocks.py:429-471."""
-    if block_name == 'unary':
+    if block_name in DEFORMABLE_SIMPLE and deformable_enabled(config):
+        return SimpleBlock(block_name, in_dim, out_dim, radius, layer_ind, config)
+    elif block_name in DEFORMABLE_RESNET and deformable_enabled(config):
+        return ResnetBottleneckBlock(block_name, in_dim, out_dim, radius, layer_ind, config)
+    elif block_name == 'unary':
         return UnaryBlock(in_dim, out_dim, config.use_batch_norm, config.batch_norm_momentum)
     elif block_name in ['simple', 'simple_strided']:
         return SimpleBlock(block_name, in_dim, out_dim, radius, layer_ind, config)
@@ -213,19 +247,15 @@ class SimpleBlock(nn.Module):
         self.block_name = block_name
         self.in_dim = in_dim
         self.out_dim = out_dim
-        self.KPConv = KPConv(config.num_kernel_points, config.in_points_dim, in_dim, out_dim // 2,
-                             current_extent, radius,
-                             fixed_kernel_points=config.fixed_kernel_points,
-                             KP_influence=config.KP_influence,
-                             aggregation_mode=config.aggregation_mode,
-                             deformable='deform' in block_name, modulated=config.modulated)
+        self.KPConv = _block_kpconv(block_name, config, in_dim, out_dim // 2, current_extent, radius)
         self.batch_norm = BatchNormBlock(out_dim // 2, self.use_bn, self.bn_momentum)
         self.leaky_relu = nn.LeakyReLU(0.1)
 
     def stem_route(self, x) -> bool:
         """Whether forward(x, ...) runs as the fused stem call: stem.stem_route's rule, in the linear / sum mode
-        only (the stem kernel has no other)."""
-        return (kpconv_modes.is_default_mode(self.KPConv.KP_influence, self.KPConv.aggregation_mode)
+        only (the stem kernel has no other) and never for a deformable KPConv (the stem kernel is rigid)."""
+        return (not self.KPConv.deformable
+                and kpconv_modes.is_default_mode(self.KPConv.KP_influence, self.KPConv.aggregation_mode)
                 and stem.stem_route(x, self.KPConv.weights, self.use_bn))
 
     def forward(self, x, batch):
@@ -265,12 +295,7 @@ class ResnetBottleneckBlock(nn.Module):
             self.unary1 = UnaryBlock(in_dim, out_dim // 4, self.use_bn, self.bn_momentum)
         else:
             self.unary1 = nn.Identity()
-        self.KPConv = KPConv(config.num_kernel_points, config.in_points_dim, out_dim // 4,
-                             out_dim // 4, current_extent, radius,
-                             fixed_kernel_points=config.fixed_kernel_points,
-                             KP_influence=config.KP_influence,
-                             aggregation_mode=config.aggregation_mode,
-                             deformable='deform' in block_name, modulated=config.modulated)
+        self.KPConv = _block_kpconv(block_name, config, out_dim // 4, out_dim // 4, current_extent, radius)
         self.batch_norm_conv = BatchNormBlock(out_dim // 4, self.use_bn, self.bn_momentum)
         self.unary2 = UnaryBlock(out_dim // 4, out_dim, self.use_bn, self.bn_momentum, no_relu=True)
         if in_dim != out_dim:
@@ -296,7 +321,9 @@ class ResnetBottleneckBlock(nn.Module):
         strided = 'strided' in self.block_name
         projected = isinstance(self.unary_shortcut, UnaryBlock)
         # Inference: unary2, the shortcut projection, both norms, the add and the LeakyReLU are ONE fused
-        # operator that never writes the un-normalised projections (ops.block_tail; csrc/block_tail.hip).
+        # operator that never writes the un-normalised projections (ops.block_tail; csrc/block_tail.hip).  The tail
+        # starts from the KPConv's output tensor and is indifferent to which KPConv wrote it: a deformable block
+        # takes it as well.
         mid = self.unary2.in_dim
         fused = (features.is_cuda and not torch.is_grad_enabled() and self.use_bn
                  and ops.block_tail_tile_rows(mid, self.in_dim if projected else 0, self.out_dim) > 0)

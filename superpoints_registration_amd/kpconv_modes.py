@@ -6,7 +6,7 @@ aggregation_mode in {'sum', 'closest'}, rigid kernel points.
 
 KPConv.forward (kpconv_blocks.py) calls ops.kpconv for linear / sum and this module for the other five combinations;
 linear / sum is valid here too -- the cross-check of these kernels against the shipped ones.  Deformable and modulated
-KPConv are not here.
+KPConv (linear / sum only, opt-in) is the `deformable` subpackage.
 """
 import torch
 
