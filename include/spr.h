@@ -598,6 +598,35 @@ int spr_kpconv_deform_bwd_offsets(const float* q_xyz, int nq, const float* s_xyz
                                   int n_kp, float kp_extent, const float* offset_features, int of_stride,
                                   int modulated, const float* dwfm, float* d_offset_features, void* stream);
 
+/* The regulariser of deformable KPConv (csrc/deform_reg.hip): KPConv's fitting loss (the squared distance from every
+ * deformed kernel point to its nearest input point) and repulsive loss (a query's kernel points may not collapse onto
+ * each other), value and gradient at the offset features in one launch.  Inputs as spr_kpconv_deform_fwd's;
+ * R = repulse_extent (in units of e); K = n_kp <= 16:
+ *   D[n,p]  = kernel_points[p] + e of[n, 3p:3p+3]            (float32, the arithmetic of min_d2 above)
+ *   y[n,k]  = s[nbr[n,k]] - q[n]                             real entries only: an index outside [0, ns) is a shadow
+ *   m[n,p]  = min over real k of |y[n,k] - D[n,p]|^2;  k* = the lowest column that attains it
+ *             a row with no real entry: m[n,p] = 0 and no k*
+ *   fit     = 1/(nq K) sum_{n,p} m[n,p] / e^2
+ *   L       = D / e;  dist[n,i,j] = |L[n,i] - L[n,j]|
+ *   rep     = 1/(nq K) sum_n sum_i sum_{j != i} min(dist[n,i,j] - R, 0)^2
+ *   out[3]  = (2 fit + rep, fit, rep), float32; the sums are float64 per-workgroup partials (in ws) added in block
+ *             order: no atomics, two runs give the same bits
+ * d_offset_features (NULL = not wanted: nothing but the partials is stored): [nq, (3 + modulated) K] contiguous, every
+ * element written.  In the repulsive term the OTHER kernel points are constants, as KPConv's authors detach them:
+ *   d of[n, 3p:3p+3] = 1/(nq K) [4 (D[n,p] - y[n,k*]) / e + 2 sum_{j != p} min(dist[n,p,j] - R, 0) (L[n,p] - L[n,j]) / dist[n,p,j]]
+ *   d of[n, 3K + p]  = 0                                     (modulation logits)
+ * A pair with dist == 0 contributes 0 to the gradient (the authors' sqrt yields NaN there); a row with no real
+ * neighbour contributes 0 to the fit term and to its gradient.
+ * Deliberate deviation: KPConv's authors let a shadow entry take part in the minimum as the point (1e6, 1e6, 1e6).  For
+ * a row that holds a real neighbour the two definitions agree (coordinates are far below 1e6); an all-shadow row would
+ * add about 3e12 / e^2 to a mean of O(1) terms.  The pyramid never builds such a row (a pooled query lies within half a
+ * cell diagonal of one of its own points).  min_d2 of spr_kpconv_deform_fwd keeps the far-point contract. */
+size_t spr_deform_reg_workspace_size(int nq);
+int spr_deform_reg(const float* q_xyz, int nq, const float* s_xyz, int ns, const int* nbr, int nbr_stride, int kmax,
+                   const float* kernel_points, int n_kp, float kp_extent, const float* offset_features, int of_stride,
+                   int modulated, float repulse_extent, float* out, float* d_offset_features, void* ws,
+                   size_t ws_bytes, void* stream);
+
 /* Per-point input features: spr_kpconv_fwd (impl 0 and 2) runs 2 <= cin <= 8 with any cout >= 1 and at most 16
  * kernel points on the small-Cin kernel (k_kpconv_few: exact f32, the cin = 1 kernel's influence and data movement);
  * spr_kpconv_workspace_bytes covers its support records.  Host only: the dispatch rule, for callers and tests. */

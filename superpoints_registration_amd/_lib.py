@@ -85,6 +85,8 @@ SIGNATURES = {
                                       _vp, _sz, _vp]),
     "spr_kpconv_deform_bwd_offsets": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _f, _vp, _i, _i, _vp, _vp,
                                            _vp]),
+    "spr_deform_reg_workspace_size": (_sz, [_i]),
+    "spr_deform_reg": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _i, _f, _vp, _i, _i, _f, _vp, _vp, _vp, _sz, _vp]),
     "spr_kpconv_few_supported": (_i, [_i, _i, _i]),
     "spr_kpconv_stem_supported": (_i, [_i, _i, _i]),
     "spr_kpconv_stem_workspace_size": (_sz, [_i, _i, _i, _i, _i]),

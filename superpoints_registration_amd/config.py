@@ -50,6 +50,11 @@ _COMMON = dict(
     # opt-in: only with it true does block_decider build the `*_deformable*` block names (deformable / modulated
     # KPConv, the `deformable` subpackage; linear influence and sum aggregation only).  No shipped config sets it.
     deformable_kpconv=False,
+    # the regulariser that holds deformed kernel points on the geometry (the `deform_reg` subpackage; KPConv's
+    # deform_fitting_power, repulse_extent and deform_lr_factor): compute_loss adds deform_fitting_power x (2 fitting +
+    # repulsive loss) of every deformable block, configure_optimizers trains the offset parameters at base_lr x
+    # deform_lr_factor.  KPConv's authors train with 1.0 / 1.2 / 0.1; 0.0 and 1.0 here change nothing.
+    deform_fitting_power=0.0, repulse_extent=1.2, deform_lr_factor=1.0,
     # solver section of the YAML files (read by training.configure_optimizers / Trainer)
     optimizer='AdamW', base_lr=0.0001, weight_decay=0.0001, grad_clip=0.1, scheduler='step',
     scheduler_param=[127800, 0.5], reg_success_thresh_rot=10, reg_success_thresh_trans=0.1,

@@ -228,6 +228,10 @@ class KPConvDeformable(nn.Module):
         self.min_d2 = None
         self.deformed_KP = None
         self.offset_features = None
+        # set (by the encoder, under cfg.deform_fitting_power > 0): forward() keeps references to its points and rows
+        # for the regulariser (the deform_reg subpackage); off, the module holds nothing more than the three above
+        self.keep_reg_inputs = False
+        self.reg_inputs = None
 
         self.weights = Parameter(torch.zeros((self.K, in_channels, out_channels), dtype=torch.float32),
                                  requires_grad=True)
@@ -267,6 +271,7 @@ class KPConvDeformable(nn.Module):
 
     def forward(self, q_pts, s_pts, neighb_inds, x):
         self.offset_features = self._offset_conv(q_pts, s_pts, neighb_inds, x) + self.offset_bias
+        self.reg_inputs = (q_pts, s_pts, neighb_inds) if self.keep_reg_inputs else None
         kp = self.kernel_points.detach()
         out, self.min_d2 = kpconv_deform(q_pts, s_pts, neighb_inds, x, self.weights, kp, self.KP_extent,
                                          self.offset_features, self.modulated, impl=self.impl, want_min_d2=True)

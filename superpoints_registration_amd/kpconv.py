@@ -119,6 +119,12 @@ class KPFEncoder(nn.Module):
         self._plans = blocks
         self.encoder_blocks = nn.ModuleList(
             block_decider(b.name, b.radius, b.in_dim, b.out_dim, b.level, config) for b in blocks)
+        if config.get('deform_fitting_power', 0.0) > 0:
+            # the regulariser on the deformed kernel points (the deform_reg subpackage, RegTR.compute_loss) reads each
+            # deformable block's last forward: its points and rows stay referenced until the next one
+            for m in self.encoder_blocks.modules():
+                if hasattr(m, 'keep_reg_inputs'):
+                    m.keep_reg_inputs = True
         # skip taps: the input of every strided block, plus the final features
         self.encoder_skips = [i for i, b in enumerate(blocks) if b.down]
         self.encoder_skip_dims = [b.in_dim for b in blocks if b.down]

@@ -505,6 +505,16 @@ class RegTR(nn.Module):
             losses['feature'] = ops.sum_scaled(torch.stack(feat), 1.0 / len(feat))  # mean over pairs (:314)
             losses['T'] = ops.sum_scaled(torch.stack(t_l1), 1.0)                    # sum over pairs (:353)
         losses['total'] = losses['T'] + 0.1 * losses['feature'] + losses['overlap']
+        power = float(cfg.get('deform_fitting_power', 0.0))
+        if power > 0:
+            # KPConv's p2p_fitting_regularizer over the encoder's deformable blocks, from the forward that left
+            # kpconv_meta: one term per encode call (per cloud on a batch of clouds and pairs, not per pair); on the
+            # tape when that forward was, a plain value under no_grad.  None without a deformable block.
+            from . import deform_reg
+            terms = deform_reg.regularizer_terms(self.kpf_encoder, power, float(cfg.get('repulse_extent', 1.2)))
+            if terms is not None:
+                losses['deform_reg'], losses['deform_fit'], losses['deform_rep'] = terms
+                losses['total'] = losses['total'] + losses['deform_reg']
         return losses
 
     def _refined_pose(self, xyz_c, overlap, val, val2, ind, cu, cu_host, B, cond, pair_keys=None):

@@ -240,10 +240,20 @@ def configure_optimizers(model: torch.nn.Module, cfg):
         base_lr = cfg.base_lr
     else:
         raise NotImplementedError(f"scheduler '{scheduler_type}' (only 'step' / 'none' are shipped)")
+    factor = float(cfg.get('deform_lr_factor', 1.0))
+    if factor == 1.0:
+        params = model.parameters()
+    else:
+        # KPConv's deform_lr_factor: the offset parameters of the deformable blocks (offset_conv.weights, offset_bias)
+        # train at base_lr x factor; the scheduler scales both groups
+        named = list(model.named_parameters())
+        slow = lambda n: 'offset' in n and n.rsplit('.', 1)[-1] != 'kernel_points'   # the fixed points are no weights
+        params = [{'params': [p for n, p in named if not slow(n)]},
+                  {'params': [p for n, p in named if slow(n)], 'lr': base_lr * factor}]
     if cfg.optimizer == 'AdamW':
-        opt = torch.optim.AdamW(model.parameters(), lr=base_lr, weight_decay=cfg.weight_decay)
+        opt = torch.optim.AdamW(params, lr=base_lr, weight_decay=cfg.weight_decay)
     elif cfg.optimizer == 'Adam':
-        opt = torch.optim.Adam(model.parameters(), lr=base_lr, weight_decay=cfg.weight_decay)
+        opt = torch.optim.Adam(params, lr=base_lr, weight_decay=cfg.weight_decay)
     else:
         raise NotImplementedError(cfg.optimizer)
     if scheduler_type == 'step':
