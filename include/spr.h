@@ -627,6 +627,48 @@ int spr_deform_reg(const float* q_xyz, int nq, const float* s_xyz, int ns, const
                    int modulated, float repulse_extent, float* out, float* d_offset_features, void* ws,
                    size_t ws_bytes, void* stream);
 
+/* ---- ICP for all pairs: point-to-point refinement of a pose, and its evaluation (fitness, inlier RMSE) -----------
+ * The loop of Open3D's registration_icp with TransformationEstimationPointToPoint, which the reference's KITTI loader
+ * runs on every ground-truth pose (data_loaders/kitti_pred.py:161-183: raw scans, threshold 0.2 m, 200 iterations),
+ * for all nb pairs of a batch in one call; max_iter = 0 is a pure evaluation of pose_init.  Open3D is not available
+ * here: parity with it is unpinned, the definition below is the contract.
+ * Contract, per pair, in IEEE float64 on the exactly converted float32 inputs, one rounding per operation, no FMA:
+ *   s'_i[k]  = ((R[k][0] x + R[k][1] y) + R[k][2] z) + t[k]                  (T = [R | t], src -> tgt)
+ *   d2(a, b) = ((ax-bx)^2 + (ay-by)^2) + (az-bz)^2
+ *   E(T), the evaluation under T:
+ *     corr_i      = the LOCAL target index j minimising (d2(s'_i, tgt_j), j) if that d2 < max_dist * max_dist (strict),
+ *                   else -1
+ *     count       = #{corr_i >= 0}
+ *     fitness     = count / n_src                                             (0 for an empty source)
+ *     inlier_rmse = sqrt(sum of the matched d2 / count)                       (0 when count = 0)
+ *   T_0 = pose_init; evaluate E(T_0); then for k = 0 .. max_iter - 1:
+ *     U = the unweighted Kabsch solve of the pairs (s'_i, tgt_corr_i): R from the SVD of sum (a - mean a)(b - mean b)^T
+ *         with the sign fix at det <= 0, t = mean b - R mean a -- the arithmetic of spr_weighted_procrustes kept in
+ *         float64; count = 0 gives U = I
+ *     T_{k+1} = U o T_k, composed in float64; evaluate E(T_{k+1})
+ *     stop after this pass if |fitness_{k+1} - fitness_k| < rel_fitness and |rmse_{k+1} - rmse_k| < rel_rmse
+ *   iterations = the number of steps k run; every output is that of the LAST evaluation.
+ * One pass over the correspondences serves the evaluation of T_k and the solve for T_{k+1}: a call makes
+ * iterations + 1 association passes per pair.  The order of the moment sums is the implementation's, fixed and a
+ * function of the pair alone (per-block float64 partials added in block order, no floating-point atomics): every
+ * output of a pair has the same bits whatever batch, position or neighbours it is called with, and run to run.  A
+ * pair that has stopped is frozen: later passes of the call neither touch it nor do association work for it.
+ * Empty sources and targets are legal (fitness 0, pose = pose_init).  status [nb] i32: 0, or -1 when the pair has a
+ * non-finite coordinate or pose: pose = pose_init, fitness = rmse = 0, iterations = count = 0, corr = -1 for that
+ * pair only.  Geometry never overflows the target's cell table (spr_gt_overlap's rule: a cloud whose box needs more
+ * than 16 n + 4096 cells at edge max_dist (1 + 2^-8) gets coarser cells, same result).
+ * The call reads one integer back from the device per four passes (none when max_iter < 4); a workspace below
+ * spr_icp_pairs_workspace_size(ns, nt, nb) is refused before anything is enqueued.
+ *   src_xyz [ns,3] f32, src_cu [nb+1] i32, tgt_xyz [nt,3] f32, tgt_cu [nb+1] i32, pose_init [nb,3,4] f64
+ *   max_dist > 0, max_iter >= 0
+ *   pose [nb,3,4] f32 (= pose64 rounded), pose64 [nb,3,4] f64, fitness [nb] f64, inlier_rmse [nb] f64,
+ *   iterations [nb] i32, count [nb] i32, corr [ns] i32, status [nb] i32 */
+size_t spr_icp_pairs_workspace_size(int ns, int nt, int nb);
+int spr_icp_pairs(const float* src_xyz, const int* src_cu, int ns, const float* tgt_xyz, const int* tgt_cu, int nt,
+                  const double* pose_init, int nb, double max_dist, int max_iter, double rel_fitness, double rel_rmse,
+                  float* pose, double* pose64, double* fitness, double* inlier_rmse, int* iterations, int* count,
+                  int* corr, int* status, void* ws, size_t ws_bytes, void* stream);
+
 /* Per-point input features: spr_kpconv_fwd (impl 0 and 2) runs 2 <= cin <= 8 with any cout >= 1 and at most 16
  * kernel points on the small-Cin kernel (k_kpconv_few: exact f32, the cin = 1 kernel's influence and data movement);
  * spr_kpconv_workspace_bytes covers its support records.  Host only: the dispatch rule, for callers and tests. */

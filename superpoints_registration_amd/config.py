@@ -55,6 +55,11 @@ _COMMON = dict(
     # repulsive loss) of every deformable block, configure_optimizers trains the offset parameters at base_lr x
     # deform_lr_factor.  KPConv's authors train with 1.0 / 1.2 / 0.1; 0.0 and 1.0 here change nothing.
     deform_fitting_power=0.0, repulse_extent=1.2, deform_lr_factor=1.0,
+    # opt-in, inference only: polish the predicted pose by point-to-point ICP on the input clouds (the `icp` subpackage,
+    # all pairs in one call).  icp_distance: the correspondence threshold in the clouds' units (None: twice
+    # first_subsampling_dl, about two point spacings of a voxel-filtered input); icp_max_iter: the most steps per pair.
+    # forward() then returns the polished pose as 'pose', the network's as 'pose_coarse', and 'icp_fitness' / 'icp_rmse'.
+    icp_refine=False, icp_distance=None, icp_max_iter=30,
     # solver section of the YAML files (read by training.configure_optimizers / Trainer)
     optimizer='AdamW', base_lr=0.0001, weight_decay=0.0001, grad_clip=0.1, scheduler='step',
     scheduler_param=[127800, 0.5], reg_success_thresh_rot=10, reg_success_thresh_trans=0.1,

@@ -40,29 +40,12 @@
 // the edge grows (x 1.25 per step) until it fits.  Coarser cells are as correct as fine ones (more candidates per
 // query, same minimum), so no geometry overflows the table; only non-finite coordinates are refused
 // (corr_count[0] = -1 -> ops raises).
-#include <rocprim/device/device_scan.hpp>
-
-#include "spr_common.h"
+//
+// The grid description, the records, the grid fit and the nine-run walk live in ov_grid.h, shared with icp.hip.
+#include "ov_grid.h"
 
 namespace spr {
 namespace {
-
-struct OvGrid {
-  double mn[3];
-  double inv_h;
-  int dim[3];
-  int off;  // first cell of this cloud in the table
-};
-
-struct alignas(32) OvRec {
-  double x, y, z;
-  int idx;  // local to the cloud
-  int pad;
-};
-
-constexpr int kOvCellsPerPoint = 16;
-constexpr int kOvCellsBase = 4096;
-constexpr double kOvMaxCoord = 1073741824.0;  // 2^30 cells
 
 // s' = ((R0 x + R1 y) + R2 z) + t, one rounding per operation
 __device__ __forceinline__ void ov_transform(const float* __restrict__ T, float xf, float yf, float zf, double* o) {
@@ -73,13 +56,6 @@ __device__ __forceinline__ void ov_transform(const float* __restrict__ T, float 
     a = __dadd_rn(a, __dmul_rn((double)T[4 * k + 2], z));
     o[k] = __dadd_rn(a, (double)T[4 * k + 3]);
   }
-}
-
-// cell coordinate of p in a grid, clamped to [-2, 2^30] (so that the int conversion is defined)
-__device__ __forceinline__ int ov_cell(double p, double mn, double inv_h) {
-  double v = (p - mn) * inv_h;
-  v = fmin(fmax(v, -2.0), kOvMaxCoord);
-  return (int)floor(v);
 }
 
 // point p of the combined sequence [all targets, all sources] of cloud c (c < nb: target of pair c, otherwise the
@@ -143,25 +119,8 @@ __global__ __launch_bounds__(256) void k_ov_bbox(const float* __restrict__ src, 
   if (sbad) {
     atomicOr(err, 1);
   } else if (end > beg) {
-    const double budget = (double)kOvCellsPerPoint * (double)(end - beg) + (double)kOvCellsBase;
-    double h = h0;
-    // the finest edge >= h0 whose grid fits the cloud's share of the table (h -> inf gives 1 x 1 x 1)
-    for (int it = 0; it < 4096; ++it) {
-      const double inv = 1.0 / h;
-      double cells = 1.0;
-      for (int d = 0; d < 3; ++d) cells *= floor(fmin((smx[d][0] - smn[d][0]) * inv, kOvMaxCoord)) + 1.0;
-      g.inv_h = inv;
-      if (cells <= budget) break;
-      h *= 1.25;
-    }
-    for (int d = 0; d < 3; ++d) {
-      g.mn[d] = smn[d][0];
-      g.dim[d] = ov_cell(smx[d][0], g.mn[d], g.inv_h) + 1;
-    }
-    if ((double)g.dim[0] * (double)g.dim[1] * (double)g.dim[2] > budget) {  // not reachable for finite boxes
-      atomicOr(err, 1);
-      g.dim[0] = g.dim[1] = g.dim[2] = 1;
-    }
+    const double bmn[3] = {smn[0][0], smn[1][0], smn[2][0]}, bmx[3] = {smx[0][0], smx[1][0], smx[2][0]};
+    if (!ov_fit_grid(bmn, bmx, end - beg, h0, g)) atomicOr(err, 1);  // not reachable for finite boxes
   }
   info[c] = g;
 }
@@ -179,10 +138,6 @@ __global__ void k_ov_offsets(OvGrid* info, const int* __restrict__ src_cu, const
     info[c].off = off;
     off += info[c].dim[0] * info[c].dim[1] * info[c].dim[2];
   }
-}
-
-__device__ __forceinline__ int ov_grid_cell(const OvGrid& g, int cx, int cy, int cz) {
-  return g.off + (cz * g.dim[1] + cy) * g.dim[0] + cx;
 }
 
 __global__ __launch_bounds__(256) void k_ov_count(const float* __restrict__ src, const float* __restrict__ tgt,
@@ -220,23 +175,6 @@ __global__ __launch_bounds__(256) void k_ov_scatter(const float* __restrict__ sr
   rec[start[cell_of[p]] + rank[p]] = r;
 }
 
-struct OvRuns9 {
-  int2 r0, r1, r2, r3, r4, r5, r6, r7, r8;
-};
-// a nine-element array indexed by the running run number would be demoted to scratch memory (radius_neighbors.hip)
-__device__ __forceinline__ int2 ov_pick9(int k, const OvRuns9& a) {
-  int2 v = a.r0;
-  v = (k == 1) ? a.r1 : v;
-  v = (k == 2) ? a.r2 : v;
-  v = (k == 3) ? a.r3 : v;
-  v = (k == 4) ? a.r4 : v;
-  v = (k == 5) ? a.r5 : v;
-  v = (k == 6) ? a.r6 : v;
-  v = (k == 7) ? a.r7 : v;
-  v = (k == 8) ? a.r8 : v;
-  return v;
-}
-
 // Thread t owns record t: a point of cloud c, looked up in the table of the other cloud of its pair.
 __global__ __launch_bounds__(256) void k_ov_scan(int np, int nt, int nb, const int* __restrict__ ccu,
                                                  const OvGrid* __restrict__ info, const int* __restrict__ start,
@@ -252,47 +190,8 @@ __global__ __launch_bounds__(256) void k_ov_scan(int np, int nt, int nb, const i
   const int cx = ov_cell(me.x, g.mn[0], g.inv_h);
   const int cy = ov_cell(me.y, g.mn[1], g.inv_h);
   const int cz = ov_cell(me.z, g.mn[2], g.inv_h);
-  const int xlo = max(cx - 1, 0), xhi = min(cx + 1, g.dim[0] - 1);
-  auto run_of = [&](int k) -> int2 {
-    const int z = cz + k / 3 - 1, y = cy + k % 3 - 1;
-    const bool in = xlo <= xhi && z >= 0 && z < g.dim[2] && y >= 0 && y < g.dim[1];
-    if (!in) return make_int2(0, 0);
-    return make_int2(start[ov_grid_cell(g, xlo, y, z)], start[ov_grid_cell(g, xhi, y, z) + 1]);
-  };
-  OvRuns9 runs;
-  runs.r0 = run_of(0); runs.r1 = run_of(1); runs.r2 = run_of(2);
-  runs.r3 = run_of(3); runs.r4 = run_of(4); runs.r5 = run_of(5);
-  runs.r6 = run_of(6); runs.r7 = run_of(7); runs.r8 = run_of(8);
-  double best = r2;  // strict: only d2 < r2 can replace it
-  int best_i = -1;
-  // the nine record runs as ONE candidate sequence, four 32-byte records in flight
-  int k = 0, j = runs.r0.x, e = runs.r0.y;
-  while (k < 9) {
-    OvRec s4[4];
-    bool v4[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      while (k < 9 && j >= e) {
-        ++k;
-        const int2 r = ov_pick9(k, runs);
-        j = r.x;
-        e = r.y;
-      }
-      v4[u] = k < 9;
-      s4[u] = rec[v4[u] ? j : 0];
-      j += v4[u] ? 1 : 0;
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const double dx = __dsub_rn(me.x, s4[u].x), dy = __dsub_rn(me.y, s4[u].y), dz = __dsub_rn(me.z, s4[u].z);
-      double d2 = __dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy));
-      d2 = __dadd_rn(d2, __dmul_rn(dz, dz));
-      // lexicographic (d2, index); best_i = -1 stands for (r2, +inf)
-      const bool better = v4[u] && (d2 < best || (d2 == best && best_i >= 0 && s4[u].idx < best_i));
-      best = better ? d2 : best;
-      best_i = better ? s4[u].idx : best_i;
-    }
-  }
+  double best;
+  const int best_i = ov_nearest(rec, ov_runs(g, start, cx, cy, cz), me.x, me.y, me.z, r2, best);
   // rows are addressed by the point's ORIGINAL index, not by its place in the cell order
   if (c < nb) {
     const int o = ccu[c] + me.idx;
@@ -338,12 +237,6 @@ __global__ __launch_bounds__(256) void k_ov_compact(int ns, int nb, const int* _
 
 size_t ov_cells(int ns, int nt, int nb) {
   return (size_t)kOvCellsPerPoint * ((size_t)ns + (size_t)nt) + (size_t)kOvCellsBase * 2 * (size_t)nb;
-}
-
-size_t ov_scan_temp_bytes(size_t n) {
-  size_t b = 0;
-  (void)rocprim::exclusive_scan(nullptr, b, (int*)nullptr, (int*)nullptr, 0, n > 0 ? n : 1, rocprim::plus<int>());
-  return align_up(b, 256) + 256;
 }
 
 struct OvWs {

@@ -107,9 +107,11 @@ static __device__ void svd3_jacobi(const double A[3][3], double U[3][3], double 
   }
 }
 
-// The serial end of the solve, shared with ransac.hip: the pose [R | t] (12 floats, row-major [3,4], rounded to float32)
-// from the reduced covariance cov [3x3, row-major] and the weighted centroids ca, cb.
-static __device__ void procrustes_pose(const double* cov, const double* ca, const double* cb, float* out) {
+// The serial end of the solve, shared with ransac.hip and icp.hip: the pose [R | t] (12 values, row-major [3,4], rounded
+// to float32 when T is float, kept in float64 when T is double) from the reduced covariance cov [3x3, row-major] and
+// the weighted centroids ca, cb.
+template <class T>
+static __device__ void procrustes_pose(const double* cov, const double* ca, const double* cb, T* out) {
   double A[3][3], U[3][3], S[3], V[3][3];
   for (int r = 0; r < 3; ++r)
     for (int c = 0; c < 3; ++c) A[r][c] = cov[3 * r + c];
@@ -129,10 +131,10 @@ static __device__ void procrustes_pose(const double* cov, const double* ca, cons
   for (int r = 0; r < 3; ++r) {
     double t = cb[r];
     for (int c = 0; c < 3; ++c) {
-      out[4 * r + c] = (float)R[r][c];
+      out[4 * r + c] = (T)R[r][c];
       t -= R[r][c] * ca[c];
     }
-    out[4 * r + 3] = (float)t;
+    out[4 * r + 3] = (T)t;
   }
 }
 

@@ -3,7 +3,9 @@
 KittiDataset.__getitem__ (data_loaders/kitti_pred.py:203-230) runs, per scan and on the CPU, kiss-icp's first-point
 voxel filter at config.first_subsampling_dl, the crop to config.crop_radius and the ground cut of config.remove_ground.
 prepare_pairs does the same for every scan of a batch with one library call (ops.prepare_scans) and one device->host
-copy.  (The loader's ICP refinement of the ground-truth pose, :161-183, is a cached offline step and stays outside.)
+copy.  The loader's ICP refinement of the ground-truth pose (:161-183: Open3D point-to-point ICP on the raw scans,
+threshold 0.2 m, 200 iterations, cached on disk because it takes seconds per pair) is refine_pose=True: all pairs of
+the batch in one call of the `icp` subpackage.
 """
 from typing import List, Optional, Sequence
 
@@ -14,7 +16,8 @@ from . import ops
 
 def prepare_pairs(src_scans: Sequence[torch.Tensor], tgt_scans: Sequence[torch.Tensor], cfg,
                   pose: Optional[torch.Tensor] = None, intensity: bool = False, normals_radius: Optional[float] = None,
-                  normals_limit: int = 40) -> dict:
+                  normals_limit: int = 40, refine_pose: bool = False, icp_distance: float = 0.2,
+                  icp_max_iter: int = 200) -> dict:
     """src_scans / tgt_scans: B raw scans each, [n_i, 3] or [n_i, 4] float32 device tensors (4 columns:
     np.fromfile(...).reshape(-1, 4) as it is, x y z reflectance; all scans of a call have the same width).  cfg: the
     experiment's config (first_subsampling_dl; crop_radius and remove_ground default to 0.0 and False).  pose: [B,3,4]
@@ -29,7 +32,11 @@ def prepare_pairs(src_scans: Sequence[torch.Tensor], tgt_scans: Sequence[torch.T
     normals_limit nearest kept points within that radius (normals.estimate) and oriented towards the sensor, the
     scan's origin: 'src_point_feats' / 'tgt_point_feats' are then [1, nx, ny, nz], or [1, reflectance, nx, ny, nz]
     with intensity=True -- direction_cols (1,) or (2,) for the augmentation.  A point with fewer than 3 kept points
-    in range has the zero normal."""
+    in range has the zero normal.
+    refine_pose=True (needs `pose`): point-to-point ICP from `pose` on the RAW scans' xyz, before the voxel filter, as
+    the loader does it (icp.icp_pairs with max_dist icp_distance, at most icp_max_iter steps); 'pose' is then the
+    refined pose [B,3,4] float32 and 'icp_fitness' / 'icp_rmse' ([B] float64) tell how well it fits.  Everything else
+    in the dict is what it is without the flag."""
     src, tgt = list(src_scans), list(tgt_scans)
     B = len(src)
     if B < 1 or len(tgt) != B:
@@ -41,6 +48,8 @@ def prepare_pairs(src_scans: Sequence[torch.Tensor], tgt_scans: Sequence[torch.T
                          f"{sorted(map(str, widths))}")
     if intensity and next(iter(widths)) != (4,):
         raise ValueError("prepare_pairs: intensity=True needs [n, 4] scans (x y z reflectance)")
+    if refine_pose and pose is None:
+        raise ValueError("prepare_pairs: refine_pose=True needs the pose to refine")
     lens = [int(s.shape[0]) for s in scans]
     if min(lens) < 1:
         b = lens.index(min(lens))
@@ -70,4 +79,9 @@ def prepare_pairs(src_scans: Sequence[torch.Tensor], tgt_scans: Sequence[torch.T
         feats = [torch.cat([f, n], dim=1) for f, n in zip(first, torch.split(nrm, out_lens))]
     if feats is not None:
         out['src_point_feats'], out['tgt_point_feats'] = feats[:B], feats[B:]
+    if refine_pose:
+        from . import icp
+        raw = [s[:, :3].to(torch.float32).contiguous() for s in scans]
+        r = icp.icp_pairs(raw[:B], raw[B:], pose, float(icp_distance), int(icp_max_iter))
+        out['pose'], out['icp_fitness'], out['icp_rmse'] = r['pose'], r['fitness'], r['inlier_rmse']
     return out

@@ -212,15 +212,34 @@ class RegTR(nn.Module):
         `tgt_point_feats`, lists of [n_i, C] float32 device tensors row-aligned with the clouds, or `cloud_point_feats`
         aligned with `clouds`.  Without them (in_feats_dim = 1 only) the encoder runs on a column of ones."""
         shared = None
+        icp_refine = bool(self.cfg.get('icp_refine', False))
+        if icp_refine and ('clouds' in batch or (self.training and torch.is_grad_enabled())):
+            raise NotImplementedError("cfg.icp_refine polishes the pose of src_xyz / tgt_xyz batches in inference "
+                                      "(model.eval() or torch.no_grad()): not in training, not over shared clouds")
         if 'clouds' in batch:
             shared = shared_clouds.check_batch(batch)       # raises on the host, before any launch
         feats = batch_point_feats(self.cfg.get('in_feats_dim', 1), batch, shared)   # likewise
         if not self.training and torch.is_grad_enabled():
             with torch.no_grad():
-                return self._forward(batch, shared, feats)
+                out = self._forward(batch, shared, feats)
+                return self._icp_polish(out, batch) if icp_refine else out
         if self.training and torch.is_grad_enabled():
             ops.prime_weight_ranges(self.parameters())      # one measuring launch for every weight the step moved
-        return self._forward(batch, shared, feats)
+        out = self._forward(batch, shared, feats)
+        return self._icp_polish(out, batch) if icp_refine else out
+
+    def _icp_polish(self, out, batch):
+        """cfg.icp_refine: point-to-point ICP from the predicted pose on the input clouds, all pairs in one call; the
+        network's pose stays in the output as 'pose_coarse'."""
+        from . import icp
+        cfg = self.cfg
+        dist = cfg.get('icp_distance', None)
+        dist = 2.0 * float(cfg.first_subsampling_dl) if dist is None else float(dist)
+        r = icp.icp_pairs([c.to(torch.float32) for c in batch['src_xyz']], [c.to(torch.float32) for c in batch['tgt_xyz']],
+                          out['pose'], dist, int(cfg.get('icp_max_iter', 30)))
+        out['pose_coarse'] = out['pose']
+        out['pose'], out['icp_fitness'], out['icp_rmse'] = r['pose'], r['fitness'], r['inlier_rmse']
+        return out
 
     def _forward(self, batch, shared=None, feats=None):
         if shared is not None:
