@@ -669,6 +669,66 @@ int spr_icp_pairs(const float* src_xyz, const int* src_cu, int ns, const float* 
                   float* pose, double* pose64, double* fitness, double* inlier_rmse, int* iterations, int* count,
                   int* corr, int* status, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Point-to-plane ICP for all pairs, with robust kernels ---------------------------------------------------------
+ * The loop of Open3D's registration_icp with TransformationEstimationPointToPlane (optionally with a Huber or Tukey
+ * kernel) for all nb pairs of a batch in one call.  Arguments, outputs, status, workspace rule, chunked read-back and
+ * frozen pairs are spr_icp_pairs'; the additional inputs are
+ *   tgt_normals [nt,3] f32   row-aligned with tgt_xyz; used as given, NOT renormalised
+ *   kernel                   0 = L2, 1 = Huber, 2 = Tukey (any other value is refused on the host)
+ *   kernel_k                 the kernel's parameter k, in the clouds' units; read only when kernel != 0, and then
+ *                            refused on the host unless > 0 (NaN is refused)
+ * Open3D is not available here and the reference never calls this estimate: the definition below, written from
+ * Open3D's published behaviour, is the contract.
+ * Contract, per pair, in IEEE float64 on the exactly converted float32 inputs, one rounding per operation, no FMA:
+ *   E(T) is EXACTLY that of "ICP for all pairs": the same s', d2, strict threshold and lowest-index tie rule give
+ *   corr, count, fitness and inlier_rmse -- the RMSE stays the POINT distance, as in Open3D's RegistrationResult.
+ *   For every matched i, with j = corr_i:
+ *     a = s'_i, b = tgt_j, n = tgt_normals_j; c = the per-axis minimum of the pair's target cloud (a conditioning
+ *     shift: exact, independent of any order)
+ *     r  = ((ax-bx) nx + (ay-by) ny) + (az-bz) nz
+ *     p  = a - c;  J = [py nz - pz ny, pz nx - px nz, px ny - py nx, nx, ny, nz]        ( = [(a - c) x n ; n] )
+ *     w  = 1                                              L2
+ *          1 if |r| <= k else k / |r|                     Huber
+ *          (1 - (r/k)(r/k))^2 if |r| <= k else 0          Tukey: q = r / k; u = 1 - q q; w = u u
+ *     A_kl += (w J_k) J_l for k <= l (21 entries);  g_k += (w J_k) r
+ *   A zero normal adds nothing to A and g but counts in fitness and inlier_rmse like any match.
+ *   Solve A x = -g by unpivoted LDL^T, A_lk = A_kl.  With m = max_i A_ii, for k = 0 .. 5:
+ *     d_k  = A_kk - sum_{p<k} (L_kp d_p) L_kp             subtracted one by one, p ascending
+ *     the step is refused unless d_k > 1e-12 m
+ *     L_ik = (A_ik - sum_{p<k} (L_ip d_p) L_kp) / d_k     for i = k+1 .. 5, subtracted likewise
+ *   y_i = -g_i - sum_{p<i} L_ip y_p (i ascending);  x_i = y_i / d_i - sum_{p>i} L_pi x_p (i descending, p ascending).
+ *   U = I when count = 0 or the step is refused (a flat patch has an exact zero pivot: the pose then stays, and the
+ *   pair stops after one step because nothing moved).  Deviation: Open3D refuses on |det A| < 1e-6, an absolute
+ *   threshold that depends on the clouds' units; the relative pivot rule does not.
+ *   Otherwise, with omega = x[0:3], v = x[3:6]:
+ *     t = v - omega x c:  t_0 = v_0 - (omega_1 c_2 - omega_2 c_1), t_1 = v_1 - (omega_2 c_0 - omega_0 c_2),
+ *                         t_2 = v_2 - (omega_0 c_1 - omega_1 c_0)
+ *       (in exact arithmetic (omega, t) is Open3D's minimiser, which linearises about the world origin)
+ *     U = [Rz(omega_2) Ry(omega_1) Rx(omega_0) | t], Open3D's TransformVector6dToMatrix4d (not the exponential map);
+ *       with s., c. the sine and cosine of omega_0 (x), omega_1 (y), omega_2 (z):
+ *       [cz cy, (cz sy) sx - sz cx, (cz sy) cx + sz sx;  sz cy, (sz sy) sx + cz cx, (sz sy) cx - cz sx;  -sy, cy sx, cy cx]
+ *   T_0 = pose_init; evaluate E(T_0); then for k = 0 .. max_iter - 1:
+ *     T_{k+1} = U o T_k, composed in float64; evaluate E(T_{k+1})
+ *     stop after this pass if |fitness_{k+1} - fitness_k| < rel_fitness and |rmse_{k+1} - rmse_k| < rel_rmse
+ *   iterations = the number of steps k run; every output is that of the LAST evaluation.
+ * One pass over the correspondences serves the evaluation of T_k and the solve for T_{k+1}: a call makes
+ * iterations + 1 association passes per pair.  The order of the sums of A, g and d2 is the implementation's, fixed and a
+ * function of the pair alone (per-block float64 partials added in block order, no floating-point atomics): every
+ * output of a pair has the same bits whatever batch, position or neighbours it is called with, and run to run.  A
+ * pair that has stopped is frozen: later passes of the call neither touch it nor do association work for it.
+ * Negating every normal of a pair changes no output bit (J and r change sign together).
+ * Empty sources and targets are legal (fitness 0, pose = pose_init).  status [nb] i32: 0, or -1 when the pair has a
+ * non-finite coordinate, normal or pose: pose = pose_init, fitness = rmse = 0, iterations = count = 0, corr = -1 for
+ * that pair only.  The cell-table rule, the read-back rule and the workspace rule are spr_icp_pairs', with
+ * spr_icp_plane_pairs_workspace_size(ns, nt, nb).  Out of scope: source-side or symmetric normals, coloured and
+ * generalised ICP. */
+size_t spr_icp_plane_pairs_workspace_size(int ns, int nt, int nb);
+int spr_icp_plane_pairs(const float* src_xyz, const int* src_cu, int ns, const float* tgt_xyz, const float* tgt_normals,
+                        const int* tgt_cu, int nt, const double* pose_init, int nb, double max_dist, int max_iter,
+                        double rel_fitness, double rel_rmse, int kernel, double kernel_k, float* pose, double* pose64,
+                        double* fitness, double* inlier_rmse, int* iterations, int* count, int* corr, int* status,
+                        void* ws, size_t ws_bytes, void* stream);
+
 /* Per-point input features: spr_kpconv_fwd (impl 0 and 2) runs 2 <= cin <= 8 with any cout >= 1 and at most 16
  * kernel points on the small-Cin kernel (k_kpconv_few: exact f32, the cin = 1 kernel's influence and data movement);
  * spr_kpconv_workspace_bytes covers its support records.  Host only: the dispatch rule, for callers and tests. */

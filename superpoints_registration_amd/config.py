@@ -60,6 +60,10 @@ _COMMON = dict(
     # first_subsampling_dl, about two point spacings of a voxel-filtered input); icp_max_iter: the most steps per pair.
     # forward() then returns the polished pose as 'pose', the network's as 'pose_coarse', and 'icp_fitness' / 'icp_rmse'.
     icp_refine=False, icp_distance=None, icp_max_iter=30,
+    # icp_method: 'point_to_point', or 'point_to_plane' (the `icp_plane` subpackage): target normals estimated at
+    # icp_normals_radius (None: 2.5 x first_subsampling_dl, one conv radius of level 0), kernel icp_kernel = 'l2',
+    # 'huber' or 'tukey' with parameter icp_kernel_k (a residual in the clouds' units; required with the robust ones).
+    icp_method='point_to_point', icp_normals_radius=None, icp_kernel='l2', icp_kernel_k=None,
     # solver section of the YAML files (read by training.configure_optimizers / Trainer)
     optimizer='AdamW', base_lr=0.0001, weight_decay=0.0001, grad_clip=0.1, scheduler='step',
     scheduler_param=[127800, 0.5], reg_success_thresh_rot=10, reg_success_thresh_trans=0.1,

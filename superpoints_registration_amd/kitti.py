@@ -5,7 +5,7 @@ voxel filter at config.first_subsampling_dl, the crop to config.crop_radius and 
 prepare_pairs does the same for every scan of a batch with one library call (ops.prepare_scans) and one device->host
 copy.  The loader's ICP refinement of the ground-truth pose (:161-183: Open3D point-to-point ICP on the raw scans,
 threshold 0.2 m, 200 iterations, cached on disk because it takes seconds per pair) is refine_pose=True: all pairs of
-the batch in one call of the `icp` subpackage.
+the batch in one call of the `icp` subpackage, or with icp_method='point_to_plane' of the `icp_plane` subpackage.
 """
 from typing import List, Optional, Sequence
 
@@ -17,7 +17,9 @@ from . import ops
 def prepare_pairs(src_scans: Sequence[torch.Tensor], tgt_scans: Sequence[torch.Tensor], cfg,
                   pose: Optional[torch.Tensor] = None, intensity: bool = False, normals_radius: Optional[float] = None,
                   normals_limit: int = 40, refine_pose: bool = False, icp_distance: float = 0.2,
-                  icp_max_iter: int = 200) -> dict:
+                  icp_max_iter: int = 200, icp_method: str = 'point_to_point',
+                  icp_normals_radius: Optional[float] = None, icp_kernel: str = 'l2',
+                  icp_kernel_k: Optional[float] = None) -> dict:
     """src_scans / tgt_scans: B raw scans each, [n_i, 3] or [n_i, 4] float32 device tensors (4 columns:
     np.fromfile(...).reshape(-1, 4) as it is, x y z reflectance; all scans of a call have the same width).  cfg: the
     experiment's config (first_subsampling_dl; crop_radius and remove_ground default to 0.0 and False).  pose: [B,3,4]
@@ -36,7 +38,11 @@ def prepare_pairs(src_scans: Sequence[torch.Tensor], tgt_scans: Sequence[torch.T
     refine_pose=True (needs `pose`): point-to-point ICP from `pose` on the RAW scans' xyz, before the voxel filter, as
     the loader does it (icp.icp_pairs with max_dist icp_distance, at most icp_max_iter steps); 'pose' is then the
     refined pose [B,3,4] float32 and 'icp_fitness' / 'icp_rmse' ([B] float64) tell how well it fits.  Everything else
-    in the dict is what it is without the flag."""
+    in the dict is what it is without the flag.
+    icp_method='point_to_plane' refines by point-to-plane ICP instead (icp_plane.icp_pairs, kernel icp_kernel = 'l2',
+    'huber' or 'tukey' with parameter icp_kernel_k): the normals of the RAW target scans are estimated at
+    icp_normals_radius (metres, required with this method; normals_limit nearest points) and face the sensor at the
+    origin, like those of normals_radius."""
     src, tgt = list(src_scans), list(tgt_scans)
     B = len(src)
     if B < 1 or len(tgt) != B:
@@ -50,6 +56,10 @@ def prepare_pairs(src_scans: Sequence[torch.Tensor], tgt_scans: Sequence[torch.T
         raise ValueError("prepare_pairs: intensity=True needs [n, 4] scans (x y z reflectance)")
     if refine_pose and pose is None:
         raise ValueError("prepare_pairs: refine_pose=True needs the pose to refine")
+    if icp_method not in ('point_to_point', 'point_to_plane'):
+        raise ValueError(f"prepare_pairs: icp_method {icp_method!r}, expected 'point_to_point' or 'point_to_plane'")
+    if refine_pose and icp_method == 'point_to_plane' and icp_normals_radius is None:
+        raise ValueError("prepare_pairs: icp_method='point_to_plane' needs icp_normals_radius")
     lens = [int(s.shape[0]) for s in scans]
     if min(lens) < 1:
         b = lens.index(min(lens))
@@ -80,8 +90,15 @@ def prepare_pairs(src_scans: Sequence[torch.Tensor], tgt_scans: Sequence[torch.T
     if feats is not None:
         out['src_point_feats'], out['tgt_point_feats'] = feats[:B], feats[B:]
     if refine_pose:
-        from . import icp
         raw = [s[:, :3].to(torch.float32).contiguous() for s in scans]
-        r = icp.icp_pairs(raw[:B], raw[B:], pose, float(icp_distance), int(icp_max_iter))
+        if icp_method == 'point_to_plane':
+            from . import icp_plane
+            nrm = icp_plane.estimate_target_normals(raw[B:], float(icp_normals_radius), int(normals_limit),
+                                                    viewpoint=torch.zeros((B, 3), dtype=torch.float32, device=dev))
+            r = icp_plane.icp_pairs(raw[:B], raw[B:], nrm, pose, float(icp_distance), int(icp_max_iter),
+                                    kernel=icp_kernel, kernel_k=icp_kernel_k)
+        else:
+            from . import icp
+            r = icp.icp_pairs(raw[:B], raw[B:], pose, float(icp_distance), int(icp_max_iter))
         out['pose'], out['icp_fitness'], out['icp_rmse'] = r['pose'], r['fitness'], r['inlier_rmse']
     return out

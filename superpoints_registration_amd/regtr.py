@@ -229,14 +229,26 @@ class RegTR(nn.Module):
         return self._icp_polish(out, batch) if icp_refine else out
 
     def _icp_polish(self, out, batch):
-        """cfg.icp_refine: point-to-point ICP from the predicted pose on the input clouds, all pairs in one call; the
-        network's pose stays in the output as 'pose_coarse'."""
-        from . import icp
+        """cfg.icp_refine: ICP from the predicted pose on the input clouds, all pairs in one call -- point-to-point, or
+        with cfg.icp_method = 'point_to_plane' point-to-plane on target normals estimated at cfg.icp_normals_radius;
+        the network's pose stays in the output as 'pose_coarse'."""
         cfg = self.cfg
         dist = cfg.get('icp_distance', None)
         dist = 2.0 * float(cfg.first_subsampling_dl) if dist is None else float(dist)
-        r = icp.icp_pairs([c.to(torch.float32) for c in batch['src_xyz']], [c.to(torch.float32) for c in batch['tgt_xyz']],
-                          out['pose'], dist, int(cfg.get('icp_max_iter', 30)))
+        src, tgt = [c.to(torch.float32) for c in batch['src_xyz']], [c.to(torch.float32) for c in batch['tgt_xyz']]
+        method = cfg.get('icp_method', 'point_to_point')
+        if method == 'point_to_plane':
+            from . import icp_plane
+            radius = cfg.get('icp_normals_radius', None)
+            radius = 2.5 * float(cfg.first_subsampling_dl) if radius is None else float(radius)
+            r = icp_plane.icp_pairs(src, tgt, None, out['pose'], dist, int(cfg.get('icp_max_iter', 30)),
+                                    kernel=cfg.get('icp_kernel', 'l2'), kernel_k=cfg.get('icp_kernel_k', None),
+                                    normals_radius=radius)
+        elif method == 'point_to_point':
+            from . import icp
+            r = icp.icp_pairs(src, tgt, out['pose'], dist, int(cfg.get('icp_max_iter', 30)))
+        else:
+            raise ValueError(f"cfg.icp_method {method!r}, expected 'point_to_point' or 'point_to_plane'")
         out['pose_coarse'] = out['pose']
         out['pose'], out['icp_fitness'], out['icp_rmse'] = r['pose'], r['fitness'], r['inlier_rmse']
         return out
