@@ -729,6 +729,58 @@ int spr_icp_plane_pairs(const float* src_xyz, const int* src_cu, int ns, const f
                         double* fitness, double* inlier_rmse, int* iterations, int* count, int* corr, int* status,
                         void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Registration metrics for all pairs: RPMNet / DCP errors, modified Chamfer distance, inlier ratio -------------
+ * What the reference computes at the end of every experiment (benchmark/benchmark_modelnet.py: compute_metrics, right
+ * at batch size 1 only; models/generic_reg_model.py: compute_IR), for all nb pairs of a batch in one call.  Per pair:
+ * the source cloud, the reference (target) cloud, optionally the clean raw shape in the reference's frame (Chamfer),
+ * optionally a set of correspondences (inlier ratio), the ground-truth pose G and the predicted pose P, src -> tgt.
+ * Contract, per pair, in IEEE float64 on the exactly converted float32 inputs, one rounding per operation, no FMA:
+ *   dot3     = (a0 b0 + a1 b1) + a2 b2;  T x = dot3(row, x) + t per row;  d2(a, b) as in "ICP for all pairs"
+ *   Ginv     = [Rg^T | -(Rg^T tg)];  (A o B)_R[r][q] = dot3(A_R[r][:], B_R[:][q]),  (A o B)_t[r] = dot3(A_R[r][:], B_t) + A_t[r]
+ *   C        = Ginv o P;  D = P o Ginv
+ *   deg(x)   = (x 180) / pi
+ *   e(R)     = (deg(atan2(R21, R22)), deg(-asin(clamp(R20, -1, 1))), deg(atan2(R10, R00)))
+ *              -- scipy's as_euler('xyz', degrees=True); at gimbal lock this closed form is the contract
+ *   r_mse    = ((u0^2 + u1^2) + u2^2) / 3,  r_mae = ((|u0| + |u1|) + |u2|) / 3    with u = e(Rg) - e(Rp)
+ *   t_mse, t_mae: the same with u = tg - tp
+ *   err_r_deg = deg(acos(clamp(0.5 (((C00 + C11) + C22) - 1), -1, 1)))
+ *   err_t     = sqrt((Ct0^2 + Ct1^2) + Ct2^2);  trans_err = the same of Dt (se3_compare's translation error; its
+ *               rotation angle is err_r_deg's in exact arithmetic)
+ *   Chamfer (raw_cu != NULL):  a_i = P src_i,  c_j = D raw_j
+ *     d2_src_i = min_j d2(a_i, raw_j),  d2_ref_i = min_j d2(ref_i, c_j);  nn_* = the lowest LOCAL j attaining it
+ *     chamfer_src = sum_i d2_src_i / n_src,  chamfer_ref = sum_i d2_ref_i / n_ref  (0 for an empty query cloud)
+ *     chamfer_dist = chamfer_src + chamfer_ref
+ *   Inlier ratio (corr_cu != NULL):
+ *     inlier_count = #{k : d2(G corr_src_k, corr_tgt_k) < acceptance_radius * acceptance_radius}   (strict)
+ *     inlier_ratio = inlier_count / n_corr                                        (0 for an empty set)
+ * d2_* and nn_* are determined exactly by the contract.  The order of the two mean sums is the implementation's, fixed
+ * and a function of the pair alone (per-block float64 partials added in block order, no floating-point atomics): every
+ * output of a pair has the same bits whatever batch, position or neighbours it is called with, and run to run.
+ * metrics [nb, SPR_EVAL_COLS] f64, columns in this order:
+ *   r_mse, r_mae, t_mse, t_mae, err_r_deg, err_t, trans_err, chamfer_src, chamfer_ref, chamfer_dist, inlier_count,
+ *   inlier_ratio;  a part that was not asked for (raw_cu / corr_cu NULL) leaves its columns 0 and its d2 / nn untouched
+ * status [nb] i32: 0;  -1 when the pair has a non-finite coordinate or pose entry: all columns 0, d2 = 0, nn = -1 for
+ * that pair only;  -2 when its raw cloud is empty while its source or reference is not: the Chamfer columns 0, d2 = 0,
+ * nn = -1, every other column as defined.
+ * Nearest neighbours are exact brute force, O(n m) per pair and direction: 8 float64 operations and a compare per
+ * (query, target), targets staged in LDS tiles of SPR_EVAL_TILE points, SPR_EVAL_QUERIES queries per workgroup.
+ * Right for object-sized clouds (ModelNet: 717 x 2048); a grid-accelerated search for scan-sized clouds is out of scope.
+ * The call reads nothing back from the device; a workspace below spr_eval_pairs_workspace_size(ns, nt, nr, nc, nb) is
+ * refused before anything is enqueued.
+ *   src_xyz [ns,3] f32, src_cu [nb+1] i32; ref_xyz [nt,3], ref_cu; raw_xyz [nr,3], raw_cu (both NULL: no Chamfer);
+ *   corr_src, corr_tgt [nc,3] f32, corr_cu [nb+1] (all NULL: no inlier ratio; otherwise acceptance_radius > 0)
+ *   pose_gt, pose_pred [nb,3,4] f64
+ *   d2_src [ns] f64, nn_src [ns] i32, d2_ref [nt] f64, nn_ref [nt] i32: each may be NULL (not wanted) */
+#define SPR_EVAL_COLS 12
+#define SPR_EVAL_TILE 256    /* targets per LDS tile */
+#define SPR_EVAL_QUERIES 128 /* queries per workgroup */
+size_t spr_eval_pairs_workspace_size(int ns, int nt, int nr, int nc, int nb);
+int spr_eval_pairs(const float* src_xyz, const int* src_cu, int ns, const float* ref_xyz, const int* ref_cu, int nt,
+                   const float* raw_xyz, const int* raw_cu, int nr, const float* corr_src, const float* corr_tgt,
+                   const int* corr_cu, int nc, const double* pose_gt, const double* pose_pred, int nb,
+                   double acceptance_radius, double* metrics, double* d2_src, int* nn_src, double* d2_ref,
+                   int* nn_ref, int* status, void* ws, size_t ws_bytes, void* stream);
+
 /* Per-point input features: spr_kpconv_fwd (impl 0 and 2) runs 2 <= cin <= 8 with any cout >= 1 and at most 16
  * kernel points on the small-Cin kernel (k_kpconv_few: exact f32, the cin = 1 kernel's influence and data movement);
  * spr_kpconv_workspace_bytes covers its support records.  Host only: the dispatch rule, for callers and tests. */

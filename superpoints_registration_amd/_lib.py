@@ -58,6 +58,9 @@ SIGNATURES = {
     "spr_icp_plane_pairs_workspace_size": (_sz, [_i, _i, _i]),
     "spr_icp_plane_pairs": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _d, _i, _d, _d, _i, _d, _vp, _vp, _vp, _vp,
                                  _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "spr_eval_pairs_workspace_size": (_sz, [_i, _i, _i, _i, _i]),
+    "spr_eval_pairs": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _d, _vp, _vp, _vp,
+                            _vp, _vp, _vp, _vp, _sz, _vp]),
     "spr_philox4x32_host": (_i, [_vp, _vp, _vp]),
     "spr_augment_draw": (_i, [_u64, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
     "spr_augment_workspace_bytes": (_sz, [_i, _i, _i, _i]),
